@@ -454,6 +454,28 @@ def native_abi_leg(pipe, ws, ucfg, vcfg, B, T, dtype, dev_index, lat, pe, ne, im
         nat.close()
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_ELEMS = 4 << 20          # float32 values + float64 flat indices = 48 MB
+
+
+def dump_outputs(outdir: str, arrays) -> None:
+    """--dump-outputs: every array a caller of the timed path receives, as <outdir>/<name>.npy in float32.  An array that would
+    take the total past 64 MB is replaced by a fixed sample (seed 0) of its elements: <name>_sample.npy holds the values and
+    <name>_sample_index.npy their flat indices (float64, exact below 2**53), so two builds stay comparable element for element."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().contiguous().numpy()
+        if a.nbytes <= DUMP_LIMIT_BYTES:
+            np.save(os.path.join(outdir, f"{name}.npy"), a)
+            continue
+        g = torch.Generator().manual_seed(0)
+        idx = torch.randperm(a.size, generator=g)[:DUMP_SAMPLE_ELEMS].sort().values.numpy()
+        np.save(os.path.join(outdir, f"{name}_sample.npy"), a.reshape(-1)[idx])
+        np.save(os.path.join(outdir, f"{name}_sample_index.npy"), idx.astype(np.float64))
+    log(f"outputs of the last timed step written to {outdir}: {', '.join(arrays)}")
+
+
 def self_launch(n: int, argv) -> int:
     """Start `n` ranks of this script (one per GPU) as CHILD processes of a parent that has not initialised the GPU, the way
     the driver's own command does it: `python -m torch.distributed.run --nnodes=1 --nproc-per-node n --master-addr 127.0.0.1
@@ -504,7 +526,15 @@ def main(argv=None):
                          "cannot take one graph launch of ~14 k kernel nodes of a batch-8 loop (DESIGN.md, round-4 note)")
     ap.add_argument("--fake-pipeline", action="store_true",
                     help="CPU rehearsal of the multi-rank control flow (gloo, no GPU, no kernels): NOT a measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (the decoded images, gathered on rank 0) "
+                         "as DIR/<name>.npy in float32, at most 64 MB in all; inputs and weights are seeded, so two builds can be "
+                         "compared output for output (bench_outputs/ is git-ignored for this)")
     args = ap.parse_args(argv)
+    if args.steps < 0 or args.warmup < 0:
+        ap.error("--steps and --warmup must be >= 0")
+    if args.dump_outputs is not None and args.steps < 1:
+        ap.error("--dump-outputs needs at least one timed step (--steps >= 1)")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: no launcher in front of us.  This parent never touches a GPU (no torch.cuda call,
@@ -588,6 +618,8 @@ def main(argv=None):
     log(f"timed region done: {dt:.3f} s for {args.steps} step(s)")
     if rank == 0:
         img = out["img"]
+        if args.dump_outputs is not None:
+            dump_outputs(args.dump_outputs, {"images": img})       # before any later leg reuses the pipeline's buffers
         assert img.shape[0] == B * world and bool(torch.isfinite(img).all()), "non-finite output image"
         line = {
             "metric": "512x512 try-on images/sec @ 50 DDIM steps (6-cond ControlNet)",
