@@ -10,10 +10,13 @@ stacks on the CFG-duplicated batch, PL:629-664) -> 50 x [6 ControlNet passes -> 
 DDIM] -> VAE decode -> [0,1] image, inputs already resident in HBM.  Weights are seeded
 random-init SD1.5-shaped tensors (no checkpoints exist offline), data is synthetic.
 
-Prints ONE JSON line on rank 0 with the contract fields plus `roofline` (implicit-GEMM conv/linear kernel, MFMA
-bound), `cpu_baseline` (the CPU oracle timed on this host's cores on a bounded sample of denoising steps), `parity` (the
-HIP step of the benchmarked configuration against that oracle on identical inputs), `throughput_mode` (BASELINE
-configs[2], batch 8, with its own roofline) and `stress_mode` (BASELINE configs[4], 768x768 bf16 batch 4).
+A plain run sets up, warms up, times the steps, writes --dump-outputs if asked and prints ONE JSON line on rank 0 with
+the contract fields.  `--full` adds everything else the benchmark measures or checks: `clock` (sclk / power sampled
+during the timed region) and, after it, `phases_ms`, `roofline` (implicit-GEMM conv/linear kernel, MFMA bound),
+`cpu_baseline` (the CPU oracle timed on this host's cores on a bounded sample of denoising steps), `parity` (the HIP step
+of the benchmarked configuration against that oracle on identical inputs), `native_abi` (the same request through the C
+ABI alone), `throughput_mode` (BASELINE configs[2], batch 8, with its own roofline, and `throughput_sweep`) and
+`stress_mode` (BASELINE configs[4], 768x768 bf16 batch 4).  The --no-* switches drop single legs of a --full run.
 """
 import argparse
 import json
@@ -506,6 +509,10 @@ def main(argv=None):
     ap.add_argument("--dtype", default="fp16", choices=["fp16", "bf16"])
     ap.add_argument("--resolution", type=int, default=512, help="512 (the metric) or 768 (BASELINE config 5 stress)")
     ap.add_argument("--tiny", action="store_true", help="width-reduced config (plumbing check only, not the metric)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure, also measure and check everything else: clock, phases_ms, roofline, cpu_baseline + "
+                         "parity, native_abi, throughput_mode (+ throughput_sweep), stress_mode.  Off: the run does only what the "
+                         "headline figure needs")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-graph", action="store_true", help="eager launches (needed under rocprofv3 --pmc, which cannot "
@@ -535,6 +542,9 @@ def main(argv=None):
         ap.error("--steps and --warmup must be >= 0")
     if args.dump_outputs is not None and args.steps < 1:
         ap.error("--dump-outputs needs at least one timed step (--steps >= 1)")
+    if not args.full:
+        # a plain run: set up, warm up, time the steps, dump, print the line - no leg beside the headline figure
+        args.no_roofline = args.no_cpu_baseline = args.no_throughput_mode = args.no_stress_mode = args.no_native_abi = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: no launcher in front of us.  This parent never touches a GPU (no torch.cuda call,
@@ -603,7 +613,7 @@ def main(argv=None):
         sync()
         log(f"warmup {i} done")
     barrier()
-    sampler = ClockSampler().start() if (rank == 0 and not fake) else None
+    sampler = ClockSampler().start() if (rank == 0 and not fake and args.full) else None
     t0 = time.perf_counter()
     for _ in range(args.steps):
         one()
@@ -646,11 +656,11 @@ def main(argv=None):
                                  "expected": [round(float(make_inputs(ucfg, vcfg, 1, device, 42, j)[0].mean()), 6) for j in range(world * B)]}
         if clock is not None:
             line["clock"] = dict(clock, source="rocm-smi --showclocks --showpower polled during the timed region (medians); peak clock 2400 MHz")
-        if args.steps:
+        if args.steps and args.full:
             # `run_local`, not `one`: everything from here on runs on rank 0 ALONE - a collective here waits for ranks that are already
             # at the closing barrier (found by the two-rank rehearsal on a GPU box; the CPU rehearsal takes this path too)
             phases = call_phases(pipe, run_local, sync)
-        if not fake and args.steps:
+        if not fake and args.steps and args.full:
             line["phases_ms"] = dict(phases, how="HIP events at the phase boundaries of ONE extra pipeline call after "
                                      "the timed region: condition embedding / per-call preparation / denoising loop / VAE decode + post-processing")
         if not args.no_roofline:

@@ -96,3 +96,21 @@ def test_bench_launches_its_own_ranks_without_torchrun():
     bad = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--fake-pipeline",
                           "--batch", "-1"], cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert bad.returncode != 0
+
+
+def test_bench_full_two_rank_rehearsal():
+    """`--full` with two ranks: what follows the timed region (the extra phase-timing call) runs on rank 0 alone, while rank 1
+    already waits at the closing barrier - the run must still end with one line and exit code 0."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
+    env.update(OMP_NUM_THREADS="1")
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1",
+                        "--fake-pipeline", "--full"], cwd=root, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["n_gpus"] == 2 and d["rehearsal"]["gathered_image_means"] == d["rehearsal"]["expected"]

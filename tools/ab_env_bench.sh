@@ -7,10 +7,10 @@ out=gpurun_out/ab_${VAR}.txt
 : > $out
 for rep in 1 2; do
   for v in $A $B; do
-    env $VAR=$v python3 bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-roofline --no-stress-mode --no-native-abi --throughput-sweep "" > gpurun_out/ab_tmp.json 2> gpurun_out/ab_tmp.err
-    python3 - "$VAR=$v rep $rep" >> $out <<'PY'
+    env $VAR=$v python3 bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-roofline --no-stress-mode --no-native-abi --throughput-sweep "" > ${out%/*}/ab_tmp.json 2> ${out%/*}/ab_tmp.err
+    python3 - "$VAR=$v rep $rep" ${out%/*}/ab_tmp.json >> $out <<'PY'
 import json, sys
-d = json.loads(open("gpurun_out/ab_tmp.json").read().strip().splitlines()[-1])
+d = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])
 print(sys.argv[1], "batch 1:", d["value"], "images/s", d["ms_per_step"], "ms;  batch 8:", d["throughput_mode"]["value"], "images/s", d["throughput_mode"]["ms_per_step"], "ms", flush=True)
 PY
   done

@@ -5,7 +5,7 @@ cd "$(dirname "$0")/.."
 VAR=${1:-edgestyle_amd/lib/ablate/libes_wnt.so}
 for v in base variant; do
   if [ $v = variant ]; then export ES_HIP_LIB=$PWD/$VAR; else unset ES_HIP_LIB; fi
-  ES_DUMP_GEMM=1 ES_DUMP_GEMM_NAME=gemm_launches_$v.json python bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-throughput-mode --no-stress-mode > gpurun_out/bench_$v.json 2>/dev/null
+  echo "$v: $(ES_DUMP_GEMM=1 ES_DUMP_GEMM_NAME=gemm_launches_$v.json python bench.py --full --steps 3 --warmup 2 --no-cpu-baseline --no-throughput-mode --no-stress-mode 2>/dev/null)"
 done
 python - <<'PY'
 import json

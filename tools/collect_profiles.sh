@@ -8,12 +8,12 @@ out=gpurun_out/final
 mkdir -p $out
 export TMPDIR=/tmp
 if [ "$PART" = a ] || [ "$PART" = all ]; then
-# 1. the default bench line (driver's flags)
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $out/${R}_bench_default_run.json 2> $out/${R}_bench_default_run.err
+# 1. the bench line with every leg beside the headline (--full), 20 timed steps after 5 warm-up steps
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $out/${R}_bench_default_run.json 2> $out/${R}_bench_default_run.err
 # 2. rocprofv3 kernel stats at batch 1, batch 8 and BASELINE configs[4] (768 x 768, bf16, batch 4)
-bash tools/prof_bench.sh ${R}_bench_b1 --steps 2 --warmup 1 --no-cpu-baseline --no-throughput-mode --no-stress-mode --no-roofline
-bash tools/prof_bench.sh ${R}_bench_b8 --batch 8 --steps 1 --warmup 1 --no-cpu-baseline --no-throughput-mode --no-stress-mode --no-roofline
-ES_PROF_TIMEOUT=400 bash tools/prof_bench.sh ${R}_bench_768_b4 --resolution 768 --dtype bf16 --batch 4 --steps 1 --warmup 1 --no-cpu-baseline --no-throughput-mode --no-stress-mode --no-roofline --no-native-abi
+bash tools/prof_bench.sh ${R}_bench_b1 --full --steps 2 --warmup 1 --no-cpu-baseline --no-throughput-mode --no-stress-mode --no-roofline
+bash tools/prof_bench.sh ${R}_bench_b8 --batch 8 --full --steps 1 --warmup 1 --no-cpu-baseline --no-throughput-mode --no-stress-mode --no-roofline
+ES_PROF_TIMEOUT=400 bash tools/prof_bench.sh ${R}_bench_768_b4 --resolution 768 --dtype bf16 --batch 4 --full --steps 1 --warmup 1 --no-cpu-baseline --no-throughput-mode --no-stress-mode --no-roofline --no-native-abi
 cp gpurun_out/${R}_bench_b1_kernel_stats.csv gpurun_out/${R}_bench_b8_kernel_stats.csv gpurun_out/${R}_bench_768_b4_kernel_stats.csv \
    gpurun_out/${R}_bench_b1_under_rocprof.json gpurun_out/${R}_bench_b8_under_rocprof.json gpurun_out/${R}_bench_768_b4_under_rocprof.json $out/ 2>/dev/null
 # 4. clock / power while the loop runs

@@ -13,7 +13,7 @@ EXTRA="$@"
 export ES_TRAFFIC_WORKLOAD="batch $B${EXTRA:+ ($EXTRA)}"
 out=gpurun_out/traffic_$TAG
 rm -rf $out; mkdir -p $out
-ES_DUMP_GEMM=1 ES_DUMP_GEMM_NAME=traffic_$TAG/launches.json python3 bench.py --batch $B $EXTRA --steps 1 --warmup 1 --no-cpu-baseline --no-throughput-mode --no-stress-mode --no-native-abi > $out/dump.log 2>&1 || exit 1
+ES_DUMP_GEMM=1 ES_DUMP_GEMM_NAME=traffic_$TAG/launches.json python3 bench.py --full --batch $B $EXTRA --steps 1 --warmup 1 --no-cpu-baseline --no-throughput-mode --no-stress-mode --no-native-abi > $out/dump.log 2>&1 || exit 1
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout -k 10 600 rocprofv3 --pmc $c --output-format csv -d $out/$c -o run -- python3 bench.py --batch $B $EXTRA --steps 1 --warmup 1 --no-graph --no-cpu-baseline --no-roofline --no-throughput-mode --no-stress-mode --no-native-abi > $out/$c.log 2>&1
   echo "$c pass exit code $?" | tee -a $out/status.txt
