@@ -1203,6 +1203,11 @@ int launch_attn(const es_attn_desc& d, hipStream_t st) {
 // against ~1.2 us of vector issue).
 int attn_kvres = [] { const char* e = getenv("ES_ATTN_KVRES"); return e ? atoi(e) : 1; }();
 
+// which kernel the last es_attention launch of this process went to (es_attention_last_kernel: tests assert the variant they mean to run)
+enum { ATTN_K_NONE = 0, ATTN_K_GENERIC16 = 1, ATTN_K_GENERIC32 = 2, ATTN_K_TILE32 = 3, ATTN_K_TILE32_2BLOCKS = 4, ATTN_K_PP32 = 5, ATTN_K_PP64 = 6,
+       ATTN_K_KVRES = 7 };
+int attn_last_kernel = ATTN_K_NONE;
+
 template <typename T>
 int dispatch(const es_attn_desc& d, hipStream_t st) {
   // 32 queries per wave (128 per block) only when that still yields >= 2 blocks per CU; else 16 per wave
@@ -1211,8 +1216,10 @@ int dispatch(const es_attn_desc& d, hipStream_t st) {
   // the text-token cross-attention (77 keys) of the 64 x 64 and 32 x 32 levels: K / V resident in registers
   if (attn_kvres && d.Skv <= 96 && d.Sq >= 64 && (d.d == 40 || d.d == 80)) {
     const long long groups = (long long)((d.heads + 7) / 8) * d.N;           // workgroups per strip of queries
-    if (attn_kvres == 2 || groups >= (d.d == 40 ? 12 : 64))
+    if (attn_kvres == 2 || groups >= (d.d == 40 ? 12 : 64)) {
+      attn_last_kernel = ATTN_K_KVRES;
       return d.d == 40 ? launch_attn_kvres<T, 3, 3, true>(d, st) : launch_attn_kvres<T, 5, 5, false>(d, st);
+    }
   }
   static const bool tile32 = !(getenv("ES_ATTN32") && atoi(getenv("ES_ATTN32")) == 0);   // A/B switch (tools)
   if (big && tile32) {
@@ -1230,16 +1237,18 @@ int dispatch(const es_attn_desc& d, hipStream_t st) {
     static const int pp = getenv("ES_ATTN_PP") ? atoi(getenv("ES_ATTN_PP")) : -1;
     if (d.d == 40 && pp != 0 && d.Skv % 64 == 0 && d.Skv >= 128) {
       const long long wg256 = (long long)((d.Sq + 255) / 256) * d.heads * d.N;
-      if (pp == 2) return launch_attn40pp<T, 2>(d, st);
-      if (pp == 1 || (pp == -1 && wg256 >= 256)) return launch_attn40pp<T, 1>(d, st);
+      if (pp == 2) { attn_last_kernel = ATTN_K_PP64; return launch_attn40pp<T, 2>(d, st); }
+      if (pp == 1 || (pp == -1 && wg256 >= 256)) { attn_last_kernel = ATTN_K_PP32; return launch_attn40pp<T, 1>(d, st); }
     }
     if (d.d == 40 && qb2 == 2 && (long long)((d.Sq + 255) / 256) * d.heads * d.N >= big_thr) {
+      attn_last_kernel = ATTN_K_TILE32_2BLOCKS;
       return launch_attn32<T, 3, 3, true, 2>(d, st);
     }
-    if (d.d == 40) return launch_attn32<T, 3, 3, true>(d, st);
-    if (d.d == 80 && tile32_80) return launch_attn32<T, 5, 5, false>(d, st);
+    if (d.d == 40) { attn_last_kernel = ATTN_K_TILE32; return launch_attn32<T, 3, 3, true>(d, st); }
+    if (d.d == 80 && tile32_80) { attn_last_kernel = ATTN_K_TILE32; return launch_attn32<T, 5, 5, false>(d, st); }
   }
   // (64 queries per wave was measured slower: 309 registers -> one wave per SIMD)
+  attn_last_kernel = big && (d.d == 40 || d.d == 48 || d.d == 80) ? ATTN_K_GENERIC32 : ATTN_K_GENERIC16;    // QF = 2 | 1 below
   switch (d.d) {
     case 8: return launch_attn<T, 1, 1, 2, 64, true>(d, st);
     case 16: return launch_attn<T, 1, 1, 2, 64>(d, st);
@@ -1265,6 +1274,8 @@ extern "C" int es_attn_debug_read(unsigned long long* host16) {
   return (int)hipMemcpyFromSymbol(host16, HIP_SYMBOL(es_attn_dbg), 16 * sizeof(unsigned long long));
 }
 #endif
+
+extern "C" int es_attention_last_kernel(void) { return attn_last_kernel; }
 
 extern "C" int es_attention_set_kvres(int on) { const int prev = attn_kvres; attn_kvres = on; return prev; }
 

@@ -1147,6 +1147,8 @@ extern "C" int es_conv_gemm(const es_gemm_desc* d, void* stream) {
   if (d->C1 % 8 || d->C2 % 8 || (d->C2 && !d->x2)) { es_set_error("es_conv_gemm: channels must be multiples of 8"); return -1; }
   if (d->C2 && (d->C1 % BK || d->C2 % BK)) { es_set_error("es_conv_gemm: concatenated sources need C1, C2 multiples of 64"); return -1; }
   if ((size_t)d->rows_padded * d->Kpad * 2 >= 0x7FFFFFFFull) { es_set_error("es_conv_gemm: weights larger than 2 GiB (32-bit buffer offsets)"); return -1; }
+  // before oversize() / the dry launch_in_chunks(): both divide by the sample size and by Hout * Wout * (rows_padded / 8)
+  if (d->N < 1 || d->Hout < 1 || d->Wout < 1 || d->Cout < 1) { es_set_error("es_conv_gemm: empty problem"); return -1; }
   const bool chunked = oversize(*d);       // activations beyond the 32-bit buffer offsets: runs of whole samples, one launch each (launch_in_chunks)
   if (chunked) {
     const char* why = nullptr;
@@ -1173,7 +1175,6 @@ extern "C" int es_conv_gemm(const es_gemm_desc* d, void* stream) {
   if (d->splitk < 1 || d->splitk > d->Kpad / BK) { es_set_error("es_conv_gemm: bad splitk"); return -1; }
   if (d->splitk > 1 && (!d->workspace || d->act == ES_ACT_GEGLU)) { es_set_error("es_conv_gemm: splitk needs workspace and no GEGLU"); return -1; }
   if (d->act == ES_ACT_GEGLU && ((d->bn != 128 && d->bn != 256) || d->Cout % 32)) { es_set_error("es_conv_gemm: GEGLU needs bn=128 | 256, Cout%32==0"); return -1; }
-  if (d->N < 1 || d->Hout < 1 || d->Wout < 1) { es_set_error("es_conv_gemm: empty problem"); return -1; }
   if (d->stages != 0 && (d->stages < 2 || d->stages > 4)) { es_set_error("es_conv_gemm: stages must be 0 (auto), 2, 3 or 4"); return -1; }
   if (d->waves != 0 && d->waves != 4 && d->waves != 8) { es_set_error("es_conv_gemm: waves must be 0 (auto), 4 or 8"); return -1; }
   if (d->ln_colsum && (d->ksize != 1 || d->stride != 1 || d->C2 || d->C1 % BK || d->Kpad != d->C1 || d->splitk != 1 ||

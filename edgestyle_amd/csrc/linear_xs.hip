@@ -175,7 +175,12 @@ __global__ __launch_bounds__(512, 2) void linear_xs_kernel(const es_xs_desc p) {
     const float* bsel2 = p.ngroups > 1 ? p.gn_beta_g[grp] : p.gn_beta;
     const float* gst = (const float*)(smem + XS_STAGES * XS_STAGE);
     const int cpg = K / p.gn_groups;
-    const unsigned inv = (65536u + (unsigned)cpg - 1u) / (unsigned)cpg;          // c / cpg == (c * inv) >> 16 for c < 2^14
+    // c / cpg == (c * inv) >> 20 for every c < K <= 640 and every cpg <= 640: with e = inv * cpg - 2^20 < cpg, (c * inv) / 2^20 is
+    // c / cpg + c * e / (cpg * 2^20), and c * e < 640 * 640 < 2^20 keeps the excess below 1 / cpg; c * inv < 2^30 fits 32 bits.
+    // (A 2^16 reciprocal is NOT exact there: cpg = 640 sent channels 637..639 to group 1.)
+    // (tests/test_numerics_cpu.py checks a Python copy of this map against c / cpg and finds it by the TEXT of the next line and of the
+    //  shift below: change the two together with that test.)
+    const unsigned inv = ((1u << 20) + (unsigned)cpg - 1u) / (unsigned)cpg;
 #pragma unroll
     for (int kc = 0; kc < KC; ++kc) {
       const int cb = kc * 32 + fq * 8;
@@ -183,7 +188,7 @@ __global__ __launch_bounds__(512, 2) void linear_xs_kernel(const es_xs_desc p) {
       const f32x4 b0v = *(const f32x4*)(bsel2 + cb), b1v = *(const f32x4*)(bsel2 + cb + 4);
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
-        const int g = (int)(((unsigned)(cb + e) * inv) >> 16);
+        const int g = (int)(((unsigned)(cb + e) * inv) >> 20);
         const float gam = e < 4 ? g0v[e & 3] : g1v[e & 3], bet = e < 4 ? b0v[e & 3] : b1v[e & 3];
         const float a = gst[g * 2] * gam, b = __builtin_fmaf(gst[g * 2 + 1], gam, bet);
 #pragma unroll
@@ -578,6 +583,10 @@ extern "C" int es_linear_xs(const es_xs_desc* d, void* stream) {
     if (d->ngroups <= 1 && (!d->gn_gamma || !d->gn_beta)) { es_set_error("es_linear_xs: gn_part without gn_gamma / gn_beta"); return -1; }
     for (int g = 0; g < d->ngroups && d->ngroups > 1; ++g)
       if (!d->gn_gamma_g[g] || !d->gn_beta_g[g]) { es_set_error("es_linear_xs: gn_part without gn_gamma_g / gn_beta_g for every group"); return -1; }
+    // the statistics are per SAMPLE and gamma / beta / weights per GROUP: a sample split between two groups is no GroupNorm of either,
+    // and the chunked path below cuts groups into runs of whole samples
+    for (int g = 0; g < d->ngroups && d->ngroups > 1; ++g)
+      if (((long long)d->mt_end[g] * 128) % d->gn_hw) { es_set_error("es_linear_xs: gn_part needs weight groups of whole samples (mt_end * 128 a multiple of gn_hw)"); return -1; }
   }
   if (d->residual && (d->K != 320 || d->geglu || d->ln)) { es_set_error("es_linear_xs: a residual needs K = 320, no GEGLU, no LayerNorm fold (rows of ldo elements, like out)"); return -1; }
   es_xs_desc dd = *d;

@@ -195,6 +195,10 @@ int es_attention(const es_attn_desc* d, void* stream);
  * K/V-resident kernel - 0 never, 1 (default; ES_ATTN_KVRES in the environment) where it wins (>= 12 samples at head_dim 40, >= 64 at 80:
  * profiles/r05_xattn_bench.txt), 2 every eligible launch.  Returns the previous setting. */
 int es_attention_set_kvres(int on);
+/* test query: the kernel the last es_attention launch of this process went to - 1 generic tile (16 queries per wave), 2 generic tile
+ * (32 queries per wave: head_dim 40 | 48 | 80 in large launches), 3 32x32 score tile, 4 32x32 score tile with two query blocks per wave,
+ * 5 | 6 head_dim-40 ping-pong kernel with 32 | 64 queries per wave, 7 K/V-resident; 0 before the first launch. */
+int es_attention_last_kernel(void);
 
 /* GroupNorm (+SiLU) over NHWC with optional channel-concat of two sources.
  * Replaces torch group_norm + silu of ResnetBlock2D.norm1/norm2, conv_norm_out, Transformer2DModel.norm.

@@ -1,0 +1,691 @@
+"""Numerics at trained-model statistics: input generators, a per-row error metric and CPU baselines.
+
+The kernel tests in test_ops_gpu.py feed randn activations and judge by max|y - ref| / max|ref| over the whole tensor.  Both hide
+the mistakes this code base is most exposed to: the folds form variances in one pass (E[x^2] - mean^2) and cancel
+`x W'^T - mean colsum(W')` by a factor mean / sigma, real token streams have |mean| / sigma of 10-30 per token and a few channels
+two orders of magnitude above the rest, and one loud row sets the denominator of a whole-tensor metric.
+
+This module is plain Python (no fixtures):
+
+* generators (seeded, CPU, values rounded through the storage dtype before anything else sees them) that ASSERT their own
+  postconditions: `token_rows`, `group_maps`, `spike_and_sea`, `late_risers`, `common_shift`, `one_loud_query`, `loud_values`;
+* `row_err(y, ref64)`: max over rows r and columns c of |y[r, c] - ref64[r, c]| / rms_c(ref64[r, :]) - every row is its own scale;
+* for every operation three CPU computations on the SAME rounded inputs and rounded weights:
+    `*_ref64`     the plain operation in fp64 (the truth),
+    `*_base_ref`  the textbook op sequence in fp32 with every op's output rounded to the storage dtype (what the reference
+                  computes under fp16 autocast),
+    `*_base_alg`  the algorithm the kernel is DESIGNED to run, in fp32 (one-pass variance, the folded forms, a lazily raised
+                  softmax reference) - with an optional planted `defect`, for the tests that show the bars have teeth.
+
+Bars (tests/test_numerics_gpu.py): row_err(kernel) <= MARGIN * row_err(base_alg) always; in the required tier (ratio <= 30,
+outlier gain <= 100, peak <= 2e4) also row_err(kernel) <= MARGIN * row_err(base_ref).  MARGIN = 2 separates "rounds in a different
+order" from "lost a bit or more" and is not tuned per case.  In the probe tier (ratio 100, 300) only the first bar holds, with
+PROBE_MARGIN = 4: there the error is cancellation noise whose size depends on the order of summation.
+
+`python -m tests.numerics --report` (GPU) runs the cases of test_numerics_gpu.py and writes the measured table to tests/NUMERICS.md.
+"""
+import math
+
+import torch
+import torch.nn.functional as F
+
+MARGIN = 2.0
+PROBE_MARGIN = 4.0
+LAZY = 8.0                      # csrc/attention.hip: the running softmax reference may sit up to 2^8 below the true maximum
+REQUIRED_RATIOS = (0, 3, 10, 30)
+PROBE_RATIOS = (100, 300)
+FP16_NORMAL_MIN_LOG2 = -14
+
+
+def rnd(x: torch.Tensor, dtype) -> torch.Tensor:
+    """x rounded to the storage dtype (round to nearest even, subnormals kept), returned in fp32"""
+    return x.to(torch.float32).to(dtype).to(torch.float32)
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# metric
+# ----------------------------------------------------------------------------------------------------------------
+def row_err(y: torch.Tensor, ref64: torch.Tensor, both: bool = False):
+    """max over rows r, columns c of |y[r, c] - ref64[r, c]| / rms_c(ref64[r, :]); rows = everything but the last dimension (tokens,
+    pixels, (sample, head, query)).  No row is left out and no row may have a reference rms of 0.  both=True: also the row-rms
+    variant max_r rms_c(y - ref64) / rms_c(ref64) (for the report).  A non-finite y gives inf."""
+    r = ref64.detach().to("cpu", torch.float64).reshape(-1, ref64.shape[-1])
+    v = y.detach().to("cpu", torch.float64).reshape(-1, ref64.shape[-1])
+    assert r.shape == v.shape, (r.shape, v.shape)
+    rms = r.pow(2).mean(dim=1).sqrt()
+    assert bool((rms > 0).all()) and bool(torch.isfinite(rms).all()), "a reference row with rms 0 (or not finite): fix the generator"
+    d = (v - r).abs()
+    if not bool(torch.isfinite(d).all()):
+        return (float("inf"), float("inf")) if both else float("inf")
+    e_max = float((d.max(dim=1).values / rms).max())
+    if not both:
+        return e_max
+    return e_max, float((d.pow(2).mean(dim=1).sqrt() / rms).max())
+
+
+def old_metric(y: torch.Tensor, ref: torch.Tensor) -> float:
+    """the whole-tensor metric of test_ops_gpu.py (rel_err): max|y - ref| / max|ref|"""
+    a, b = y.detach().double().cpu(), ref.detach().double().cpu()
+    return float((a - b).abs().max() / (b.abs().max() + 1e-6))
+
+
+def finite_where_representable(y: torch.Tensor, ref64: torch.Tensor, dtype) -> bool:
+    """Overflow bar: wherever ref64 rounded to the storage dtype is finite, y is finite."""
+    ok = torch.isfinite(ref64.detach().cpu().to(torch.float32).to(dtype).float())
+    return bool(torch.isfinite(y.detach().cpu().float())[ok].all())
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# generators
+# ----------------------------------------------------------------------------------------------------------------
+def _gen(seed):
+    return torch.Generator().manual_seed(int(seed))
+
+
+def _outlier_gains(C, frac, gain, g):
+    """per-channel gain: `frac` of the channels (a fixed set, as in a trained model) carry `gain` (a number, or a (lo, hi) range
+    drawn uniformly) times the standard deviation of the rest"""
+    gains = torch.ones(C, dtype=torch.float64)
+    n = int(round(frac * C)) if frac > 0 else 0
+    if n:
+        idx = torch.randperm(C, generator=g)[:n]
+        lo, hi = (gain, gain) if not isinstance(gain, (tuple, list)) else gain
+        gains[idx] = lo + (hi - lo) * torch.rand(n, generator=g, dtype=torch.float64)
+    return gains
+
+
+def ratio_tolerance(ratio, dtype) -> float:
+    """+-10 % of the nominal |mean| / std; bf16 cannot hold a ratio of 300 that well after rounding (8 significant bits on values
+    300 standard deviations from 0): +-35 % there only"""
+    return 0.35 if (dtype == torch.bfloat16 and ratio >= 300) else 0.10
+
+
+def measured_ratio(x: torch.Tensor, dim=-1) -> torch.Tensor:
+    x = x.double()
+    return x.mean(dim=dim).abs() / x.std(dim=dim, unbiased=False)
+
+
+def token_rows(M, C, ratio, outlier_frac=0.0, outlier_gain=(50.0, 100.0), peak=4.0, dtype=torch.float16, seed=0):
+    """[M, C] fp32 tensor of dtype-rounded values: every row's actual |mean| / std (fp64, on the rounded values) lies within
+    ratio_tolerance() of `ratio` (ratio 0: below 0.05), a fixed `outlier_frac` of the channels carries `outlier_gain` times the
+    spread of the rest, and max|x| == peak (up to rounding).  Rows are standardised AFTER the outlier channels have been scaled and
+    then shifted (sign per row): adding a constant to randn * sigma instead leaves a heavy-tailed row std and ratios spread by 4x."""
+    g = _gen(seed)
+    x = torch.randn(M, C, generator=g, dtype=torch.float64) * _outlier_gains(C, outlier_frac, outlier_gain, g)
+    x = (x - x.mean(dim=1, keepdim=True)) / x.std(dim=1, unbiased=False, keepdim=True)
+    sign = torch.where(torch.rand(M, 1, generator=g) < 0.5, -1.0, 1.0).double()
+    x = x + sign * float(ratio)
+    x = x * (float(peak) / float(x.abs().max()))
+    x = rnd(x, dtype)
+    r = measured_ratio(x)
+    tol = ratio_tolerance(ratio, dtype)
+    if ratio == 0:
+        assert float(r.max()) < 0.05, float(r.max())
+    else:
+        assert float(r.min()) >= ratio * (1 - tol) and float(r.max()) <= ratio * (1 + tol), (ratio, float(r.min()), float(r.max()))
+    assert abs(float(x.abs().max()) / peak - 1) < 2 ** -7 and bool(torch.isfinite(x).all())
+    return x
+
+
+def group_maps(N, C, H, groups, ratio, outlier_frac=0.0, outlier_gain=(50.0, 100.0), peak=4.0, dtype=torch.float16, seed=0,
+               dominant_channel=False, W=None):
+    """[N, H, W, C] (NHWC) fp32 tensor of dtype-rounded values: every (sample, group)'s |mean| / std over its H * W * C / groups values
+    is within ratio_tolerance() of `ratio`.  dominant_channel: ONE channel of every group holds >= 90 % of the group's variance
+    (that fraction is asserted) - the group statistics are then those of a single channel."""
+    g = _gen(seed)
+    W = W or H
+    cpg = C // groups
+    gains = _outlier_gains(C, outlier_frac, outlier_gain, g)
+    if dominant_channel:
+        gains = torch.ones(C, dtype=torch.float64)
+        gains[torch.arange(groups) * cpg + torch.randint(0, cpg, (groups,), generator=g)] = 10.0 * math.sqrt(cpg)
+    x = torch.randn(N, H * W, C, generator=g, dtype=torch.float64) * gains
+    xg = x.reshape(N, H * W, groups, cpg)
+    xg = (xg - xg.mean(dim=(1, 3), keepdim=True)) / xg.std(dim=(1, 3), unbiased=False, keepdim=True)
+    sign = torch.where(torch.rand(N, 1, groups, 1, generator=g) < 0.5, -1.0, 1.0).double()
+    xg = xg + sign * float(ratio)
+    xg = xg * (float(peak) / float(xg.abs().max()))
+    x = rnd(xg.reshape(N, H, W, C), dtype)
+    xs = x.double().reshape(N, H * W, groups, cpg)
+    r = xs.mean(dim=(1, 3)).abs() / xs.std(dim=(1, 3), unbiased=False)
+    tol = ratio_tolerance(ratio, dtype)
+    if ratio == 0:
+        assert float(r.max()) < 0.05, float(r.max())
+    else:
+        assert float(r.min()) >= ratio * (1 - tol) and float(r.max()) <= ratio * (1 + tol), (ratio, float(r.min()), float(r.max()))
+    if dominant_channel:
+        dev = (xs - xs.mean(dim=(1, 3), keepdim=True)).pow(2).sum(dim=1)            # [N, groups, cpg]: each channel's part of the group's
+        assert float((dev.max(dim=-1).values / dev.sum(dim=-1)).min()) >= 0.9       # squared deviations from the group mean
+    assert bool(torch.isfinite(x).all())
+    return x
+
+
+def _unit(shape, g):
+    u = torch.randn(*shape, generator=g, dtype=torch.float64)
+    return u / u.norm(dim=-1, keepdim=True)
+
+
+def _softmax64(q, k, heads, scale=None):
+    """fp64 logits (natural units) [N, heads, Sq, Skv] of the [N, S, heads * d] layouts"""
+    N, Sq, Cc = q.shape
+    d = Cc // heads
+    qh = q.double().reshape(N, Sq, heads, d).transpose(1, 2)
+    kh = k.double().reshape(N, -1, heads, d).transpose(1, 2)
+    return qh @ kh.transpose(-1, -2) * (scale if scale is not None else 1.0 / math.sqrt(d))
+
+
+def spike_and_sea(N, heads, Sq, Skv, d, spread_log2, dtype=torch.float16, seed=0, control=False):
+    """q, k [N, S, heads * d], v: for >= 90 % of the (sample, head, query) rows of the fp64 softmax one key holds the maximum, every
+    other key's weight is below 2^-14 of it (the fp16 normal range) and the other keys together - the sea - hold between 2.5 % and
+    50 % of the mass; the sea's V carries a common offset (+1.5 against -1.5 for the spike), so losing the sea moves the output.
+    control=True: the same construction with a sea mass below 1 % asserted instead (a tail that is negligible)."""
+    assert Skv >= 1024
+    g = _gen(seed)
+    u = _unit((N, 1, heads, d), g)
+    q = math.sqrt(d) * u + 0.05 * torch.randn(N, Sq, heads, d, generator=g, dtype=torch.float64)
+    k = 0.05 * torch.randn(N, Skv, heads, d, generator=g, dtype=torch.float64)
+    v = torch.randn(N, Skv, heads, d, generator=g, dtype=torch.float64) + 1.5
+    pos = torch.randint(0, Skv, (N, heads), generator=g)
+    ni, hi = torch.meshgrid(torch.arange(N), torch.arange(heads), indexing="ij")
+    k[ni, pos, hi] = u[:, 0] * (spread_log2 * math.log(2.0))
+    v[ni, pos, hi] = v[ni, pos, hi] - 3.0
+    q, k, v = (rnd(t.reshape(N, -1, heads * d), dtype) for t in (q, k, v))
+    s = _softmax64(q, k, heads)
+    top2 = s.topk(2, dim=-1).values
+    gap_log2 = (top2[..., 0] - top2[..., 1]) / math.log(2.0)
+    w = torch.softmax(s, dim=-1)
+    sea = 1.0 - w.max(dim=-1).values
+    if control:
+        assert float(sea.median()) < 0.01, float(sea.median())
+    else:
+        ok = (gap_log2 > -FP16_NORMAL_MIN_LOG2) & (sea >= 0.025) & (sea <= 0.5)
+        assert float(ok.double().mean()) >= 0.9, (float(ok.double().mean()), float(gap_log2.min()), float(sea.median()))
+    assert bool((s.argmax(dim=-1) == pos[:, :, None]).all())
+    return q, k, v
+
+
+def late_risers(N, heads, Sq, Skv, d, tile=64, step_log2=10.0, dtype=torch.float16, seed=0):
+    """The per-key-tile maximum of every query rises by about `step_log2` from one tile of `tile` keys to the next, for at least four
+    tiles (asserted in fp64: every rise within 2 of step_log2): the running reference is re-raised and the accumulators rescaled
+    again and again."""
+    g = _gen(seed)
+    ntile = Skv // tile
+    assert ntile >= 5
+    u = _unit((N, 1, heads, d), g)
+    q = math.sqrt(d) * u + 0.1 * torch.randn(N, Sq, heads, d, generator=g, dtype=torch.float64)
+    k = 0.3 * torch.randn(N, Skv, heads, d, generator=g, dtype=torch.float64)
+    k = k - (k * u).sum(dim=-1, keepdim=True) * u                       # the calm keys carry nothing along u
+    rises = min(ntile - 1, 6)
+    for t in range(1, rises + 1):
+        p = t * tile + int(torch.randint(0, tile, (1,), generator=g))
+        k[:, p] = k[:, p] + u[:, 0] * (t * step_log2 * math.log(2.0) + 2.0)
+    v = torch.randn(N, Skv, heads, d, generator=g, dtype=torch.float64)
+    q, k, v = (rnd(t.reshape(N, -1, heads * d), dtype) for t in (q, k, v))
+    s = _softmax64(q, k, heads) / math.log(2.0)
+    tm = s[..., :ntile * tile].reshape(N, heads, Sq, ntile, tile).max(dim=-1).values
+    inc = tm[..., 1:rises + 1] - tm[..., :rises]
+    assert rises >= 4 and float((inc[..., 1:] - step_log2).abs().max()) < 2.0 and float(inc[..., 0].min()) > 3.0, \
+        (float(inc.min()), float(inc.max()))
+    return q, k, v
+
+
+def common_shift(N, heads, Sq, Skv, d, shift=300.0, dtype=torch.float16, seed=0):
+    """randn q, k, v plus a shared q / k component that moves ALL logits of a query by `shift` (+ or -): softmax does not care, the
+    kernel's first-tile reference has to absorb it.  The component sits in one coordinate with values exact in bf16, so the shift is
+    common to every key exactly.  Asserted: every query's logits have |mean| within 5 % of |shift| and a spread that stays O(1)."""
+    g = _gen(seed)
+    q = torch.randn(N, Sq, heads, d, generator=g, dtype=torch.float64)
+    k = torch.randn(N, Skv, heads, d, generator=g, dtype=torch.float64)
+    v = torch.randn(N, Skv, heads, d, generator=g, dtype=torch.float64)
+    a = 2.0 ** round(math.log2(math.sqrt(abs(shift) * math.sqrt(d))))
+    b = abs(shift) * math.sqrt(d) / a
+    b = float(torch.tensor(b).to(torch.bfloat16))                       # exact in both storage dtypes
+    q[..., 0] = a * (1.0 if shift > 0 else -1.0)
+    k[..., 0] = b
+    q, k, v = (rnd(t.reshape(N, -1, heads * d), dtype) for t in (q, k, v))
+    s = _softmax64(q, k, heads)
+    assert float((s.mean(dim=-1).abs() / abs(shift) - 1).abs().max()) < 0.05 and float(s.std(dim=-1).max()) < 3.0
+    assert (float(s.mean()) > 0) == (shift > 0)
+    return q, k, v
+
+
+def one_loud_query(N, heads, Sq, Skv, d, wave=32, gain_log2=20.0, dtype=torch.float16, seed=0):
+    """One query of every `wave` consecutive queries spikes on a key of a LATE tile (its maximum rises by ~gain_log2 there), the
+    others stay calm: the kernels' rescale branch is wave-uniform (__all(calm)), so the calm queries of that wave are rescaled by
+    2^0 alongside.  Asserted: exactly the chosen queries have a logit range above gain_log2 - 4, all others below 8."""
+    g = _gen(seed)
+    q = 0.5 * torch.randn(N, Sq, heads, d, generator=g, dtype=torch.float64)
+    k = 0.5 * torch.randn(N, Skv, heads, d, generator=g, dtype=torch.float64)
+    v = torch.randn(N, Skv, heads, d, generator=g, dtype=torch.float64)
+    u = _unit((d,), g)
+    q = q - (q * u).sum(dim=-1, keepdim=True) * u
+    k = k - (k * u).sum(dim=-1, keepdim=True) * u
+    loud = torch.arange(0, Sq, wave) + torch.randint(0, min(wave, Sq), ((Sq + wave - 1) // wave,), generator=g)
+    loud = loud[loud < Sq]
+    key = Skv - 1 - int(torch.randint(0, min(16, Skv // 2), (1,), generator=g))
+    amp = math.sqrt(gain_log2 * math.log(2.0) * math.sqrt(d))
+    q[:, loud] = q[:, loud] + u * amp
+    k[:, key] = k[:, key] + u * amp
+    q, k, v = (rnd(t.reshape(N, -1, heads * d), dtype) for t in (q, k, v))
+    s = _softmax64(q, k, heads) / math.log(2.0)
+    rng = s.max(dim=-1).values - s.median(dim=-1).values
+    mask = torch.zeros(Sq, dtype=torch.bool)
+    mask[loud] = True
+    assert float(rng[:, :, mask].min()) > gain_log2 - 4 and float(rng[:, :, ~mask].max()) < 8.0, \
+        (float(rng[:, :, mask].min()), float(rng[:, :, ~mask].max()))
+    return q, k, v
+
+
+def loud_values(N, heads, Sq, Skv, d, peak=2.0e4, dtype=torch.float16, seed=0):
+    """calm logits (randn q, k) and V scaled so that max|V| == peak: the output is a convex combination of V rows, so every
+    intermediate the reference stores stays below peak, and P V must not overflow on the way."""
+    g = _gen(seed)
+    q = torch.randn(N, Sq, heads * d, generator=g, dtype=torch.float64)
+    k = torch.randn(N, Skv, heads * d, generator=g, dtype=torch.float64)
+    v = torch.randn(N, Skv, heads * d, generator=g, dtype=torch.float64)
+    v = v * (peak / float(v.abs().max()))
+    q, k, v = (rnd(t, dtype) for t in (q, k, v))
+    assert float(v.abs().max()) <= peak * (1 + 2 ** -8) and bool(torch.isfinite(v).all())
+    return q, k, v
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# LayerNorm -> Linear (-> GEGLU)
+# ----------------------------------------------------------------------------------------------------------------
+def ln_case(x, Cout, dtype, geglu=False, bias=True, seed=0, eps=1e-5):
+    """weights of a LayerNorm + Linear pair for the rows x [M, C]: W rounded to the storage dtype (the weights the fold is SPECIFIED
+    to equal are the unfolded rounded W), gamma / beta / bias fp32"""
+    g = _gen(seed + 7919)
+    C = x.shape[1]
+    return dict(x=x, dtype=dtype, geglu=geglu, eps=eps,
+                gamma=1 + 0.2 * torch.randn(C, generator=g), beta=0.1 * torch.randn(C, generator=g),
+                W=rnd(torch.randn(Cout, C, generator=g) / math.sqrt(C), dtype),
+                b=(torch.randn(Cout, generator=g) * 0.1) if bias else None)
+
+
+def ln_ref64(c):
+    x = c["x"].double()
+    y = F.layer_norm(x, (x.shape[1],), c["gamma"].double(), c["beta"].double(), c["eps"])
+    y = F.linear(y, c["W"].double(), None if c["b"] is None else c["b"].double())
+    if c["geglu"]:
+        h, gate = y.chunk(2, dim=-1)
+        y = h * F.gelu(gate)
+    return y
+
+
+def ln_intermediates_peak(c) -> float:
+    """largest magnitude (fp64) among what the REFERENCE would store in the storage dtype: the LayerNorm output, the Linear output,
+    the GEGLU product"""
+    x = c["x"].double()
+    n = F.layer_norm(x, (x.shape[1],), c["gamma"].double(), c["beta"].double(), c["eps"])
+    y = F.linear(n, c["W"].double(), None if c["b"] is None else c["b"].double())
+    m = max(float(n.abs().max()), float(y.abs().max()))
+    if c["geglu"]:
+        h, gate = y.chunk(2, dim=-1)
+        m = max(m, float((h * F.gelu(gate)).abs().max()))
+    return m
+
+
+def ln_base_ref(c):
+    """two-pass LayerNorm -> round -> Linear with fp32 accumulation -> round (-> GELU -> round -> product -> round)"""
+    dt = c["dtype"]
+    x = c["x"].float()
+    n = rnd(F.layer_norm(x, (x.shape[1],), c["gamma"], c["beta"], c["eps"]), dt)
+    y = rnd(F.linear(n, c["W"], c["b"]), dt)
+    if c["geglu"]:
+        h, gate = y.chunk(2, dim=-1)
+        y = rnd(h * rnd(F.gelu(gate), dt), dt)
+    return y
+
+
+def _chain_sums(x, order):
+    """fp32 sums of x and x^2 along the last dimension in the order the LayerNorm-folding kernels form them (every step rounded to
+    fp32; the products and the 8-wide partial dot products are taken exactly, in fp64):
+      "mfma8"   es_conv_gemm: both sums ride on the matrix core - one chain of 16x16x32 MFMAs per row.  A lane supplies 8 consecutive
+                channels of an operand, and the accumulator takes one such 8-channel partial dot product after the other (four per
+                instruction): with this order the emulation reproduces the kernels' error at |mean| / std = 300 to four digits on
+                the MI355X (C = 320, 640, 1280), with one rounding per 32 channels it is 2-4 times too small there;
+      "xs"      es_linear_xs: a row's channels sit in four lanes, lane f holding channels 32 i + 8 f .. + 7 of every 32-channel
+                chunk i; each lane runs s += v, ss = fma(v, v, ss) over its values in order, then (l0 + l1) + (l2 + l3)."""
+    M, K = x.shape
+    xd = x.double()
+    if order == "mfma8":
+        s = torch.zeros(M, dtype=torch.float32)
+        ss = torch.zeros(M, dtype=torch.float32)
+        for i in range(0, K, 8):
+            blk = xd[:, i:i + 8]
+            s = (s.double() + blk.sum(dim=1)).float()
+            ss = (ss.double() + (blk * blk).sum(dim=1)).float()
+        return s[:, None], ss[:, None]
+    assert order == "xs" and K % 32 == 0
+    lanes = xd.reshape(M, K // 32, 4, 8).permute(0, 2, 1, 3).reshape(M, 4, K // 4)
+    s = torch.zeros(M, 4, dtype=torch.float32)
+    ss = torch.zeros(M, 4, dtype=torch.float32)
+    for j in range(K // 4):
+        v = lanes[:, :, j]
+        s = (s.double() + v).float()
+        ss = (ss.double() + v * v).float()
+    fold = lambda t: ((t[:, 0] + t[:, 1]) + (t[:, 2] + t[:, 3]))[:, None]
+    return fold(s), fold(ss)
+
+
+def one_pass_stats(x, dim, eps, partial_dtype=None, chunks=1, order="tree"):
+    """mean and rstd as the kernels form them: fp32 sums of x and x^2, var = E[x^2] - mean^2 clamped at 0.
+    order: "tree" (torch's blocked fp32 sums) or one of _chain_sums' orders (2-d x, dim 1) - at |mean| / std of 100 and more the
+    variance is what the rounding of these sums leaves, and a tree sum is several times more accurate than a chain of the same length.
+    partial_dtype (a planted defect): the sums are formed in `chunks` partial sums that are rounded to that dtype before they are
+    added up."""
+    x = x.float()
+    cnt = x.shape[dim] if isinstance(dim, int) else math.prod(x.shape[d] for d in dim)
+    if partial_dtype is not None:
+        assert isinstance(dim, int)
+        parts = x.chunk(chunks, dim=dim)
+        s = sum(rnd(p.sum(dim=dim, keepdim=True), partial_dtype) for p in parts)
+        ss = sum(rnd((p * p).sum(dim=dim, keepdim=True), partial_dtype) for p in parts)
+    elif order != "tree":
+        assert dim == 1 and x.dim() == 2
+        s, ss = _chain_sums(x, order)
+    else:
+        s, ss = x.sum(dim=dim, keepdim=True), (x * x).sum(dim=dim, keepdim=True)
+    mean = s * (1.0 / cnt) if order != "tree" else s / cnt
+    var = (ss * (1.0 / cnt) if order != "tree" else ss / cnt) - mean * mean
+    return mean, torch.rsqrt(var.clamp_min(0.0) + eps)
+
+
+def fold_weights(c):
+    """ops.pack_weight_ln's definitions: W' = round(W * gamma), colsum of the ROUNDED W' (fp64 sum, rounded once to fp32), folded
+    bias W beta + b (fp64, rounded once)"""
+    Wf = rnd(c["W"] * c["gamma"][None, :], c["dtype"])
+    colsum = Wf.double().sum(dim=1).float()
+    fb = c["W"].double() @ c["beta"].double()
+    if c["b"] is not None:
+        fb = fb + c["b"].double()
+    return Wf, colsum, fb.float()
+
+
+def ln_base_alg(c, form="fold", defect=None):
+    """form "fold" (es_conv_gemm, ln_colsum): rstd * (x W'^T - mean * colsum(W')) + (W beta + b), one-pass statistics, rounded once.
+    form "xs" (es_linear_xs): the row is normalised in registers, x * rstd + (-mean * rstd) rounded to the storage dtype, then
+    multiplied with W'.
+    defect: "colsum_unrounded" (colsum taken from W * gamma before rounding), "partial_sums_fp16" (the statistics' partial sums of 64
+    channels rounded to fp16)."""
+    dt = c["dtype"]
+    x = c["x"].float()
+    Wf, colsum, fb = fold_weights(c)
+    if defect == "colsum_unrounded":
+        colsum = (c["W"].double() * c["gamma"].double()[None, :]).sum(dim=1).float()
+    if defect == "partial_sums_fp16":
+        mean, rstd = one_pass_stats(x, 1, c["eps"], partial_dtype=torch.float16, chunks=x.shape[1] // 64)
+    else:
+        mean, rstd = one_pass_stats(x, 1, c["eps"], order="mfma8" if form == "fold" else "xs")
+    if form == "fold":
+        y = rstd * (x @ Wf.t() - mean * colsum[None, :]) + fb[None, :]
+    else:
+        xn = rnd(torch.addcmul(-mean * rstd, x, rstd), dt)
+        y = xn @ Wf.t() + fb[None, :]
+    if c["geglu"]:
+        h, gate = y.chunk(2, dim=-1)
+        y = h * F.gelu(gate)
+    return rnd(y, dt)
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# GroupNorm (-> SiLU) and GroupNorm -> 1x1 projection
+# ----------------------------------------------------------------------------------------------------------------
+def gn_case(x, groups, dtype, silu=False, eps=1e-5, seed=0, Cout=0, ngroups=1):
+    """x [N, H, W, C] NHWC.  Cout > 0: a 1x1 projection behind the GroupNorm (Transformer2DModel.norm -> proj_in).  ngroups > 1: that
+    many parameter sets (grouped launches)."""
+    g = _gen(seed + 104729)
+    C = x.shape[-1]
+    c = dict(x=x, groups=groups, dtype=dtype, silu=silu, eps=eps,
+             gamma=[1 + 0.2 * torch.randn(C, generator=g) for _ in range(ngroups)],
+             beta=[0.2 * torch.randn(C, generator=g) for _ in range(ngroups)])
+    if Cout:
+        c["W"] = [rnd(torch.randn(Cout, C, generator=g) / math.sqrt(C), dtype) for _ in range(ngroups)]
+        c["b"] = [torch.randn(Cout, generator=g) * 0.1 for _ in range(ngroups)]
+    return c
+
+
+def _gn_groups_view(x, groups):
+    N, H, W, C = x.shape
+    return x.reshape(N, H * W, groups, C // groups)
+
+
+def _per_set(c, counts, fn):
+    """apply fn(x_slice, i) to the sample ranges of a grouped launch"""
+    counts = counts or [c["x"].shape[0]]
+    out, a = [], 0
+    for i, n in enumerate(counts):
+        out.append(fn(c["x"][a:a + n], i))
+        a += n
+    return torch.cat(out, 0)
+
+
+def gn_ref64(c, counts=None):
+    def one(x, i):
+        xg = _gn_groups_view(x.double(), c["groups"])
+        mean = xg.mean(dim=(1, 3), keepdim=True)
+        var = xg.var(dim=(1, 3), unbiased=False, keepdim=True)
+        y = ((xg - mean) / torch.sqrt(var + c["eps"])).reshape(x.shape) * c["gamma"][i].double() + c["beta"][i].double()
+        if c["silu"]:
+            y = F.silu(y)
+        if "W" in c:
+            y = y @ c["W"][i].double().t() + c["b"][i].double()
+        return y
+    return _per_set(c, counts, one)
+
+
+def gn_intermediates_peak(c, counts=None) -> float:
+    keep = {k: c[k] for k in c if k not in ("W", "b")}
+    m = float(gn_ref64(dict(keep, silu=False), counts).abs().max())
+    return max(m, float(gn_ref64(c, counts).abs().max()))
+
+
+def gn_base_ref(c, counts=None):
+    """two-pass GroupNorm in fp32 -> round (-> SiLU -> round) (-> projection with fp32 accumulation -> round)"""
+    dt = c["dtype"]
+
+    def one(x, i):
+        xg = _gn_groups_view(x.float(), c["groups"])
+        mean = xg.mean(dim=(1, 3), keepdim=True)
+        var = ((xg - mean) ** 2).mean(dim=(1, 3), keepdim=True)
+        y = rnd(((xg - mean) * torch.rsqrt(var + c["eps"])).reshape(x.shape) * c["gamma"][i] + c["beta"][i], dt)
+        if c["silu"]:
+            y = rnd(F.silu(y), dt)
+        if "W" in c:
+            y = rnd(y @ c["W"][i].t() + c["b"][i], dt)
+        return y
+    return _per_set(c, counts, one)
+
+
+def xs_group_of_channel(c: int, cpg: int) -> int:
+    """the integer channel -> group map of csrc/linear_xs.hip (GroupNorm in front): a 2^20 reciprocal"""
+    inv = ((1 << 20) + cpg - 1) // cpg
+    return ((c * inv) & 0xFFFFFFFF) >> 20
+
+
+def xs_group_of_channel_2_16(c: int, cpg: int) -> int:
+    """the map that code used before: a 2^16 reciprocal - inexact for cpg = 640 (a planted defect here)"""
+    inv = (65536 + cpg - 1) // cpg
+    return (c * inv) >> 16
+
+
+GN_MAX_CHUNK = 64               # csrc/norm.hip: pixel chunks per sample of the statistics pass
+
+
+def gn_chunked_stats(xg, eps):
+    """GroupNorm statistics of xg [N, HW, groups, cpg] summed the way the kernels sum them - in three short levels, never as one long
+    sum: a channel's pixels inside a chunk of max(16, HW / 64) pixels, the channels of a group, the chunks of a sample
+    (gn_stats_kernel + the prologue of gn_apply_kernel; the slab kernel and the producer's epilogue have the same three levels with
+    other chunk sizes).  Every level's result is rounded to fp32 once (taken in fp64 inside the level - a little better than the
+    kernels' chains of at most a few dozen fp32 additions there).  A flat fp32 sum over a group of 40960 values and more is up to ten
+    times noisier than this at |mean| / std = 30, and than the kernels."""
+    N, HW, G, cpg = xg.shape
+    ppb = max(16, HW // GN_MAX_CHUNK)
+    nchunk = (HW + ppb - 1) // ppb
+    pad = nchunk * ppb - HW
+    xd = xg.double()
+    if pad:
+        xd = torch.cat([xd, torch.zeros(N, pad, G, cpg, dtype=torch.float64)], 1)
+    xd = xd.reshape(N, nchunk, ppb, G, cpg)
+
+    def levels(t):
+        t = t.sum(dim=2).float()                    # pixels of a chunk, per channel
+        t = t.double().sum(dim=3).float()           # channels of a group
+        return t.double().sum(dim=1).float()        # chunks of a sample -> [N, G]
+    cnt = float(cpg) * float(HW)
+    mean = levels(xd) / cnt
+    var = (levels(xd * xd) / cnt - mean * mean).clamp_min(0.0)
+    return mean.reshape(N, 1, G, 1), torch.rsqrt(var + eps).reshape(N, 1, G, 1)
+
+
+def gn_base_alg(c, counts=None, defect=None, stats_from=None):
+    """one-pass statistics (fp32 sums in the kernels' chunking: gn_chunked_stats; E[x^2] - mean^2 clamped at 0); x * (rstd gamma) + (beta - mean rstd gamma) (-> SiLU) rounded
+    once; then the projection.  stats_from: another tensor of x's shape from which the STATISTICS are taken (the producer hand-over:
+    sums of the fp32 accumulators, while the rounded values are normalised).
+    defect "wrong_group_tail": the last three channels are normalised with the statistics of another group - what the 2^16
+    reciprocal did to channels 637..639 of K = 640 with one group: they took (rstd, -mean rstd) of a "group 1" that nobody had
+    written.  With several groups the stand-in is the first group's pair; with one group it is (0, 0), memory read as zeros."""
+    dt = c["dtype"]
+    G = c["groups"]
+
+    def one(x, i, xs=None):
+        xg = _gn_groups_view(x.float(), G)
+        sg = xg if xs is None else _gn_groups_view(xs.float(), G)
+        mean, rstd = gn_chunked_stats(sg, c["eps"])
+        N, HW, _, cpg = xg.shape
+        mean_c = mean.expand(N, 1, G, cpg).reshape(N, 1, G * cpg).clone()
+        rstd_c = rstd.expand(N, 1, G, cpg).reshape(N, 1, G * cpg).clone()
+        if defect == "wrong_group_tail":
+            if G > 1:
+                mean_c[:, :, -3:] = mean.reshape(N, 1, G)[:, :, :1]
+                rstd_c[:, :, -3:] = rstd.reshape(N, 1, G)[:, :, :1]
+            else:
+                mean_c[:, :, -3:] = 0.0
+                rstd_c[:, :, -3:] = 0.0
+        a = rstd_c * c["gamma"][i]
+        b = c["beta"][i] - mean_c * a
+        y = x.float().reshape(N, HW, -1) * a + b
+        if c["silu"]:
+            y = F.silu(y)
+        y = rnd(y, dt).reshape(x.shape)
+        if "W" in c:
+            y = rnd(y @ c["W"][i].t() + c["b"][i], dt)
+        return y
+    if stats_from is None:
+        return _per_set(c, counts, one)
+    assert counts is None
+    return one(c["x"], 0, stats_from)
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# a VAE-decoder up block: ResnetBlock2D x 3 (GroupNorm -> SiLU -> conv3x3, twice, + x) and nearest 2x upsampling + conv3x3
+# ----------------------------------------------------------------------------------------------------------------
+def vae_up_block(sd, p, x, groups, eps, mode, dtype=None, peaks=None, nres=3):
+    """x [N, C, H, W].  mode "ref64": the plain block in fp64; "fp32": the same in fp32 (what the reference runs its VAE in), the
+    output rounded once; "ref": fp32 with EVERY op's output rounded to the storage dtype (GroupNorm, SiLU, convolution, sum);
+    "alg": what the engine's launches are designed to compute - GroupNorm with one-pass chunked statistics and x * a + b -> SiLU
+    rounded once, convolution + bias (+ residual) in the fp32 accumulator rounded once.  peaks: a list that receives max|t| of every
+    tensor the block stores."""
+    import torch.nn.functional as F
+    f64 = mode == "ref64"
+    cast = (lambda t: t.double()) if f64 else (lambda t: t.float())
+    r = (lambda t: rnd(t, dtype)) if mode in ("ref", "alg") else (lambda t: t)
+
+    def note(t):
+        if peaks is not None:
+            peaks.append(float(t.abs().max()))
+        return t
+
+    def gn_silu(t, q):
+        w, b = cast(sd[q + ".weight"]), cast(sd[q + ".bias"])
+        if mode != "alg":
+            return note(r(F.silu(note(r(F.group_norm(t, groups, w, b, eps))))))
+        N, C, H, W = t.shape
+        tg = t.permute(0, 2, 3, 1).reshape(N, H * W, groups, C // groups)
+        mean, rstd = gn_chunked_stats(tg, eps)
+        a = (rstd.expand(N, 1, groups, C // groups).reshape(N, 1, C) * w)
+        sh = b - mean.expand(N, 1, groups, C // groups).reshape(N, 1, C) * a
+        y = F.silu(t.permute(0, 2, 3, 1).reshape(N, H * W, C) * a + sh)
+        return note(r(y).reshape(N, H, W, C).permute(0, 3, 1, 2).contiguous())
+
+    def conv(t, q, res=None):
+        y = F.conv2d(t, cast(sd[q + ".weight"]), cast(sd[q + ".bias"]), padding=1)
+        if res is None:
+            return note(r(y))
+        return note(r(y + res)) if mode == "alg" else note(r(note(r(y)) + res))
+
+    h = note(cast(x))
+    for j in range(nres):
+        q = f"{p}.resnets.{j}"
+        t = conv(gn_silu(h, q + ".norm1"), q + ".conv1")
+        h = conv(gn_silu(t, q + ".norm2"), q + ".conv2", res=h)
+    h = conv(F.interpolate(h, scale_factor=2.0, mode="nearest"), f"{p}.upsamplers.0.conv")
+    return rnd(h, dtype) if mode == "fp32" else h
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# attention
+# ----------------------------------------------------------------------------------------------------------------
+def _heads(t, heads):
+    N, S, Cc = t.shape
+    return t.reshape(N, S, heads, Cc // heads).transpose(1, 2)
+
+
+def _unheads(o):
+    N, h, S, d = o.shape
+    return o.transpose(1, 2).reshape(N, S, h * d)
+
+
+def attn_ref64(q, k, v, heads, scale=None):
+    w = torch.softmax(_softmax64(q, k, heads, scale), dim=-1)
+    return _unheads(w @ _heads(v.double(), heads))
+
+
+def attn_base_ref(q, k, v, heads, dtype, scale=None):
+    """fp32 scores, softmax against the TRUE maximum, P rounded to the storage dtype with subnormals, P V in fp32, rounded"""
+    d = q.shape[-1] // heads
+    s = _heads(q.float(), heads) @ _heads(k.float(), heads).transpose(-1, -2) * (scale if scale is not None else 1.0 / math.sqrt(d))
+    p = rnd(torch.softmax(s, dim=-1), dtype)
+    return rnd(_unheads(p @ _heads(v.float(), heads)), dtype)
+
+
+def attn_base_alg(q, k, v, heads, dtype, scale=None, offset=0.0, defect=None, tile=64):
+    """csrc/attention.hip's design: Q pre-multiplied by scale * log2(e) and re-rounded to the storage dtype; P = 2^(s - m) with a
+    reference m that sits `offset` (0 .. LAZY) below the row maximum; the row sum from the fp32 P, P rounded to the storage dtype
+    for the P V product (fp32 accumulation), the quotient rounded once.
+    defects: "flush_p" - P below 2^-14 becomes zero on its way into the product (a conversion or a matrix core that flushes fp16
+    subnormals); "stale_reference" - the reference stays at the FIRST tile's maximum and is never raised, so P overflows the
+    storage dtype's range where later tiles rise."""
+    d = q.shape[-1] // heads
+    sl2 = (scale if scale is not None else 1.0 / math.sqrt(d)) * 1.4426950408889634
+    s = _heads(rnd(q.float() * sl2, dtype), heads) @ _heads(k.float(), heads).transpose(-1, -2)
+    if defect == "stale_reference":
+        m = s[..., :tile].max(dim=-1, keepdim=True).values
+    else:
+        m = s.max(dim=-1, keepdim=True).values - float(offset)
+    p = torch.exp2(s - m)
+    l = p.sum(dim=-1, keepdim=True)
+    if defect == "flush_p":
+        p = torch.where(p < 2.0 ** FP16_NORMAL_MIN_LOG2, torch.zeros_like(p), p)
+    p = rnd(p, dtype)
+    return rnd(_unheads((p @ _heads(v.float(), heads)) / l), dtype)
+
+
+def attn_design_err(q, k, v, heads, dtype, ref64, scale=None):
+    """row_err of the design: the worse of the two ends of the reference's allowed range (at the maximum: small P lowest; LAZY
+    below it: large P highest)"""
+    return max(row_err(attn_base_alg(q, k, v, heads, dtype, scale, offset=o), ref64) for o in (0.0, LAZY))
+
+
+if __name__ == "__main__":
+    import sys
+    if "--attn-child" in sys.argv:
+        from tests import test_numerics_gpu as T
+        T.attention_child(sys.argv[sys.argv.index("--attn-child") + 1:])
+    elif "--report" in sys.argv:
+        from tests import test_numerics_gpu as T
+        rest = [a for a in sys.argv[sys.argv.index("--report") + 1:] if not a.startswith("-")]
+        T.write_report(rest[0] if rest else None)
+    else:
+        print(__doc__)

@@ -535,3 +535,90 @@ def test_big_tile_epilogue_forms():
     assert ok(lib.ACT_NONE, 320, 1, 4096, 1) == 0          # ... not beside a residual
     assert ok(lib.ACT_NONE, 320, 1, 64, 0) == 0            # ... nor when a half spans samples
     assert ok(lib.ACT_SILU, 320, 0, 4096, 0) == 0 and ok(lib.ACT_NONE, 4, 0, 4096, 0) == 0
+
+
+class _DryPlan:
+    """A recording plan in dry mode (es_plan_set_dry(1)): every C-ABI compute call validates its descriptor and records it, and
+    launches nothing - the entry points' checks can be exercised with host buffers, without a GPU."""
+
+    def __enter__(self):
+        self.L = lib.load()
+        self.plan = ctypes.c_void_p(self.L.es_plan_create())
+        assert self.L.es_plan_begin_record(self.plan) == 0
+        self.was = self.L.es_plan_set_dry(1)
+        return self
+
+    def __exit__(self, *a):
+        self.L.es_plan_set_dry(self.was)
+        self.L.es_plan_end_record(self.plan)
+        self.L.es_plan_destroy(self.plan)
+
+    def size(self):
+        return self.L.es_plan_size(self.plan)
+
+
+def test_linear_xs_refuses_a_weight_group_boundary_inside_a_group_norm_sample():
+    """es_linear_xs with GroupNorm in front (gn_part) and several weight groups: a row block takes its statistics from one sample
+    and its gamma / beta / weights from one group, so every group must end on a sample boundary ((mt_end * 128) % gn_hw == 0).
+    Host-side validation, through the dry recorder with host buffers."""
+    buf = (ctypes.c_char * 4096)()
+    p = ctypes.addressof(buf)
+
+    def desc(mt_end, hw):
+        d = lib.XsDesc()
+        d.x = d.out = d.gn_part = p
+        d.M, d.K, d.Cout, d.rows_padded, d.ldo = 8 * 1024, 320, 320, 320, 320
+        d.nslices, d.chunks_per_slice, d.dtype = 1, 5, lib.ES_F16
+        d.gn_groups, d.gn_nchunk, d.gn_hw, d.gn_eps = 32, 4, hw, 1e-6
+        d.ngroups = len(mt_end)
+        for g, e in enumerate(mt_end):
+            d.mt_end[g] = e
+            d.w_g[g] = d.bias_g[g] = d.gn_gamma_g[g] = d.gn_beta_g[g] = p
+        return d
+
+    with _DryPlan() as dry:
+        L = dry.L
+        # 8 samples of 1024 rows; groups of 2 + 6 samples: accepted, recorded, not launched
+        assert L.es_linear_xs(ctypes.byref(desc([16, 64], 1024)), None) == 0 and dry.size() == 1
+        # the first group ends after 1.5 samples (whole 256-row blocks, as the ungrouped check demands): refused, nothing recorded
+        assert L.es_linear_xs(ctypes.byref(desc([12, 64], 1024)), None) == -1
+        assert b"es_linear_xs: gn_part needs weight groups of whole samples" in L.es_last_error()
+        # ... also when a later boundary is the misplaced one
+        assert L.es_linear_xs(ctypes.byref(desc([16, 26, 64], 1024)), None) == -1
+        assert b"whole samples" in L.es_last_error()
+        # samples of 256 rows: every 256-row block boundary is a sample boundary
+        assert L.es_linear_xs(ctypes.byref(desc([12, 26, 64], 256)), None) == 0
+        assert dry.size() == 2
+
+
+def test_conv_gemm_refuses_an_empty_problem_before_it_sizes_the_launch():
+    """es_conv_gemm: N, Hout, Wout, Cout >= 1 are checked BEFORE the launch is sized for the 32-bit buffer offsets (oversize() and the
+    dry launch_in_chunks() divide by the sample size and by Hout * Wout * (rows_padded / 8)): a malformed descriptor returns -1 with
+    a message.  The descriptors below are oversize ones (operand limit lowered) with split-K, the form that reached the divisions."""
+    buf = (ctypes.c_char * 4096)()
+    p = ctypes.addressof(buf)
+
+    def desc(**kw):
+        d = lib.GemmDesc()
+        d.x = d.w = d.out = d.workspace = p
+        d.N, d.Hsrc, d.Wsrc, d.C1 = 4, 16, 16, 1280
+        d.Hout, d.Wout, d.Cout, d.rows_padded, d.Kpad = 16, 16, 1280, 1280, 9 * 1280
+        d.ksize, d.stride, d.pad, d.splitk, d.bn, d.dtype = 3, 1, 1, 2, 128, lib.ES_F16
+        for k, v in kw.items():
+            setattr(d, k, v)
+        return d
+
+    with _DryPlan() as dry:
+        L = dry.L
+        prev = L.es_set_operand_limit(1 << 20)             # 655 KB per sample: the 4-sample launch is cut into single samples
+        try:
+            assert L.es_conv_gemm(ctypes.byref(desc()), None) == 0 and dry.size() == 1
+            for bad in (dict(N=0), dict(Hout=0), dict(Wout=0), dict(Hout=0, Wout=0), dict(N=-1), dict(Cout=0, rows_padded=0)):
+                assert L.es_conv_gemm(ctypes.byref(desc(**bad)), None) == -1, bad
+                assert L.es_last_error() == b"es_conv_gemm: empty problem", (bad, L.es_last_error())
+            # rows_padded is checked against the N tile before anything divides by it, too
+            assert L.es_conv_gemm(ctypes.byref(desc(rows_padded=1284)), None) == -1
+            assert L.es_last_error() == b"es_conv_gemm: bad rows_padded"
+            assert dry.size() == 1                          # a rejected call never enters the plan
+        finally:
+            L.es_set_operand_limit(prev)

@@ -599,42 +599,45 @@ def test_linear_with_folded_layer_norm(dtype):
     from edgestyle_amd import ops
     g = torch.Generator().manual_seed(66)
     tol = 4e-3 if dtype == torch.float16 else 2.5e-2
+    prev_xs = ops.XS_ENABLED
     ops.XS_ENABLED = False                                # this test is about the tiled kernel's fold; linear_xs has its own
-    for M, C, Cout, geglu in [(300, 320, 960, False), (200, 640, 640, False), (257, 320, 2560, True), (130, 1280, 1280, False)]:
-        x = q16(torch.randn(M, C, generator=g) * 1.5 + 0.7 + torch.randn(M, 1, generator=g), dtype)
-        gamma = 1 + 0.2 * torch.randn(C, generator=g)
-        beta = 0.1 * torch.randn(C, generator=g)
-        w = torch.randn(Cout, C, generator=g) / math.sqrt(C)
-        b = torch.randn(Cout, generator=g) * 0.1
-        y = F.linear(F.layer_norm(x, (C,), gamma, beta, 1e-5), w, b)
-        if geglu:
-            h, gate = y.chunk(2, dim=-1)
-            y = h * F.gelu(gate)
-        pw = ops.pack_weight_ln(w, b, gamma, beta, 1e-5, dtype, DEV, geglu=geglu)
-        xd = x.to(DEV, dtype)
-        outs = [ops.linear(xd, pw)]
-        for knob, val in (("FORCE_WAVES", 8), ("FORCE_BN", 64)):
-            if knob == "FORCE_BN" and geglu:
-                continue
-            setattr(ops, knob, val)
-            try:
-                outs.append(ops.linear(xd, pw))
-            finally:
-                setattr(ops, knob, 0)
-        for o in outs:
-            assert rel_err(o, y) < tol, (M, C, Cout, geglu)
-    # grouped: three weight sets with their own LayerNorm parameters over 2 + 4 + 2 samples of 64 tokens... 128-row groups
-    C, Cout, counts = 320, 960, [256, 512, 256]
-    xg = q16(torch.randn(sum(counts), C, generator=g) * 2 + 0.3, dtype)
-    pws, refs, a = [], [], 0
-    for n in counts:
-        gamma, beta = 1 + 0.2 * torch.randn(C, generator=g), 0.1 * torch.randn(C, generator=g)
-        w, b = torch.randn(Cout, C, generator=g) / math.sqrt(C), torch.randn(Cout, generator=g) * 0.1
-        pws.append(ops.pack_weight_ln(w, b, gamma, beta, 1e-5, dtype, DEV))
-        refs.append(F.linear(F.layer_norm(xg[a:a + n], (C,), gamma, beta, 1e-5), w, b))
-        a += n
-    yg = ops.linear(xg.to(DEV, dtype), pws, group_n=counts)
-    ops.XS_ENABLED = True
+    try:
+        for M, C, Cout, geglu in [(300, 320, 960, False), (200, 640, 640, False), (257, 320, 2560, True), (130, 1280, 1280, False)]:
+            x = q16(torch.randn(M, C, generator=g) * 1.5 + 0.7 + torch.randn(M, 1, generator=g), dtype)
+            gamma = 1 + 0.2 * torch.randn(C, generator=g)
+            beta = 0.1 * torch.randn(C, generator=g)
+            w = torch.randn(Cout, C, generator=g) / math.sqrt(C)
+            b = torch.randn(Cout, generator=g) * 0.1
+            y = F.linear(F.layer_norm(x, (C,), gamma, beta, 1e-5), w, b)
+            if geglu:
+                h, gate = y.chunk(2, dim=-1)
+                y = h * F.gelu(gate)
+            pw = ops.pack_weight_ln(w, b, gamma, beta, 1e-5, dtype, DEV, geglu=geglu)
+            xd = x.to(DEV, dtype)
+            outs = [ops.linear(xd, pw)]
+            for knob, val in (("FORCE_WAVES", 8), ("FORCE_BN", 64)):
+                if knob == "FORCE_BN" and geglu:
+                    continue
+                setattr(ops, knob, val)
+                try:
+                    outs.append(ops.linear(xd, pw))
+                finally:
+                    setattr(ops, knob, 0)
+            for o in outs:
+                assert rel_err(o, y) < tol, (M, C, Cout, geglu)
+        # grouped: three weight sets with their own LayerNorm parameters over 2 + 4 + 2 samples of 64 tokens... 128-row groups
+        C, Cout, counts = 320, 960, [256, 512, 256]
+        xg = q16(torch.randn(sum(counts), C, generator=g) * 2 + 0.3, dtype)
+        pws, refs, a = [], [], 0
+        for n in counts:
+            gamma, beta = 1 + 0.2 * torch.randn(C, generator=g), 0.1 * torch.randn(C, generator=g)
+            w, b = torch.randn(Cout, C, generator=g) / math.sqrt(C), torch.randn(Cout, generator=g) * 0.1
+            pws.append(ops.pack_weight_ln(w, b, gamma, beta, 1e-5, dtype, DEV))
+            refs.append(F.linear(F.layer_norm(xg[a:a + n], (C,), gamma, beta, 1e-5), w, b))
+            a += n
+        yg = ops.linear(xg.to(DEV, dtype), pws, group_n=counts)
+    finally:
+        ops.XS_ENABLED = prev_xs
     assert rel_err(yg, torch.cat(refs)) < tol
 
 
@@ -926,92 +929,95 @@ def test_linear_xs_row_stationary_kernel(dtype):
     from edgestyle_amd import ops
     g = torch.Generator().manual_seed(99)
     tol = 4e-3 if dtype == torch.float16 else 2.5e-2
+    prev_min_m = ops.XS_MIN_M
     ops.XS_MIN_M = 0                                      # no size policy here: every instantiation must be exercised
-    cases = [  # M, C, Cout, geglu, ln, bias
-        (57344 // 8, 320, 960, False, True, False),      # to_q|k|v: 28 row blocks x 9 slices
-        (2048, 320, 2560, True, True, True),             # decoder GEGLU: 8 row blocks x 20 slices
-        (1000, 640, 1920, False, True, False),           # ragged M, K = 640
-        (512, 640, 5120, True, True, True),              # K = 640 GEGLU (4 stages per output line)
-        (300, 320, 320, False, False, True),             # proj_in-like plain layer, ragged
-        (256, 640, 640, False, False, True),
-        (40, 320, 1280, True, False, True),              # fewer rows than one wave pair
-    ]
-    for M, C, Cout, geglu, ln, bias in cases:
-        x = q16(torch.randn(M, C, generator=g) * 1.5 + 0.7 + torch.randn(M, 1, generator=g), dtype)
-        gamma = 1 + 0.2 * torch.randn(C, generator=g)
-        beta = 0.1 * torch.randn(C, generator=g)
-        w = torch.randn(Cout, C, generator=g) / math.sqrt(C)
-        b = torch.randn(Cout, generator=g) * 0.1 if bias else None
-        xin = F.layer_norm(x, (C,), gamma, beta, 1e-5) if ln else x
-        y = F.linear(xin, w, b)
-        if geglu:
-            h, gate = y.chunk(2, dim=-1)
-            y = h * F.gelu(gate)
-        if ln:
-            pw = ops.pack_weight_ln(w, b, gamma, beta, 1e-5, dtype, DEV, geglu=geglu)
-        else:
-            pw = ops.pack_weight(w, b, dtype, DEV, geglu=geglu)
-        xd = x.to(DEV, dtype)
-        assert ops.xs_eligible(M, pw, None, None, 1)
-        ops.XS_ENABLED = False
-        try:
-            tiled = ops.linear(xd, pw)
-        finally:
-            ops.XS_ENABLED = True
-        got = ops.linear(xd, pw)
-        assert rel_err(got, y) < tol, (M, C, Cout, geglu, ln, rel_err(got, y))
-        assert rel_err(got, tiled) < tol, (M, C, Cout, geglu, ln)
-    # grouped: four weight sets over [2, 6, 4, 2] x 256 rows (the lockstep encoder's group table), GEGLU
-    C, Cout, counts = 320, 2560, [512, 1536, 1024, 512]
-    xg = q16(torch.randn(sum(counts), C, generator=g) * 2 + 0.3, dtype)
-    pws, refs, a = [], [], 0
-    for n in counts:
-        gamma, beta = 1 + 0.2 * torch.randn(C, generator=g), 0.1 * torch.randn(C, generator=g)
-        w, b = torch.randn(Cout, C, generator=g) / math.sqrt(C), torch.randn(Cout, generator=g) * 0.1
-        pws.append(ops.pack_weight_ln(w, b, gamma, beta, 1e-5, dtype, DEV, geglu=True))
-        hh, gate = F.linear(F.layer_norm(xg[a:a + n], (C,), gamma, beta, 1e-5), w, b).chunk(2, dim=-1)
-        refs.append(hh * F.gelu(gate))
-        a += n
-    yg = ops.linear(xg.to(DEV, dtype), pws, group_n=counts)
-    again = ops.linear(xg.to(DEV, dtype), pws, group_n=counts)
-    assert rel_err(yg, torch.cat(refs)) < tol
-    assert torch.equal(yg, again)                         # deterministic: same launch twice, bit for bit
-    # residual (es_xs_desc.residual; round 4): out = x W^T + bias + residual at K = 320 - Attention.to_out / proj_out of the 64 x 64
-    # level - many stages per workgroup (every counted wait of the steady state), few (the tails), N slices, ragged M, grouped
-    # (M > 32768: one slice per row block - 5 or 20 stages per workgroup, the steady state of the counted waits; below that the N range
-    #  is split and a workgroup runs one or two stages)
-    for M, Cout, counts in ((2048, 320, None), (700, 1280, None), (40, 320, None), (256 * 14, 320, [512, 1536, 1024, 512]), (8192, 640, None),
-                            (40000, 320, None), (33000, 1280, None), (256 * 160, 640, [8192, 16384, 8192, 8192])):
-        x = q16(torch.randn(M, 320, generator=g) * 1.5, dtype)
-        res = q16(torch.randn(M, Cout, generator=g) * 2.0, dtype)
-        ws = [(torch.randn(Cout, 320, generator=g) / math.sqrt(320), torch.randn(Cout, generator=g) * 0.1) for _ in (counts or [M])]
-        pws = [ops.pack_weight(w, b, dtype, DEV) for w, b in ws]
-        rows = counts or [M]
-        ref = torch.cat([F.linear(x[sum(rows[:i]):sum(rows[:i + 1])], w, b) for i, (w, b) in enumerate(ws)]) + res
-        kw = dict(group_n=counts) if counts else {}
-        pw = pws if counts else pws[0]
-        xd, rd = x.to(DEV, dtype), res.to(DEV, dtype)
-        ops.XS_RESIDUAL = False
-        try:
-            tiled = ops.linear(xd, pw, residual=rd, **kw)
-        finally:
-            ops.XS_RESIDUAL = True
-        prof = ops.PROFILE
-        class Rec:                                          # which kernel ran: the profiler hook sees the descriptor kind
-            descs, metas = [], []
-            def next(self, meta):
-                self.metas.append(meta); return None
-        ops.PROFILE = Rec()
-        try:
-            got = ops.linear(xd, pw, residual=rd, **kw)
-            assert ops.PROFILE.metas[-1][3].get("kernel") == "linear_xs" and ops.PROFILE.metas[-1][3]["residual"]
-        finally:
-            ops.PROFILE = prof
-        again = ops.linear(xd, pw, residual=rd, **kw)
-        torch.cuda.synchronize()
-        assert rel_err(got, ref) < tol, (M, Cout, rel_err(got, ref))
-        assert rel_err(got, tiled) < tol and torch.equal(got, again)
-    ops.XS_MIN_M = 8192
+    try:
+        cases = [  # M, C, Cout, geglu, ln, bias
+            (57344 // 8, 320, 960, False, True, False),      # to_q|k|v: 28 row blocks x 9 slices
+            (2048, 320, 2560, True, True, True),             # decoder GEGLU: 8 row blocks x 20 slices
+            (1000, 640, 1920, False, True, False),           # ragged M, K = 640
+            (512, 640, 5120, True, True, True),              # K = 640 GEGLU (4 stages per output line)
+            (300, 320, 320, False, False, True),             # proj_in-like plain layer, ragged
+            (256, 640, 640, False, False, True),
+            (40, 320, 1280, True, False, True),              # fewer rows than one wave pair
+        ]
+        for M, C, Cout, geglu, ln, bias in cases:
+            x = q16(torch.randn(M, C, generator=g) * 1.5 + 0.7 + torch.randn(M, 1, generator=g), dtype)
+            gamma = 1 + 0.2 * torch.randn(C, generator=g)
+            beta = 0.1 * torch.randn(C, generator=g)
+            w = torch.randn(Cout, C, generator=g) / math.sqrt(C)
+            b = torch.randn(Cout, generator=g) * 0.1 if bias else None
+            xin = F.layer_norm(x, (C,), gamma, beta, 1e-5) if ln else x
+            y = F.linear(xin, w, b)
+            if geglu:
+                h, gate = y.chunk(2, dim=-1)
+                y = h * F.gelu(gate)
+            if ln:
+                pw = ops.pack_weight_ln(w, b, gamma, beta, 1e-5, dtype, DEV, geglu=geglu)
+            else:
+                pw = ops.pack_weight(w, b, dtype, DEV, geglu=geglu)
+            xd = x.to(DEV, dtype)
+            assert ops.xs_eligible(M, pw, None, None, 1)
+            ops.XS_ENABLED = False
+            try:
+                tiled = ops.linear(xd, pw)
+            finally:
+                ops.XS_ENABLED = True
+            got = ops.linear(xd, pw)
+            assert rel_err(got, y) < tol, (M, C, Cout, geglu, ln, rel_err(got, y))
+            assert rel_err(got, tiled) < tol, (M, C, Cout, geglu, ln)
+        # grouped: four weight sets over [2, 6, 4, 2] x 256 rows (the lockstep encoder's group table), GEGLU
+        C, Cout, counts = 320, 2560, [512, 1536, 1024, 512]
+        xg = q16(torch.randn(sum(counts), C, generator=g) * 2 + 0.3, dtype)
+        pws, refs, a = [], [], 0
+        for n in counts:
+            gamma, beta = 1 + 0.2 * torch.randn(C, generator=g), 0.1 * torch.randn(C, generator=g)
+            w, b = torch.randn(Cout, C, generator=g) / math.sqrt(C), torch.randn(Cout, generator=g) * 0.1
+            pws.append(ops.pack_weight_ln(w, b, gamma, beta, 1e-5, dtype, DEV, geglu=True))
+            hh, gate = F.linear(F.layer_norm(xg[a:a + n], (C,), gamma, beta, 1e-5), w, b).chunk(2, dim=-1)
+            refs.append(hh * F.gelu(gate))
+            a += n
+        yg = ops.linear(xg.to(DEV, dtype), pws, group_n=counts)
+        again = ops.linear(xg.to(DEV, dtype), pws, group_n=counts)
+        assert rel_err(yg, torch.cat(refs)) < tol
+        assert torch.equal(yg, again)                         # deterministic: same launch twice, bit for bit
+        # residual (es_xs_desc.residual; round 4): out = x W^T + bias + residual at K = 320 - Attention.to_out / proj_out of the 64 x 64
+        # level - many stages per workgroup (every counted wait of the steady state), few (the tails), N slices, ragged M, grouped
+        # (M > 32768: one slice per row block - 5 or 20 stages per workgroup, the steady state of the counted waits; below that the N range
+        #  is split and a workgroup runs one or two stages)
+        for M, Cout, counts in ((2048, 320, None), (700, 1280, None), (40, 320, None), (256 * 14, 320, [512, 1536, 1024, 512]), (8192, 640, None),
+                                (40000, 320, None), (33000, 1280, None), (256 * 160, 640, [8192, 16384, 8192, 8192])):
+            x = q16(torch.randn(M, 320, generator=g) * 1.5, dtype)
+            res = q16(torch.randn(M, Cout, generator=g) * 2.0, dtype)
+            ws = [(torch.randn(Cout, 320, generator=g) / math.sqrt(320), torch.randn(Cout, generator=g) * 0.1) for _ in (counts or [M])]
+            pws = [ops.pack_weight(w, b, dtype, DEV) for w, b in ws]
+            rows = counts or [M]
+            ref = torch.cat([F.linear(x[sum(rows[:i]):sum(rows[:i + 1])], w, b) for i, (w, b) in enumerate(ws)]) + res
+            kw = dict(group_n=counts) if counts else {}
+            pw = pws if counts else pws[0]
+            xd, rd = x.to(DEV, dtype), res.to(DEV, dtype)
+            ops.XS_RESIDUAL = False
+            try:
+                tiled = ops.linear(xd, pw, residual=rd, **kw)
+            finally:
+                ops.XS_RESIDUAL = True
+            prof = ops.PROFILE
+            class Rec:                                          # which kernel ran: the profiler hook sees the descriptor kind
+                descs, metas = [], []
+                def next(self, meta):
+                    self.metas.append(meta); return None
+            ops.PROFILE = Rec()
+            try:
+                got = ops.linear(xd, pw, residual=rd, **kw)
+                assert ops.PROFILE.metas[-1][3].get("kernel") == "linear_xs" and ops.PROFILE.metas[-1][3]["residual"]
+            finally:
+                ops.PROFILE = prof
+            again = ops.linear(xd, pw, residual=rd, **kw)
+            torch.cuda.synchronize()
+            assert rel_err(got, ref) < tol, (M, Cout, rel_err(got, ref))
+            assert rel_err(got, tiled) < tol and torch.equal(got, again)
+    finally:
+        ops.XS_MIN_M = prev_min_m
 
 
 @pytest.mark.parametrize("N,H,C1,C2,Cout,stride,up,Ct,splitk,bn", [
@@ -1285,6 +1291,19 @@ def test_clock_probe_reads_a_plausible_shader_clock():
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
 @pytest.mark.parametrize("C,H,counts", [(320, 32, None), (320, 16, [2, 6, 4, 2]), (640, 32, [16, 8, 8]), (640, 16, None)])
 def test_group_norm_in_front_of_the_row_stationary_projection(dtype, C, H, counts):
+    _gn_in_front_of_the_projection(dtype, C, H, counts, 32)
+
+
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
+@pytest.mark.parametrize("C,G", [(640, 1), (640, 2), (320, 1), (320, 5)])
+def test_group_norm_in_front_of_the_row_stationary_projection_group_counts(dtype, C, G):
+    """... with 1, 2 and 5 GroupNorm groups (640, 320 and 64 channels per group): the fused kernel finds a channel's group with an
+    integer reciprocal, which has to be exact for every (K, groups) es_linear_xs accepts - a 2^16 reciprocal sent channels 637..639 of
+    (640, 1) to a group that does not exist (tests/test_numerics_cpu.py shows on the CPU that this case catches it)."""
+    _gn_in_front_of_the_projection(dtype, C, 32, None, G)
+
+
+def _gn_in_front_of_the_projection(dtype, C, H, counts, G):
     """Transformer2DModel.norm -> proj_in as one read (ops.gn_proj_in: es_group_norm stats_only + es_linear_xs gn_part) against a plain
     fp32 GroupNorm + 1x1 convolution, and against the two-launch path it replaces (same arithmetic up to the rounding of the normalised
     value: the fused form computes x * (rstd gamma) + (beta - mean rstd gamma), the stand-alone one (x - mean) rstd gamma + beta)."""
@@ -1308,22 +1327,22 @@ def test_group_norm_in_front_of_the_row_stationary_projection(dtype, C, H, count
     pws = [ops.pack_weight(w, b, dtype, DEV) for w, b in zip(ws, bs)]
     gd, bd = [t.to(DEV) for t in gam], [t.to(DEV) for t in bet]
     xin = nhwc(xq, dtype)
-    assert ops.gn_fold_ok(N * H * H, H * H, 32, pws[0], pws if counts else None, counts)
+    assert ops.gn_fold_ok(N * H * H, H * H, G, pws[0], pws if counts else None, counts)
     if counts:
-        y = ops.gn_proj_in(xin, gd, bd, 32, 1e-6, pws, group_n=counts)
+        y = ops.gn_proj_in(xin, gd, bd, G, 1e-6, pws, group_n=counts)
     else:
-        y = ops.gn_proj_in(xin, gd[0], bd[0], 32, 1e-6, pws[0])
+        y = ops.gn_proj_in(xin, gd[0], bd[0], G, 1e-6, pws[0])
     old = ops.GN_FOLD
     ops.GN_FOLD = False
     try:
-        y2 = ops.gn_proj_in(xin, gd, bd, 32, 1e-6, pws, group_n=counts) if counts else ops.gn_proj_in(xin, gd[0], bd[0], 32, 1e-6, pws[0])
+        y2 = ops.gn_proj_in(xin, gd, bd, G, 1e-6, pws, group_n=counts) if counts else ops.gn_proj_in(xin, gd[0], bd[0], G, 1e-6, pws[0])
     finally:
         ops.GN_FOLD = old
     torch.cuda.synchronize()
     a = 0
     refs = []
     for i, n in enumerate(counts or [N]):
-        h = F.group_norm(xq[a:a + n], 32, gam[i], bet[i], 1e-6)
+        h = F.group_norm(xq[a:a + n], G, gam[i], bet[i], 1e-6)
         refs.append(F.conv2d(q16(h, dtype), ws[i], bs[i]))
         a += n
     ref = torch.cat(refs, 0)
