@@ -596,13 +596,21 @@ def conv_gemm(x: torch.Tensor, pw: PackedWeight, *, stride: int = 1, pad: Option
     if out is None:
         out = torch.empty((N, Hout, Wout, cstore), dtype=x.dtype, device=x.device)
     M = N * Hout * Wout
+    # the library is handed data_ptr() and the shape: a view with other strides (a channel slice, a transposed map) would be read or
+    # written as if it were dense - refused here, a caller that holds such a view makes it contiguous itself
+    for what, t, numel in (("x", x, None), ("x2", x2, nsrc * H * W * C2), ("residual", residual, M * cstore), ("out", out, M * cstore)):
+        if t is None:
+            continue
+        if not t.is_contiguous():
+            raise L.EdgeStyleHipError(f"conv_gemm: {what} must be contiguous (got shape {tuple(t.shape)}, strides {t.stride()})")
+        if t.dtype != x.dtype or (numel is not None and t.numel() != numel):
+            raise L.EdgeStyleHipError(f"conv_gemm: {what} has {t.numel()} {t.dtype} elements, the launch needs {numel} {x.dtype}")
     # (a residual rides on es_linear_xs at K = 320 - Attention.to_out / proj_out of the 64 x 64 level - unless this launch carries the
     #  two-word residual stream of a bf16 pipeline, which only es_conv_gemm implements)
-    xs_res = residual is None or (XS_RESIDUAL and pw.kpad == 320 and not pw.geglu and pw.ln_colsum is None and residual.is_contiguous()
-                                  and residual.numel() == M * cstore and not (wide and wide_stream(x.dtype)))
+    xs_res = residual is None or (XS_RESIDUAL and pw.kpad == 320 and not pw.geglu and pw.ln_colsum is None
+                                  and not (wide and wide_stream(x.dtype)))
     if (k == 1 and stride == 1 and not upsample and x2 is None and temb is None and xs_res and not tails
             and x_rep == 1 and act == L.ACT_NONE and out_scale == 1.0 and out_scale_dev is None and splitk is None and FORCE_BN == 0
-            and x.is_contiguous() and out.is_contiguous()
             and xs_eligible(M, pw, pws, group_n, Hout * Wout)):
         linear_xs(x.reshape(M, C1), pws if pws is not None else pw, M, out.reshape(M, cstore),
                   None if pws is None else [n * Hout * Wout for n in group_n], residual=residual)

@@ -22,7 +22,11 @@ outlier gain <= 100, peak <= 2e4) also row_err(kernel) <= MARGIN * row_err(base_
 order" from "lost a bit or more" and is not tuned per case.  In the probe tier (ratio 100, 300) only the first bar holds, with
 PROBE_MARGIN = 4: there the error is cancellation noise whose size depends on the order of summation.
 
-`python -m tests.numerics --report` (GPU) runs the cases of test_numerics_gpu.py and writes the measured table to tests/NUMERICS.md.
+The implicit-GEMM convolution has a metric of its own, the misrounded share (`misrounded`, `conv_case`, `conv_ref64`, `conv_base_ref`,
+`conv_base_alg`, further down): an extra rounding inside the launch is invisible to row_err and plain to it.
+
+`python -m tests.numerics --report` (GPU) runs the cases of test_numerics_gpu.py and the convolution sweep of test_conv_gpu.py and writes
+the measured tables to tests/NUMERICS.md (`--only conv`: the convolution table alone).
 """
 import math
 
@@ -579,6 +583,348 @@ def gn_base_alg(c, counts=None, defect=None, stats_from=None):
 
 
 # ----------------------------------------------------------------------------------------------------------------
+# implicit-GEMM convolution (es_conv_gemm): the misrounded share
+# ----------------------------------------------------------------------------------------------------------------
+# With fp32 accumulation and ONE rounding a convolution's output equals the correctly rounded fp64 result except where the fp64 value
+# sits within the accumulation noise of a rounding boundary: 0.1-0.2 % of the elements in fp16, next to none in bf16.  An extra
+# rounding anywhere (split-K slabs stored in the storage dtype, a bias added behind the rounding) moves that share to 25-40 %, while
+# max|y - ref| / max|ref| and row_err move by a factor of under two - the rounding of the output dominates both.  So the convolution
+# is judged by `misrounded`, against a bar that is recomputed from independent fp32 implementations of the same launch.
+MISROUNDED_FLOOR = 100          # elements: the bar where the largest baseline count is under 50 (bf16, small cases)
+CONV_MIN_ELEMENTS = 20000       # a case of this size keeps that floor below 0.5 % - fifty times under what one extra rounding makes
+BM_CONV = 128                   # pixels per workgroup tile of csrc/gemm_conv.hip (the planted tile defects cut here)
+
+
+def round64(ref64: torch.Tensor, dtype) -> torch.Tensor:
+    """ref64 correctly rounded to the storage dtype (returned in fp32).  fp64 -> fp32 -> dtype rounds twice: where the fp32 value sits
+    on a tie of the storage dtype the second rounding cannot know on which side the fp64 value was.  Both neighbours of such a value
+    are formed (the fp32 value as it is, and nudged one fp32 step towards the fp64 value) and the one closer in fp64 is taken."""
+    r = ref64.detach().to("cpu", torch.float64)
+    r32 = r.float()
+    d = r - r32.double()
+    toward = torch.where(d > 0, torch.full_like(r32, float("inf")), torch.full_like(r32, float("-inf")))
+    nudged = torch.where(d == 0, r32, torch.nextafter(r32, toward))
+    h1, h2 = r32.to(dtype).float(), nudged.to(dtype).float()
+    take2 = (h2.double() - r).abs() < (h1.double() - r).abs()
+    return torch.where(take2, h2, h1)
+
+
+def misrounded(y: torch.Tensor, ref64: torch.Tensor, dtype, count: bool = False):
+    """share (count=True: number) of elements with y != ref64 correctly rounded to the storage dtype; a NaN counts as different"""
+    want = round64(ref64, dtype)
+    v = y.detach().to("cpu", torch.float32)
+    assert v.shape == want.shape, (v.shape, want.shape)
+    n = int((v != want).sum())
+    return n if count else n / max(1, want.numel())
+
+
+def differs(y: torch.Tensor, z: torch.Tensor, count: bool = False):
+    """share of elements in which two results in the storage dtype differ (forms with a residual round twice BY DESIGN: they are
+    judged by the share that differs from base_alg, not from the correctly rounded truth)"""
+    a, b = y.detach().to("cpu", torch.float32), z.detach().to("cpu", torch.float32)
+    assert a.shape == b.shape, (a.shape, b.shape)
+    n = int((a != b).sum())
+    return n if count else n / max(1, a.numel())
+
+
+def misrounded_bar(counts) -> int:
+    """largest number of differing elements a launch may show: MARGIN x the largest count among the independent fp32 implementations
+    of the same launch, MISROUNDED_FLOOR elements where that count is under 50"""
+    top = max(counts)
+    return int(math.floor(MARGIN * top)) if top >= 50 else MISROUNDED_FLOOR
+
+
+def conv_out_hw(H, W, k, stride, pad, upsample, out_hw=None):
+    if out_hw is not None:
+        return tuple(out_hw)
+    Hin, Win = (2 * H, 2 * W) if upsample else (H, W)
+    return (Hin + 2 * pad - k) // stride + 1, (Win + 2 * pad - k) // stride + 1
+
+
+def silu_maps(N, C, H, W, ratio, dtype, seed=0, outlier_frac=0.01, outlier_gain=50.0):
+    """post-SiLU activation maps [N, H, W, C] (what every 3x3 convolution of a ResnetBlock2D reads): silu of group_maps at |mean| / std
+    = `ratio` per (sample, group) with 1 % outlier channels at x50, rounded to the storage dtype.  Asserted: the values are those of a
+    SiLU (>= its minimum -0.2785, <= the peak), rounded, and in front of the SiLU the loudest channel's rms is >= 10 x the quietest
+    channel's (group_maps standardises every group: an outlier channel stands x50 over the other channels of ITS group)."""
+    groups = 32 if C % 32 == 0 else (8 if C % 8 == 0 else 1)
+    x = group_maps(N, C, H, groups, ratio, outlier_frac, outlier_gain, 4.0, dtype, seed=seed, W=W)
+    y = rnd(F.silu(x.double()), dtype)
+    assert float(y.min()) >= -0.2785 * (1 + 2.0 ** -7) and float(y.max()) <= 4.0 and torch.equal(y, rnd(y, dtype))
+    if outlier_frac > 0 and C >= 100:
+        top = (x.double().reshape(N, -1, C) - x.double().reshape(N, -1, C).mean(dim=1, keepdim=True)).pow(2).mean(dim=(0, 1)).sqrt()
+        assert float(top.max()) >= 10.0 * float(top.min()), (float(top.max()), float(top.min()))
+    return y
+
+
+def conv_case(N, H, W, C1, Cout, dtype, k=3, stride=1, pad=None, upsample=False, out_hw=None, C2=0, tails=(), temb=False, silu=False,
+              scale=1.0, residual=False, residual_lo=False, bias=True, inputs="randn", weights="randn", seed=0):
+    """One es_conv_gemm launch, everything seeded, NHWC and rounded to the storage dtype (returned in fp32): x [N, H, W, C1] (+ x2 with C2
+    channels, + tail sources [N, Hout, Wout, Ct] of a 1x1 convolution summed in, + temb [N, Cout], + residual and its low word),
+    w [Cout, C1 + C2, k, k], wt [Cout, sum(tails)], b fp32, and the geometry.
+    inputs:  "randn" zero-mean; "silu0" / "silu3" post-SiLU maps (silu_maps at ratio 0 / 3); "near_2^10" activations of magnitude about
+             2^10 with random signs (for weights="subnormal"); "peak" randn scaled so that the largest fp64 OUTPUT lies at 2e4 .. 3e4.
+    weights: "randn" / sqrt(fan-in); "subnormal" every |w| < 2^-14 (fp16 subnormals: a flush to zero returns the bias); "zero".
+    Every postcondition is asserted."""
+    assert (C1 + C2) % 8 == 0 and C1 % 8 == 0, "es_conv_gemm takes channels in multiples of 8 (conv_in is padded 4 -> 8)"
+    g = _gen(seed + 15485863)
+    pad = (1 if k == 3 else 0) if pad is None else pad
+    Hout, Wout = conv_out_hw(H, W, k, stride, pad, upsample, out_hw)
+    Ct, Ctot = sum(tails), C1 + C2
+    if inputs in ("silu0", "silu3"):
+        xa = silu_maps(N, Ctot, H, W, 0 if inputs == "silu0" else 3, dtype, seed=seed)
+    elif inputs == "near_2^10":
+        sgn = torch.where(torch.rand(N, H, W, Ctot, generator=g) < 0.5, -1.0, 1.0)
+        xa = rnd(sgn * 1024.0 * (1 + 0.1 * torch.randn(N, H, W, Ctot, generator=g)), dtype)
+        assert float(xa.abs().min()) > 512.0 and float(xa.abs().max()) < 2048.0
+    else:
+        xa = torch.randn(N, H, W, Ctot, generator=g)
+        xa = rnd(xa - xa.mean(), dtype)
+        assert abs(float(xa.double().mean())) < 1e-3
+    fan = k * k * Ctot + Ct
+    if weights == "subnormal":
+        lim = 2.0 ** FP16_NORMAL_MIN_LOG2
+        mk = lambda *s: rnd(lim * (0.1 + 0.89 * torch.rand(*s, generator=g)) * torch.where(torch.rand(*s, generator=g) < 0.5, -1.0, 1.0), dtype)
+    elif weights == "zero":
+        mk = lambda *s: torch.zeros(*s)
+    else:
+        mk = lambda *s: rnd(torch.randn(*s, generator=g) / math.sqrt(fan), dtype)
+    w = mk(Cout, Ctot, k, k)
+    wt = mk(Cout, Ct) if Ct else None
+    if weights == "subnormal":
+        assert float(w.abs().max()) < 2.0 ** FP16_NORMAL_MIN_LOG2 and float((w != 0).double().mean()) > 0.99
+    c = dict(dtype=dtype, N=N, H=H, W=W, C1=C1, C2=C2, Cout=Cout, k=k, stride=stride, pad=pad, upsample=bool(upsample),
+             out_hw=(Hout, Wout), silu=bool(silu), scale=float(torch.tensor(scale, dtype=torch.float32)),
+             x=xa[..., :C1].contiguous(), x2=xa[..., C1:].contiguous() if C2 else None, w=w, wt=wt,
+             b=(0.1 * torch.randn(Cout, generator=g)) if bias else None,
+             tails=[rnd(torch.randn(N, Hout, Wout, t, generator=g), dtype) for t in tails],
+             temb=rnd(torch.randn(N, Cout, generator=g), dtype) if temb else None, res=None, res_lo=None)
+    if residual:
+        c["res"] = rnd(torch.randn(N, Hout, Wout, Cout, generator=g), dtype)
+        if residual_lo:         # the low word of a value pair: what is left of a sum after its rounding - below half a unit of the high word
+            full = c["res"].double() * (1 + 2.0 ** -9 * torch.randn(N, Hout, Wout, Cout, generator=g, dtype=torch.float64))
+            c["res"] = rnd(full, dtype)
+            c["res_lo"] = rnd(full - c["res"].double(), dtype)
+    if inputs == "peak":
+        for _ in range(3):
+            top = float(conv_ref64(c).abs().max())
+            if 2.2e4 <= top <= 2.8e4:
+                break
+            s = 2.5e4 / top
+            c["x"] = rnd(c["x"] * s, dtype)
+            if C2:
+                c["x2"] = rnd(c["x2"] * s, dtype)
+            c["tails"] = [rnd(t * s, dtype) for t in c["tails"]]
+        top = float(conv_ref64(c).abs().max())
+        assert 2.0e4 <= top <= 3.0e4, top
+    if weights == "subnormal":                  # a flush of the weights would return the bias: the signal must stand clear of it
+        sig = conv_ref64(c) - (c["b"].double() if bias else 0.0)
+        assert float(sig.pow(2).mean().sqrt()) > 0.1, float(sig.pow(2).mean().sqrt())
+    return c
+
+
+def _conv_sources(c, t=lambda v: v):
+    x = t(c["x"]) if c["x2"] is None else torch.cat([t(c["x"]), t(c["x2"])], dim=-1)
+    return x.permute(0, 3, 1, 2)                # NCHW for F.conv2d
+
+
+def _conv_plain(c, t):
+    """the convolution (+ tail 1x1 convolution) without bias or epilogue, NHWC, in t's precision (t = .double() or .float())"""
+    x = _conv_sources(c, t)
+    if c["upsample"]:
+        x = F.interpolate(x, scale_factor=2.0, mode="nearest")
+    Hout, Wout = c["out_hw"]
+    k, s, p = c["k"], c["stride"], c["pad"]
+    need_h, need_w = (Hout - 1) * s + k - x.shape[2] - p, (Wout - 1) * s + k - x.shape[3] - p     # bottom / right padding of an explicit out_hw
+    x = F.pad(x, (p, max(need_w, 0), p, max(need_h, 0)))
+    y = F.conv2d(x, t(c["w"]), None, stride=s)[:, :, :Hout, :Wout]
+    assert y.shape[2:] == (Hout, Wout), (y.shape, c["out_hw"])
+    y = y.permute(0, 2, 3, 1)
+    if c["tails"]:
+        y = y + torch.cat([t(v) for v in c["tails"]], dim=-1) @ t(c["wt"]).t()
+    return y
+
+
+def conv_ref64(c):
+    """the plain operation with the whole epilogue in fp64: ((conv + bias) + temb) -> SiLU -> * scale -> + residual (+ its low word)"""
+    d = lambda v: v.double()
+    y = _conv_plain(c, d)
+    if c["b"] is not None:
+        y = y + d(c["b"])
+    if c["temb"] is not None:
+        y = y + d(c["temb"])[:, None, None, :]
+    if c["silu"]:
+        y = F.silu(y)
+    y = y * c["scale"]
+    if c["res"] is not None:
+        y = y + d(c["res"])
+        if c["res_lo"] is not None:
+            y = y + d(c["res_lo"])
+    return y
+
+
+def conv_torch32(c):
+    """torch's own fp32 convolution with the epilogue in fp32, rounded where the kernel rounds: an independent order of summation"""
+    return conv_epilogue(c, _conv_plain(c, lambda v: v.float()))
+
+
+def conv_base_ref(c):
+    """the textbook fp32 sequence with every op's output rounded to the storage dtype: conv + bias | tail conv | their sum | + temb |
+    SiLU | * scale | + residual.  (The reference has no two-word stream: a low word is added with the residual.)"""
+    dt = c["dtype"]
+    f = lambda v: v.float()
+    keep = dict(c, tails=[], wt=None)
+    y = _conv_plain(keep, f)
+    y = rnd(y + c["b"] if c["b"] is not None else y, dt)
+    if c["tails"]:
+        y = rnd(y + rnd(torch.cat(c["tails"], dim=-1) @ c["wt"].t(), dt), dt)
+    if c["temb"] is not None:
+        y = rnd(y + c["temb"][:, None, None, :], dt)
+    if c["silu"]:
+        y = rnd(F.silu(y), dt)
+    if c["scale"] != 1.0:
+        y = rnd(y * c["scale"], dt)
+    if c["res"] is not None:
+        y = rnd(y + (c["res"] if c["res_lo"] is None else c["res"] + c["res_lo"]), dt)
+    return y
+
+
+def conv_epilogue(c, acc, wide=False, defect=None, temb_rows=None):
+    """csrc/gemm_conv.hip's epilogue on the fp32 accumulators [N, Hout, Wout, Cout]: ((acc + bias) + temb), SiLU, * scale, ROUND, then
+    + residual in fp32 and ROUND AGAIN.  wide: the two-word stream - the fp32 sum over the rounded value, the residual and its low
+    word, stored as hi = round(sum) and lo = round(sum - hi); returns (hi, lo)."""
+    dt = c["dtype"]
+    y = acc.float()
+    late_bias = defect == "late_bias" and c["b"] is not None
+    if c["b"] is not None and not late_bias:
+        y = y + c["b"]
+    if c["temb"] is not None:
+        y = y + (c["temb"][:, None, None, :] if temb_rows is None else temb_rows)
+    if c["silu"]:
+        y = F.silu(y)
+    y = rnd(y * torch.tensor(c["scale"], dtype=torch.float32), dt)
+    if late_bias:
+        y = rnd(y + c["b"], dt)
+    if c["res"] is None:
+        return y
+    s = y + c["res"]
+    if wide:
+        if c["res_lo"] is not None:
+            s = s + c["res_lo"]
+        hi = rnd(s, dt)
+        return hi, rnd(s - hi, dt)
+    return rnd(s, dt)
+
+
+def conv_im2col(c, korder=0, defect=None):
+    """(A [M, K], Wm [Cout, K]) in the kernel's K order: tap-major (ky, kx, c) over the concatenated sources, or chunk-major
+    (c / 64, ky, kx, c % 64) for korder 1, the tail channels last.  Rows are output pixels m = (n, oy, ox); a tap outside the
+    (upsampled) image reads zero.  Geometry defects (planted):
+      "hw_swapped"       the pixel decode divides by Hout where it should divide by Wout
+      "right_tap"        the right-hand tap column (kx = k - 1) is dropped at ox == Wout - 1
+      "wrap_next_sample" a tap below the last row of sample n reads row 0 .. of sample n + 1 (a flat offset with no range check)"""
+    N, H, W, k, s, p = c["N"], c["H"], c["W"], c["k"], c["stride"], c["pad"]
+    Hout, Wout = c["out_hw"]
+    x = c["x"] if c["x2"] is None else torch.cat([c["x"], c["x2"]], dim=-1)
+    up = 1 if c["upsample"] else 0
+    Hin, Win = H << up, W << up
+    Ctot = x.shape[-1]
+    m = torch.arange(N * Hout * Wout)
+    n, rem = m // (Hout * Wout), m % (Hout * Wout)
+    oy, ox = (rem // Wout, rem % Wout) if defect != "hw_swapped" else (rem // Hout, rem % Hout)
+    cols = []
+    for ky in range(k):
+        for kx in range(k):
+            iy, ix = oy * s - p + ky, ox * s - p + kx
+            ok = (iy >= 0) & (iy < Hin) & (ix >= 0) & (ix < Win)
+            nn, yy = n, iy
+            if defect == "wrap_next_sample":
+                wrap = (iy >= Hin) & (ix >= 0) & (ix < Win) & (n + 1 < N)
+                nn, yy = torch.where(wrap, n + 1, n), torch.where(wrap, iy - Hin, iy)
+                ok = ok | wrap
+            if defect == "right_tap" and kx == k - 1:
+                ok = ok & (ox != Wout - 1)
+            v = x[nn.clamp(0, N - 1), (yy >> up).clamp(0, H - 1), (ix >> up).clamp(0, W - 1)]
+            cols.append(torch.where(ok[:, None], v, torch.zeros_like(v)))
+    A = torch.stack(cols, dim=1)                                        # [M, k * k, Ctot]
+    Wm = c["w"].permute(0, 2, 3, 1).reshape(c["Cout"], k * k, Ctot)
+    if korder == 1:
+        assert k == 3 and Ctot % 64 == 0 and c["C1"] % 64 == 0
+        A = A.reshape(-1, k * k, Ctot // 64, 64).permute(0, 2, 1, 3)
+        Wm = Wm.reshape(-1, k * k, Ctot // 64, 64).permute(0, 2, 1, 3)
+    A, Wm = A.reshape(A.shape[0], -1), Wm.reshape(c["Cout"], -1)
+    if c["tails"]:
+        A = torch.cat([A] + [t.reshape(-1, t.shape[-1]) for t in c["tails"]], dim=1)
+        Wm = torch.cat([Wm, c["wt"]], dim=1)
+    return A.contiguous(), Wm.contiguous()
+
+
+def _chain_dot(A, Wm, width):
+    """fp32 accumulators of A Wm^T formed as es_conv_gemm's matrix-core chain forms them (see _chain_sums, "mfma8"): one `width`-wide
+    partial dot product after the other, each taken exactly (fp64) and added with one rounding to fp32.  width 8: what a lane
+    supplies to a 16x16x32 MFMA; width 32: one rounding per instruction - the other reading of the same hardware."""
+    M, K = A.shape
+    pad = (-K) % width
+    if pad:
+        A, Wm = F.pad(A, (0, pad)), F.pad(Wm, (0, pad))
+    G = (K + pad) // width
+    Ad = A.double().reshape(M, G, width).permute(1, 0, 2)
+    Wd = Wm.double().reshape(-1, G, width).permute(1, 2, 0)
+    acc = torch.zeros(M, Wm.shape[0], dtype=torch.float32)
+    for g0 in range(0, G, 64):
+        part = torch.bmm(Ad[g0:g0 + 64], Wd[g0:g0 + 64])
+        for j in range(part.shape[0]):
+            acc = (acc.double() + part[j]).float()
+    return acc
+
+
+def conv_splitk_slices(K, splitk):
+    """[k0, k1) of every split-K slice: the kernel cuts the Kpad / 64 K-steps at floor(nk * z / splitk)"""
+    nk = (K + 63) // 64
+    return [(64 * (nk * z // splitk), min(K, 64 * (nk * (z + 1) // splitk))) for z in range(splitk)]
+
+
+def conv_base_alg(c, chain=8, splitk=1, korder=0, wide=False, defect=None):
+    """The launch as designed, in fp32 on the CPU: im2col in the kernel's K order, chains of `chain`-wide partial dot products, split-K
+    slices cut where the kernel cuts them - each its own fp32 chain, the slabs summed in slice order in fp32 - then the kernel's
+    epilogue (conv_epilogue).  wide: returns (hi, lo) of the two-word stream.
+    Planted defects: conv_im2col's geometry defects, and
+      "rounded_slabs"   the split-K slabs are rounded to the storage dtype before the reduce
+      "late_bias"       the bias is added behind the rounding (and the sum rounded again)
+      "tile_unwritten"  the second 128-pixel tile (the last, if there is one only) is never stored: NaN, as a sentinel-filled output shows it
+      "temb_first_pixel" every pixel of a 128-pixel tile takes the time-embedding row of the tile's FIRST pixel's sample"""
+    dt = c["dtype"]
+    N, (Hout, Wout), Cout = c["N"], c["out_hw"], c["Cout"]
+    A, Wm = conv_im2col(c, korder, defect if defect in ("hw_swapped", "right_tap", "wrap_next_sample") else None)
+    acc = None
+    for k0, k1 in conv_splitk_slices(A.shape[1], splitk):
+        slab = _chain_dot(A[:, k0:k1], Wm[:, k0:k1], chain) if k1 > k0 else torch.zeros(A.shape[0], Cout)
+        if defect == "rounded_slabs":
+            slab = rnd(slab, dt)
+        acc = slab if acc is None else acc + slab
+    temb_rows = None
+    if defect == "temb_first_pixel":
+        m = torch.arange(N * Hout * Wout)
+        first = (m // BM_CONV) * BM_CONV // (Hout * Wout)
+        temb_rows = c["temb"][first].reshape(N, Hout, Wout, Cout)
+    out = conv_epilogue(c, acc.reshape(N, Hout, Wout, Cout), wide, defect, temb_rows)
+    if defect == "tile_unwritten":
+        M = N * Hout * Wout
+        t0 = BM_CONV if M > BM_CONV else 0
+        for o in (out if wide and c["res"] is not None else (out,)):
+            o.reshape(M, Cout)[t0:t0 + BM_CONV] = float("nan")
+    return out
+
+
+def conv_baselines(c, splitk=1, korder=0, wide=False):
+    """name -> result of the independent fp32 implementations of one launch that set the misrounded bar (the GPU test adds the device
+    library's unfold + matmul): base_alg with chains of 8, with chains of 32, torch's fp32 convolution.  wide (with a residual): (hi, lo) pairs."""
+    out = {"alg8": conv_base_alg(c, 8, splitk, korder, wide), "alg32": conv_base_alg(c, 32, splitk, korder, wide)}
+    t = _conv_plain(c, lambda v: v.float())
+    out["torch32"] = conv_epilogue(c, t, wide)
+    return out
+
+
+# ----------------------------------------------------------------------------------------------------------------
 # a VAE-decoder up block: ResnetBlock2D x 3 (GroupNorm -> SiLU -> conv3x3, twice, + x) and nearest 2x upsampling + conv3x3
 # ----------------------------------------------------------------------------------------------------------------
 def vae_up_block(sd, p, x, groups, eps, mode, dtype=None, peaks=None, nres=3):
@@ -685,7 +1031,8 @@ if __name__ == "__main__":
         T.attention_child(sys.argv[sys.argv.index("--attn-child") + 1:])
     elif "--report" in sys.argv:
         from tests import test_numerics_gpu as T
-        rest = [a for a in sys.argv[sys.argv.index("--report") + 1:] if not a.startswith("-")]
-        T.write_report(rest[0] if rest else None)
+        only = sys.argv[sys.argv.index("--only") + 1] if "--only" in sys.argv else None
+        rest = [a for a in sys.argv[sys.argv.index("--report") + 1:] if not a.startswith("-") and a != only]
+        T.write_report(rest[0] if rest else None, only=only)
     else:
         print(__doc__)

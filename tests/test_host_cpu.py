@@ -622,3 +622,33 @@ def test_conv_gemm_refuses_an_empty_problem_before_it_sizes_the_launch():
             assert dry.size() == 1                          # a rejected call never enters the plan
         finally:
             L.es_set_operand_limit(prev)
+
+
+def test_conv_gemm_refuses_operands_that_are_not_dense(monkeypatch):
+    """ops.conv_gemm hands data_ptr() and the shape to the library: a channel slice, a transposed map or an operand of another size
+    or dtype as x, x2, residual or out would be read or written as if it were dense - EdgeStyleHipError, before anything is recorded
+    or launched.  The same call with the views made contiguous goes through (dry recorder, host buffers); a time-embedding table may
+    be a column slice of a wider one (es_gemm_desc.temb_stride), and a slice along the samples is dense."""
+    monkeypatch.setattr(ops, "_stream", lambda: None)
+    g = torch.Generator().manual_seed(0)
+    N, H, W, C1, C2, Cout = 2, 6, 4, 64, 64, 128
+    pw = ops.pack_weight(torch.randn(Cout, C1 + C2, 3, 3, generator=g), torch.randn(Cout, generator=g), torch.float16, "cpu")
+    wide_x = torch.randn(N, H, W, 2 * C1, generator=g).half()
+    wide_o = torch.zeros(N, H, W, 2 * Cout).half()
+    x, x2 = torch.randn(N, H, W, C1, generator=g).half(), torch.randn(N, H, W, C2, generator=g).half()
+    res, temb = torch.randn(N, H, W, Cout, generator=g).half(), torch.randn(N, Cout + 64, generator=g).half()
+    bad = [dict(x=wide_x[..., :C1]), dict(x=torch.randn(N, W, H, C1, generator=g).half().transpose(1, 2)), dict(x2=wide_x[..., C1:]),
+           dict(residual=wide_o[..., :Cout]), dict(out=wide_o[..., Cout:]), dict(residual=res[:1]), dict(out=torch.zeros(N, H, W, Cout)),
+           dict(x2=torch.randn(N, H, W + 1, C2, generator=g).half()[:, :, :W])]
+    with _DryPlan() as dry:
+        for kw in bad:
+            a = dict(x=x, x2=x2, residual=res, out=None, temb=temb[:, 64:])
+            a.update(kw)
+            with pytest.raises(lib.EdgeStyleHipError, match="conv_gemm: (x|x2|residual|out) "):
+                ops.conv_gemm(a.pop("x"), pw, splitk=1, **a)
+            assert dry.size() == 0, kw
+        y = ops.conv_gemm(wide_x[..., :C1].contiguous(), pw, x2=wide_x[..., C1:].contiguous(), residual=wide_o[..., :Cout].contiguous(),
+                          temb=temb[:, 64:], splitk=1)
+        assert dry.size() == 1 and y.shape == (N, H, W, Cout)
+        ops.conv_gemm(x[1:], pw, x2=x2[1:], residual=res[1:], out=wide_o.reshape(2 * N, H, W, Cout)[1:2], splitk=1)
+        assert dry.size() == 2

@@ -215,3 +215,161 @@ def test_planted_stale_softmax_reference_exceeds_the_bar(dtype, step):
     e_alg = nm.attn_design_err(q, k, v, 2, dtype, ref)
     assert math.isfinite(e_alg) and e_alg <= nm.MARGIN * e_ref
     assert nm.row_err(nm.attn_base_alg(q, k, v, 2, dtype, defect="stale_reference"), ref) > _bar(e_alg, e_ref)
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# convolution: the misrounded share
+# ----------------------------------------------------------------------------------------------------------------
+OLD_CONV_TOL = {torch.float16: 3e-3, torch.bfloat16: 2e-2}          # test_ops_gpu.py::test_conv_gemm
+CONV_INPUT_CLASSES = [("randn", "randn"), ("silu0", "randn"), ("silu3", "randn"), ("peak", "randn"), ("near_2^10", "subnormal")]
+
+
+def _conv_counts(c, ref, splitk=1, korder=0, against=None):
+    """name -> number of elements of every independent fp32 implementation that differ from the correctly rounded truth (or, for a
+    form with a residual, from `against` = base_alg)"""
+    dt = c["dtype"]
+    base = nm.conv_baselines(c, splitk, korder)
+    if against is None:
+        return {k: nm.misrounded(v, ref, dt, count=True) for k, v in base.items()}
+    return {k: nm.differs(v, against, count=True) for k, v in base.items() if k != "alg8"}
+
+
+def test_round64_breaks_the_ties_of_a_double_rounding():
+    """1 + 2^-11 + 2^-40 lies ABOVE the fp16 tie between 1 and 1 + 2^-10; fp64 -> fp32 lands on the tie and fp32 -> fp16 rounds it to
+    even, i.e. down.  round64 must round up; exact ties still go to even, and misrounded counts NaN as different."""
+    v = torch.tensor([1 + 2.0 ** -11 + 2.0 ** -40, 1 + 2.0 ** -11 - 2.0 ** -40, 1 + 2.0 ** -11, 1 + 3 * 2.0 ** -11, -(1 + 2.0 ** -11 + 2.0 ** -40)],
+                     dtype=torch.float64)
+    assert float(v[:1].float().half()) == 1.0                                           # the double rounding this guards against
+    assert nm.round64(v, torch.float16).tolist() == [1 + 2.0 ** -10, 1.0, 1.0, 1 + 2.0 ** -9, -(1 + 2.0 ** -10)]
+    y = torch.tensor([1 + 2.0 ** -10, 1.0, float("nan"), 1 + 2.0 ** -9, -1.0])
+    assert nm.misrounded(y, v, torch.float16, count=True) == 2 and nm.misrounded(y, v, torch.float16) == 0.4
+    assert nm.misrounded_bar([3, 49]) == nm.MISROUNDED_FLOOR and nm.misrounded_bar([50, 7]) == 100 and nm.misrounded_bar([400]) == 800
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_conv_generators_and_references_agree_with_each_other(dtype):
+    """conv_im2col (the kernel's K orders, the upsample, stride 2, an explicit out_hw, the concat, tail sources) times the weights in
+    fp64 equals conv_ref64's F.conv2d, for every geometry class of the GPU sweep; the split-K slices tile K"""
+    for kw in [dict(H=5, W=7), dict(H=9, W=12, stride=2), dict(H=10, W=14, stride=2, pad=0, out_hw=(5, 7)), dict(H=3, W=8, upsample=True),
+               dict(H=1, W=37), dict(H=37, W=1), dict(H=13, W=1, k=1), dict(H=1, W=1, k=1), dict(H=6, W=5, C2=64, tails=(64, 128)),
+               dict(H=12, W=10, upsample=True, korder=1), dict(H=9, W=12, stride=2, korder=1, C2=64, tails=(64,))]:
+        kw = dict(kw)
+        korder = kw.pop("korder", 0)
+        c = nm.conv_case(2, kw.pop("H"), kw.pop("W"), 64, 24, dtype, bias=False, seed=3, **kw)
+        A, Wm = nm.conv_im2col(c, korder)
+        want = nm.conv_ref64(c)
+        got = (A.double() @ Wm.double().t()).reshape(want.shape)
+        assert float((got - want).abs().max()) <= 1e-12 * max(1.0, float(want.abs().max())), kw
+    for K, sk in [(576, 1), (576, 3), (704, 5), (2880, 7), (72, 2)]:
+        sl = nm.conv_splitk_slices(K, sk)
+        assert sl[0][0] == 0 and sl[-1][1] == K and all(a[1] == b[0] or (a[1] == K and b[0] >= K) for a, b in zip(sl, sl[1:]))
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_conv_design_is_inside_every_bar(dtype):
+    """base_alg with chains of 8 (the launch as designed) against the bars the GPU test applies, for every input class: its
+    misrounded count within MARGIN x the largest count of the OTHER fp32 implementations (chains of 32, torch's fp32 convolution; the
+    floor of 100 elements where those are under 50), row_err within MARGIN x base_ref, finite wherever the truth is representable -
+    3x3 at K = 2880 with split-K 4, 1x1 at K = 64, and the epilogue forms (with a residual: nothing differs from base_alg by
+    definition; the others' distance to it is what sets the GPU bar)."""
+    shapes = [dict(N=3, H=9, W=12, C1=320, Cout=160, splitk=4), dict(N=3, H=9, W=12, C1=1280, Cout=64, splitk=4),
+              dict(N=3, H=13, W=11, C1=64, Cout=64, k=1, splitk=1)]
+    for inputs, weights in CONV_INPUT_CLASSES:
+        for sh in shapes:
+            sh = dict(sh)
+            sk = sh.pop("splitk")
+            c = nm.conv_case(dtype=dtype, inputs=inputs, weights=weights, seed=11, **sh)
+            ref = nm.conv_ref64(c)
+            assert ref.numel() >= nm.CONV_MIN_ELEMENTS
+            cnt = _conv_counts(c, ref, sk)
+            bar = nm.misrounded_bar([cnt["alg32"], cnt["torch32"]])
+            y = nm.conv_base_alg(c, 8, sk)
+            e, e_ref = nm.row_err(y, ref), nm.row_err(nm.conv_base_ref(c), ref)
+            print(f"conv design {inputs}/{weights} {sh} {dtype}: misrounded " + " ".join(f"{k} {v / ref.numel():.4%}" for k, v in cnt.items())
+                  + f"  bar {bar} elements  row_err {e:.3e} base_ref {e_ref:.3e}")
+            assert cnt["alg8"] <= bar, (inputs, sh, cnt, bar)
+            assert 0 < e <= nm.MARGIN * e_ref and nm.finite_where_representable(y, ref, dtype), (inputs, sh, e, e_ref)
+            if inputs == "peak":
+                assert 2.0e4 <= float(ref.abs().max()) <= 3.0e4 and bool(torch.isfinite(y).all())
+    c = nm.conv_case(3, 9, 12, 128, 192, dtype, C2=64, temb=True, silu=True, scale=0.7, residual=True, seed=12)
+    alg = nm.conv_base_alg(c, 8, 2)
+    cnt = _conv_counts(c, None, 2, against=alg)
+    print(f"conv design +temb +SiLU +scale +residual {dtype}: differing from base_alg " + " ".join(f"{k} {v / alg.numel():.4%}" for k, v in cnt.items()))
+    assert max(cnt.values()) < 0.01 * alg.numel()                   # two legitimate fp32 orders: far below what one extra rounding makes
+    c = nm.conv_case(3, 9, 12, 128, 192, torch.bfloat16, k=1, residual=True, residual_lo=True, seed=13)
+    hi, lo = nm.conv_base_alg(c, 8, 1, wide=True)
+    ref = nm.conv_ref64(c)
+    one = nm.conv_base_alg(c, 8, 1)
+    # the convolution's own value is rounded BEFORE the sum in both forms (the design): the pair saves the second rounding, no more
+    assert 0 < nm.row_err(hi + lo, ref) < nm.row_err(one, ref)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_conv_zero_weights_return_the_rounded_bias_and_subnormal_weights_are_kept(dtype):
+    c = nm.conv_case(3, 9, 12, 64, 96, dtype, weights="zero", seed=14)
+    y = nm.conv_base_alg(c, 8, 3)
+    assert torch.equal(y, nm.rnd(c["b"], dtype).expand_as(y)) and nm.misrounded(y, nm.conv_ref64(c), dtype) == 0
+    c = nm.conv_case(3, 9, 12, 64, 96, dtype, inputs="near_2^10", weights="subnormal", seed=15)
+    ref = nm.conv_ref64(c)
+    cnt = _conv_counts(c, ref)
+    flushed = nm.conv_base_alg(dict(c, w=torch.zeros_like(c["w"])), 8)          # what a flush of fp16 subnormals would return: the bias
+    assert nm.misrounded(flushed, ref, dtype, count=True) > 0.9 * ref.numel() > nm.misrounded_bar(cnt.values())
+    assert nm.row_err(flushed, ref) > _bar(nm.row_err(nm.conv_base_alg(c, 8), ref), nm.row_err(nm.conv_base_ref(c), ref))
+
+
+ROUNDING_DEFECTS = ["rounded_slabs", "late_bias"]
+GEOMETRY_DEFECTS = [  # defect, the case it is planted in
+    ("hw_swapped", dict(N=3, H=9, W=12, C1=64, Cout=96)),                                   # non-square
+    ("right_tap", dict(N=3, H=9, W=12, C1=64, Cout=320, stride=2)),                         # even width, stride 2: tap kx = 2 of the last column reads column W - 1
+    ("wrap_next_sample", dict(N=3, H=9, W=12, C1=64, Cout=96)),
+    ("tile_unwritten", dict(N=3, H=9, W=12, C1=64, Cout=96)),                               # 324 pixels: three tiles
+    ("temb_first_pixel", dict(N=3, H=9, W=12, C1=64, Cout=96, temb=True)),                  # 108 pixels per sample: tiles straddle samples
+]
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("defect", ROUNDING_DEFECTS)
+def test_planted_extra_rounding_in_the_convolution_exceeds_the_misrounded_bar_and_passes_the_old_metric(defect, dtype):
+    """split-K slabs rounded to the storage dtype before the reduce, and the bias added behind the rounding: 25-40 % of the elements
+    leave the correctly rounded value (the bar: under 1 %), while test_conv_gemm's max|y - ref| / max|ref| against torch's fp32
+    convolution PASSES both, and row_err cannot tell them from the design within MARGIN (printed)."""
+    for inputs, weights in CONV_INPUT_CLASSES[:3]:
+        for sh in [dict(N=3, H=9, W=12, C1=320, Cout=160), dict(N=3, H=9, W=12, C1=1280, Cout=64)]:
+            c = nm.conv_case(dtype=dtype, inputs=inputs, weights=weights, seed=21, **sh)
+            ref = nm.conv_ref64(c)
+            cnt = _conv_counts(c, ref, 4)
+            bar = nm.misrounded_bar(cnt.values())
+            bad = nm.conv_base_alg(c, 8, 4, defect=defect)
+            n_bad = nm.misrounded(bad, ref, dtype, count=True)
+            old = nm.old_metric(bad, nm._conv_plain(c, lambda v: v.float()) + c["b"])
+            e_bad, e_alg, e_ref = nm.row_err(bad, ref), nm.row_err(nm.conv_base_alg(c, 8, 4), ref), nm.row_err(nm.conv_base_ref(c), ref)
+            print(f"conv {defect} {inputs} {sh} {dtype}: misrounded {n_bad / ref.numel():.2%} (design "
+                  + " ".join(f"{k} {v / ref.numel():.4%}" for k, v in cnt.items()) + f", bar {bar / ref.numel():.3%})  old metric {old:.2e} "
+                  f"(passes < {OLD_CONV_TOL[dtype]:g})  row_err defect / design {e_bad / e_alg:.2f}")
+            assert n_bad > 10 * bar, (defect, inputs, sh, n_bad, bar)
+            assert old < OLD_CONV_TOL[dtype], (defect, old)
+            assert e_bad <= 1.1 * _bar(e_alg, e_ref)        # ... and the per-row metric does not separate them either: why the share is needed
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("defect,shape", GEOMETRY_DEFECTS, ids=[d for d, _ in GEOMETRY_DEFECTS])
+def test_planted_geometry_defects_in_the_convolution_exceed_the_bars(defect, shape, dtype):
+    """a swapped H / W in the pixel decode, a dropped tap at the right edge, a bottom tap that reads the next sample, a tile that is
+    never stored, a time-embedding row taken per tile where a tile straddles two samples: each is outside the misrounded bar AND
+    outside the row_err bars (or not finite)"""
+    c = nm.conv_case(dtype=dtype, seed=22, **shape)
+    ref = nm.conv_ref64(c)
+    assert ref.numel() >= nm.CONV_MIN_ELEMENTS
+    cnt = _conv_counts(c, ref)
+    bar = nm.misrounded_bar(cnt.values())
+    bad = nm.conv_base_alg(c, 8, defect=defect)
+    n_bad = nm.misrounded(bad, ref, dtype, count=True)
+    e_bad, e_alg, e_ref = nm.row_err(bad, ref), nm.row_err(nm.conv_base_alg(c, 8), ref), nm.row_err(nm.conv_base_ref(c), ref)
+    print(f"conv {defect} {shape} {dtype}: misrounded {n_bad / ref.numel():.2%} (bar {bar / ref.numel():.3%})  row_err {e_bad:.2e} (design {e_alg:.2e})")
+    assert n_bad > bar and n_bad > 0.01 * ref.numel(), (defect, n_bad, bar)
+    assert e_bad > _bar(e_alg, e_ref), (defect, e_bad, e_alg, e_ref)
+    if defect == "tile_unwritten":
+        assert e_bad == float("inf") and nm.BM_CONV * c["Cout"] <= n_bad <= nm.BM_CONV * c["Cout"] + bar
+    if defect == "hw_swapped":                   # ... and invisible on a square image
+        sq = nm.conv_case(dtype=dtype, seed=22, **dict(shape, W=shape["H"]))
+        assert torch.equal(nm.conv_base_alg(sq, 8, defect=defect), nm.conv_base_alg(sq, 8))

@@ -581,13 +581,45 @@ def test_vae_up_block_near_the_fp16_range():
 # ----------------------------------------------------------------------------------------------------------------
 # report
 # ----------------------------------------------------------------------------------------------------------------
-def write_report(path=None):
-    """python -m tests.numerics --report: run every case above without asserting and write the measured table"""
+CONV_MARKER = "<!-- convolution table: everything below this line is written by `python -m tests.numerics --report` -->"
+
+
+def _write_conv_table(f, conv_rows):
+    """the convolution sweep's rows (tests/test_conv_gpu.py): the misrounded share beside the row_err bars"""
+    f.write("\n" + CONV_MARKER + "\n\n")
+    f.write(f"Convolution sweep, measured on {torch.cuda.get_device_name(0)}, torch {torch.__version__}; {len(conv_rows)} launches judged.  "
+            "`differs`: elements that differ from the correctly rounded fp64 result (forms with a residual: from `base_alg`); the bar is "
+            "2 x the largest baseline count, 100 elements where that is under 50.  The device library's unfold + mm was among the baselines "
+            f"of {sum('device' in r['counts'] for r in conv_rows)} of them.\n\n")
+    f.write("| case | elements | kernel differs | share | alg32 | torch32 | device mm | alg8 | bar | kernel / base_alg | kernel / base_ref |\n")
+    f.write("|---|---|---|---|---|---|---|---|---|---|---|\n")
+    for r in conv_rows:
+        n = r["numel"]
+        pct = lambda k: "-" if k not in r["counts"] else f"{r['counts'][k] / n:.3%}"
+        f.write(f"| {r['case']} | {n} | {r['kernel']} | {r['kernel'] / n:.3%} | {pct('alg32')} | {pct('torch32')} | {pct('device')} | {pct('alg8')} | "
+                f"{r['bar']} | {_div(r['kernel_err'], r['base_alg']):.2f} | {_div(r['kernel_err'], r['base_ref']):.2f} |\n")
+
+
+def write_report(path=None, only=None):
+    """python -m tests.numerics --report [--only conv]: run every case above and the convolution sweep of tests/test_conv_gpu.py
+    without asserting and write the measured tables (--only conv: the convolution table alone, the other is kept as it is)"""
     global RECORD
     import tempfile
     import pathlib
     assert torch.cuda.is_available(), "the report is measured on the GPU"
+    doc = os.path.join(ROOT, "tests", "NUMERICS.md")
     RECORD = []
+    if only == "conv":
+        from tests import test_conv_gpu as CV
+        conv_rows = CV.report_rows()
+        RECORD = None
+        text = open(doc).read().split(CONV_MARKER)[0].rstrip("\n") + "\n"
+        path = path or doc
+        with open(path, "w") as f:
+            f.write(text)
+            _write_conv_table(f, conv_rows)
+        print(f"{len(conv_rows)} convolution launches -> {path}")
+        return
     for C in (320, 640, 1280):
         for dt in DTYPES:
             test_layer_norm_fold_at_trained_statistics(C, dt)
@@ -611,8 +643,10 @@ def write_report(path=None):
             for dt in DTYPES:
                 test_transformer_block_with_outlier_channels(C, heads, H, ffo, dt)
     test_vae_up_block_near_the_fp16_range()
-    rows, RECORD = RECORD, None
-    doc = os.path.join(ROOT, "tests", "NUMERICS.md")
+    rows = list(RECORD)
+    from tests import test_conv_gpu as CV
+    conv_rows = CV.report_rows()
+    RECORD = None
     marker = "<!-- measured table: everything below this line is written by `python -m tests.numerics --report` -->"
     head = open(doc).read().split(marker)[0] if os.path.exists(doc) else "# Numerics at trained-model statistics\n\n"
     try:
@@ -631,4 +665,5 @@ def write_report(path=None):
             f.write(f"| {r['case']} | {r['tier']} | {r['kernel']:.2e} | {r['kernel_rms']:.2e} | {'-' if alg is None else format(alg, '.2e')} | "
                     f"{r['base_ref']:.2e} | {'-' if alg is None else format(_div(r['kernel'], alg), '.2f')} | {_div(r['kernel'], r['base_ref']):.2f} | "
                     f"{'yes' if r['finite'] else 'NO'} |\n")
-    print(f"{len(rows)} cases -> {path}")
+        _write_conv_table(f, conv_rows)
+    print(f"{len(rows)} cases, {len(conv_rows)} convolution launches -> {path}")
