@@ -1009,11 +1009,58 @@ def gather_row(table: torch.Tensor, idx: torch.Tensor, out: torch.Tensor):
 
 
 _fusion_scratch = {}
+_FUSION_PLANES = (("g1", 3), ("be1", 3), ("g2", 1), ("be2", 1))
+_FUSION_VECTORS = (("w1", 6), ("b1", 3), ("w2", 3), ("b2", 1), ("w3", 1), ("b3", 1))
+
+
+def _fusion_check(res, res_bs, params: dict, N: int, HW: int, Cc: int, scales_dev, out, addend=None):
+    """The library gets data_ptr()s, N, HW, C and six batch strides: everything it will read or write is checked here, before a
+    descriptor exists.  A residual may be a view into a batched buffer ([n >= N, ...] with any batch stride >= HW * C); inside a
+    sample it is dense."""
+    def refuse(msg):
+        raise L.EdgeStyleHipError("fusion_block: " + msg)
+    if len(res) != 6 or len(res_bs) != 6:
+        refuse("six residuals and six batch strides")
+    if N < 1 or HW < 1 or Cc < 8 or Cc % 8:
+        refuse(f"N {N}, HW {HW}, C {Cc}: C must be a positive multiple of 8")
+    dt, per = res[0].dtype, HW * Cc
+    if dt not in _DT:
+        refuse(f"residual dtype {dt} (fp16 or bf16)")
+    for i, (t, bs) in enumerate(zip(res, res_bs)):
+        name = f"residual {i} "
+        if t.dtype != dt:
+            refuse(name + f"has dtype {t.dtype}, residual 0 has {dt}")
+        if t.dim() < 2 or t.shape[0] < 1 or t[0].numel() != per or not t[0].is_contiguous():
+            refuse(name + f"of shape {tuple(t.shape)}, strides {tuple(t.stride())} is not dense [n, HW * C = {per}] inside a sample")
+        bs = int(bs)
+        if bs < per:
+            refuse(name + f"batch stride {bs} < HW * C = {per}")
+        if bs % 8 or t.data_ptr() % 16:
+            refuse(name + f"is read in 16-byte pieces: batch stride {bs} must be a multiple of 8 elements, the address of 16 bytes")
+        if t.shape[0] > 1 and bs != t.stride(0):
+            refuse(name + f"batch stride {bs} is not the view's ({t.stride(0)})")
+        if (t.shape[0] - 1) * (t.stride(0) if t.shape[0] > 1 else 0) + per < (N - 1) * bs + per:
+            refuse(name + f"holds {t.shape[0]} samples at stride {t.stride(0)}: fewer than (N - 1) * {bs} + {per} elements")
+    for name, k in _FUSION_PLANES:
+        t = params[name]
+        if t.dtype != dt or t.numel() != per * k or not t.is_contiguous():
+            refuse(f"{name} must be a contiguous {dt} plane of HW * C * {k} = {per * k} values (got {t.dtype}, {t.numel()})")
+    for name, k in _FUSION_VECTORS:
+        t = params[name]
+        if t.dtype != torch.float32 or t.numel() != Cc * k or not t.is_contiguous():
+            refuse(f"{name} must hold C * {k} = {Cc * k} contiguous fp32 values (got {t.dtype}, {t.numel()})")
+    for name, t in (("out", out), ("addend", addend)):
+        if t is not None and (t.numel() != N * per or not t.is_contiguous() or t.dtype != dt
+                              or (name == "out" and tuple(t.shape) != (N, HW, Cc))):
+            refuse(f"{name} must be a contiguous [N, HW, C] tensor of the compute dtype (got {tuple(t.shape)}, {t.dtype})")
+    if scales_dev is not None and (scales_dev.dtype != torch.float32 or scales_dev.numel() < 6 or not scales_dev.is_contiguous()):
+        refuse("scales_dev must hold 6 contiguous fp32 values")
 
 
 def _fusion_desc(res, res_bs, params: dict, N: int, HW: int, Cc: int, scales, scales_dev, out, eps, slot: int,
                  addend: Optional[torch.Tensor] = None):
     t0 = res[0]
+    _fusion_check(res, res_bs, params, N, HW, Cc, scales_dev, out, addend)
     key = (t0.device, N, slot)
     sc = _fusion_scratch.get(key)
     if sc is None:
@@ -1033,8 +1080,6 @@ def _fusion_desc(res, res_bs, params: dict, N: int, HW: int, Cc: int, scales, sc
     d.scratch, d.u, d.out = sc.data_ptr(), u.data_ptr(), out.data_ptr()
     d.N, d.HW, d.C, d.eps, d.dtype = N, HW, Cc, eps, _dt(t0)
     if addend is not None:
-        if addend.numel() != N * HW * Cc or not addend.is_contiguous() or addend.dtype != t0.dtype:
-            raise L.EdgeStyleHipError("fusion addend must be a contiguous [N,HW,C] tensor of the compute dtype")
         d.addend = addend.data_ptr()
     return d, u, out
 
@@ -1052,6 +1097,8 @@ def fusion_blocks(blocks, N: int, scales, scales_dev=None, eps: float = 1e-5, ad
     fusion_block; returns the list of [N,HW,Cc] outputs.  addends: optional list of [N,HW,Cc] tensors added to the
     outputs (the UNet skip tensors: saves the 13 separate adds of PL:500-510)."""
     keep, outs = [], []
+    for k, (res, res_bs, params, HW, Cc) in enumerate(blocks):       # all of them before the first launch
+        _fusion_check(res, res_bs, params, N, HW, Cc, scales_dev, None, None if addends is None else addends[k])
     for k0 in range(0, len(blocks), L.FUSION_MAX_BATCH):
         part = blocks[k0:k0 + L.FUSION_MAX_BATCH]
         arr = (L.FusionDesc * len(part))()

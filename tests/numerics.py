@@ -26,7 +26,11 @@ The implicit-GEMM convolution has a metric of its own, the misrounded share (`mi
 `conv_base_alg`, further down): an extra rounding inside the launch is invisible to row_err and plain to it.
 
 `python -m tests.numerics --report` (GPU) runs the cases of test_numerics_gpu.py and the convolution sweep of test_conv_gpu.py and writes
-the measured tables to tests/NUMERICS.md (`--only conv`: the convolution table alone).
+the measured tables to tests/NUMERICS.md (`--only conv`: the convolution table alone; `--only fusion`, `--only sampler`: the sweep of
+test_fusion_gpu.py or the trajectories of test_sampler_gpu.py alone).
+
+The fusion block (`fusion_case`, `fusion_ref64`, `fusion_base_ref`, `fusion_base_alg`, `fusion_grids`; judged per SAMPLE, `sample_err`) and the
+sampler step (`unipc_apply`, `ddim_apply`, `run_trajectory`, `traj_err`) have sections of their own at the end.
 """
 import math
 
@@ -1022,6 +1026,417 @@ def attn_design_err(q, k, v, heads, dtype, ref64, scale=None):
     """row_err of the design: the worse of the two ends of the reference's allowed range (at the maximum: small P lowest; LAZY
     below it: large P highest)"""
     return max(row_err(attn_base_alg(q, k, v, heads, dtype, scale, offset=o), ref64) for o in (0.0, LAZY))
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# the fusion block (csrc/fusion.hip): interleave + ControlNetBlock, judged per SAMPLE against fp64
+# ----------------------------------------------------------------------------------------------------------------
+# Layouts are the kernel's: residuals [N, HW, C] (NHWC), w1 [C, 3, 2], b1 [C, 3], g1 / be1 [HW, C, 3], w2 [C, 3], b2 [C], g2 / be2
+# [HW, C], w3 / b3 [C] - what ops.pack_fusion_params makes of a ControlNetBlock's state dict (fusion_state_dict is its inverse).
+FU_MAX_CHUNK = 256              # csrc/fusion.hip: partial sums per sample (workgroups of passes A and B)
+FU_MAX_CB = 512                 # ... workgroups of pass C
+FUSION_KINDS = ("randn",) + tuple(f"ratio_{r}" for r in REQUIRED_RATIOS + PROBE_RATIOS) + \
+    ("outliers", "loud_net", "gated_off", "constant", "u_offset_10", "u_offset_30")
+FUSION_DEFECTS = ("stale_column", "partials_past_64", "scale_behind_bias", "count_c_hw", "variance_unclamped", "sample_stride_dense")
+
+
+def fusion_kind_required(kind) -> bool:
+    return not (kind.startswith("ratio_") and int(kind[6:]) in PROBE_RATIOS)
+
+
+def fusion_grids(C, HW):
+    """(nchunk, cb): the workgroups per sample of passes A / B and of pass C - a Python mirror of fusion_grids() in csrc/fusion.hip"""
+    ch8 = C // 8
+    items = HW * ch8
+    q = ch8 // math.gcd(ch8, 256)
+
+    def pick(want, cap):
+        n = (want // q) * q
+        if n < q:
+            n = q
+        while n > cap:
+            n -= q
+        return n if n >= 1 else (1 if want < 1 else min(want, cap))
+    return pick(items // 2048, FU_MAX_CHUNK), pick(items // 1024, FU_MAX_CB)
+
+
+def fusion_fixed_column(C, nb) -> bool:
+    """a thread of a pass with nb workgroups per sample keeps one 8-channel column (its parameters are loaded once)"""
+    return (nb * 256) % (C // 8) == 0
+
+
+def _fusion_z64(res, scales, w1, b1):
+    """[N, HW, C, 3] fp64: the first grouped convolution on the scaled residuals"""
+    r = [t.double() * float(s) for t, s in zip(res, scales)]
+    w, b = w1.double(), b1.double()
+    return torch.stack([w[:, q, 0] * r[2 * q] + w[:, q, 1] * r[2 * q + 1] + b[:, q] for q in range(3)], dim=-1)
+
+
+def _fusion_u64(z, p, eps):
+    N = z.shape[0]
+    mean = z.reshape(N, -1).mean(dim=1).reshape(N, 1, 1, 1)
+    var = z.reshape(N, -1).var(dim=1, unbiased=False).reshape(N, 1, 1, 1)
+    y = F.silu((z - mean) / torch.sqrt(var + eps) * p["g1"].double() + p["be1"].double())
+    return (y * p["w2"].double()).sum(dim=-1) + p["b2"].double()
+
+
+def fusion_case(N, C, HW, dtype, kind="randn", scales=(1.0, 0.5, 1.0, 2.0, 1.0, 0.0), seed=0, addend=False, eps=1e-5):
+    """One es_fusion_block launch, seeded: dict with `res` (six [N, HW, C] residuals, rounded to the storage dtype, fp32), `params` (the
+    ten parameter tensors in the kernel's storage: w1 b1 w2 b2 w3 b3 fp32, the four affine planes rounded to `dtype`, in
+    ops.pack_fusion_params' layout), `scales` (six fp32-exact host scales), `addend` ([N, HW, C] or None).  kind (FUSION_KINDS):
+      randn          zero-mean residuals, small biases
+      ratio_r        the fp64 LayerNorm-1 input z of EVERY sample has |mean| / std = r over its 3 C HW values (asserted, ratio_tolerance)
+      outliers       1 % of the channels (at least one) at 50 .. 100 times the spread of the rest, in all six nets
+      loud_net       net 3 at 2e3, the others at 1
+      gated_off      all scales 0: z == b1[c, q] - a variance that is small and not 0
+      constant       scales 0 and b1 == 0: variance exactly 0, the output depends on the planes alone
+      u_offset_r     second_conv bias such that the fp64 LayerNorm-2 input u has |mean| / std = r (10, 30)"""
+    assert kind in FUSION_KINDS and C % 8 == 0, kind
+    g = _gen(seed + 32452843)
+    f32 = lambda t: t.to(torch.float32)
+    scales = [float(torch.tensor(s, dtype=torch.float32)) for s in scales]
+    res = [torch.randn(N, HW, C, generator=g, dtype=torch.float64) for _ in range(6)]
+    p = dict(w1=f32(0.7 * torch.randn(C, 3, 2, generator=g)), b1=f32(0.1 * torch.randn(C, 3, generator=g)),
+             g1=rnd(1 + 0.1 * torch.randn(HW, C, 3, generator=g), dtype), be1=rnd(0.1 * torch.randn(HW, C, 3, generator=g), dtype),
+             w2=f32(0.6 * torch.randn(C, 3, generator=g)), b2=f32(0.1 * torch.randn(C, generator=g)),
+             g2=rnd(1 + 0.1 * torch.randn(HW, C, generator=g), dtype), be2=rnd(0.1 * torch.randn(HW, C, generator=g), dtype),
+             w3=f32(torch.randn(C, generator=g)), b3=f32(0.1 * torch.randn(C, generator=g)))
+    if kind == "outliers":
+        gains = _outlier_gains(C, max(0.01, 1.0 / C), (50.0, 100.0), g)
+        assert int((gains > 1).sum()) == max(1, int(round(0.01 * C)))
+        res = [t * gains * (8.0 / 100.0) for t in res]                 # the quiet channels at 0.08, the loud ones at 4 .. 8
+    if kind == "loud_net":
+        res[3] = res[3] * 2.0e3
+    if kind in ("gated_off", "constant"):
+        scales = [0.0] * 6
+    if kind == "constant":
+        p["b1"] = torch.zeros(C, 3)
+    res = [rnd(t, dtype) for t in res]
+    if kind.startswith("ratio_"):
+        ratio = int(kind[6:])
+        z = _fusion_z64(res, scales, p["w1"], p["b1"]).reshape(N, -1)
+        shift = ratio * float(z.std(dim=1, unbiased=False).mean()) - float(z.mean())
+        p["b1"] = f32(p["b1"].double() + (shift if seed % 2 == 0 else -shift - 2 * float(z.mean())))
+        r = measured_ratio(_fusion_z64(res, scales, p["w1"], p["b1"]).reshape(N, -1))
+        tol = ratio_tolerance(ratio, dtype)
+        if ratio == 0:
+            assert float(r.max()) < 0.05, float(r.max())
+        else:
+            assert float(r.min()) >= ratio * (1 - tol) and float(r.max()) <= ratio * (1 + tol), (ratio, float(r.min()), float(r.max()))
+    if kind.startswith("u_offset_"):
+        ratio = int(kind[9:])
+        u = _fusion_u64(_fusion_z64(res, scales, p["w1"], p["b1"]), p, eps).reshape(N, -1)
+        p["b2"] = f32(p["b2"].double() + ratio * float(u.std(dim=1, unbiased=False).mean()) - float(u.mean()))
+        r = measured_ratio(_fusion_u64(_fusion_z64(res, scales, p["w1"], p["b1"]), p, eps).reshape(N, -1))
+        assert float(r.min()) >= ratio * 0.9 and float(r.max()) <= ratio * 1.1, (ratio, float(r.min()), float(r.max()))
+    c = dict(N=N, C=C, HW=HW, dtype=dtype, kind=kind, eps=eps, res=res, params=p, scales=scales,
+             addend=rnd(torch.randn(N, HW, C, generator=g), dtype) if addend else None)
+    z = _fusion_z64(res, scales, p["w1"], p["b1"]).reshape(N, -1)
+    var = z.var(dim=1, unbiased=False)
+    if kind == "gated_off":
+        assert torch.equal(z.reshape(N, HW, C, 3)[0, 0], p["b1"].double()) and 0 < float(var.max()) < 0.1
+    if kind == "constant":
+        assert float(z.abs().max()) == 0.0
+    if kind == "loud_net":
+        assert 5.0e2 < float(res[3].pow(2).mean().sqrt()) < 8.0e3 and float(res[2].pow(2).mean().sqrt()) < 4.0     # (8 values at the smallest shape)
+    if kind == "outliers":
+        rms = res[0].double().pow(2).mean(dim=(0, 1)).sqrt()
+        assert float(rms.max()) >= 30.0 * float(rms.median()) or C < 100
+    assert all(bool(torch.isfinite(t).all()) and torch.equal(t, rnd(t, dtype)) for t in res)
+    assert all(torch.equal(p[k], rnd(p[k], dtype)) for k in ("g1", "be1", "g2", "be2"))
+    return c
+
+
+def fusion_state_dict(c, prefix, H, W):
+    """the ControlNetBlock state dict (fp64) that ops.pack_fusion_params packs into c["params"]"""
+    p, C = {k: v.double() for k, v in c["params"].items()}, c["C"]
+    assert H * W == c["HW"]
+    return {f"{prefix}.first_conv.weight": p["w1"].reshape(3 * C, 2, 1, 1), f"{prefix}.first_conv.bias": p["b1"].reshape(3 * C),
+            f"{prefix}.first_normalization.weight": p["g1"].permute(1, 2, 0).reshape(3 * C, H, W),
+            f"{prefix}.first_normalization.bias": p["be1"].permute(1, 2, 0).reshape(3 * C, H, W),
+            f"{prefix}.second_conv.weight": p["w2"].reshape(C, 3, 1, 1), f"{prefix}.second_conv.bias": p["b2"],
+            f"{prefix}.second_normalization.weight": p["g2"].permute(1, 0).reshape(C, H, W),
+            f"{prefix}.second_normalization.bias": p["be2"].permute(1, 0).reshape(C, H, W),
+            f"{prefix}.third_conv.weight": p["w3"].reshape(C, 1, 1, 1), f"{prefix}.third_conv.bias": p["b3"]}
+
+
+def _fusion_scales(c, scales_dev=None):
+    """the six effective scales: host scale x device scale (both fp32 values; their product is taken exactly)"""
+    return [s * (1.0 if scales_dev is None else float(scales_dev[i])) for i, s in enumerate(c["scales"])]
+
+
+def fusion_ref64(c, scales_dev=None):
+    """the plain operation in fp64, [N, HW, C]: interleave, three grouped 1x1 convolutions, two LayerNorms over the whole sample with
+    affine planes, SiLU (+ the addend)"""
+    p, N, eps = c["params"], c["N"], c["eps"]
+    u = _fusion_u64(_fusion_z64(c["res"], _fusion_scales(c, scales_dev), p["w1"], p["b1"]), p, eps)
+    mean = u.reshape(N, -1).mean(dim=1).reshape(N, 1, 1)
+    var = u.reshape(N, -1).var(dim=1, unbiased=False).reshape(N, 1, 1)
+    v = F.silu((u - mean) / torch.sqrt(var + eps) * p["g2"].double() + p["be2"].double())
+    out = v * p["w3"].double() + p["b3"].double()
+    return out if c["addend"] is None else out + c["addend"].double()
+
+
+def fusion_base_ref(c, scales_dev=None):
+    """the textbook fp32 sequence with every op's output rounded to the storage dtype: scaled residuals | first_conv | LayerNorm
+    (two-pass) | SiLU | second_conv | LayerNorm | SiLU | third_conv | + addend"""
+    p, N, eps, dt = c["params"], c["N"], c["eps"], c["dtype"]
+    sc = _fusion_scales(c, scales_dev)
+    r = [rnd(t * torch.tensor(s, dtype=torch.float32), dt) for t, s in zip(c["res"], sc)]
+    z = rnd(torch.stack([p["w1"][:, q, 0] * r[2 * q] + p["w1"][:, q, 1] * r[2 * q + 1] + p["b1"][:, q] for q in range(3)], dim=-1), dt)
+
+    def ln(t, gam, bet):
+        flat = t.reshape(N, -1)
+        mean = flat.mean(dim=1).reshape([N] + [1] * (t.dim() - 1))
+        var = ((t - mean) ** 2).reshape(N, -1).mean(dim=1).reshape(mean.shape)
+        return rnd((t - mean) * torch.rsqrt(var + eps) * gam + bet, dt)
+    y = rnd(F.silu(ln(z, p["g1"], p["be1"])), dt)
+    u = rnd((y * p["w2"]).sum(dim=-1) + p["b2"], dt)
+    v = rnd(F.silu(ln(u, p["g2"], p["be2"])), dt)
+    out = rnd(v * p["w3"] + p["b3"], dt)
+    return out if c["addend"] is None else rnd(out + c["addend"], dt)
+
+
+def _wave_tree(t):
+    """wave_sum of common.h over the last dimension (64 lanes): neighbours first, then quads, eights, ... - every level rounded to fp32"""
+    while t.shape[-1] > 1:
+        t = t.reshape(*t.shape[:-1], t.shape[-1] // 2, 2)
+        t = t[..., 0] + t[..., 1]
+    return t[..., 0]
+
+
+def fusion_sums(v, nb, drop_from=None):
+    """fp32 (sum, sum of squares) per sample of v [N, items, k] as csrc/fusion.hip forms them with nb workgroups per sample, in three
+    levels: a thread's chain over its items (stride nb * 256) and the k values of each in order (s += v; ss = fma(v, v, ss)), the
+    workgroup (wave_sum, then the four waves in order), the nb partials (reduce_partials: lane l chains partials l, l + 64, ..., then
+    wave_sum).  drop_from (a planted defect): the partials from that index on are never read."""
+    N, items, k = v.shape
+    stride = nb * 256
+    J = (items + stride - 1) // stride
+    if J * stride != items:
+        v = torch.cat([v, torch.zeros(N, J * stride - items, k)], dim=1)
+    v = v.float().reshape(N, J, stride, k)
+    s, ss = torch.zeros(N, stride), torch.zeros(N, stride)
+    for j in range(J):
+        for e in range(k):
+            t = v[:, j, :, e]
+            s = s + t
+            ss = (ss.double() + t.double() * t.double()).float()
+    out = []
+    for t in (s, ss):
+        w = _wave_tree(t.reshape(N, nb, 4, 64))
+        part = ((w[..., 0] + w[..., 1]) + w[..., 2]) + w[..., 3]                                # [N, nb]
+        if drop_from is not None:
+            part = part[:, :drop_from]
+        lanes = torch.cat([part, torch.zeros(N, 256 - part.shape[1])], dim=1).reshape(N, 4, 64)
+        acc = lanes[:, 0]
+        for j in range(1, 4):
+            acc = acc + lanes[:, j]
+        out.append(_wave_tree(acc))
+    return out[0], out[1]
+
+
+def _fusion_stats(v, nb, cnt, eps, defect):
+    s, ss = fusion_sums(v, nb, drop_from=64 if defect == "partials_past_64" else None)
+    cnt = torch.tensor(float(cnt), dtype=torch.float32)
+    mean = s / cnt
+    var = ((ss / cnt).double() - mean.double() * mean.double()).float()                         # fma(-mean, mean, ss / cnt)
+    if defect != "variance_unclamped":
+        var = var.clamp_min(0.0)
+    return mean, torch.rsqrt(var + eps)
+
+
+def _fusion_columns(t, C, items, nb, stale):
+    """the per-channel parameter t [C, ...] as every 8-channel item sees it, [HW, C, ...]: its own column, or (stale) the column of
+    the FIRST item of the thread that handles it with nb workgroups per sample"""
+    ch8 = C // 8
+    i = torch.arange(items)
+    col = ((i % (nb * 256)) % ch8) if stale else (i % ch8)
+    ch = (col[:, None] * 8 + torch.arange(8)[None, :]).reshape(items // ch8, C)
+    return t[ch]
+
+
+def fusion_base_alg(c, nchunk=None, cb=None, defect=None, scales_dev=None, layout=None, want_u=False):
+    """csrc/fusion.hip as designed, in fp32 on the CPU: r * (scale * scale_dev) first; z = w1[0] r0 + w1[1] r1 + b1; one-pass sums in
+    the kernel's three levels (fusion_sums: a thread's items at stride nchunk * 256, its 24 values in (q, e) order); mean = s / cnt,
+    var = ss / cnt - mean^2 clamped at 0; u = b2 + sum_q w2 y_q rounded to the storage dtype; the statistics of the ROUNDED u;
+    w3 v + b3 rounded; with an addend a second rounding.  nchunk, cb: the grids (default: fusion_grids).
+    layout: [(flat buffer, offset, batch stride)] x 6 - where the residuals sit in memory (for "sample_stride_dense").
+    Planted defects (FUSION_DEFECTS):
+      stale_column        a thread keeps the parameter column of its first item (wrong wherever nb * 256 is no multiple of C / 8)
+      partials_past_64    reduce_partials reads the first 64 partial sums only
+      scale_behind_bias   the second net's scale of every pair multiplies w r + b1 instead of r
+      count_c_hw          LayerNorm 1 divides by C HW instead of 3 C HW
+      variance_unclamped  a negative one-pass variance is not clamped
+      sample_stride_dense sample n of every net is read at n HW C instead of n * res_bs"""
+    assert defect is None or defect in FUSION_DEFECTS, defect
+    p, N, C, HW, eps, dt = c["params"], c["N"], c["C"], c["HW"], c["eps"], c["dtype"]
+    g_n, g_c = fusion_grids(C, HW)
+    nchunk, cb = nchunk or g_n, cb or g_c
+    items = HW * (C // 8)
+    stale = defect == "stale_column"
+    res = c["res"]
+    if defect == "sample_stride_dense":
+        assert layout is not None
+        res = [torch.stack([buf[off + n * HW * C: off + (n + 1) * HW * C] for n in range(N)]).reshape(N, HW, C).float() for buf, off, _ in layout]
+    sc = [torch.tensor(a, dtype=torch.float32) * (torch.tensor(1.0) if scales_dev is None else scales_dev[i].float())
+          for i, a in enumerate(c["scales"])]
+    col = lambda t, nb: _fusion_columns(t, C, items, nb, True) if stale else t
+    w1, b1, w2, b2 = (col(p[k], nchunk) for k in ("w1", "b1", "w2", "b2"))
+    zs = []
+    for q in range(3):
+        if defect == "scale_behind_bias":
+            zs.append(w1[..., q, 0] * (res[2 * q] * sc[2 * q]) + (w1[..., q, 1] * res[2 * q + 1] + b1[..., q]) * sc[2 * q + 1])
+        else:
+            zs.append(w1[..., q, 0] * (res[2 * q] * sc[2 * q]) + w1[..., q, 1] * (res[2 * q + 1] * sc[2 * q + 1]) + b1[..., q])
+    z = torch.stack(zs, dim=-1)                                                                 # [N, HW, C, 3]
+    order = z.reshape(N, items, 8, 3).transpose(2, 3).reshape(N, items, 24)                     # a thread's (q, e) order
+    mean1, rstd1 = _fusion_stats(order, nchunk, (1 if defect == "count_c_hw" else 3) * C * HW, eps, defect)
+    y = F.silu((z - mean1.reshape(N, 1, 1, 1)) * rstd1.reshape(N, 1, 1, 1) * p["g1"] + p["be1"])
+    u = b2 + w2[..., 0] * y[..., 0]
+    u = u + w2[..., 1] * y[..., 1]
+    u = rnd(u + w2[..., 2] * y[..., 2], dt)
+    if want_u:
+        return u
+    mean2, rstd2 = _fusion_stats(u.reshape(N, items, 8), nchunk, C * HW, eps, defect)
+    v = F.silu((u - mean2.reshape(N, 1, 1)) * rstd2.reshape(N, 1, 1) * p["g2"] + p["be2"])
+    out = rnd(col(p["w3"], cb) * v + col(p["b3"], cb), dt)
+    return out if c["addend"] is None else rnd(out + c["addend"], dt)
+
+
+def fusion_layout(c, seed=0, dense=False):
+    """Where a launch's residuals sit in memory: six (flat NaN-padded fp32 buffer, offset, batch stride) - nets 1, 3 and 5 are the three
+    thirds of ONE dense [3 N, HW, C] buffer (the batched openpose pass), nets 0, 2 and 4 have buffers of their own with batch strides
+    of HW C + 8, + 24 and + 64 elements (NaN in the gaps, 16-byte alignment kept) behind a NaN prefix.  dense: all strides HW C."""
+    N, per = c["N"], c["HW"] * c["C"]
+    nan = float("nan")
+    pose = torch.full((3 * N * per + 16,), nan)
+    out = [None] * 6
+    for j, k in enumerate((1, 3, 5)):
+        pose[8 + j * N * per: 8 + (j + 1) * N * per] = c["res"][k].reshape(-1)
+        out[k] = (pose, 8 + j * N * per, per)
+    for j, k in enumerate((0, 2, 4)):
+        bs = per if dense else per + (8, 24, 64)[j]
+        off = 8 * (j + 1)
+        buf = torch.full((off + N * bs + 8,), nan)
+        for n in range(N):
+            buf[off + n * bs: off + n * bs + per] = c["res"][k][n].reshape(-1)
+        out[k] = (buf, off, bs)
+    return out
+
+
+def nearly_constant_fusion_case(N, C, HW, dtype, seed=0):
+    """`gated_off` with b1 = 100 +- 1e-3: every sample's z is constant up to 1e-5 of its value, so the noise of the one-pass
+    E[z^2] - mean^2 (about 1e-3) exceeds both the true variance (1e-6) and eps, and its sign is a matter of summation order.  No error
+    bar can hold here (the design's own result is noise); what must hold is that the output is finite: the clamp at 0."""
+    c = fusion_case(N, C, HW, dtype, "gated_off", seed=seed)
+    c["params"]["b1"] = (100.0 + 1e-3 * torch.randn(C, 3, generator=_gen(seed + 1), dtype=torch.float64)).float()
+    c["kind"] = "nearly_constant"
+    return c
+
+
+def sample_err(y, ref64, both=False):
+    """row_err with one SAMPLE as the row: a LayerNorm over the whole sample gives the sample one scale"""
+    N = ref64.shape[0]
+    return row_err(y.reshape(N, -1), ref64.reshape(N, -1), both=both)
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# the sampler step (es_cfg_unipc_step, es_cfg_ddim_step): a linear recombination with a host-made fp32 coefficient table
+# ----------------------------------------------------------------------------------------------------------------
+def traj_err(x, ref64) -> float:
+    """max|x - ref| / rms(ref) over the whole latent tensor; inf where x is not finite"""
+    r, v = ref64.detach().double().cpu(), x.detach().double().cpu()
+    if not bool(torch.isfinite(v).all()):
+        return float("inf")
+    return float((v - r).abs().max() / r.pow(2).mean().sqrt())
+
+
+def guided_eps(noise, B, gs, cfg, t):
+    """the guided noise of the step kernels in t's precision: eu + gs * (ec - eu) over the two halves of noise [2 B | B, ...]"""
+    n = noise.to(t)
+    if not cfg:
+        return n
+    return n[:B] + torch.tensor(gs, dtype=t) * (n[B:] - n[:B])
+
+
+def unipc_apply(row, eps, x, last, m0, m1):
+    """one es_cfg_unipc_step in the precision of x (fp64: the truth for a given table; fp32: base_alg), row = the 12 coefficients of
+    the step.  Returns (next x, last = corrected sample, m0 = x0, m1 = previous x0)."""
+    c = row.to(x.dtype)
+    x0 = (x - c[1] * eps) / c[0]
+    xc = (c[3] * last + c[4] * m0 + c[5] * m1 + c[6] * x0) if float(c[2]) != 0.0 else x
+    return c[7] * xc + c[8] * x0 + c[9] * m0, xc, x0, m0
+
+
+def ddim_apply(row, eps, x):
+    c = row.to(x.dtype)
+    x0 = (x - c[1] * eps) / c[0]
+    return c[2] * x0 + c[3] * eps
+
+
+def unipc_oracle_step64(s, eps, x):
+    """oracle.UniPC.step without its closing cast to fp32: the trajectory stays in fp64 from end to end"""
+    a_t, s_t = s._alpha_sigma(s.sigmas[s.step_index])
+    x0 = (x.double() - s_t * eps.double()) / a_t
+    sample = x.double()
+    if s.step_index > 0 and s.last_sample is not None:
+        sample = s._uni_c(x0, s.last_sample, s.this_order)
+    s.model_outputs = s.model_outputs[1:] + [x0]
+    s.this_order = min(min(s.solver_order, len(s.timesteps) - s.step_index), s.lower_order_nums + 1)
+    s.last_sample = sample
+    prev = s._uni_p(sample, s.this_order)
+    if s.lower_order_nums < s.solver_order:
+        s.lower_order_nums += 1
+    s.step_index += 1
+    return prev
+
+
+def sampler_eps(T, shape, dtype, seed=0):
+    """T model outputs [2 B | B, H, W, L] rounded to the storage dtype, and the fp32 start latents"""
+    g = _gen(seed + 49979687)
+    return [rnd(torch.randn(*shape, generator=g), dtype) for _ in range(T)]
+
+
+def run_trajectory(kind, table, eps_list, x0, B, gs, cfg, prec):
+    """the whole trajectory through unipc_apply / ddim_apply in precision `prec`; returns the list of per-step states
+    (x, last, m0, m1) - DDIM: (x,)"""
+    x = x0.to(prec)
+    last, m0, m1 = (torch.zeros_like(x) for _ in range(3))
+    out = []
+    for i, noise in enumerate(eps_list):
+        e = guided_eps(noise, B, gs, cfg, prec)
+        if kind == "unipc":
+            x, last, m0, m1 = unipc_apply(table[i], e, x, last, m0, m1)
+            out.append((x, last, m0, m1))
+        else:
+            x = ddim_apply(table[i], e, x)
+            out.append((x,))
+    return out
+
+
+def sinusoid64(t, dim):
+    """the timestep embedding in fp64: [cos | sin] of t * exp(-ln(1e4) k / half)"""
+    half = dim // 2
+    a = t.double()[:, None] * torch.exp(-math.log(10000.0) * torch.arange(half, dtype=torch.float64) / half)[None]
+    return torch.cat([torch.cos(a), torch.sin(a)], dim=-1)
+
+
+def sinusoid32(t, dim, dtype):
+    """... as torch computes it in fp32, rounded once: the baseline of the kernel's misrounded count"""
+    half = dim // 2
+    a = t.float()[:, None] * torch.exp(-math.log(10000.0) * torch.arange(half, dtype=torch.float32) / half)[None]
+    return rnd(torch.cat([torch.cos(a), torch.sin(a)], dim=-1), dtype)
+
+
+def vae_sample_ref(mom, noise, L, scaling, prec, dtype=None):
+    """(mean + exp(0.5 clamp(logvar, -30, 20)) noise) scaling for NHWC moments [N, H, W, 2 L] and NCHW noise, in `prec`; dtype: every
+    op's output rounded to it (base_ref)"""
+    r = (lambda v: rnd(v, dtype)) if dtype is not None else (lambda v: v)
+    m = mom.to(prec)
+    mean, logvar = m[..., :L], m[..., L:2 * L].clamp(-30.0, 20.0)
+    std = r(torch.exp(r(0.5 * logvar)))
+    return r(r(mean + r(std * noise.to(prec).permute(0, 2, 3, 1))) * scaling)
 
 
 if __name__ == "__main__":

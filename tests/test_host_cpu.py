@@ -652,3 +652,67 @@ def test_conv_gemm_refuses_operands_that_are_not_dense(monkeypatch):
         assert dry.size() == 1 and y.shape == (N, H, W, Cout)
         ops.conv_gemm(x[1:], pw, x2=x2[1:], residual=res[1:], out=wide_o.reshape(2 * N, H, W, Cout)[1:2], splitk=1)
         assert dry.size() == 2
+
+
+def test_fusion_block_refuses_operands_the_launch_cannot_read(monkeypatch):
+    """ops.fusion_block / ops.fusion_blocks hand data_ptr()s, N, HW, C and six batch strides to the library: a residual or a parameter of
+    another dtype, a residual that is not dense inside a sample, a batch stride below HW C (or another than the view's), a view with
+    fewer samples than the launch reads, affine planes packed for another size, parameter vectors of another length, an `out` that is
+    not a contiguous [N, HW, C] and a short scales_dev - EdgeStyleHipError, before anything is recorded or launched (dry recorder, host
+    buffers).  Views into a batched buffer - dense or with gaps between the samples - stay legal."""
+    from tests import numerics as nm
+    monkeypatch.setattr(ops, "_stream", lambda: None)
+    N, HW, Cc = 2, 6, 16
+    per = HW * Cc
+    c = nm.fusion_case(N, Cc, HW, torch.float16, seed=1)
+    params = {k: v.to(torch.float16 if k in ("g1", "be1", "g2", "be2") else torch.float32) for k, v in c["params"].items()}
+    pose = torch.cat([c["res"][k] for k in (1, 3, 5)]).half()                                   # [3 N, HW, C], as the batched pass leaves it
+    gaps = torch.zeros(N, per + 24).half()
+    res = [c["res"][0].half(), pose[0:], gaps[:, :per].view(N, HW, Cc), pose[N:], c["res"][4].half().reshape(N, 2, 3, Cc), pose[2 * N:]]
+    bs = [per, per, per + 24, per, per, per]
+    scales = [1.0, 0.5, 1.0, 2.0, 1.0, 0.0]
+    wide = torch.zeros(N, HW, 2 * Cc).half()
+    other = nm.fusion_case(N, Cc, HW + 2, torch.float16, seed=1)["params"]
+
+    def swap(i, t, stride=None):
+        r, b = list(res), list(bs)
+        r[i] = t
+        if stride is not None:
+            b[i] = stride
+        return dict(res=r, res_bs=b)
+
+    def par(**kw):
+        p = dict(params)
+        p.update(kw)
+        return dict(params=p)
+    bad = [swap(0, res[0].bfloat16()), swap(2, res[2].float()),                               # residual dtypes
+           swap(0, wide[..., :Cc]), swap(4, torch.zeros(N, Cc, HW).half().transpose(1, 2)),    # not dense inside a sample
+           swap(0, res[0], per - 8), swap(2, res[2], per),                                    # stride below HW C; not the view's stride
+           swap(2, torch.zeros(N, per + 4).half()[:, :per].view(N, HW, Cc), per + 4), swap(0, torch.zeros(N * per + 4).half()[4:].view(N, HW, Cc)),   # 16-byte pieces
+           swap(5, pose[2 * N + 1:]), swap(0, res[0][:1]), swap(3, torch.zeros(N, HW + 1, Cc).half()),     # too few samples; another size
+           par(g1=other["g1"].half()), par(be2=other["be2"].half()), par(g2=params["g1"]),   # planes of another size
+           par(be1=params["be1"].float()), par(w1=params["w1"].half()), par(b3=params["b3"].double()),    # parameter dtypes
+           par(w1=params["w1"][:, :, 0].contiguous()), par(b1=params["b1"][:-1]), par(w2=params["w2"][1:]), par(b2=params["b2"][:8]),
+           par(w3=params["b1"]), par(b3=torch.zeros(Cc + 8)),                                 # parameter lengths
+           dict(out=wide[..., :Cc]), dict(out=torch.zeros(N, HW, Cc)), dict(out=torch.zeros(N * HW, Cc).half()), dict(out=torch.zeros(N + 1, HW, Cc).half()),
+           dict(scales_dev=torch.ones(5)), dict(scales_dev=torch.ones(6).half()), dict(scales_dev=torch.ones(6, dtype=torch.float64))]
+    with _DryPlan() as dry:
+        for kw in bad:
+            a = dict(res=res, res_bs=bs, params=params, out=None, scales_dev=None)
+            a.update(kw)
+            with pytest.raises(lib.EdgeStyleHipError, match="fusion_block: "):
+                ops.fusion_block(a["res"], a["res_bs"], a["params"], N, HW, Cc, scales, a["scales_dev"], out=a["out"])
+            assert dry.size() == 0, kw
+            blocks = [(res, bs, params, HW, Cc)] * 13 + [(a["res"], a["res_bs"], a["params"], HW, Cc)]
+            if a["out"] is None:                # the 14th block is refused before the first 13 are recorded
+                with pytest.raises(lib.EdgeStyleHipError, match="fusion_block: "):
+                    ops.fusion_blocks(blocks, N, scales, a["scales_dev"])
+                assert dry.size() == 0, kw
+        with pytest.raises(lib.EdgeStyleHipError, match="fusion_block: addend"):
+            ops.fusion_blocks([(res, bs, params, HW, Cc)], N, scales, addends=[wide[..., :Cc]])
+        assert dry.size() == 0
+        out = torch.zeros(N + 2, HW, Cc).half()
+        y = ops.fusion_block(res, bs, params, N, HW, Cc, scales, torch.ones(6), out=out[1:N + 1])
+        assert dry.size() == 1 and y.data_ptr() == out[1].data_ptr()
+        outs = ops.fusion_blocks([(res, bs, params, HW, Cc)] * 3, N, scales, addends=[torch.zeros(N, HW, Cc).half()] * 3)
+        assert dry.size() == 2 and len(outs) == 3 and outs[0].shape == (N, HW, Cc)

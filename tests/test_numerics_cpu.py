@@ -373,3 +373,239 @@ def test_planted_geometry_defects_in_the_convolution_exceed_the_bars(defect, sha
     if defect == "hw_swapped":                   # ... and invisible on a square image
         sq = nm.conv_case(dtype=dtype, seed=22, **dict(shape, W=shape["H"]))
         assert torch.equal(nm.conv_base_alg(sq, 8, defect=defect), nm.conv_base_alg(sq, 8))
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# the fusion block
+# ----------------------------------------------------------------------------------------------------------------
+FUSION_GRID_PINS = {  # (C, HW) -> (nchunk, cb, a thread keeps its column in passes A / B, in pass C): read off fusion_grids() in csrc/fusion.hip
+    (8, 1): (1, 1, True, True), (24, 35): (3, 3, True, True),
+    (64, 256): (1, 2, True, True),          # items = 2048: items / 2048 = 1 workgroup in A / B, items / 1024 = 2 in pass C
+    (320, 4096): (80, 160, True, True), (320, 9216): (180, 360, True, True), (320, 16384): (255, 510, True, True),
+    (64, 65536): (256, 512, True, True), (1280, 64): (5, 10, True, True),
+    (2056, 16): (2, 257, False, True),      # q = 257 > 256: passes A and B reload their parameters per item, pass C does not
+    (4168, 8): (2, 4, False, False),        # q = 521 > 512: all three passes reload per item
+}
+OLD_FUSION_SHAPES = [(64, 16), (320, 8), (1280, 8), (320, 64), (128, 8), (64, 32)]      # (C, S) of test_fusion_block_* in test_ops_gpu.py
+
+
+def test_fusion_grid_mirror_is_pinned():
+    for (C, HW), (nchunk, cb, fix_ab, fix_c) in FUSION_GRID_PINS.items():
+        assert nm.fusion_grids(C, HW) == (nchunk, cb), (C, HW, nm.fusion_grids(C, HW))
+        assert nm.fusion_fixed_column(C, nchunk) == fix_ab and nm.fusion_fixed_column(C, cb) == fix_c, (C, HW)
+        assert nchunk <= nm.FU_MAX_CHUNK and cb <= nm.FU_MAX_CB
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_fusion_generator_meets_its_postconditions(dtype):
+    for kind in nm.FUSION_KINDS:
+        for (N, C, HW) in [(3, 24, 35), (2, 64, 256), (1, 2056, 16)]:
+            if kind.startswith("u_offset") and C == 24:
+                N = 1           # b2 is shared by the samples: 840 heavy-tailed values per sample do not pin every sample's ratio to 10 %
+            c = nm.fusion_case(N, C, HW, dtype, kind, seed=C + len(kind))
+            assert len(c["res"]) == 6 and all(t.shape == (N, HW, C) for t in c["res"]) and len(c["params"]) == 10
+            ref = nm.fusion_ref64(c)
+            assert ref.shape == (N, HW, C) and bool(torch.isfinite(ref).all()) and float(ref.reshape(N, -1).std(dim=1).min()) > 0
+    with pytest.raises(AssertionError):
+        nm.fusion_case(1, 64, 16, dtype, "no_such_kind")
+
+
+def test_fusion_ref64_equals_the_oracle_and_the_packing():
+    """fusion_ref64 == oracle.controlnet_block(interleave_tensors(...)) on double tensors to 1e-12, and ops.pack_fusion_params packs the
+    state dict of fusion_state_dict into exactly the case's parameter tensors (layout and storage dtypes)"""
+    from edgestyle_amd import ops
+    from oracle import sd15_oracle as O
+    for (N, C, H, W, kind, dtype) in [(2, 24, 5, 7, "randn", torch.float16), (3, 64, 4, 4, "ratio_10", torch.bfloat16),
+                                      (1, 8, 1, 1, "outliers", torch.float16), (1, 40, 3, 2, "u_offset_30", torch.bfloat16)]:
+        c = nm.fusion_case(N, C, H * W, dtype, kind, seed=C)
+        sd = nm.fusion_state_dict(c, "blk", H, W)
+        nchw = [(t.double() * s).reshape(N, H, W, C).permute(0, 3, 1, 2) for t, s in zip(c["res"], c["scales"])]
+        want = O.controlnet_block(sd, "blk", O.interleave_tensors(nchw)).permute(0, 2, 3, 1).reshape(N, H * W, C)
+        got = nm.fusion_ref64(c)
+        assert got.dtype == want.dtype == torch.float64
+        assert float((got - want).abs().max()) <= 1e-12 * max(1.0, float(want.abs().max())), (C, float((got - want).abs().max()))
+        packed = ops.pack_fusion_params(sd, "blk", dtype, "cpu")
+        for k, v in c["params"].items():
+            assert packed[k].dtype == (dtype if k in ("g1", "be1", "g2", "be2") else torch.float32) and packed[k].is_contiguous(), k
+            assert packed[k].shape == v.shape and torch.equal(packed[k].float(), v), k
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_fusion_design_is_inside_the_bar_in_the_required_tier(dtype):
+    """sample_err(base_alg) <= MARGIN * sample_err(base_ref), both > 0, for every required input kind at a one-workgroup shape, a
+    several-workgroup shape and a per-item-reload shape - before the GPU test relies on it"""
+    for kind in nm.FUSION_KINDS:
+        if not nm.fusion_kind_required(kind):
+            continue
+        for (N, C, HW) in [(2, 64, 256), (1, 1280, 64), (2, 2056, 16)]:
+            c = nm.fusion_case(N, C, HW, dtype, kind, seed=7, addend=(C == 1280))
+            ref = nm.fusion_ref64(c)
+            e_alg, e_ref = nm.sample_err(nm.fusion_base_alg(c), ref), nm.sample_err(nm.fusion_base_ref(c), ref)
+            print(f"numerics: fusion design {kind} {dtype} C{C} HW{HW}: base_alg {e_alg:.3e} base_ref {e_ref:.3e}")
+            assert 0 < e_alg <= nm.MARGIN * e_ref and e_ref > 0, (kind, C, HW, e_alg, e_ref)
+
+
+def test_fusion_gpu_table_rows_have_a_design_inside_the_bars():
+    """every row of tests/test_fusion_gpu.py's table under a million elements per net: the generator's postconditions hold, and in the
+    required tier the DESIGN is inside the bar the GPU test applies to the kernel (base_alg <= MARGIN x base_ref) - a row whose
+    yardsticks disagree by a draw of rounding luck (samples of 8 outputs) is found here, not on the GPU"""
+    from tests import test_fusion_gpu as FG
+    for row in FG.TABLE:
+        if row["N"] * row["C"] * row["HW"] > 1_000_000:
+            continue
+        c = FG.make_case(row)
+        ref = nm.fusion_ref64(c)
+        e_alg, e_ref = nm.sample_err(nm.fusion_base_alg(c), ref), nm.sample_err(nm.fusion_base_ref(c), ref)
+        assert e_alg > 0 and e_ref > 0, FG.row_id(row)
+        if nm.fusion_kind_required(row["kind"]):
+            assert e_alg <= nm.MARGIN * e_ref, (FG.row_id(row), e_alg, e_ref)
+
+
+def _fusion_defect(c, defect, **kw):
+    """(error of the planted defect, the bar of the same data, whether the old metric at 4e-3 passes the defect)"""
+    ref = nm.fusion_ref64(c)
+    e_alg, e_ref = nm.sample_err(nm.fusion_base_alg(c, **{k: v for k, v in kw.items() if k != "layout"}), ref), nm.sample_err(nm.fusion_base_ref(c), ref)
+    y = nm.fusion_base_alg(c, defect=defect, **kw)
+    e = nm.sample_err(y, ref)
+    old = nm.old_metric(y, ref)
+    old_passes = old < 4e-3                     # NaN compares false: a non-finite output fails the old metric as well
+    print(f"numerics: fusion defect {defect} C{c['C']} HW{c['HW']} N{c['N']} {c['dtype']} {c['kind']}: defect {e:.3e}  bar {_bar(e_alg, e_ref):.3e}  "
+          f"old metric {old:.3e} -> {'PASSES' if old_passes else 'fails'} at 4e-3")
+    return e, _bar(e_alg, e_ref), old_passes
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_fusion_planted_defects_are_outside_the_bar(dtype):
+    same = lambda c, defect, **kw: torch.equal(nm.fusion_base_alg(c, defect=defect, **kw), nm.fusion_base_alg(c, **{k: v for k, v in kw.items() if k != "layout"}))
+    # stale_column: invisible at every shape test_ops_gpu.py uses (its grids keep every thread on one column), visible at C = 2056, 4168
+    from tests import helpers as H
+    for C, S in OLD_FUSION_SHAPES + sorted(set(H.REF_FUSION_LEVELS)):
+        nchunk, cb = nm.fusion_grids(C, S * S)
+        assert nm.fusion_fixed_column(C, nchunk) and nm.fusion_fixed_column(C, cb), (C, S)
+    for C, S in [(64, 16), (320, 8), (128, 8)]:
+        assert same(nm.fusion_case(2, C, S * S, dtype, seed=C), "stale_column")
+    for C, HW in [(2056, 16), (4168, 8)]:
+        e, bar, _ = _fusion_defect(nm.fusion_case(2, C, HW, dtype, seed=C), "stale_column")
+        assert e > bar, (C, e, bar)
+    # partials_past_64: the emulation run with the grid forced, on as many pixels as give every thread one item
+    for nchunk in (1, 40, 64):
+        assert same(nm.fusion_case(1, 320, nchunk * 256 // 40 + 3, dtype, seed=nchunk), "partials_past_64", nchunk=nchunk)
+    for nchunk in (80, 180, 255):
+        e, bar, _ = _fusion_defect(nm.fusion_case(1, 320, nchunk * 256 // 40, dtype, seed=nchunk), "partials_past_64", nchunk=nchunk)
+        assert e > bar, (nchunk, e, bar)
+    c = nm.fusion_case(2, 64, 256, dtype, seed=5)
+    for defect in ("scale_behind_bias", "count_c_hw"):
+        e, bar, _ = _fusion_defect(c, defect)
+        assert e > bar, (defect, e, bar)
+    c1 = nm.fusion_case(2, 64, 256, dtype, scales=[1.0] * 6, seed=5)
+    e, bar, _ = _fusion_defect(c1, "scale_behind_bias")                 # with all scales 1 there is nothing to misplace: another order of
+    assert e <= bar                                                     # additions and no more
+    # sample_stride_dense: visible only where the batch strides differ from HW C
+    c = nm.fusion_case(3, 24, 35, dtype, seed=6)
+    assert same(c, "sample_stride_dense", layout=nm.fusion_layout(c, dense=True))
+    e, bar, _ = _fusion_defect(c, "sample_stride_dense", layout=nm.fusion_layout(c))
+    assert e > bar
+    c = nm.fusion_case(1, 24, 35, dtype, seed=6)
+    assert same(c, "sample_stride_dense", layout=nm.fusion_layout(c))  # ... and only with more than one sample
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_fusion_unclamped_variance(dtype):
+    """A one-pass variance can come out negative only where the noise of E[z^2] - mean^2 exceeds the true variance, and it makes
+    rsqrt(var + eps) a NaN only where that noise exceeds eps as well - where the result is no longer accurate in any case.  On `constant`
+    (z == 0 exactly: s = ss = 0, var = 0 - 0) and on `gated_off` (var(b1) ~ 1e-2 >> 1e-7 of noise) the fp32 variance is never negative:
+    the planted defect computes the same bits as the design there (asserted), so these two kinds do not guard the clamp.  What guards it
+    is a sample that is constant up to 1e-5 of its value (b1 = 100 +- 1e-3 behind scales of 0): the design stays finite, the defect does
+    not - the finiteness bar of the GPU sweep is the one that holds there."""
+    for kind in ("constant", "gated_off"):
+        c = nm.fusion_case(2, 64, 256, dtype, kind, seed=3)
+        assert torch.equal(nm.fusion_base_alg(c, defect="variance_unclamped"), nm.fusion_base_alg(c))
+        assert bool(torch.isfinite(nm.fusion_base_alg(c)).all())
+    found = 0
+    for seed in range(6):
+        c = nm.nearly_constant_fusion_case(2, 64, 256, dtype, seed)
+        good, bad = nm.fusion_base_alg(c), nm.fusion_base_alg(c, defect="variance_unclamped")
+        assert bool(torch.isfinite(good).all()) and nm.finite_where_representable(good, nm.fusion_ref64(c), dtype)
+        if not bool(torch.isfinite(bad).all()):
+            found += 1
+            assert not nm.finite_where_representable(bad, nm.fusion_ref64(c), dtype)
+            print(f"numerics: fusion defect variance_unclamped seed {seed} {dtype}: not finite; old metric {nm.old_metric(bad, nm.fusion_ref64(c))} -> fails at 4e-3")
+    assert found >= 1, "no seed drove the one-pass variance below -eps: the case no longer guards the clamp"
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# the sampler step: coefficient tables applied as the kernels apply them, against the oracle's schedulers
+# ----------------------------------------------------------------------------------------------------------------
+# Worst per-step figure max|x - ref| / rms(ref) over every trajectory below, measured on the CPU (tests/NUMERICS.md, "Sampler step"):
+# the fp32 table applied in fp64, and the whole recombination in fp32 (base_alg).  The assertions allow 4 x these, because the figures
+# depend on the seed of eps; 1e-4 is where a figure would become a finding about the formulation.
+UNIPC_TABLE_ERR, UNIPC_FP32_ERR = 1.4e-6, 3.2e-6
+DDIM_TABLE_ERR, DDIM_FP32_ERR = 3.9e-7, 2.3e-6
+SAMPLER_SHAPE = (2, 8, 8, 4)
+
+
+def _unipc_trajectories(T, spacing, order, seed):
+    from edgestyle_amd.schedulers import UniPCMultistepScheduler
+    from oracle import sd15_oracle as O
+    mine = UniPCMultistepScheduler(solver_order=order, timestep_spacing=spacing)
+    orc = O.UniPC(solver_order=order, timestep_spacing=spacing)
+    ts = orc.set_timesteps(T)
+    assert mine.set_timesteps(T).tolist() == ts.tolist()
+    table = mine.coef_table()
+    assert table.shape == (T, 12) and table.dtype == torch.float32
+    eps = nm.sampler_eps(T, SAMPLER_SHAPE, torch.float16, seed)
+    x0 = torch.randn(*SAMPLER_SHAPE, generator=torch.Generator().manual_seed(seed)).float()
+    t64 = nm.run_trajectory("unipc", table, eps, x0, SAMPLER_SHAPE[0], 1.0, False, torch.float64)
+    t32 = nm.run_trajectory("unipc", table, eps, x0, SAMPLER_SHAPE[0], 1.0, False, torch.float32)
+    x, e_table, e_alg = x0.double(), 0.0, 0.0
+    for i in range(T):
+        x = nm.unipc_oracle_step64(orc, eps[i], x)
+        e_table, e_alg = max(e_table, nm.traj_err(t64[i][0], x)), max(e_alg, nm.traj_err(t32[i][0], x))
+    # the oracle's own step (which hands an fp32 sample on) agrees with its fp64 form to fp32 rounding
+    orc.set_timesteps(T)
+    y = x0
+    for i in range(T):
+        y = orc.step(eps[i], int(ts[i]), y)
+    assert nm.traj_err(y, x) < 1e-5
+    return e_table, e_alg
+
+
+def test_unipc_table_applied_as_the_kernel_applies_it_matches_the_oracle():
+    """UniPCMultistepScheduler.coef_table() applied as es_cfg_unipc_step's linear recombination, in fp64 and in fp32, against
+    oracle.UniPC fed the same eps over whole trajectories: T in {1, 2, 3, 4, 10, 50} (1 and 2: warm-up and lower_order_final meet),
+    both spacings, solver_order 1 and 2, every step including the last"""
+    worst_t, worst_a = 0.0, 0.0
+    for T in (1, 2, 3, 4, 10, 50):
+        for spacing in ("leading", "linspace"):
+            for order in (1, 2):
+                e_table, e_alg = _unipc_trajectories(T, spacing, order, seed=T)
+                print(f"numerics: unipc T {T} {spacing} order {order}: fp32 table in fp64 {e_table:.3e}  all fp32 {e_alg:.3e}")
+                assert e_table < 1e-4 and e_alg < 1e-4, (T, spacing, order, e_table, e_alg)
+                worst_t, worst_a = max(worst_t, e_table), max(worst_a, e_alg)
+    print(f"numerics: unipc worst: fp32 table {worst_t:.3e}  all fp32 {worst_a:.3e}")
+    assert worst_t <= 4 * UNIPC_TABLE_ERR and worst_a <= 4 * UNIPC_FP32_ERR, (worst_t, worst_a)
+
+
+def test_ddim_table_applied_as_the_kernel_applies_it_matches_the_oracle():
+    from edgestyle_amd.schedulers import DDIMScheduler
+    from oracle import sd15_oracle as O
+    worst_t, worst_a = 0.0, 0.0
+    for T in (1, 2, 10, 50):
+        mine, orc = DDIMScheduler(), O.DDIM()
+        ts = orc.set_timesteps(T)
+        assert mine.set_timesteps(T).tolist() == ts.tolist()
+        table = mine.coef_table()
+        assert table.shape == (T, 4)
+        eps = nm.sampler_eps(T, SAMPLER_SHAPE, torch.float16, seed=T)
+        x0 = torch.randn(*SAMPLER_SHAPE, generator=torch.Generator().manual_seed(T)).float()
+        t64 = nm.run_trajectory("ddim", table, eps, x0, SAMPLER_SHAPE[0], 1.0, False, torch.float64)
+        t32 = nm.run_trajectory("ddim", table, eps, x0, SAMPLER_SHAPE[0], 1.0, False, torch.float32)
+        orc.alphas_cumprod, orc.final_alpha_cumprod = orc.alphas_cumprod.double(), orc.alphas_cumprod[0].double()
+        x = x0.double()
+        for i in range(T):                      # every step, the last (alphas_cumprod[0]) included
+            x = orc.step(eps[i].double(), int(ts[i]), x)
+            e_table, e_alg = nm.traj_err(t64[i][0], x), nm.traj_err(t32[i][0], x)
+            assert e_table < 1e-4 and e_alg < 1e-4, (T, i, e_table, e_alg)
+            worst_t, worst_a = max(worst_t, e_table), max(worst_a, e_alg)
+        print(f"numerics: ddim T {T}: worst so far fp32 table {worst_t:.3e}  all fp32 {worst_a:.3e}")
+    assert worst_t <= 4 * DDIM_TABLE_ERR and worst_a <= 4 * DDIM_FP32_ERR, (worst_t, worst_a)

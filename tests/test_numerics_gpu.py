@@ -600,15 +600,66 @@ def _write_conv_table(f, conv_rows):
                 f"{r['bar']} | {_div(r['kernel_err'], r['base_alg']):.2f} | {_div(r['kernel_err'], r['base_ref']):.2f} |\n")
 
 
+FUSION_MARKERS = ("<!-- fusion table begin: written by `python -m tests.numerics --report --only fusion` -->", "<!-- fusion table end -->")
+SAMPLER_MARKERS = ("<!-- sampler table begin: written by `python -m tests.numerics --report --only sampler` -->", "<!-- sampler table end -->")
+
+
+def _replace_between(text, markers, body):
+    begin, end = markers
+    assert begin in text and end in text, f"tests/NUMERICS.md has lost its marker lines {markers}"
+    return text[:text.index(begin) + len(begin)] + "\n\n" + body.rstrip("\n") + "\n\n" + text[text.index(end):]
+
+
+def _fusion_section():
+    from tests import test_fusion_gpu as FG
+    rows, secs = FG.report_rows()
+    out = [f"Fusion sweep, measured on {torch.cuda.get_device_name(0)}, torch {torch.__version__}; {len(rows)} launches judged in {secs:.1f} s "
+           "(CPU baselines included).  Error per sample: max|y - ref64| / rms(ref64) over the sample.", "",
+           "| case | tier | kernel | base_alg | base_ref | kernel / base_alg | kernel / base_ref | old metric |", "|---|---|---|---|---|---|---|---|"]
+    for r in rows:
+        out.append(f"| {r['case']} | {r['tier']} | {r['kernel']:.2e} | {r['base_alg']:.2e} | {r['base_ref']:.2e} | {_div(r['kernel'], r['base_alg']):.2f} | "
+                   f"{_div(r['kernel'], r['base_ref']):.2f} | {r['old_metric']:.1e} |")
+    return "\n".join(out), len(rows)
+
+
+def _sampler_section():
+    from tests import test_sampler_gpu as SG
+    rows, secs = SG.report_rows()
+    out = [f"Sampler trajectories, measured on {torch.cuda.get_device_name(0)}, torch {torch.__version__}; {len(rows)} trajectories in {secs:.1f} s.  "
+           "Per trajectory the step at which kernel / base_alg of the fp32 latents is largest; error: max|x - ref64| / rms(ref64).", "",
+           "| trajectory | step | kernel | base_alg | kernel / base_alg |", "|---|---|---|---|---|"]
+    for r in rows:
+        out.append(f"| {r['case']} | {r.get('step')} | {r['kernel']:.2e} | {r['base_alg']:.2e} | {r['ratio']:.2f} |")
+    return "\n".join(out), len(rows)
+
+
+def _write_sections(doc, path, which):
+    text = open(doc).read()
+    for name in which:
+        body, n = _fusion_section() if name == "fusion" else _sampler_section()
+        text = _replace_between(text, FUSION_MARKERS if name == "fusion" else SAMPLER_MARKERS, body)
+        print(f"{n} {name} cases -> {path}")
+    with open(path, "w") as f:
+        f.write(text)
+
+
 def write_report(path=None, only=None):
-    """python -m tests.numerics --report [--only conv]: run every case above and the convolution sweep of tests/test_conv_gpu.py
-    without asserting and write the measured tables (--only conv: the convolution table alone, the other is kept as it is)"""
+    """python -m tests.numerics --report [--only conv | fusion | sampler]: run every case above and the convolution sweep of
+    tests/test_conv_gpu.py without asserting and write the measured tables (--only conv: the convolution table alone, the other is kept
+    as it is; --only fusion, --only sampler: the table of tests/test_fusion_gpu.py or tests/test_sampler_gpu.py alone, between its marker
+    lines)"""
     global RECORD
     import tempfile
     import pathlib
     assert torch.cuda.is_available(), "the report is measured on the GPU"
     doc = os.path.join(ROOT, "tests", "NUMERICS.md")
     RECORD = []
+    if only in ("fusion", "sampler"):           # their tables sit between marker lines of their own, above the first measured table
+        try:
+            _write_sections(doc, path or doc, [only])
+        finally:
+            RECORD = None
+        return
     if only == "conv":
         from tests import test_conv_gpu as CV
         conv_rows = CV.report_rows()
