@@ -1289,6 +1289,18 @@ extern "C" int es_attention(const es_attn_desc* d, void* stream) {
     for (int v : ok_d) ok = ok || d->d == v;
     if (!ok) { es_set_error("es_attention: unsupported head_dim (8,16,24,32,40,48,64,80,128,160,512)"); return -3; }
   }
+  {   // the kernels address K and V through buffer resources with a 32-bit byte range ((Skv - 1) * ld + d) * 2 and step their 32-bit tile
+      // offsets up to two 64-key tiles past the last key: both must stay below 2^31
+    const long long ldkv[2] = {d->ldk, d->ldv};
+    for (long long ld : ldkv) {
+      if (ld < d->d) { es_set_error("es_attention: a k / v row stride below head_dim"); return -1; }
+      const long long range = ((long long)(d->Skv - 1) * ld + d->d) * 2, steps = ((long long)d->Skv + 2 * 64) * ld * 2;
+      if (range >= (1ll << 31) || steps >= (1ll << 31)) {
+        es_set_error("es_attention: k / v too long for 32-bit buffer offsets ((Skv + 128) * ld * 2 must stay below 2^31)");
+        return -1;
+      }
+    }
+  }
   ES_PLAN_RECORD(ES_OP_ATTENTION, d, sizeof(*d));       // after validation: a rejected call never enters a recording plan
   hipStream_t st = (hipStream_t)stream;
   int rc = d->dtype == ES_F16 ? dispatch<f16>(*d, st) : dispatch<bf16>(*d, st);

@@ -761,15 +761,40 @@ def linear(x: torch.Tensor, pw: PackedWeight, **kw) -> torch.Tensor:
 
 def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, scale: Optional[float] = None,
               out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """q: [N,Sq,heads*d] view (any row stride), k/v: [N,Skv,heads*d] views -> [N,Sq,heads*d] contiguous."""
+    """q: [N,Sq,heads*d] view (any row stride), k/v: [N,Skv,heads*d] views -> [N,Sq,heads*d] contiguous.
+    The launch takes data_ptr()s, one (N, heads, Sq, Skv, d) and the row and batch strides: whatever it would read or write differently
+    from what the tensors hold is refused here, before anything is recorded or launched."""
+    def bad(msg):
+        return L.EdgeStyleHipError("attention: " + msg)
+    if q.dtype not in (torch.float16, torch.bfloat16):
+        raise bad(f"q must be fp16 or bf16, not {q.dtype}")
+    if q.dim() != 3 or k.dim() != 3 or v.dim() != 3:
+        raise bad("q, k, v must be [N, S, heads * d]")
     N, Sq, Cq = q.shape
     Skv = k.shape[1]
+    if heads < 1 or Cq % heads != 0:
+        raise bad(f"width {Cq} is not a multiple of heads {heads}")
     dh = Cq // heads
     if out is None:
         out = torch.empty((N, Sq, Cq), dtype=q.dtype, device=q.device)
-    for t in (q, k, v, out):
+    for name, t in (("k", k), ("v", v), ("out", out)):
+        if t.dtype != q.dtype or t.device != q.device:
+            raise bad(f"{name} is {t.dtype} on {t.device}, q is {q.dtype} on {q.device}")
+    if k.shape != v.shape:
+        raise bad(f"k {tuple(k.shape)} and v {tuple(v.shape)} differ")
+    if k.shape[0] != N or k.shape[2] != Cq:
+        raise bad(f"k / v {tuple(k.shape)} do not match q {tuple(q.shape)} in N or width")
+    if out.dim() != 3 or out.shape != q.shape:
+        raise bad(f"out {tuple(out.shape)} is not q's shape {tuple(q.shape)}")
+    for name, t in (("q", q), ("k", k), ("v", v), ("out", out)):
         if t.stride(2) != 1:
-            raise L.EdgeStyleHipError("attention: innermost stride must be 1")
+            raise bad("innermost stride must be 1")
+        if t.stride(1) < Cq:
+            raise bad(f"{name}: row stride {t.stride(1)} below the width {Cq}")
+        unit = 8 if name == "out" else 16       # bytes: q, k, v are read as 16-byte vectors, out is written in 8-byte pieces
+        es = t.element_size()
+        if (t.stride(1) * es) % unit or (N > 1 and (t.stride(0) * es) % unit) or t.data_ptr() % unit:
+            raise bad(f"{name}: row stride, batch stride and address must be multiples of {unit} bytes")
     d = L.AttnDesc()
     d.q, d.k, d.v, d.o = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr()
     d.N, d.heads, d.Sq, d.Skv, d.d = N, heads, Sq, Skv, dh

@@ -8,7 +8,8 @@ two orders of magnitude above the rest, and one loud row sets the denominator of
 This module is plain Python (no fixtures):
 
 * generators (seeded, CPU, values rounded through the storage dtype before anything else sees them) that ASSERT their own
-  postconditions: `token_rows`, `group_maps`, `spike_and_sea`, `late_risers`, `common_shift`, `one_loud_query`, `loud_values`;
+  postconditions: `token_rows`, `group_maps`, `spike_and_sea`, `late_risers`, `common_shift`, `one_loud_query`, `loud_values`,
+  `last_key_decides`;
 * `row_err(y, ref64)`: max over rows r and columns c of |y[r, c] - ref64[r, c]| / rms_c(ref64[r, :]) - every row is its own scale;
 * for every operation three CPU computations on the SAME rounded inputs and rounded weights:
     `*_ref64`     the plain operation in fp64 (the truth),
@@ -26,8 +27,8 @@ The implicit-GEMM convolution has a metric of its own, the misrounded share (`mi
 `conv_base_alg`, further down): an extra rounding inside the launch is invisible to row_err and plain to it.
 
 `python -m tests.numerics --report` (GPU) runs the cases of test_numerics_gpu.py and the convolution sweep of test_conv_gpu.py and writes
-the measured tables to tests/NUMERICS.md (`--only conv`: the convolution table alone; `--only fusion`, `--only sampler`: the sweep of
-test_fusion_gpu.py or the trajectories of test_sampler_gpu.py alone).
+the measured tables to tests/NUMERICS.md (`--only conv`: the convolution table alone; `--only fusion`, `--only sampler`, `--only attention`:
+the sweep of test_fusion_gpu.py, the trajectories of test_sampler_gpu.py or the rows of test_attention_gpu.py alone).
 
 The fusion block (`fusion_case`, `fusion_ref64`, `fusion_base_ref`, `fusion_base_alg`, `fusion_grids`; judged per SAMPLE, `sample_err`) and the
 sampler step (`unipc_apply`, `ddim_apply`, `run_trajectory`, `traj_err`) have sections of their own at the end.
@@ -240,7 +241,8 @@ def late_risers(N, heads, Sq, Skv, d, tile=64, step_log2=10.0, dtype=torch.float
 def common_shift(N, heads, Sq, Skv, d, shift=300.0, dtype=torch.float16, seed=0):
     """randn q, k, v plus a shared q / k component that moves ALL logits of a query by `shift` (+ or -): softmax does not care, the
     kernel's first-tile reference has to absorb it.  The component sits in one coordinate with values exact in bf16, so the shift is
-    common to every key exactly.  Asserted: every query's logits have |mean| within 5 % of |shift| and a spread that stays O(1)."""
+    common to every key exactly.  Asserted: every query's logits have |mean| within 5 % of |shift| and (from 8 keys on) a spread that
+    stays O(1)."""
     g = _gen(seed)
     q = torch.randn(N, Sq, heads, d, generator=g, dtype=torch.float64)
     k = torch.randn(N, Skv, heads, d, generator=g, dtype=torch.float64)
@@ -252,7 +254,9 @@ def common_shift(N, heads, Sq, Skv, d, shift=300.0, dtype=torch.float16, seed=0)
     k[..., 0] = b
     q, k, v = (rnd(t.reshape(N, -1, heads * d), dtype) for t in (q, k, v))
     s = _softmax64(q, k, heads)
-    assert float((s.mean(dim=-1).abs() / abs(shift) - 1).abs().max()) < 0.05 and float(s.std(dim=-1).max()) < 3.0
+    assert float((s.mean(dim=-1).abs() / abs(shift) - 1).abs().max()) < 0.05
+    if Skv >= 8:                # below that the sample spread of a query's few logits says little (and is undefined for one key)
+        assert float(s.std(dim=-1).max()) < 3.0
     assert (float(s.mean()) > 0) == (shift > 0)
     return q, k, v
 
@@ -294,6 +298,28 @@ def loud_values(N, heads, Sq, Skv, d, peak=2.0e4, dtype=torch.float16, seed=0):
     v = v * (peak / float(v.abs().max()))
     q, k, v = (rnd(t, dtype) for t in (q, k, v))
     assert float(v.abs().max()) <= peak * (1 + 2 ** -8) and bool(torch.isfinite(v).all())
+    return q, k, v
+
+
+def last_key_decides(N, heads, Sq, Skv, d, dtype=torch.float16, seed=0):
+    """Calm logits, except that key Skv - 1 carries a logit about 12 (natural units) above the rest for EVERY query, and its V row is
+    offset by -3 against +1.5 for the others (as in spike_and_sea): a kernel that drops the last valid key - the one a ragged tile's
+    mask sits next to - returns the others' mean, three units away.  Asserted in fp64: that key's softmax weight is >= 0.99 in
+    every row."""
+    g = _gen(seed)
+    q = 0.5 * torch.randn(N, Sq, heads, d, generator=g, dtype=torch.float64)
+    k = 0.5 * torch.randn(N, Skv, heads, d, generator=g, dtype=torch.float64)
+    v = torch.randn(N, Skv, heads, d, generator=g, dtype=torch.float64) + 1.5
+    u = _unit((d,), g)
+    q = q - (q * u).sum(dim=-1, keepdim=True) * u
+    k = k - (k * u).sum(dim=-1, keepdim=True) * u
+    amp = math.sqrt(12.0 * math.sqrt(d))
+    q = q + u * amp
+    k[:, Skv - 1] = k[:, Skv - 1] + u * amp
+    v[:, Skv - 1] = v[:, Skv - 1] - 3.0
+    q, k, v = (rnd(t.reshape(N, -1, heads * d), dtype) for t in (q, k, v))
+    w = torch.softmax(_softmax64(q, k, heads), dim=-1)
+    assert float(w[..., Skv - 1].min()) >= 0.99, float(w[..., Skv - 1].min())
     return q, k, v
 
 
@@ -1000,16 +1026,26 @@ def attn_base_ref(q, k, v, heads, dtype, scale=None):
     return rnd(_unheads(p @ _heads(v.float(), heads)), dtype)
 
 
-def attn_base_alg(q, k, v, heads, dtype, scale=None, offset=0.0, defect=None, tile=64):
+def attn_base_alg(q, k, v, heads, dtype, scale=None, offset=0.0, defect=None, tile=64, rowsum="fp32"):
     """csrc/attention.hip's design: Q pre-multiplied by scale * log2(e) and re-rounded to the storage dtype; P = 2^(s - m) with a
     reference m that sits `offset` (0 .. LAZY) below the row maximum; the row sum from the fp32 P, P rounded to the storage dtype
     for the P V product (fp32 accumulation), the quotient rounded once.
+    rowsum="rounded": the ONES forms (head widths with d % 16 == 8: 8, 24, 40 - every kernel that runs them) keep 1.0 in V's first pad
+    column, so the row sum comes out of the matrix core with the P V product: it is the sum of the ROUNDED P.
     defects: "flush_p" - P below 2^-14 becomes zero on its way into the product (a conversion or a matrix core that flushes fp16
     subnormals); "stale_reference" - the reference stays at the FIRST tile's maximum and is never raised, so P overflows the
-    storage dtype's range where later tiles rise."""
+    storage dtype's range where later tiles rise; "pad_key_admitted" - one key of a ragged tile's padding (zero K row: score 0, zero V
+    row) joins the softmax; "last_key_dropped" - the last valid key is left out."""
     d = q.shape[-1] // heads
     sl2 = (scale if scale is not None else 1.0 / math.sqrt(d)) * 1.4426950408889634
-    s = _heads(rnd(q.float() * sl2, dtype), heads) @ _heads(k.float(), heads).transpose(-1, -2)
+    kh, vh = _heads(k.float(), heads), _heads(v.float(), heads)
+    if defect == "pad_key_admitted":
+        kh = torch.cat([kh, torch.zeros_like(kh[:, :, :1])], dim=2)
+        vh = torch.cat([vh, torch.zeros_like(vh[:, :, :1])], dim=2)
+    if defect == "last_key_dropped":
+        assert kh.shape[2] >= 2
+        kh, vh = kh[:, :, :-1], vh[:, :, :-1]
+    s = _heads(rnd(q.float() * sl2, dtype), heads) @ kh.transpose(-1, -2)
     if defect == "stale_reference":
         m = s[..., :tile].max(dim=-1, keepdim=True).values
     else:
@@ -1019,13 +1055,123 @@ def attn_base_alg(q, k, v, heads, dtype, scale=None, offset=0.0, defect=None, ti
     if defect == "flush_p":
         p = torch.where(p < 2.0 ** FP16_NORMAL_MIN_LOG2, torch.zeros_like(p), p)
     p = rnd(p, dtype)
-    return rnd(_unheads((p @ _heads(v.float(), heads)) / l), dtype)
+    if rowsum == "rounded":
+        l = p.sum(dim=-1, keepdim=True)
+    else:
+        assert rowsum == "fp32"
+    return rnd(_unheads((p @ vh) / l), dtype)
 
 
-def attn_design_err(q, k, v, heads, dtype, ref64, scale=None):
+def attn_ones(d) -> bool:
+    """head widths whose kernels take the row sum from the ones column (rowsum="rounded")"""
+    return d % 16 == 8
+
+
+def attn_design_err(q, k, v, heads, dtype, ref64, scale=None, rowsum="fp32"):
     """row_err of the design: the worse of the two ends of the reference's allowed range (at the maximum: small P lowest; LAZY
     below it: large P highest)"""
-    return max(row_err(attn_base_alg(q, k, v, heads, dtype, scale, offset=o), ref64) for o in (0.0, LAZY))
+    return max(row_err(attn_base_alg(q, k, v, heads, dtype, scale, offset=o, rowsum=rowsum), ref64) for o in (0.0, LAZY))
+
+
+ATTN_INPUT_KINDS = ("randn", "shift-300", "shift+300", "last_key_decides", "one_loud_query", "loud_values_2e4")
+
+
+def attn_inputs(kind, N, heads, Sq, Skv, d, dtype, seed):
+    """(q, k, v) of one input class of the ragged-length cases, at any Skv >= 1 ("one_loud_query", "last_key_decides": Skv >= 2; the
+    loud key of one_loud_query sits among the last 16 keys - the ragged tile)"""
+    if kind == "randn":
+        g = _gen(seed)
+        return tuple(rnd(torch.randn(N, S, heads * d, generator=g, dtype=torch.float64), dtype) for S in (Sq, Skv, Skv))
+    if kind in ("shift-300", "shift+300"):
+        return common_shift(N, heads, Sq, Skv, d, 300.0 if kind == "shift+300" else -300.0, dtype, seed=seed)
+    if kind == "last_key_decides":
+        return last_key_decides(N, heads, Sq, Skv, d, dtype, seed=seed)
+    if kind == "one_loud_query":
+        return one_loud_query(N, heads, Sq, Skv, d, wave=32, dtype=dtype, seed=seed)
+    assert kind == "loud_values_2e4", kind
+    return loud_values(N, heads, Sq, Skv, d, 2.0e4, dtype, seed=seed)
+
+
+# Ragged lengths and poisoned views (tests/test_attention_gpu.py).  The kernels read K and V through buffer resources whose range check does
+# the predication and Q under `chunk < d / 8` with a clamped row: what lies behind a view must never reach the result, whatever it holds.
+ATTN_NAN_BITS = {torch.float16: 0x7E5A, torch.bfloat16: 0x7FA5}         # quiet NaNs with a payload no arithmetic produces
+ATTN_HUGE = {torch.float16: 6.0e4, torch.bfloat16: 3.0e38}              # finite, alternating sign: a max-reduction hides a NaN, not these
+ATTN_GUARD_ROWS = 64
+ATTN_PAD_COLS = 8
+
+
+def attn_poison_fill(numel, dtype, poison):
+    """flat tensor of the storage dtype filled with the poison: "nan" (the payload NaN) or "huge" (+-ATTN_HUGE, alternating)"""
+    if poison == "nan":
+        return torch.full((numel,), ATTN_NAN_BITS[dtype], dtype=torch.int16).view(dtype)
+    assert poison == "huge"
+    t = torch.full((numel,), ATTN_HUGE[dtype], dtype=torch.float32)
+    t[1::2] = -ATTN_HUGE[dtype]
+    t = t.to(dtype)
+    assert bool(torch.isfinite(t.float()).all()) and float(t.float().abs().min()) >= 0.99 * ATTN_HUGE[dtype]
+    return t
+
+
+def view_recipe(t):
+    """(storage offset, size, stride) of a view: with the whole buffer (t._base) enough to make the same view again elsewhere"""
+    return (int(t.storage_offset()), tuple(int(x) for x in t.shape), tuple(int(x) for x in t.stride()))
+
+
+def view_from(buf, recipe):
+    off, size, stride = recipe
+    return torch.as_strided(buf, size, stride, off)
+
+
+def attn_views(q, k, v, heads, dtype, poison, batch_slice=False):
+    """q [N, Sq, C], k, v [N, Skv, C] (fp32 tensors of dtype-rounded values) as column slices of ONE buffer [N, S_alloc, 3 * (C + 8)] of
+    the storage dtype: columns q | 8 pad | k | 8 pad | v | 8 pad (the chunk behind the last head of every operand is padding, the chunk
+    behind any other head is the next head), S_alloc = max(Sq, Skv) + 64 rows, and 64 rows' worth of elements between the samples (the
+    batch stride is larger than S_alloc * ld).  Every element that is not an operand element holds the poison.  batch_slice: the buffer
+    has a poisoned sample in front and one behind, the views are buf[1 : N + 1].
+    Returns the three views (each a view of the flat buffer, view._base) and the mask of poisoned elements (flat, bool)."""
+    N, Sq, C = q.shape
+    Skv = k.shape[1]
+    assert k.shape == v.shape and k.shape[0] == N and k.shape[2] == C and C % heads == 0 and (C // heads) % 8 == 0
+    ld = 3 * (C + ATTN_PAD_COLS)
+    s_alloc = max(Sq, Skv) + ATTN_GUARD_ROWS
+    bs = (s_alloc + ATTN_GUARD_ROWS) * ld
+    nb = N + (2 if batch_slice else 0)
+    buf = attn_poison_fill(nb * bs, dtype, poison)
+    mask = torch.ones(nb * bs, dtype=torch.bool)
+    views = []
+    for i, t in enumerate((q, k, v)):
+        off = (bs if batch_slice else 0) + i * (C + ATTN_PAD_COLS)
+        size, stride = (N, t.shape[1], C), (bs, ld, 1)
+        view = torch.as_strided(buf, size, stride, off)
+        view.copy_(t.to(dtype))
+        torch.as_strided(mask, size, stride, off).fill_(False)
+        views.append(view)
+    return views[0], views[1], views[2], mask
+
+
+def attn_out_guarded(N, Sq, C, dtype, device="cpu"):
+    """An `out` view [N, Sq, C] with ldo = C + 8 inside a buffer that is NaN (the payload NaN) everywhere: in the 8 padding columns of every
+    row, in 64 rows before the first sample, after the last and between samples.  Returns (out, check): out._base is the flat buffer;
+    check(out_buf) raises unless every guard element still holds the NaN's bit pattern (compared as integers) and the view holds no NaN."""
+    ldo = C + ATTN_PAD_COLS
+    bso = (Sq + ATTN_GUARD_ROWS) * ldo
+    numel = ATTN_GUARD_ROWS * ldo + N * bso
+    recipe = (ATTN_GUARD_ROWS * ldo, (N, Sq, C), (bso, ldo, 1))
+    guard = torch.ones(numel, dtype=torch.bool)
+    view_from(guard, recipe).fill_(False)
+    bits = ATTN_NAN_BITS[dtype]
+    out = view_from(attn_poison_fill(numel, dtype, "nan").to(device), recipe)
+
+    def check(out_buf):
+        b = out_buf.detach().to("cpu").reshape(-1)
+        assert b.dtype == dtype and b.numel() == numel, (b.dtype, b.numel(), numel)
+        raw = b.view(torch.int16).to(torch.int32) & 0xFFFF
+        hit = guard & (raw != bits)
+        assert not bool(hit.any()), f"{int(hit.sum())} guard elements of `out` were overwritten, the first at flat index {int(hit.nonzero()[0])} " \
+                                    f"(row {int(hit.nonzero()[0]) // ldo}, column {int(hit.nonzero()[0]) % ldo} of rows of {ldo})"
+        inside = view_from(b, recipe).float()
+        assert not bool(torch.isnan(inside).any()), f"{int(torch.isnan(inside).sum())} NaNs inside the `out` view (unwritten or poisoned elements)"
+    return out, check
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -1442,8 +1588,13 @@ def vae_sample_ref(mom, noise, L, scaling, prec, dtype=None):
 if __name__ == "__main__":
     import sys
     if "--attn-child" in sys.argv:
-        from tests import test_numerics_gpu as T
-        T.attention_child(sys.argv[sys.argv.index("--attn-child") + 1:])
+        args = sys.argv[sys.argv.index("--attn-child") + 1:]
+        if args[2] == "views":          # IN OUT views: the rows of tests/test_attention_gpu.py (views, guarded outputs, three launches each)
+            from tests import test_attention_gpu as A
+            A.attention_views_child(args)
+        else:
+            from tests import test_numerics_gpu as T
+            T.attention_child(args)
     elif "--report" in sys.argv:
         from tests import test_numerics_gpu as T
         only = sys.argv[sys.argv.index("--only") + 1] if "--only" in sys.argv else None

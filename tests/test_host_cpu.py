@@ -716,3 +716,80 @@ def test_fusion_block_refuses_operands_the_launch_cannot_read(monkeypatch):
         assert dry.size() == 1 and y.data_ptr() == out[1].data_ptr()
         outs = ops.fusion_blocks([(res, bs, params, HW, Cc)] * 3, N, scales, addends=[torch.zeros(N, HW, Cc).half()] * 3)
         assert dry.size() == 2 and len(outs) == 3 and outs[0].shape == (N, HW, Cc)
+
+
+def test_attention_refuses_operands_the_launch_cannot_read(monkeypatch):
+    """ops.attention hands data_ptr()s, one (N, heads, Sq, Skv, d) and row / batch strides to the library: k / v / out of another dtype,
+    N, width or length than that launch reads, a width that is no multiple of heads, a view whose address, row stride or batch stride
+    is not a whole number of 16-byte vectors (out: of 8-byte pieces) or whose rows overlap - EdgeStyleHipError, before anything is
+    recorded or launched (dry recorder, host buffers).  Column slices of a fused buffer, batch slices and a strided `out` stay legal.
+    es_attention itself refuses k / v whose 32-bit buffer range or tile offsets would pass 2^31."""
+    monkeypatch.setattr(ops, "_stream", lambda: None)
+    N, heads, Sq, Skv, Cc = 2, 2, 6, 5, 80
+    z = lambda *s: torch.zeros(*s).half()
+    q, k, v = z(N, Sq, Cc), z(N, Skv, Cc), z(N, Skv, Cc)
+    fused = z(N, Skv + 3, 3 * Cc + 24)
+    bad = {
+        "q must be fp16 or bf16": dict(q=q.float(), k=k.float(), v=v.float()),
+        "q, k, v must be .N, S, heads . d.": dict(q=q[0]),
+        "k is torch.bfloat16": dict(k=k.bfloat16()),
+        "v is torch.float32": dict(v=v.float()),
+        "out is torch.bfloat16": dict(out=q.bfloat16()),
+        "k is torch.float16 on meta": dict(k=k.to("meta")),
+        "k .* and v .* differ": dict(v=z(N, Skv + 1, Cc)),
+        "k / v .* do not match q .* in N or width": dict(k=z(N + 1, Skv, Cc), v=z(N + 1, Skv, Cc)),
+        "k / v .* do not match q .* in N or width#": dict(k=z(N, Skv, Cc + 8), v=z(N, Skv, Cc + 8)),
+        "width 80 is not a multiple of heads 3": dict(heads=3),
+        "out .* is not q's shape": dict(out=z(N, Sq + 1, Cc)),
+        "out .* is not q's shape#": dict(out=z(N * Sq, Cc)),
+        "innermost stride must be 1": dict(q=z(N, Cc, Sq).transpose(1, 2)),
+        "q: row stride 40 below the width 80": dict(q=torch.as_strided(z(4096), (N, Sq, Cc), (Sq * Cc, 40, 1))),
+        "k: row stride, batch stride and address must be multiples of 16 bytes": dict(k=z(N, Skv, Cc + 4)[..., :Cc]),
+        "v: row stride, batch stride and address must be multiples of 16 bytes": dict(v=z(N, Skv * Cc + 4)[:, :Skv * Cc].view(N, Skv, Cc)),
+        "q: row stride, batch stride and address must be multiples of 16 bytes": dict(q=z(N * Sq * Cc + 4)[4:].view(N, Sq, Cc)),
+        "out: row stride, batch stride and address must be multiples of 8 bytes": dict(out=z(N, Sq, Cc + 2)[..., :Cc]),
+        "out: row stride, batch stride and address must be multiples of 8 bytes#": dict(out=z(N * Sq * Cc + 2)[2:].view(N, Sq, Cc)),
+    }
+    with _DryPlan() as dry:
+        for msg, kw in bad.items():
+            a = dict(q=q, k=k, v=v, heads=heads, out=None)
+            a.update(kw)
+            with pytest.raises(lib.EdgeStyleHipError, match="attention: " + msg.rstrip("#")):
+                ops.attention(a["q"], a["k"], a["v"], a["heads"], out=a["out"])
+            assert dry.size() == 0, msg
+        y = ops.attention(q, k, v, heads)
+        assert dry.size() == 1 and y.shape == q.shape and y.is_contiguous()
+        # q | k | v as column slices of one fused projection (with padding columns), batch slices, an `out` with padded rows and samples
+        ops.attention(fused[:, :Sq - 2, :Cc], fused[:, :, Cc + 8:2 * Cc + 8], fused[:, :, 2 * Cc + 16:3 * Cc + 16], heads)
+        assert dry.size() == 2
+        big, outb = z(N + 2, Sq, Cc), z(N + 1, Sq + 3, Cc + 4)
+        y = ops.attention(big[1:N + 1], k, v, heads, out=outb[1:, 2:Sq + 2, :Cc])
+        assert dry.size() == 3 and y.data_ptr() == outb[1, 2].data_ptr()
+        ops.attention(torch.as_strided(z(128), (1, 1, Cc), (3, Cc, 1)), k[:1], v[:1], heads)      # one sample: its batch stride is never used
+        assert dry.size() == 4
+
+        # the library's own limit: ((Skv - 1) * ld + d) * 2 and (Skv + 2 * 64) * ld * 2 must fit in 31 bits, for k and for v
+        L = dry.L
+        hostbuf = (ctypes.c_char * 4096)()
+
+        def desc(**kw):
+            d = lib.AttnDesc()
+            d.q = d.k = d.v = d.o = ctypes.addressof(hostbuf)
+            d.N, d.heads, d.Sq, d.Skv, d.d = 1, 1, 64, 4096, 40
+            d.ldq = d.ldk = d.ldv = d.ldo = 40
+            d.bsq = d.bsk = d.bsv = d.bso = 0
+            d.scale, d.dtype = 1.0, lib.ES_F16
+            for name, val in kw.items():
+                setattr(d, name, val)
+            return d
+        assert L.es_attention(ctypes.byref(desc()), None) == 0 and dry.size() == 5
+        edge = (1 << 30) // (4096 + 128)                    # the largest row stride (elements) whose tile offsets stay below 2^31 ...
+        edge -= edge % 8
+        assert (4096 + 128) * edge * 2 < 1 << 31 <= (4096 + 128) * (edge + 8) * 2
+        assert L.es_attention(ctypes.byref(desc(ldk=edge, ldv=edge)), None) == 0 and dry.size() == 6
+        for kw in (dict(ldk=edge + 8), dict(ldv=edge + 8), dict(Skv=1 << 26), dict(Skv=(1 << 31) - 1, ldk=8, ldv=8, d=8)):
+            assert L.es_attention(ctypes.byref(desc(**kw)), None) == -1, kw
+            assert b"es_attention: k / v too long for 32-bit buffer offsets" in L.es_last_error(), (kw, L.es_last_error())
+            assert dry.size() == 6, kw
+        assert L.es_attention(ctypes.byref(desc(ldk=32)), None) == -1 and b"row stride below head_dim" in L.es_last_error()
+        assert dry.size() == 6

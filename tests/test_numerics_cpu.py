@@ -125,6 +125,113 @@ def test_attention_design_is_inside_the_bar(name, make, dtype):
     assert e_ref > 0 and 0 < max(e0, e8) <= nm.MARGIN * e_ref, (name, e0, e8, e_ref)
 
 
+def _attn_errs(q, k, v, heads, dtype, ref, **kw):
+    """row_err of attn_base_alg at both ends of the reference's range (offsets 0 and LAZY)"""
+    return [nm.row_err(nm.attn_base_alg(q, k, v, heads, dtype, offset=o, **kw), ref) for o in (0.0, nm.LAZY)]
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("d", [40, 80])
+@pytest.mark.parametrize("Skv", [5, 65, 77, 129])
+def test_attention_masking_defects_at_ragged_lengths(Skv, d, dtype):
+    """Key counts that end inside a tile, where the kernels mask: the design stays inside both bars on every input class, a padded key
+    admitted at score 0 (zero K row, zero V row) is outside them when all logits sit at -300 and EXACTLY as good as the design when
+    they sit at +300 (its weight is e^-300: the reason the shift-300 class exists, and why randn - weight 1 / (Skv + 1) - is a poor
+    judge of masking), and dropping the last valid key is outside them when that key decides."""
+    N, heads, Sq = 2, 2, 70
+    rowsum = "rounded" if nm.attn_ones(d) else "fp32"
+    got = {}
+    for kind in ("shift-300", "shift+300", "last_key_decides", "randn"):
+        q, k, v = nm.attn_inputs(kind, N, heads, Sq, Skv, d, dtype, seed=Skv + d)
+        ref = nm.attn_ref64(q, k, v, heads)
+        e_ref = nm.row_err(nm.attn_base_ref(q, k, v, heads, dtype), ref)
+        for rs in ("fp32", "rounded"):
+            e_alg = max(_attn_errs(q, k, v, heads, dtype, ref, rowsum=rs))
+            assert nm.attn_design_err(q, k, v, heads, dtype, ref, rowsum=rs) == e_alg
+            print(f"Skv={Skv} d={d} {dtype} {kind} rowsum={rs}: base_ref {e_ref:.3e} base_alg {e_alg:.3e}")
+            assert e_ref > 0 and 0 < e_alg <= nm.MARGIN * e_ref, (kind, rs, e_alg, e_ref)
+        e_alg = nm.attn_design_err(q, k, v, heads, dtype, ref, rowsum=rowsum)
+        got[kind] = (q, k, v, ref, e_alg, e_ref)
+    q, k, v, ref, e_alg, e_ref = got["shift-300"]
+    bad = _attn_errs(q, k, v, heads, dtype, ref, rowsum=rowsum, defect="pad_key_admitted")
+    print(f"Skv={Skv} d={d} {dtype} pad_key_admitted at -300: {min(bad):.3e} against base_alg {e_alg:.3e} base_ref {e_ref:.3e}")
+    assert min(bad) > _bar(e_alg, e_ref), (bad, e_alg, e_ref)
+    q, k, v, ref, e_alg, e_ref = got["shift+300"]
+    bad = _attn_errs(q, k, v, heads, dtype, ref, rowsum=rowsum, defect="pad_key_admitted")
+    print(f"Skv={Skv} d={d} {dtype} pad_key_admitted at +300: {max(bad):.3e} against base_alg {e_alg:.3e} base_ref {e_ref:.3e}")
+    assert max(bad) <= nm.MARGIN * min(e_alg, e_ref) and max(bad) == e_alg, (bad, e_alg, e_ref)
+    q, k, v, ref, e_alg, e_ref = got["last_key_decides"]
+    bad = _attn_errs(q, k, v, heads, dtype, ref, rowsum=rowsum, defect="last_key_dropped")
+    print(f"Skv={Skv} d={d} {dtype} last_key_dropped: {min(bad):.3e} against base_alg {e_alg:.3e} base_ref {e_ref:.3e}")
+    assert min(bad) > _bar(e_alg, e_ref), (bad, e_alg, e_ref)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_attention_generators_at_ragged_and_tiny_key_counts(dtype):
+    """the input classes of tests/test_attention_gpu.py assert their postconditions at every key count its table uses"""
+    for Skv in (1, 2, 5, 31, 33, 63, 64, 65, 77, 81, 96, 127, 129, 193, 320):
+        for d in (8, 40, 64, 512):
+            for kind in nm.ATTN_INPUT_KINDS:
+                if Skv == 1 and kind in ("one_loud_query", "last_key_decides"):
+                    continue
+                q, k, v = nm.attn_inputs(kind, 1, 2, 33, Skv, d, dtype, seed=Skv + d)
+                assert q.shape == (1, 33, 2 * d) and k.shape == v.shape == (1, Skv, 2 * d)
+                assert all(torch.equal(t, nm.rnd(t, dtype)) for t in (q, k, v))
+
+
+@pytest.mark.parametrize("poison", ["nan", "huge"])
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_attention_view_builders(dtype, poison):
+    """attn_views: the poisoned mask and the three views partition the buffer, the views equal the dense operands bit for bit, the
+    layout is the documented one; attn_out_guarded's check() notices one overwritten guard element and one NaN inside the view"""
+    N, heads, Sq, Skv, d = 3, 3, 70, 77, 40
+    C = heads * d
+    q, k, v = nm.attn_inputs("randn", N, heads, Sq, Skv, d, dtype, seed=1)
+    for sl in (False, True):
+        qv, kv, vv, mask = nm.attn_views(q, k, v, heads, dtype, poison, batch_slice=sl)
+        buf = qv._base
+        assert kv._base is buf and vv._base is buf and buf.dim() == 1 and buf.dtype == dtype and mask.shape == buf.shape
+        ld, s_alloc = 3 * (C + 8), max(Sq, Skv) + 64
+        assert qv.stride() == kv.stride() == vv.stride() == ((s_alloc + 64) * ld, ld, 1) and qv.stride(0) > s_alloc * ld
+        assert buf.numel() == (N + 2 * sl) * qv.stride(0)
+        assert kv.storage_offset() - qv.storage_offset() == C + 8 == vv.storage_offset() - kv.storage_offset()
+        assert qv.storage_offset() == (qv.stride(0) if sl else 0)
+        cover = torch.zeros(buf.numel(), dtype=torch.int32)
+        for t in (qv, kv, vv):
+            nm.view_from(cover, nm.view_recipe(t)).add_(1)
+        cover += mask.int()
+        assert bool((cover == 1).all())                                             # a partition: every element exactly once
+        for t, dense in ((qv, q), (kv, k), (vv, v)):
+            assert t.shape == dense.shape and torch.equal(t.contiguous().view(torch.int16), dense.to(dtype).view(torch.int16))
+            assert torch.equal(nm.view_from(buf, nm.view_recipe(t)), t)
+        pz = buf[mask].float()
+        if poison == "nan":
+            assert bool(torch.isnan(pz).all()) and bool((buf[mask].view(torch.int16).int() & 0xFFFF == nm.ATTN_NAN_BITS[dtype]).all())
+        else:
+            assert bool(torch.isfinite(pz).all()) and float(pz.abs().min()) > 5.9e4 and bool((pz > 0).any()) and bool((pz < 0).any())
+    out, check = nm.attn_out_guarded(N, Sq, C, dtype)
+    ob = out._base
+    assert out.shape == (N, Sq, C) and out.stride() == ((Sq + 64) * (C + 8), C + 8, 1) and out.storage_offset() == 64 * (C + 8)
+    assert ob.numel() == (64 + N * (Sq + 64)) * (C + 8) and bool(torch.isnan(ob.float()).all())
+    with pytest.raises(AssertionError, match="inside"):
+        check(ob)                                                                   # nothing written yet: the view is all NaN
+    out.copy_(q.to(dtype))
+    check(ob)
+    for where in (0, out.storage_offset() - 1, out.storage_offset() + C, out.storage_offset() + Sq * (C + 8), ob.numel() - 1):
+        hurt = ob.clone()
+        hurt[where] = 1.0
+        with pytest.raises(AssertionError, match="guard"):
+            check(hurt)
+        hurt[where] = float("nan")                                                  # another NaN than the payload one is an overwrite too
+        if (int(hurt[where].view(torch.int16)) & 0xFFFF) != nm.ATTN_NAN_BITS[dtype]:
+            with pytest.raises(AssertionError, match="guard"):
+                check(hurt)
+    hurt = ob.clone()
+    nm.view_from(hurt, nm.view_recipe(out))[N - 1, Sq - 1, C - 1] = float("nan")
+    with pytest.raises(AssertionError, match="inside"):
+        check(hurt)
+
+
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_planted_colsum_of_the_unrounded_weights_exceeds_the_bar(dtype):
     """the column sums must be those of the ROUNDED W * gamma the matrix cores multiply: taken from the unrounded product they leave

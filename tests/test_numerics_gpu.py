@@ -633,28 +633,52 @@ def _sampler_section():
     return "\n".join(out), len(rows)
 
 
+ATTENTION_MARKERS = ("<!-- attention table begin: written by `python -m tests.numerics --report --only attention` -->", "<!-- attention table end -->")
+
+
+def _attention_section():
+    from tests import test_attention_gpu as AG
+    rows, secs, cpu = AG.report_rows()
+    out = [f"Attention at ragged lengths, measured on {torch.cuda.get_device_name(0)}, torch {torch.__version__}; {len(rows)} rows (three launches each) in "
+           f"{sum(secs.values()):.1f} s, of which CPU baselines {cpu:.2f} s; per variant: " + ", ".join(f"{v} {s:.1f} s" for v, s in secs.items()) + ".  "
+           "`views`: the outputs through NaN- and huge-poisoned views equal the dense launch's bit for bit; `guards`: every guard element kept its NaN "
+           "bits and the view holds no NaN.  One key: the output is v[:, 0] bit for bit (kernel error 0, no baselines).", "",
+           "| case | kernel ids | kernel | base_alg | base_ref | kernel / base_alg | kernel / base_ref | views | guards |", "|---|---|---|---|---|---|---|---|---|"]
+    for r in rows:
+        if r["base_alg"] is None:
+            num = f"{r['kernel']:.2e} | - | - | - | -"
+        else:
+            num = f"{r['kernel']:.2e} | {r['base_alg']:.2e} | {r['base_ref']:.2e} | {_div(r['kernel'], r['base_alg']):.2f} | {_div(r['kernel'], r['base_ref']):.2f}"
+        out.append(f"| {r['case']} | {','.join(str(i) for i in r['ids'])} | {num} | {'equal' if r['same'] else 'DIFFER'} | {'intact' if r['guards'] else 'BROKEN'} |")
+    return "\n".join(out), len(rows)
+
+
+_SECTIONS = {"fusion": (_fusion_section, FUSION_MARKERS), "sampler": (_sampler_section, SAMPLER_MARKERS), "attention": (_attention_section, ATTENTION_MARKERS)}
+
+
 def _write_sections(doc, path, which):
     text = open(doc).read()
     for name in which:
-        body, n = _fusion_section() if name == "fusion" else _sampler_section()
-        text = _replace_between(text, FUSION_MARKERS if name == "fusion" else SAMPLER_MARKERS, body)
+        section, markers = _SECTIONS[name]
+        body, n = section()
+        text = _replace_between(text, markers, body)
         print(f"{n} {name} cases -> {path}")
     with open(path, "w") as f:
         f.write(text)
 
 
 def write_report(path=None, only=None):
-    """python -m tests.numerics --report [--only conv | fusion | sampler]: run every case above and the convolution sweep of
+    """python -m tests.numerics --report [--only conv | fusion | sampler | attention]: run every case above and the convolution sweep of
     tests/test_conv_gpu.py without asserting and write the measured tables (--only conv: the convolution table alone, the other is kept
-    as it is; --only fusion, --only sampler: the table of tests/test_fusion_gpu.py or tests/test_sampler_gpu.py alone, between its marker
-    lines)"""
+    as it is; --only fusion, --only sampler, --only attention: the table of tests/test_fusion_gpu.py, tests/test_sampler_gpu.py or
+    tests/test_attention_gpu.py alone, between its marker lines)"""
     global RECORD
     import tempfile
     import pathlib
     assert torch.cuda.is_available(), "the report is measured on the GPU"
     doc = os.path.join(ROOT, "tests", "NUMERICS.md")
     RECORD = []
-    if only in ("fusion", "sampler"):           # their tables sit between marker lines of their own, above the first measured table
+    if only in ("fusion", "sampler", "attention"):           # their tables sit between marker lines of their own, above the first measured table
         try:
             _write_sections(doc, path or doc, [only])
         finally:

@@ -133,14 +133,15 @@ ATTN_CASES = [
     (1, 4, 16, 16, 64),
     (1, 1, 256, 256, 512),     # VAE mid-block attention
     (1, 8, 1024, 1024, 40),
-    # >= 512 blocks of 128 queries: the 32x32-score-tile kernel (head_dim 40 / 80)
+    # >= 512 blocks of 128 queries: the 32x32-score-tile kernel at head_dim 40, the 32-queries-per-wave generic kernel at head_dim 80
     (8, 8, 1024, 1024, 40),
     (8, 8, 1000, 77, 40),      # ragged queries and keys
     (8, 8, 1024, 200, 80),
     (16, 8, 520, 136, 80),
     # >= 512 blocks of 256 queries at head_dim 40: two 32-query blocks per wave share every K / V fragment read
     (16, 8, 1024, 1024, 40),
-    (16, 8, 1000, 77, 40),     # ragged queries (last wave: one block partly, one block entirely out of range) and keys
+    (16, 8, 1000, 77, 40),     # ragged queries and keys: <= 96 keys from 12 workgroups per strip on, so this one runs on attention_kvres_kernel
+                               # (the two-block kernel's ragged last wave is in tests/test_attention_gpu.py)
     (5, 32, 900, 333, 40),
 ]
 
