@@ -298,8 +298,7 @@ struct CA {                       // keyword arguments of ops.conv_gemm
   int gn_groups = 0;              // > 0: the output is read by a GroupNorm over that many groups - hand the statistics over
 };
 
-// ---- the launch planner of edgestyle_amd/ops.py (plan_gemm, xs_eligible): identical decisions are what makes a natively built
-// context bit-identical to a Python-built one; tests/test_host_cpu.py sweeps both over the shapes of the model ---------------
+// ---- the launch planner (es_plan_gemm_choice; ops.plan_gemm_reference restates it and tests/test_load_weights_cpu.py sweeps both) ----
 #pragma clang fp contract(off)
 constexpr double PLAN_T160 = 1.25, PLAN_ALONE = 0.9, PLAN_TFIX = 2.0, PLAN_RED_FIX = 12.0, PLAN_SLAB_BYTES_PER_UNIT = 4.0e6;
 constexpr double PLAN_T320 = 2.3, PLAN_T320_FIX = 3.0;
@@ -385,20 +384,108 @@ bool xs_shape_fits(int ksize, int kpad, int cin, int ctail, int cout, bool geglu
   const int line = ch * (128 / (geglu ? ch : 2 * ch));
   return !(cout % line || cout < 4 * line);
 }
-bool xs_shape_ok(long long M, int ksize, int kpad, int cin, int ctail, int cout, bool geglu) {       // ... and where it wins
+bool xs_shape_ok(long long M, int ksize, int kpad, int cin, int ctail, int cout, bool geglu, long long min_m) {       // ... and where it wins (min_m 0: everywhere)
   if (!xs_shape_fits(ksize, kpad, cin, ctail, cout, geglu)) return false;
-  if (M < XS_MIN_M || (M < 4 * XS_MIN_M && cout < (kpad == 320 ? 960 : 1920))) return false;
+  if (min_m && (M < min_m || (M < 4 * min_m && cout < (kpad == 320 ? 960 : 1920)))) return false;
   return true;
 }
-bool gn_fold_on() { static const bool on = [] { const char* e = getenv("ES_GN_FOLD"); return !e || std::string(e) == "1"; }(); return on; }
 int choose_bn(int cout) { return (cout % 160 == 0 && cout % 128 != 0) ? 160 : 128; }
-bool big_tile_256() { static const bool on = [] { const char* e = getenv("ES_BIG_TILE_256"); return !e || e[0] != '0'; }(); return on; }
+
+// ---- the launch policy (include/edgestyle_hip.h es_launch_choose): what BOTH hosts ask between validating a call and filling its
+// descriptor - ops.conv_gemm / gn_proj_in / group_norm and the Builder below ---------------------------------------------------------
+bool wide_stream(int dtype, const es_launch_knobs& k) { return k.wide_stream == 1 || (k.wide_stream < 0 && dtype == ES_BF16); }
+// a rule of the SHAPE alone (grouped and per-net launches of a layer must agree): where the stand-alone GroupNorm is the two-launch form -
+// slabs too large for a workgroup's registers, the 64 x 64 level - the hand-over removes its statistics launch and second read
+bool gn_handover(long long hw, int c, int groups, const es_launch_knobs& k) {
+  if (!k.gn_handover || groups < 1 || c % 8 || hw % 64 || c % groups || c / groups > 64) return false;
+  return k.gn_handover == 2 || !es_group_norm_is_slab((int)hw, c, groups);
+}
+bool groups_tile_256(const es_launch_query& q) {
+  for (int g = 0; g < std::min(q.n_counts, 4); ++g) if ((q.group_n[g] * q.hw) % 256) return false;
+  return true;
+}
+// does this plain linear launch go to es_linear_xs?  (A residual rides along at K = 320 - Attention.to_out / proj_out of the 64 x 64
+// level - unless the launch carries the two-word residual stream, which only es_conv_gemm implements.)
+bool launch_takes_xs(const es_launch_query& q, const es_launch_knobs& k) {
+  const bool xs_res = !q.has_residual || (k.xs_residual && q.kpad == 320 && !q.geglu && !q.has_ln && q.residual_dense && !(q.wide && wide_stream(q.dtype, k)));
+  if (!(q.ksize == 1 && q.stride == 1 && !q.upsample && !q.C2 && !q.has_temb && xs_res && !q.n_tails && q.x_rep == 1 && q.act == ES_ACT_NONE &&
+        q.unit_scale && !q.force_splitk && !k.force_bn && k.xs_enabled)) return false;
+  if (q.ngroups > 1 && (q.ngroups > 4 || !groups_tile_256(q) || !q.groups_agree)) return false;
+  return xs_shape_ok(q.M, q.ksize, q.kpad, q.cin, q.ctail, q.cout, q.geglu != 0, k.xs_min_m);
+}
+bool launch_choose(const es_launch_query& q, const es_launch_knobs& k, es_launch_choice* o) {
+  memset(o, 0, sizeof(*o));
+  if (launch_takes_xs(q, k)) { o->route = ES_ROUTE_LINEAR_XS; return true; }
+  const bool aligned = q.C1 % BK == 0 && q.C2 % BK == 0;
+  const bool big_ok = k.big_tile && aligned && !q.geglu && !q.has_ln && groups_tile_256(q);
+  const bool small_ok = k.small_tile && aligned && !q.geglu && k.force_waves != 8;
+  // the 256 x 256 phase-interleaved tile: LayerNorm-folded and GEGLU linear layers whose N is a multiple of 256
+  const bool ln256_ok = k.big_tile_256 && (q.geglu || q.has_ln) && q.ksize == 1 && q.stride == 1 && !q.upsample && !q.C2 && !q.n_tails && !q.has_temb &&
+                        q.x_rep == 1 && q.C1 % BK == 0 && q.rows_padded % 256 == 0 && q.cout % 8 == 0 && !(q.geglu && q.has_residual) && !q.wide &&
+                        q.gn_groups == 0 && k.force_waves != 8 && groups_tile_256(q);
+  int cand[5], nc = 0;
+  if (ln256_ok) cand[nc++] = 256;
+  if (big_ok) cand[nc++] = 320;
+  cand[nc++] = 160; cand[nc++] = 128;
+  if (small_ok) cand[nc++] = 64;
+  if (k.force_bn) { cand[0] = k.force_bn; nc = 1; }
+  const bool geglu = q.geglu != 0, allow_split = !q.has_ln;
+  int bn, splitk, stages;
+  if (!plan_gemm(q.M, q.rows_padded, q.kpad, geglu, cand, nc, allow_split, &bn, &splitk, &stages)) return false;
+  if (bn == 320 && !k.force_bn && (q.force_splitk ? q.force_splitk : splitk) == 1 &&
+      !es_conv_gemm8p_form_ok(geglu ? ES_ACT_GEGLU : q.act, q.cout, q.has_temb, q.hw, q.has_residual)) {
+    // the 256 x 320 tile does not implement this epilogue form (an activation, time-embedding rows that differ inside a 128-pixel half
+    // or meet a residual): plan again without it, so that the tile planned, recorded and reported is the tile that runs
+    const int at = (int)(std::find(cand, cand + nc, 320) - cand);
+    std::copy(cand + at + 1, cand + nc, cand + at);
+    if (!plan_gemm(q.M, q.rows_padded, q.kpad, geglu, cand, nc - 1, allow_split, &bn, &splitk, &stages)) return false;
+  }
+  if (stages == 4 && !k.deep_ring) stages = 2;
+  if (q.force_splitk) { splitk = q.force_splitk; stages = q.stages; }       // (the planner's ring depth belongs to ITS split)
+  else if (q.stages) stages = q.stages;
+  if (!stages) stages = k.force_stages;
+  o->bn = bn; o->splitk = splitk; o->stages = stages;
+  // 1x1 convs / linears are short-K, latency-bound launches: two waves per SIMD on the same 128-pixel tile overlap DMA issue, fragment reads
+  // and MFMAs (tools/gemm_tune.py: 3-15 % on every 1x1 shape of a batch-1 step, none on 3x3 or on the memory-bound 1x1 launches of large batches)
+  if (k.force_waves) o->waves = k.force_waves;
+  else if (k.eight_waves && q.ksize == 1 && q.M <= 65536 && aligned && bn != 64 && bn != 320 && bn != 256 && !(stages == 4 && bn != 128) && stages != 3) o->waves = 8;
+  // XCD chunk order: keep the larger operand's tiles together on one XCD (gemm_conv.hip conv_gemm_kernel)
+  o->xcd_m_fastest = k.xcd_order < 0 ? (q.ngroups <= 1 && splitk == 1 && q.M <= 2048 && q.w_numel > q.src_numel) : k.xcd_order;
+  const int cstore = geglu ? q.cout / 2 : q.cout;
+  o->gn_partials = q.gn_groups > 0 && gn_handover(q.hw, cstore, q.gn_groups, k) && !geglu && !q.has_ln && q.cout / q.gn_groups <= (bn == 320 ? 160 : bn);
+  o->wide = q.wide && q.has_residual && wide_stream(q.dtype, k) && cstore % 8 == 0 && !geglu;
+  return true;
+}
+// Transformer2DModel.norm -> proj_in as a statistics pass and the projection on es_linear_xs, which applies the GroupNorm to the rows it
+// holds in registers: where the projection runs on that kernel anyway, and at K = 320 from 8192 rows on (profiles/r05_gn_proj_in.txt)
+bool launch_gn_fold(const es_launch_query& q, int groups, const es_launch_knobs& k) {
+  if (!(k.gn_fold && k.xs_enabled) || k.gn_handover || q.hw % 256 || groups < 1 || groups > 32) return false;
+  if (q.geglu || q.has_ln || q.kpad % groups || !xs_shape_fits(q.ksize, q.kpad, q.cin, q.ctail, q.cout, false)) return false;
+  if (q.M < (q.kpad == 320 ? 8192 : 32768)) return false;
+  return !(q.ngroups > 1 && (q.ngroups > 4 || !groups_tile_256(q) || !q.groups_agree));
+}
+// The switches es_load_weights honours (README.md), read once per build; every other knob is at its default.  ES_CHUNK_MAJOR belongs to
+// weight packing (ops.choose_korder), not to a launch.
+struct BuildEnv { es_launch_knobs knobs; bool chunk_major; };
+BuildEnv read_build_env() {
+  auto env = [](const char* name, const char* dflt) { const char* e = getenv(name); return std::string(e ? e : dflt); };
+  const std::string ho = env("ES_GN_HANDOVER", "0"), ws = env("ES_WIDE_STREAM", "auto");      // off / bf16 only by default: ops.py says why
+  BuildEnv b;
+  b.chunk_major = env("ES_CHUNK_MAJOR", "0") == "1";
+  es_launch_knobs& k = b.knobs;
+  memset(&k, 0, sizeof(k));
+  k.xs_enabled = k.big_tile = k.small_tile = k.eight_waves = k.deep_ring = 1; k.xs_min_m = XS_MIN_M; k.xcd_order = -1;
+  k.xs_residual = env("ES_XS_RESIDUAL", "1") == "1"; k.big_tile_256 = env("ES_BIG_TILE_256", "1")[0] != '0'; k.gn_fold = env("ES_GN_FOLD", "1") == "1";
+  k.gn_handover = ho == "all" ? 2 : ho == "1"; k.wide_stream = ws == "auto" ? -1 : ws == "1";
+  return b;
+}
 
 // ---- the builder ------------------------------------------------------------------------------------------------------------
 struct Builder {
   Heap heap;
   unsigned long long ws_bytes = 0;
   int dt = ES_F16;
+  const BuildEnv env = read_build_env();
   std::vector<std::pair<unsigned long long, std::vector<char>>> uploads;     // (fake address, bytes) of everything persistent with contents
   std::deque<PW> pws;
   std::map<std::string, const PW*> pack_cache;
@@ -440,18 +527,6 @@ struct Builder {
     ok(es_add(a.ptr(), b.ptr(), out.ptr(), a.numel(), dt, nullptr), "es_add");
     return out;
   }
-  // ops.gn_handover: a rule of the shape alone - where the stand-alone GroupNorm is the two-launch form
-  static bool gn_handover(long long hw, int c, int groups) {
-    static const std::string mode = [] { const char* e = getenv("ES_GN_HANDOVER"); return std::string(e ? e : "0"); }();      // off by default: measured a net loss (ops.py)
-    if ((mode != "1" && mode != "all") || c % 8 || hw % 64 || c % groups || c / groups > 64) return false;
-    return mode == "all" || !es_group_norm_is_slab((int)hw, c, groups);
-  }
-  static bool gn_handover_on() { const char* e = getenv("ES_GN_HANDOVER"); const std::string m(e ? e : "0"); return m == "1" || m == "all"; }
-  // ops.wide_stream: "auto" (default) = bf16 pipelines only
-  bool wide_stream() const {
-    static const std::string mode = [] { const char* e = getenv("ES_WIDE_STREAM"); return std::string(e ? e : "auto"); }();
-    return mode == "1" || (mode == "auto" && dt == ES_BF16);
-  }
   uint16_t enc(float f) const { return dt == ES_F16 ? f32_to_f16(f) : f32_to_bf16(f); }
   float dec(uint16_t u) const { return dt == ES_F16 ? f16_to_f32(u) : bf16_to_f32(u); }
 
@@ -474,8 +549,7 @@ struct Builder {
     p.cout = cout_eff; p.cin = cp; p.ksize = k; p.bn = bn; p.rows_padded = rows; p.kpad = kpad; p.geglu = geglu; p.ctail = ctail;
     // K order (ops.choose_korder): with ES_CHUNK_MAJOR=1 every 3x3 convolution over 64-aligned channels is packed chunk-major,
     // k = (c / 64, tap, c % 64); the default is tap-major (the chunk-major order measured 5-10 % slower, ops.py)
-    static const bool chunk_major_on = [] { const char* e = getenv("ES_CHUNK_MAJOR"); return e && e[0] == '1' && !e[1]; }();
-    const bool chunk_major = chunk_major_on && k == 3 && cp % BK == 0;
+    const bool chunk_major = env.chunk_major && k == 3 && cp % BK == 0;
     p.korder = chunk_major ? 1 : 0;
     p.w = persistent((size_t)rows * kpad * 2);
     uint16_t* dst = (uint16_t*)staged(p.w, (size_t)rows * kpad * 2);
@@ -641,6 +715,23 @@ struct Builder {
     return out;
   }
 
+  // the facts of a call the launch policy looks at (es_launch_query)
+  es_launch_query launch_query(const PWs& pl, long long M, long long hw, const CA& a, int C1, int C2, long long src_numel, bool residual_dense) const {
+    const PW* pw = pl[0];
+    es_launch_query q;
+    memset(&q, 0, sizeof(q));
+    q.M = M; q.hw = hw; q.w_numel = pw->w_numel(); q.src_numel = src_numel; q.ksize = pw->ksize; q.stride = a.stride; q.upsample = a.upsample; q.C1 = C1; q.C2 = C2;
+    q.rows_padded = pw->rows_padded; q.kpad = pw->kpad; q.cin = pw->cin; q.ctail = pw->ctail; q.cout = pw->cout; q.geglu = pw->geglu; q.has_ln = pw->ln_colsum != 0;
+    q.act = a.act; q.has_temb = (bool)a.temb; q.has_residual = (bool)a.residual; q.residual_dense = residual_dense; q.unit_scale = a.out_scale == 1.f && !a.out_scale_dev;
+    q.n_tails = (int)a.tails.size(); q.x_rep = a.x_rep; q.wide = a.wide; q.dtype = dt; q.gn_groups = a.gn_groups;
+    if (pl.size() > 1) {
+      q.ngroups = (int)pl.size(); q.n_counts = (int)a.group_n.size(); q.groups_agree = 1;
+      for (size_t g = 0; g < std::min<size_t>(a.group_n.size(), 4); ++g) q.group_n[g] = a.group_n[g];
+      for (const PW* p : pl) if ((p->ln_colsum == 0) != (pw->ln_colsum == 0)) q.groups_agree = 0;
+    }
+    return q;
+  }
+
   T conv_gemm(const T& x, const PWs& pl, const CA& a = CA()) {
     const PW* pw = pl[0];
     const bool grouped = pl.size() > 1;
@@ -661,45 +752,18 @@ struct Builder {
     T out = a.out ? a.out : empty(N, Hout, Wout, cstore);
     if (out.numel() != (long long)N * Hout * Wout * cstore || !out.contig()) fail("conv_gemm: output buffer of another size");
     const long long M = (long long)N * Hout * Wout, hw = (long long)Hout * Wout;
-    // (a residual rides on es_linear_xs at K = 320, unless the launch carries the two-word residual stream: ops.conv_gemm)
-    static const bool xs_residual = [] { const char* e = getenv("ES_XS_RESIDUAL"); return !e || std::string(e) == "1"; }();
-    const bool xs_res = !a.residual || (xs_residual && pw->kpad == 320 && !pw->geglu && !pw->ln_colsum && a.residual.contig() &&
-                                        a.residual.numel() == (long long)N * Hout * Wout * cstore && !(a.wide && wide_stream()));
-    const bool plain = k == 1 && a.stride == 1 && !a.upsample && !a.x2 && !a.temb && xs_res && a.tails.empty() && a.x_rep == 1 &&
-                       a.act == ES_ACT_NONE && a.out_scale == 1.f && !a.out_scale_dev;
-    if (plain && xs_shape_ok(M, pw->ksize, pw->kpad, pw->cin, pw->ctail, pw->cout, pw->geglu)) {
-      bool e = true;
-      if (grouped) {
-        if (pl.size() > 4) e = false;
-        for (int n : a.group_n) if ((n * hw) % 256) e = false;
-        for (const PW* q : pl) if ((q->ln_colsum == 0) != (pw->ln_colsum == 0)) e = false;
-      }
-      if (e) {
-        std::vector<long long> rows;
-        for (int n : a.group_n) rows.push_back(n * hw);
-        T xo = out;
-        linear_xs(x, grouped ? pl : PWs{pw}, M, xo, rows, a.residual);
-        return out;
-      }
+    const es_launch_query q = launch_query(pl, M, hw, a, C1, C2, x.numel() * a.x_rep + (a.x2 ? a.x2.numel() : 0),
+                                           a.residual && a.residual.contig() && a.residual.numel() == M * cstore);
+    es_launch_choice ch;
+    if (!launch_choose(q, env.knobs, &ch)) fail("plan_gemm: rows_padded fits no N tile");
+    if (ch.route == ES_ROUTE_LINEAR_XS) {
+      std::vector<long long> rows;
+      for (int n : a.group_n) rows.push_back(n * hw);
+      T xo = out;
+      linear_xs(x, grouped ? pl : PWs{pw}, M, xo, rows, a.residual);
+      return out;
     }
-    bool big_ok = C1 % BK == 0 && C2 % BK == 0 && !pw->geglu && !pw->ln_colsum;
-    if (big_ok && grouped) for (int n : a.group_n) if ((n * hw) % 256) big_ok = false;
-    // the 256 x 256 phase-interleaved tile: LayerNorm-folded and GEGLU linear layers whose N is a multiple of 256 (ops.conv_gemm: the same rule)
-    bool ln256_ok = big_tile_256() && (pw->geglu || pw->ln_colsum) && k == 1 && a.stride == 1 && !a.upsample && !a.x2 && a.tails.empty() && !a.temb &&
-                    a.x_rep == 1 && C1 % BK == 0 && pw->rows_padded % 256 == 0 && pw->cout % 8 == 0 && !(pw->geglu && a.residual) && !a.wide && a.gn_groups == 0;
-    if (ln256_ok && grouped) for (int n : a.group_n) if ((n * hw) % 256) ln256_ok = false;
-    const bool small_ok = C1 % BK == 0 && C2 % BK == 0 && !pw->geglu;
-    int cand[5], nc = 0;
-    if (ln256_ok) cand[nc++] = 256;
-    if (big_ok) cand[nc++] = 320;
-    cand[nc++] = 160; cand[nc++] = 128;
-    if (small_ok) cand[nc++] = 64;
-    int bn, splitk, stages;
-    if (!plan_gemm(M, pw->rows_padded, pw->kpad, pw->geglu, cand, nc, pw->ln_colsum == 0, &bn, &splitk, &stages)) fail("plan_gemm: rows_padded fits no N tile");
-    if (bn == 320 && splitk == 1 && !es_conv_gemm8p_form_ok(act_i, pw->cout, a.temb ? 1 : 0, hw, a.residual ? 1 : 0)) {
-      // the 256 x 320 tile does not implement this epilogue form: plan again without it (ops.conv_gemm does the same)
-      if (!plan_gemm(M, pw->rows_padded, pw->kpad, pw->geglu, cand + 1, nc - 1, pw->ln_colsum == 0, &bn, &splitk, &stages)) fail("plan_gemm: rows_padded fits no N tile");
-    }
+    const int bn = ch.bn, splitk = ch.splitk;
     es_gemm_desc d;
     memset(&d, 0, sizeof(d));
     d.x = x.ptr(); d.x2 = a.x2 ? a.x2.ptr() : nullptr; d.w = (const void*)pw->w; d.bias = (const float*)pw->bias;
@@ -708,24 +772,22 @@ struct Builder {
     d.N = N; d.Hsrc = H; d.Wsrc = Wd; d.C1 = C1; d.C2 = C2; d.Hout = Hout; d.Wout = Wout; d.Cout = pw->cout;
     d.rows_padded = pw->rows_padded; d.Kpad = pw->kpad; d.ksize = k; d.stride = a.stride; d.pad = pad; d.upsample = a.upsample;
     d.temb_stride = a.temb ? (int)a.temb_stride : 0;
-    d.act = act_i; d.splitk = splitk; d.bn = bn; d.dtype = dt; d.out_scale = a.out_scale; d.stages = stages;
-    const long long src_numel = x.numel() * a.x_rep + (a.x2 ? a.x2.numel() : 0);
-    d.xcd_m_fastest = (!grouped && splitk == 1 && M <= 2048 && pw->w_numel() > src_numel) ? 1 : 0;
+    d.act = act_i; d.splitk = splitk; d.bn = bn; d.dtype = dt; d.out_scale = a.out_scale; d.stages = ch.stages;
+    d.waves = ch.waves; d.xcd_m_fastest = ch.xcd_m_fastest;
     d.x_nmod = a.x_rep > 1 ? nsrc : 0;
     d.korder = pw->korder;
-    if (a.gn_groups > 0 && gn_handover(hw, cstore, a.gn_groups) && !pw->geglu && !pw->ln_colsum && pw->cout / a.gn_groups <= (bn == 320 ? 160 : bn)) {
+    if (ch.gn_partials) {
       T part = empty(N, (int)(2 * (hw / 64)), 1, a.gn_groups * 2, 4);
       d.gn_part = (float*)part.ptr(); d.gn_groups = a.gn_groups;
       out.gnp = part.p; out.gnp_b = part.b; out.gnp_groups = a.gn_groups;
     }
-    if (a.wide && a.residual && wide_stream() && cstore % 8 == 0 && !pw->geglu) {
+    if (ch.wide) {
       // the sum over (residual hi + lo) in fp32, stored as hi + lo (es_gemm_desc.out_lo)
       if (a.residual.lo) d.residual_lo = (const void*)a.residual.lo;
       T lo = empty(N, Hout, Wout, cstore);
       d.out_lo = lo.ptr();
       out.lo = lo.p; out.lo_b = lo.b;
     }
-    if (k == 1 && M <= 65536 && C1 % BK == 0 && C2 % BK == 0 && bn != 64 && bn != 320 && bn != 256 && !(stages == 4 && bn != 128) && stages != 3) d.waves = 8;
     if (splitk > 1) d.workspace = (float*)workspace((unsigned long long)splitk * M * pw->rows_padded * 4);
     if (pw->ln_colsum) {
       for (const PW* q : pl) if (!q->ln_colsum) fail("LayerNorm-folded weights need a plain linear launch (all groups folded)");
@@ -805,7 +867,7 @@ struct Builder {
       for (size_t g = 0; g < nl.size(); ++g) { acc += group_n[g]; d.n_end[g] = acc; d.gamma_g[g] = (const float*)nl[g].g; d.beta_g[g] = (const float*)nl[g].b; }
     } else { d.gamma = (const float*)nl[0].g; d.beta = (const float*)nl[0].b; }
     d.N = N; d.HW = (int)x.hw(); d.C1 = C1; d.C2 = C2; d.groups = groups; d.eps = eps; d.silu = silu; d.dtype = dt;
-    if (x.gnp && !x2 && gn_handover(x.hw(), C1, groups) && x.gnp_groups == groups) {      // the producer's statistics: one streaming pass
+    if (x.gnp && !x2 && gn_handover(x.hw(), C1, groups, env.knobs) && x.gnp_groups == groups) {      // the producer's statistics: one streaming pass
       d.partials = (float*)x.gnp; d.ext_chunks = (int)(2 * (x.hw() / 64));
     }
     ok(es_group_norm(&d, nullptr), "es_group_norm");
@@ -815,27 +877,15 @@ struct Builder {
 
   // Transformer2DModel.norm -> proj_in (ops.gn_proj_in: the same rule, the same two launches): a statistics pass and the projection on
   // es_linear_xs with the GroupNorm applied to the rows it holds in registers; elsewhere es_group_norm + es_conv_gemm as before
-  bool gn_fold_ok(long long M, long long hw, int groups, const PWs& pl, const std::vector<int>& group_n) const {
-    const PW* pw = pl[0];
-    if (!gn_fold_on() || gn_handover_on() || hw % 256 || groups > 32) return false;
-    if (pw->geglu || pw->ln_colsum || pw->kpad % groups || !xs_shape_fits(pw->ksize, pw->kpad, pw->cin, pw->ctail, pw->cout, pw->geglu)) return false;
-    if (M < (pw->kpad == 320 ? 8192 : 32768)) return false;
-    if (pl.size() > 1) {
-      if (pl.size() > 4) return false;
-      for (int n : group_n) if ((n * hw) % 256) return false;
-      for (const PW* q : pl)
-        if (q->rows_padded != pw->rows_padded || q->kpad != pw->kpad || q->cout != pw->cout || q->geglu != pw->geglu || q->ln_colsum) return false;
-    }
-    return true;
-  }
   T gn_proj_in(const T& x, const std::vector<Norm>& nl, int groups, float eps, const PWs& pl, const std::vector<int>& group_n = {}) {
     const int N = x.n;
     const long long hw = x.hw(), M = (long long)N * hw;
     const bool grouped = pl.size() > 1;
-    if (!(x.contig() && gn_fold_ok(M, hw, groups, pl, group_n))) {
-      CA g; g.group_n = group_n;
-      return conv_gemm(group_norm(x, nl, groups, eps, false, T(), group_n), pl, g);
-    }
+    CA g; g.group_n = group_n;
+    es_launch_query q = launch_query(pl, M, hw, g, x.c, 0, x.numel(), false);
+    for (const PW* p : pl)        // (the fold wants ONE geometry too)
+      if (p->rows_padded != pl[0]->rows_padded || p->kpad != pl[0]->kpad || p->cout != pl[0]->cout || p->geglu != pl[0]->geglu) q.groups_agree = 0;
+    if (!(x.contig() && launch_gn_fold(q, groups, env.knobs))) return conv_gemm(group_norm(x, nl, groups, eps, false, T(), group_n), pl, g);
     auto key = std::make_pair(N, groups);
     auto it = gn_partials.find(key);
     if (it == gn_partials.end()) it = gn_partials.emplace(key, persistent(es_group_norm_partials_bytes(N, groups))).first;
@@ -1586,8 +1636,17 @@ extern "C" int es_plan_gemm_choice(long long M, int rows_padded, int kpad, int g
   return 0;
 }
 extern "C" int es_linear_xs_eligible(long long M, int ksize, int kpad, int cin, int ctail, int cout, int geglu) {
-  return xs_shape_ok(M, ksize, kpad, cin, ctail, cout, geglu != 0) ? 1 : 0;
+  return xs_shape_ok(M, ksize, kpad, cin, ctail, cout, geglu != 0, XS_MIN_M) ? 1 : 0;
 }
+extern "C" int es_launch_choose(const es_launch_query* q, const es_launch_knobs* k, es_launch_choice* out) {
+  if (!q || !k || !out) { es_set_error("es_launch_choose: null argument"); return -1; }
+  if (!launch_choose(*q, *k, out)) { es_set_error("es_launch_choose: rows_padded fits no N tile"); return -1; }
+  return 0;
+}
+extern "C" int es_launch_route(const es_launch_query* q, const es_launch_knobs* k) { return q && k && launch_takes_xs(*q, *k) ? ES_ROUTE_LINEAR_XS : ES_ROUTE_CONV_GEMM; }
+extern "C" int es_launch_gn_fold(const es_launch_query* q, int groups, const es_launch_knobs* k) { return q && k && launch_gn_fold(*q, groups, *k); }
+extern "C" int es_launch_gn_handover(long long hw, int c, int groups, const es_launch_knobs* k) { return k && gn_handover(hw, c, groups, *k); }
+extern "C" int es_launch_wide_stream(int dtype, const es_launch_knobs* k) { return k && wide_stream(dtype, *k); }
 
 extern "C" int es_load_weights(const es_weights* wts, const es_model_config* mc, const es_ctx_geometry* g, int device, es_ctx** out) {
   if (!wts || !mc || !g || !out) { es_set_error("es_load_weights: null argument"); return -1; }

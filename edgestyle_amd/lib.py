@@ -137,6 +137,27 @@ class ModelConfig(C.Structure):     # es_model_config
                 ("vae_norm_eps", C.c_float), ("vae_scaling_factor", C.c_float)]
 
 
+_I32 = C.c_int32
+
+
+class LaunchQuery(C.Structure):     # es_launch_query
+    _fields_ = [(n, C.c_longlong) for n in ("M", "hw", "w_numel", "src_numel")] + \
+        [(n, _I32) for n in ("ksize", "stride", "upsample", "C1", "C2", "rows_padded", "kpad", "cin", "ctail", "cout", "geglu", "has_ln", "act",
+                             "has_temb", "has_residual", "residual_dense", "unit_scale", "n_tails", "x_rep", "wide", "dtype", "gn_groups",
+                             "ngroups", "n_counts")] + [("group_n", _I32 * 4)] + [(n, _I32) for n in ("groups_agree", "force_splitk", "stages")]
+
+
+class LaunchKnobs(C.Structure):     # es_launch_knobs
+    _fields_ = [(n, _I32) for n in ("xs_enabled", "xs_residual", "xs_min_m", "big_tile", "big_tile_256", "small_tile", "eight_waves", "deep_ring",
+                                    "gn_handover", "wide_stream", "gn_fold", "force_bn", "force_waves", "force_stages", "xcd_order")]
+
+
+class LaunchChoice(C.Structure):    # es_launch_choice
+    _fields_ = [(n, _I32) for n in ("route", "bn", "splitk", "stages", "waves", "xcd_m_fastest", "gn_partials", "wide")]
+
+
+ROUTE_CONV_GEMM, ROUTE_LINEAR_XS = 0, 1
+
 # every symbol include/edgestyle_hip.h declares: (name, restype, argtypes)
 _P, _I, _F, _L = C.c_void_p, C.c_int, C.c_float, C.c_int64
 SYMBOLS = {
@@ -210,6 +231,11 @@ SYMBOLS = {
     "es_plan_gemm_choice": (C.c_int, [C.c_longlong, _I, _I, _I, C.POINTER(C.c_int), _I, _I, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                       C.POINTER(C.c_int)]),
     "es_linear_xs_eligible": (C.c_int, [C.c_longlong, _I, _I, _I, _I, _I, _I]),
+    "es_launch_choose": (C.c_int, [C.POINTER(LaunchQuery), C.POINTER(LaunchKnobs), C.POINTER(LaunchChoice)]),
+    "es_launch_route": (C.c_int, [C.POINTER(LaunchQuery), C.POINTER(LaunchKnobs)]),
+    "es_launch_gn_fold": (C.c_int, [C.POINTER(LaunchQuery), _I, C.POINTER(LaunchKnobs)]),
+    "es_launch_gn_handover": (C.c_int, [C.c_longlong, _I, _I, C.POINTER(LaunchKnobs)]),
+    "es_launch_wide_stream": (C.c_int, [_I, C.POINTER(LaunchKnobs)]),
     "es_conv_gemm8p_form_ok": (C.c_int, [_I, _I, _I, C.c_longlong, _I]),
     "es_ctx_graph_hazard": (C.c_int, []),
     "es_plan_set_dry": (C.c_int, [_I]),

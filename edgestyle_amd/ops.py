@@ -279,20 +279,13 @@ PLAN_T64_ALONE, PLAN_T64, PLAN_T64_LONG, PLAN_SMALL_MAX_M = 0.5, 0.16, 1.5, 1638
 # 256 workgroups with K >= 1024 (tools/gemm8p_bench.py: 1.07-1.30 PFLOP/s on the batch-8 3x3 launches)
 BIG_TILE = _os.environ.get("ES_BIG_TILE", "1") == "1"
 BIG_TILE_256 = _os.environ.get("ES_BIG_TILE_256", "1") != "0"     # its 256-wide form for the LayerNorm-folded / GEGLU linear layers
-PLAN_SLAB_BYTES_PER_UNIT = float(_os.environ.get("ES_PLAN_SLAB", PLAN_SLAB_BYTES_PER_UNIT))
-PLAN_RED_FIX = float(_os.environ.get("ES_PLAN_REDFIX", PLAN_RED_FIX))
 PLAN_MIN_SLICE, PLAN_NK_NOSPLIT, PLAN_RESIDENT = 12, 10, 512
 
 
-_PLAN_TUNING = any(k in _os.environ for k in ("ES_PLAN_SLAB", "ES_PLAN_REDFIX"))
-
-
 def plan_gemm(M: int, rows_padded: int, kpad: int, geglu: bool = False, bns=(160, 128, 64), allow_split: bool = True):
-    """(bn, splitk, stages) of an es_conv_gemm launch: ONE planner for both hosts - the library's (es_plan_gemm_choice,
-    csrc/builder.hip), which es_load_weights uses itself.  `plan_gemm_reference` below is the Python copy it replaced: kept for
-    the tuning tools (cost-model knobs from the environment) and as a guard - tests/test_load_weights_cpu.py sweeps both."""
-    if _PLAN_TUNING:
-        return plan_gemm_reference(M, rows_padded, kpad, geglu, bns, allow_split)
+    """(bn, splitk, stages) of an es_conv_gemm launch among the tiles `bns`: the library's planner (es_plan_gemm_choice, csrc/builder.hip),
+    the one inside the launch policy both hosts ask (es_launch_choose).  For tools and tests; `plan_gemm_reference` below is the independent
+    restatement tests/test_load_weights_cpu.py holds the library against."""
     arr = (C.c_int * len(bns))(*[int(b) for b in bns])
     bn, sk, st = C.c_int(), C.c_int(), C.c_int()
     if L.load().es_plan_gemm_choice(int(M), int(rows_padded), int(kpad), int(bool(geglu)), arr, len(bns), int(bool(allow_split)),
@@ -305,7 +298,7 @@ def plan_gemm(M: int, rows_padded: int, kpad: int, geglu: bool = False, bns=(160
 
 
 def plan_gemm_reference(M: int, rows_padded: int, kpad: int, geglu: bool = False, bns=(160, 128, 64), allow_split: bool = True):
-    """The Python copy of the library's planner (one more round as a guard; tuning tools): (bn, splitk, stages) with the
+    """An independent restatement of the library's planner, for tests only: (bn, splitk, stages) with the
     lowest modelled time among the legal N tiles (ties go to the wider tile).  bn = 256 (the 256 x 256 phase-interleaved tile,
     offered for the LayerNorm-folded / GEGLU linear layers whose N is a multiple of 256) is decided AFTER the choice among the
     other tiles, on a model fitted on those layers (csrc/builder.hip plan_gemm, tools/ln256_bench.py)."""
@@ -403,8 +396,8 @@ _zero_bias = {}
 
 
 def xs_shape_reference(M: int, pw: "PackedWeight", min_m: int) -> bool:
-    """The Python copy of the library's es_linear_xs_eligible (kept one more round as a guard, and for min_m != the shipped 8192:
-    tests exercise every instantiation with min_m = 0).  K = 320 | 640 linear layers with an output width of whole 128-byte
+    """An independent restatement of the library's es_linear_xs_eligible (min_m = 8192) / "can the kernel run this" (min_m = 0), for
+    tests only.  K = 320 | 640 linear layers with an output width of whole 128-byte
     lines: the to_q|k|v and GEGLU projections of the 64x64 and 32x32 levels."""
     if pw.ksize != 1 or pw.kpad not in (320, 640) or pw.cin != pw.kpad or pw.ctail:
         return False
@@ -420,17 +413,33 @@ def xs_shape_reference(M: int, pw: "PackedWeight", min_m: int) -> bool:
     return True
 
 
-def xs_eligible(M: int, pw: "PackedWeight", pws, group_n, hw: int) -> bool:
-    """Does this plain linear launch go to es_linear_xs?  The shape / size rule is the library's (es_linear_xs_eligible: what
-    es_load_weights applies itself); the grouping conditions belong to the caller's launch."""
-    if not XS_ENABLED:
-        return False
+def launch_knobs(**over) -> "L.LaunchKnobs":
+    """es_launch_knobs from this module's switches and tool knobs as they stand NOW (tests and tools set the attributes)."""
+    kn = dict(xs_enabled=XS_ENABLED, xs_residual=XS_RESIDUAL, xs_min_m=XS_MIN_M, big_tile=BIG_TILE, big_tile_256=BIG_TILE_256,
+              small_tile=SMALL_TILE, eight_waves=EIGHT_WAVES, deep_ring=DEEP_RING and LANE == 0,
+              gn_handover=(2 if GN_HANDOVER_ALL else 1) if GN_HANDOVER else 0, wide_stream={"auto": -1, "1": 1}.get(WIDE_STREAM, 0),
+              gn_fold=GN_FOLD, force_bn=FORCE_BN, force_waves=FORCE_WAVES, force_stages=FORCE_STAGES, xcd_order=XCD_ORDER)
+    return L.LaunchKnobs(**{k: int(v) for k, v in dict(kn, **over).items()})
+
+
+def launch_query(M: int, hw: int, pw: "PackedWeight", pws=None, group_n=None, **facts) -> "L.LaunchQuery":
+    """es_launch_query of a launch of `pw` (grouped: `pws`, `group_n` samples each) over M pixels, hw per sample; `facts`: whatever
+    differs from a plain linear call."""
+    q = L.LaunchQuery(M=M, hw=hw, w_numel=pw.w.numel(), ksize=pw.ksize, stride=1, rows_padded=pw.rows_padded, kpad=pw.kpad, cin=pw.cin,
+                      ctail=pw.ctail, cout=pw.cout, geglu=pw.geglu, has_ln=pw.ln_colsum is not None, residual_dense=1, unit_scale=1, x_rep=1)
+    for name, v in facts.items():
+        setattr(q, name, int(v))
     if pws is not None:
-        if len(pws) > 4 or any((n * hw) % 256 for n in group_n) or any((q.ln_colsum is None) != (pw.ln_colsum is None) for q in pws):
-            return False
-    if XS_MIN_M != 8192:
-        return xs_shape_reference(M, pw, XS_MIN_M)
-    return bool(L.load().es_linear_xs_eligible(int(M), int(pw.ksize), int(pw.kpad), int(pw.cin), int(pw.ctail), int(pw.cout), int(pw.geglu)))
+        q.ngroups, q.groups_agree = len(pws), all((p.ln_colsum is None) == (pw.ln_colsum is None) for p in pws)
+    if group_n is not None:
+        q.n_counts = len(group_n)
+        q.group_n[:] = (list(group_n) + [0] * 4)[:4]
+    return q
+
+
+def xs_eligible(M: int, pw: "PackedWeight", pws, group_n, hw: int) -> bool:
+    """Does this plain linear launch go to es_linear_xs?"""
+    return L.load().es_launch_route(C.byref(launch_query(M, hw, pw, pws, group_n)), C.byref(launch_knobs(force_bn=0))) == L.ROUTE_LINEAR_XS
 
 
 def linear_xs(x: torch.Tensor, pw, M: int, out: torch.Tensor, group_rows=None, residual: Optional[torch.Tensor] = None,
@@ -529,16 +538,14 @@ def gn_handover(hw: int, c: int, groups: int) -> bool:
     large for a workgroup's registers, the 64 x 64 level - the hand-over removes its statistics launch and second read; the
     one-launch slab form of the deeper levels already reads its input once, and there the hand-over measured a net loss
     (profiles/r04_gn_handover.txt)."""
-    if not GN_HANDOVER or c % 8 or hw % 64 or c % groups or c // groups > 64:
-        return False
-    return GN_HANDOVER_ALL or not L.load().es_group_norm_is_slab(hw, c, groups)
+    return bool(L.load().es_launch_gn_handover(hw, c, groups, C.byref(launch_knobs())))
 
 
 GN_HANDOVER_ALL = _os.environ.get("ES_GN_HANDOVER", "0") == "all"     # tool switch: also where the consumer is the slab form
 
 
 def wide_stream(dtype) -> bool:
-    return WIDE_STREAM == "1" or (WIDE_STREAM == "auto" and dtype == torch.bfloat16)
+    return bool(L.load().es_launch_wide_stream(_DT.get(dtype, L.ES_F32), C.byref(launch_knobs())))
 
 
 def carry_lo(dst: torch.Tensor, src: torch.Tensor, shape=None) -> torch.Tensor:
@@ -605,36 +612,18 @@ def conv_gemm(x: torch.Tensor, pw: PackedWeight, *, stride: int = 1, pad: Option
             raise L.EdgeStyleHipError(f"conv_gemm: {what} must be contiguous (got shape {tuple(t.shape)}, strides {t.stride()})")
         if t.dtype != x.dtype or (numel is not None and t.numel() != numel):
             raise L.EdgeStyleHipError(f"conv_gemm: {what} has {t.numel()} {t.dtype} elements, the launch needs {numel} {x.dtype}")
-    # (a residual rides on es_linear_xs at K = 320 - Attention.to_out / proj_out of the 64 x 64 level - unless this launch carries the
-    #  two-word residual stream of a bf16 pipeline, which only es_conv_gemm implements)
-    xs_res = residual is None or (XS_RESIDUAL and pw.kpad == 320 and not pw.geglu and pw.ln_colsum is None
-                                  and not (wide and wide_stream(x.dtype)))
-    if (k == 1 and stride == 1 and not upsample and x2 is None and temb is None and xs_res and not tails
-            and x_rep == 1 and act == L.ACT_NONE and out_scale == 1.0 and out_scale_dev is None and splitk is None and FORCE_BN == 0
-            and xs_eligible(M, pw, pws, group_n, Hout * Wout)):
+    q = launch_query(M, Hout * Wout, pw, pws, group_n, src_numel=x.numel() * x_rep + (x2.numel() if x2 is not None else 0), stride=stride,
+                     upsample=upsample, C1=C1, C2=C2, act=act, has_temb=temb is not None, has_residual=residual is not None,
+                     unit_scale=out_scale == 1.0 and out_scale_dev is None, n_tails=len(tails), x_rep=x_rep, wide=wide, dtype=_dt(x),
+                     gn_groups=gn_groups, force_splitk=splitk or 0, stages=stages)
+    ch = L.LaunchChoice()
+    if L.load().es_launch_choose(C.byref(q), C.byref(launch_knobs()), C.byref(ch)) != 0:
+        raise L.EdgeStyleHipError(f"plan_gemm: rows_padded {pw.rows_padded} fits no N tile")
+    if ch.route == L.ROUTE_LINEAR_XS:
         linear_xs(x.reshape(M, C1), pws if pws is not None else pw, M, out.reshape(M, cstore),
                   None if pws is None else [n * Hout * Wout for n in group_n], residual=residual)
         return out
-    big_ok = BIG_TILE and C1 % BK == 0 and C2 % BK == 0 and not pw.geglu and pw.ln_colsum is None and \
-        (group_n is None or all((n * Hout * Wout) % 256 == 0 for n in group_n))
-    small_ok = SMALL_TILE and C1 % BK == 0 and C2 % BK == 0 and not pw.geglu and FORCE_WAVES != 8
-    # the 256 x 256 phase-interleaved tile (round 5): LayerNorm-folded and GEGLU linear layers whose N is a multiple of 256
-    ln256_ok = BIG_TILE_256 and (pw.geglu or pw.ln_colsum is not None) and k == 1 and stride == 1 and not upsample and x2 is None \
-        and not tails and temb is None and x_rep == 1 and C1 % BK == 0 and pw.rows_padded % 256 == 0 and pw.cout % 8 == 0 \
-        and not (pw.geglu and residual is not None) and not wide and gn_groups == 0 and FORCE_WAVES != 8 \
-        and (group_n is None or all((n * Hout * Wout) % 256 == 0 for n in group_n))
-    cand = ((256,) if ln256_ok else ()) + ((320,) if big_ok else ()) + (160, 128) + ((64,) if small_ok else ())
-    bn, auto_splitk, auto_stages = plan_gemm(M, pw.rows_padded, pw.kpad, pw.geglu,
-                                             bns=cand if FORCE_BN == 0 else (FORCE_BN,), allow_split=pw.ln_colsum is None)
-    if bn == 320 and FORCE_BN == 0 and (auto_splitk if splitk is None else splitk) == 1 and not L.load().es_conv_gemm8p_form_ok(
-            int(act_i), int(pw.cout), int(temb is not None), int(Hout * Wout), int(residual is not None)):
-        # the 256 x 320 tile does not implement this epilogue form (an activation, time-embedding rows that differ inside a 128-pixel
-        # half or meet a residual): plan again without it, so that the tile planned, recorded and reported is the tile that runs
-        bn, auto_splitk, auto_stages = plan_gemm(M, pw.rows_padded, pw.kpad, pw.geglu, bns=tuple(b for b in cand if b != 320),
-                                                 allow_split=pw.ln_colsum is None)
-    if splitk is None:
-        splitk = auto_splitk
-        stages = stages or auto_stages
+    bn, splitk = ch.bn, ch.splitk
     d = L.GemmDesc()
     d.x, d.x2, d.w = x.data_ptr(), (x2.data_ptr() if x2 is not None else None), pw.w.data_ptr()
     d.bias = pw.bias.data_ptr() if pw.bias is not None else None
@@ -649,10 +638,9 @@ def conv_gemm(x: torch.Tensor, pw: PackedWeight, *, stride: int = 1, pad: Option
     d.upsample = 1 if upsample else 0
     d.temb_stride = temb.stride(0) if temb is not None else 0
     d.act, d.splitk, d.bn, d.dtype, d.out_scale = act_i, splitk, bn, _dt(x), out_scale
-    d.stages = stages or FORCE_STAGES
+    d.stages, d.waves, d.xcd_m_fastest = ch.stages, ch.waves, ch.xcd_m_fastest
     d.korder = pw.korder
-    if (gn_groups > 0 and gn_handover(Hout * Wout, cstore, gn_groups) and not pw.geglu and pw.ln_colsum is None
-            and pw.cout // gn_groups <= (160 if bn == 320 else bn)):
+    if ch.gn_partials:
         # the consumer of `out` is a GroupNorm over gn_groups groups: hand its statistics over from this launch's epilogue
         shape = (N, 2 * (Hout * Wout // 64), gn_groups, 2)
         part = gn_part if gn_part is not None else torch.empty(shape, dtype=torch.float32, device=x.device)
@@ -660,7 +648,7 @@ def conv_gemm(x: torch.Tensor, pw: PackedWeight, *, stride: int = 1, pad: Option
             raise L.EdgeStyleHipError(f"conv_gemm: gn_part must be a contiguous fp32 {shape}")
         d.gn_part, d.gn_groups = part.data_ptr(), gn_groups
         out._gnp = (part, gn_groups)
-    if wide and residual is not None and wide_stream(x.dtype) and cstore % 8 == 0 and not pw.geglu:
+    if ch.wide:
         # this launch adds into the residual stream: the sum over (residual hi + lo) in fp32, stored as hi + lo
         lo_in = getattr(residual, "_lo", None)
         if lo_in is not None:
@@ -673,18 +661,7 @@ def conv_gemm(x: torch.Tensor, pw: PackedWeight, *, stride: int = 1, pad: Option
             raise L.EdgeStyleHipError("conv_gemm: out_lo must match out")
         d.out_lo = out_lo.data_ptr()
         out._lo = out_lo
-    # XCD chunk order: keep the larger operand's tiles together on one XCD (see conv_gemm_kernel)
-    d.xcd_m_fastest = (1 if (pws is None and splitk == 1 and M <= 2048 and pw.w.numel() > x.numel() * x_rep + (x2.numel() if x2 is not None else 0)) else 0) \
-        if XCD_ORDER < 0 else XCD_ORDER
     d.x_nmod = nsrc if x_rep > 1 else 0
-    if FORCE_WAVES:
-        d.waves = FORCE_WAVES
-    elif EIGHT_WAVES and k == 1 and M <= 65536 and C1 % BK == 0 and C2 % BK == 0 and bn not in (64, 320, 256) \
-            and not (int(d.stages) == 4 and bn != 128) and int(d.stages) != 3:
-        # 1x1 convs / linears are short-K, latency-bound launches: two waves per SIMD on the same 128-pixel tile overlap
-        # DMA issue, fragment reads and MFMAs (tools/gemm_tune.py: 3-15 % on every 1x1 shape of a batch-1 step, none on 3x3 or on the
-        # memory-bound 1x1 launches of large batches)
-        d.waves = 8
     if splitk > 1:
         ws = _get_workspace(splitk * M * pw.rows_padded * 4, x.device)
         d.workspace = ws.data_ptr()
@@ -852,23 +829,15 @@ def group_norm(x: torch.Tensor, gamma, beta, groups: int, eps: float, silu: bool
 # es_linear_xs, which normalises the rows it holds in registers (es_xs_desc.gn_part) - where the projection runs on that kernel anyway
 # (the grouped launches of the two shallow levels, the UNet's own at batch 8), and at K = 320 from 8192 rows on, where the row-stationary
 # kernel loses ~2 us to the tiled one but the apply pass it replaces costs 8-10 (profiles/r05_gn_proj_in.txt).  ES_GN_FOLD=0: two launches
-# + projection as before.  The native builder applies the same rule (csrc/builder.hip gn_proj_in).
+# + projection as before.  The rule is the library's (es_launch_gn_fold): the native builder asks it too.
 GN_FOLD = _os.environ.get("ES_GN_FOLD", "1") == "1"
 
 
 def gn_fold_ok(M: int, hw: int, groups: int, pw: "PackedWeight", pws, group_n) -> bool:
-    if not (GN_FOLD and XS_ENABLED) or GN_HANDOVER or hw % 256 or groups > 32:
-        return False
-    if pw.ksize != 1 or pw.kpad not in (320, 640) or pw.cin != pw.kpad or pw.ctail or pw.geglu or pw.ln_colsum is not None \
-            or pw.kpad % groups or not xs_shape_reference(M, pw, 0):
-        return False
-    if M < (8192 if pw.kpad == 320 else 32768):
-        return False
-    if pws is not None and (len(pws) > 4 or any((n * hw) % 256 for n in group_n)
-                            or any((q.rows_padded, q.kpad, q.cout, q.geglu, q.ln_colsum is None) != (pw.rows_padded, pw.kpad, pw.cout, pw.geglu, True)
-                                   for q in pws)):
-        return False
-    return True
+    q = launch_query(M, hw, pw, pws, group_n)
+    if pws is not None:             # (the fold wants ONE geometry too)
+        q.groups_agree = all((p.rows_padded, p.kpad, p.cout, p.geglu, p.ln_colsum is None) == (pw.rows_padded, pw.kpad, pw.cout, pw.geglu, True) for p in pws)
+    return bool(L.load().es_launch_gn_fold(C.byref(q), groups, C.byref(launch_knobs())))
 
 
 def gn_proj_in(x: torch.Tensor, gamma, beta, groups: int, eps: float, pw, group_n: Optional[Sequence[int]] = None) -> torch.Tensor:

@@ -25,7 +25,9 @@ enum { ES_ACT_NONE = 0, ES_ACT_SILU = 1, ES_ACT_GEGLU = 2 };
 
 /* 7 (round 5): es_gemm_desc.bn = 256; es_xs_desc.gn_* and es_gn_desc.stats_only (both structs grew: GroupNorm in front of a row-stationary
  * projection); es_conv_gemm8p_form_ok, es_ctx_graph_hazard, es_linear_xs_set_pp, es_attention_set_kvres, es_set_operand_limit,
- * es_group_norm_chunks, es_clock_probe.  Context images carry the version and are rebuilt across it. */
+ * es_group_norm_chunks, es_clock_probe.  Context images carry the version and are rebuilt across it.
+ * (Host-only helpers that no plan or image records - es_plan_gemm_choice, es_linear_xs_eligible, es_launch_choose and its siblings
+ * es_launch_route / es_launch_gn_fold / es_launch_gn_handover / es_launch_wide_stream - come and go without a new version.) */
 #define ES_ABI_VERSION 7
 int es_abi_version(void);
 /* sizeof the descriptor structs as compiled (0 gemm, 1 attn, 2 gn, 3 fusion, 4 ln, 5 xs): lets a binding verify its mirror */
@@ -491,6 +493,55 @@ int es_load_weights(const es_weights* w, const es_model_config* cfg, const es_ct
 int es_plan_gemm_choice(long long M, int rows_padded, int kpad, int geglu, const int* bns, int n_bns, int allow_split,
                         int* bn, int* splitk, int* stages);
 int es_linear_xs_eligible(long long M, int ksize, int kpad, int cin, int ctail, int cout, int geglu);
+/* The launch policy (host-only): every decision between "this convolution / linear call is valid" and "its descriptor is
+ * filled" - kernel, tile, split-K, ring depth, waves, XCD order, GroupNorm hand-over, two-word stream - taken in ONE place for
+ * both hosts (edgestyle_amd/ops.py conv_gemm and es_load_weights), so that they issue the same launches by construction.
+ * es_launch_query: the facts of one call the policy looks at. */
+typedef struct {
+  long long M, hw;                  /* output pixels of the launch / of one sample */
+  long long w_numel, src_numel;     /* XCD rule: elements of one packed weight set / of the sources as the launch reads them */
+  int32_t ksize, stride, upsample, C1, C2;
+  int32_t rows_padded, kpad, cin, ctail, cout, geglu, has_ln;     /* packed-weight geometry (has_ln: LayerNorm folded in) */
+  int32_t act;                      /* the caller's ES_ACT_* (GEGLU follows from the weights) */
+  int32_t has_temb, has_residual;
+  int32_t residual_dense;           /* the residual is a dense [M, Cout_store] tensor (es_linear_xs takes no other) */
+  int32_t unit_scale;               /* out_scale == 1 and no device scale */
+  int32_t n_tails, x_rep, wide;     /* wide: the caller asks for the two-word residual stream (granted by the knobs and dtype) */
+  int32_t dtype, gn_groups;         /* gn_groups > 0: a GroupNorm over that many groups reads the output */
+  int32_t ngroups;                  /* weight sets of a grouped launch (0: not grouped) */
+  int32_t n_counts, group_n[4];     /* samples per group as the caller gave them (at most 4 are looked at) */
+  int32_t groups_agree;             /* the groups' weights agree in what the rule compares: the LayerNorm fold (es_launch_choose),
+                                       the fold and the geometry (es_launch_gn_fold) */
+  int32_t force_splitk, stages;     /* caller overrides: split-K factor (0 = planned) and LDS ring depth (0 = planned) */
+} es_launch_query;
+/* every switch and tool knob that bends a decision (the Python host fills it from the attributes of edgestyle_amd.ops, es_load_weights
+ * from the environment switches it honours: README.md) */
+typedef struct {
+  int32_t xs_enabled, xs_residual, xs_min_m;                 /* es_linear_xs: at all / with a residual / from M rows on (0: every shape it runs) */
+  int32_t big_tile, big_tile_256, small_tile, eight_waves;   /* the 256 x 320, 256 x 256 and 64 x 64 tiles; 8 waves on short-K launches */
+  int32_t deep_ring;                                         /* 0: a planned 4-deep LDS ring becomes 2 */
+  int32_t gn_handover;                                       /* 0 off, 1 where the GroupNorm is the two-launch form, 2 everywhere */
+  int32_t wide_stream;                                       /* -1 auto (bf16 only), 0, 1 */
+  int32_t gn_fold;                                           /* GroupNorm in front of proj_in inside es_linear_xs */
+  int32_t force_bn, force_waves, force_stages;               /* 0 = planned */
+  int32_t xcd_order;                                         /* -1 auto, 0 tile_n fastest, 1 tile_m fastest */
+} es_launch_knobs;
+enum { ES_ROUTE_CONV_GEMM = 0, ES_ROUTE_LINEAR_XS = 1 };
+typedef struct {
+  int32_t route;                    /* ES_ROUTE_*; es_linear_xs: nothing below is set */
+  int32_t bn, splitk, stages, waves, xcd_m_fastest;          /* es_gemm_desc fields of the same names */
+  int32_t gn_partials;              /* emit the GroupNorm partial sums (es_gemm_desc.gn_part) */
+  int32_t wide;                     /* carry the two-word stream (es_gemm_desc.residual_lo / out_lo) */
+} es_launch_choice;
+/* -1 (es_last_error) when no tile fits rows_padded */
+int es_launch_choose(const es_launch_query* q, const es_launch_knobs* k, es_launch_choice* out);
+/* the decisions taken outside a GEMM call: the kernel alone (ES_ROUTE_*, no tile planned); GroupNorm + proj_in as statistics pass +
+ * es_linear_xs (q: the projection as es_launch_choose would get it, M / hw / weights / grouping are read); does a GEMM whose
+ * [.., hw, c] output feeds a GroupNorm hand its statistics over; is the residual stream of this dtype carried in two words */
+int es_launch_route(const es_launch_query* q, const es_launch_knobs* k);
+int es_launch_gn_fold(const es_launch_query* q, int groups, const es_launch_knobs* k);
+int es_launch_gn_handover(long long hw, int c, int groups, const es_launch_knobs* k);
+int es_launch_wide_stream(int dtype, const es_launch_knobs* k);
 /* Does the 256 x 320 tile (bn = 320) implement the epilogue of a splitk == 1 launch with this form?  (It keeps the common
  * forms only - bias [+ one time-embedding row per 128-pixel half] [+ residual]; split-K launches write raw partials: every
  * form.)  1 = yes.  Both hosts ask BEFORE they fix bn, so that the tile a launch is planned, recorded and reported with is the

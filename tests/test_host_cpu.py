@@ -181,6 +181,44 @@ def test_plan_gemm_returns_legal_launches():
                     assert ops.plan_gemm(M, rows, kpad, bns=bns, allow_split=False)[1] == 1
 
 
+def test_every_knob_bends_the_launch_choice_as_before():
+    """es_launch_choose under the default knobs and with ONE knob changed.  The expected choices are literals: read off the descriptors that
+    ops.conv_gemm recorded on the dry recorder, with that knob's module attribute set, at the commit before the policy moved into the library."""
+    L, XS, F16, BF16 = lib.load(), "es_linear_xs", lib.ES_F16, lib.ES_BF16
+
+    def choose(cin, cout, k, M, hw, facts, knobs, geglu=False):
+        bn = 128 if geglu else ops.choose_bn(cout)
+        pw = ops.PackedWeight(torch.empty(-(-cout // bn) * bn, k * k * cin, device="meta"), None, cout, cin, k, bn, geglu,
+                              ln_colsum=torch.empty(0) if geglu else None)
+        ch = lib.LaunchChoice()
+        q = ops.launch_query(M, hw, pw, C1=cin, src_numel=M * cin, **facts)
+        if L.es_launch_choose(ctypes.byref(q), ctypes.byref(ops.launch_knobs(**knobs)), ctypes.byref(ch)) != 0:
+            return L.es_last_error()
+        return XS if ch.route == lib.ROUTE_LINEAR_XS else (ch.bn, ch.splitk, ch.stages, ch.waves, ch.xcd_m_fastest, ch.gn_partials, ch.wide)
+    res, gn = dict(has_residual=1), dict(gn_groups=32)
+    table = [   # (cin, cout, ksize, M, hw, call facts): {changed knob: choice}
+        ((320, 960, 1, 16384, 16384, {}), {(): XS, ("xs_enabled", 0): (160, 1, 2, 8, 0, 0, 0)}),
+        ((320, 960, 1, 1024, 1024, {}), {(): (64, 1, 2, 0, 0, 0, 0), ("xs_min_m", 0): XS}),
+        ((320, 320, 1, 32768, 4096, res), {(): XS, ("xs_residual", 0): (160, 1, 2, 8, 0, 0, 0)}),
+        ((320, 320, 1, 256, 256, {}), {(): (64, 1, 2, 0, 1, 0, 0), ("small_tile", 0): (160, 1, 2, 8, 1, 0, 0), ("force_waves", 8): (160, 1, 2, 8, 1, 0, 0)}),
+        ((1280, 1280, 1, 4096, 4096, {}), {(): (128, 1, 2, 8, 0, 0, 0), ("eight_waves", 0): (128, 1, 2, 0, 0, 0, 0), ("xcd_order", 1): (128, 1, 2, 8, 1, 0, 0)}),
+        ((320, 320, 3, 57344, 4096, {}), {(): (320, 1, 2, 0, 0, 0, 0), ("big_tile", 0): (160, 1, 2, 0, 0, 0, 0)}),
+        ((320, 640, 3, 57344, 4096, {}), {(): (320, 1, 2, 0, 0, 0, 0), ("force_bn", 128): (128, 1, 2, 0, 0, 0, 0)}),
+        ((1280, 1280, 1, 1024, 1024, {}), {(): (64, 1, 4, 0, 1, 0, 0), ("deep_ring", 0): (64, 1, 2, 0, 1, 0, 0)}),
+        ((320, 320, 3, 8192, 4096, gn), {(): (160, 3, 2, 0, 0, 0, 0), ("gn_handover", 1): (160, 3, 2, 0, 0, 1, 0), ("gn_handover", 2): (160, 3, 2, 0, 0, 1, 0)}),
+        ((1280, 1280, 3, 512, 256, gn), {(): (128, 12, 2, 0, 0, 0, 0), ("gn_handover", 1): (128, 12, 2, 0, 0, 0, 0), ("gn_handover", 2): (128, 12, 2, 0, 0, 1, 0)}),
+        ((320, 320, 1, 32768, 4096, dict(res, wide=1, dtype=F16)), {(): XS, ("wide_stream", 1): (160, 1, 2, 8, 0, 0, 1)}),
+        ((320, 320, 1, 32768, 4096, dict(res, wide=1, dtype=BF16)), {(): (160, 1, 2, 8, 0, 0, 1), ("wide_stream", 0): XS}),
+    ]
+    for call, want in table:
+        for knob, choice in want.items():
+            assert choose(*call, dict([knob] if knob else [])) == choice, (call, knob)
+    # the 28672 x 1280 -> 10240 GEGLU of the 64 x 64 level (LayerNorm folded in)
+    assert choose(1280, 10240, 1, 28672, 4096, {}, {}, geglu=True) == (256, 1, 2, 0, 0, 0, 0)
+    assert choose(1280, 10240, 1, 28672, 4096, {}, dict(big_tile_256=0), geglu=True) == (128, 1, 2, 8, 0, 0, 0)
+    assert b"fits no N tile" in choose(320, 320, 3, 57344, 4096, {}, dict(force_bn=128))          # (rows_padded 320)
+
+
 def test_layer_norm_fold_algebra():
     """pack_weight_ln: Linear(LayerNorm(x)) == rstd (x (W gamma)^T - mean colsum) + (W beta + b), with the column sums
     taken from the rounded packed weights (what the kernel's epilogue computes)."""
