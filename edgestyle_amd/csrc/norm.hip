@@ -23,8 +23,10 @@ constexpr int GN_MAX_GROUPS = 64;
 #endif
 constexpr int GNU = GN_UNROLL;          // independent 16-byte loads in flight per thread in the streaming loops
 
-ES_DEVICE int gn_pixels_per_block(int HW) {
-  int ppb = HW / GN_MAX_CHUNK;
+// Pixels per chunk of the statistics pass: max(16, ceil(HW / 64)), so that ceil(HW / ppb) <= GN_MAX_CHUNK for EVERY HW - `partials` holds
+// GN_MAX_CHUNK rows per sample (es_group_norm_partials_bytes).  The one definition: the kernel, the launcher and es_group_norm_chunks ask it.
+__host__ __device__ __forceinline__ int gn_pixels_per_block(int HW) {
+  const int ppb = (HW + GN_MAX_CHUNK - 1) / GN_MAX_CHUNK;
   return ppb < 16 ? 16 : ppb;
 }
 
@@ -411,32 +413,42 @@ __global__ __launch_bounds__(256) void layer_norm_kernel(const T* __restrict__ x
   }
 }
 
-template <typename T>
-int launch_gn(const es_gn_desc& d, hipStream_t st) {
+constexpr size_t GN_LDS_LIMIT = 64 * 1024;      // dynamic LDS a launch gets without hipFuncSetAttribute
+
+// Everything launch_gn decides, as numbers: es_group_norm launches from it and es_group_norm_route reports it (one computation, no copy).
+struct GnRoute {
+  int slab;                                   // 1: gn_slab_kernel, 0: gn_stats_kernel (+ gn_apply_kernel)
+  int gpb, slots, cpt_class;                  // slab: groups per block, pixel slots (PS), register class 8 | 16 | 24
+  int ppb, nchunk, ps, lanes;                 // statistics pass: pixels per chunk, chunks per sample, pixel slots, lanes per group
+  int blocks, ipt, general;                   // apply pass: workgroups per sample, items per thread, 1 = the general (per-item index) loop
+  size_t lds_slab, lds_stats, lds_apply;
+};
+
+GnRoute gn_route(const es_gn_desc& d) {
+  GnRoute r{};
   const int C = d.C1 + d.C2;
   int cpt = 0;
   static const bool slab_on = !(getenv("ES_GN_SLAB") && getenv("ES_GN_SLAB")[0] == '0');   // tuning switch
   const int gpb = (slab_on && d.ext_chunks <= 0 && !d.stats_only) ? gn_slab_gpb(d, cpt) : 0;
   if (gpb) {
     const int W = gpb * (C / d.groups);
-    const size_t lds = (size_t)(2 * (256 / (W / 8)) * W + 2 * gpb) * sizeof(float);
-    dim3 grid(d.groups / gpb, d.N);
-    if (cpt <= 8) hipLaunchKernelGGL((gn_slab_kernel<T, 8>), grid, dim3(256), lds, st, d, gpb);
-    else if (cpt <= 16) hipLaunchKernelGGL((gn_slab_kernel<T, 16>), grid, dim3(256), lds, st, d, gpb);
-    else hipLaunchKernelGGL((gn_slab_kernel<T, 24>), grid, dim3(256), lds, st, d, gpb);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    r.slab = 1;
+    r.gpb = gpb;
+    r.slots = 256 / (W / 8);
+    r.cpt_class = cpt <= 8 ? 8 : cpt <= 16 ? 16 : 24;
+    r.lds_slab = (size_t)(2 * r.slots * W + 2 * gpb) * sizeof(float);
+    return r;
   }
-  int ppb = d.HW / GN_MAX_CHUNK;
-  if (ppb < 16) ppb = 16;
+  r.ppb = gn_pixels_per_block(d.HW);
   // ext_chunks > 0: the producing GEMM launch already wrote the per-(sample, group) partial sums (es_gemm_desc.gn_part): the
   // apply pass below reduces them in its prologue exactly as it reduces gn_stats_kernel's - no statistics launch, one read of x
-  const int nchunk = d.ext_chunks > 0 ? d.ext_chunks : (d.HW + ppb - 1) / ppb;
+  r.nchunk = d.ext_chunks > 0 ? d.ext_chunks : (d.HW + r.ppb - 1) / r.ppb;
   const int CH8 = C / 8;
-  const int PS = CH8 <= 256 ? 256 / CH8 : 1;
-  const size_t lds_stats = (size_t)2 * PS * C * sizeof(float);
-  if (d.ext_chunks <= 0) hipLaunchKernelGGL(gn_stats_kernel<T>, dim3(nchunk, d.N), dim3(256), lds_stats, st, d);
-  if (d.stats_only) return hipGetLastError() == hipSuccess ? 0 : -2;      // the consumer normalises (es_xs_desc.gn_part)
-  const long long total = (long long)d.HW * (C / 8);
+  r.ps = CH8 <= 256 ? 256 / CH8 : 1;
+  r.lanes = d.groups <= 32 ? 8 : 4;
+  r.lds_stats = (size_t)2 * r.ps * C * sizeof(float);
+  if (d.stats_only) return r;
+  const long long total = (long long)d.HW * CH8;
   // workgroups per sample: every workgroup first reduces the partials and builds the scale / shift tables (~2 us), so a thread
   // should stream more than one round of loads behind that prologue - 16 items where that still leaves >= 1024 workgroups for the
   // chip, else 8, else 4 (tools/norm_bench.py, 14 x 64^2 x 320: 32.1 / 27.7 / 28.5 us for 4 / 8 / 16; 112 samples: 215 / 188 / 180)
@@ -453,24 +465,48 @@ int launch_gn(const es_gn_desc& d, hipStream_t st) {
     const int q = CH8 / a;
     if (q <= 64) blocks = blocks < q ? q : blocks / q * q;
   }
-  const size_t lds = (size_t)(2 * C + 2 * d.groups + 256) * sizeof(float);
-  hipLaunchKernelGGL(gn_apply_kernel<T>, dim3(blocks, d.N), dim3(256), lds, st, d, nchunk);
+  r.blocks = blocks;
+  r.ipt = ipt;
+  r.general = ((long long)blocks * 256) % CH8 != 0;         // gn_apply_kernel's own test of its grid stride
+  r.lds_apply = (size_t)(2 * C + 2 * d.groups + 256) * sizeof(float);
+  return r;
+}
+
+template <typename T>
+int launch_gn(const es_gn_desc& d, const GnRoute& r, hipStream_t st) {
+  if (r.slab) {
+    dim3 grid(d.groups / r.gpb, d.N);
+    if (r.cpt_class == 8) hipLaunchKernelGGL((gn_slab_kernel<T, 8>), grid, dim3(256), r.lds_slab, st, d, r.gpb);
+    else if (r.cpt_class == 16) hipLaunchKernelGGL((gn_slab_kernel<T, 16>), grid, dim3(256), r.lds_slab, st, d, r.gpb);
+    else hipLaunchKernelGGL((gn_slab_kernel<T, 24>), grid, dim3(256), r.lds_slab, st, d, r.gpb);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+  }
+  if (d.ext_chunks <= 0) hipLaunchKernelGGL(gn_stats_kernel<T>, dim3(r.nchunk, d.N), dim3(256), r.lds_stats, st, d);
+  if (d.stats_only) return hipGetLastError() == hipSuccess ? 0 : -2;      // the consumer normalises (es_xs_desc.gn_part)
+  hipLaunchKernelGGL(gn_apply_kernel<T>, dim3(r.blocks, d.N), dim3(256), r.lds_apply, st, d, r.nchunk);
   return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+// 16-byte chunks per lane of layer_norm_kernel's instantiation for C channels (0: no instantiation holds the row)
+int ln_vpl(int C) {
+  if (C < 8 || C % 8) return 0;
+  const int vpl = (C / 8 + 63) / 64;
+  return vpl <= 4 ? vpl : vpl <= 8 ? 8 : 0;
 }
 
 template <typename T>
 int launch_ln(const void* x, void* out, const float* gamma, const float* beta, int M, int C, float eps,
               hipStream_t st, const LnGroups grp = LnGroups{}) {
-  const int CH8 = C / 8;
-  const int vpl = (CH8 + 63) / 64;
   dim3 grid((M + 3) / 4);
 #define ES_LN(V) hipLaunchKernelGGL((layer_norm_kernel<T, V>), grid, dim3(256), 0, st, (const T*)x, (T*)out, gamma, beta, M, C, eps, grp)
-  if (vpl <= 1) ES_LN(1);
-  else if (vpl <= 2) ES_LN(2);
-  else if (vpl <= 3) ES_LN(3);
-  else if (vpl <= 4) ES_LN(4);
-  else if (vpl <= 8) ES_LN(8);
-  else return -3;
+  switch (ln_vpl(C)) {
+    case 1: ES_LN(1); break;
+    case 2: ES_LN(2); break;
+    case 3: ES_LN(3); break;
+    case 4: ES_LN(4); break;
+    case 8: ES_LN(8); break;
+    default: return -3;
+  }
 #undef ES_LN
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
@@ -485,8 +521,7 @@ extern "C" size_t es_group_norm_partials_bytes(int N, int groups) {
 
 extern "C" int es_group_norm_chunks(int HW) {          // pixel chunks per sample of the statistics pass: the second extent of `partials`
   if (HW < 1) return 0;
-  int ppb = HW / GN_MAX_CHUNK;
-  if (ppb < 16) ppb = 16;
+  const int ppb = gn_pixels_per_block(HW);
   return (HW + ppb - 1) / ppb;
 }
 
@@ -499,8 +534,27 @@ extern "C" int es_group_norm_is_slab(int HW, int C, int groups) {
   return slab_on && gn_slab_gpb(d, cpt) ? 1 : 0;
 }
 
-extern "C" int es_group_norm(const es_gn_desc* d, void* stream) {
+// the checks of es_group_norm that need no pointer: null = the geometry can be launched, *r then holds its route
+static const char* gn_check_geometry(const es_gn_desc* d, GnRoute* r) {
   const int C = d->C1 + d->C2;
+  if (d->ngroups > 4) return "es_group_norm: at most 4 groups";
+  if (d->ngroups > 1 && d->n_end[d->ngroups - 1] != d->N) return "es_group_norm: group table must cover N";
+  if (d->C1 % 8 || d->C2 % 8 || d->C1 < 0 || d->C2 < 0 || C < 8) return "es_group_norm: channels must be multiples of 8";
+  if (d->groups < 1 || d->groups > GN_MAX_GROUPS || C % d->groups) return "es_group_norm: bad group count";
+  if (C > 8192) return "es_group_norm: C too large for the LDS tables";
+  if (d->N < 1 || d->HW < 1) return "es_group_norm: empty problem";
+  if ((long long)d->HW * (C / 8) >= (1ll << 30)) return "es_group_norm: sample too large for 32-bit chunk indices";
+  if (d->ext_chunks < 0 || (d->ext_chunks > 0 && (d->x2 || d->C2 || d->HW % 64 || d->ext_chunks != 2 * (d->HW / 64))))
+    return "es_group_norm: ext_chunks (statistics from the producer) needs one source, H*W % 64 == 0 and 2 * H*W / 64 entries";
+  *r = gn_route(*d);
+  // gn_apply_kernel keeps scale / shift [C], mean / rstd [groups] and 256 reduction slots in dynamic LDS and asks for no more than a launch
+  // gets by default: (2 C + 2 groups + 256) * 4 bytes <= 64 KB, i.e. C + groups <= 8064.  The slab form and the statistics pass always fit.
+  if (r->lds_slab > GN_LDS_LIMIT || r->lds_stats > GN_LDS_LIMIT || r->lds_apply > GN_LDS_LIMIT)
+    return "es_group_norm: the two-launch form's scale / shift tables exceed 64 KB of LDS (C + groups > 8064)";
+  return nullptr;
+}
+
+extern "C" int es_group_norm(const es_gn_desc* d, void* stream) {
   if (d->stats_only) {
     if (!d->x || !d->partials || d->ext_chunks) { es_set_error("es_group_norm: stats_only needs x and partials (and no ext_chunks)"); return -1; }
   } else {
@@ -508,28 +562,34 @@ extern "C" int es_group_norm(const es_gn_desc* d, void* stream) {
     for (int g = 0; g < d->ngroups && d->ngroups > 1; ++g)
       if (!d->gamma_g[g] || !d->beta_g[g]) { es_set_error("es_group_norm: null group parameter"); return -1; }
   }
-  if (d->ngroups > 4) { es_set_error("es_group_norm: at most 4 groups"); return -1; }
-  if (d->ngroups > 1 && d->n_end[d->ngroups - 1] != d->N) { es_set_error("es_group_norm: group table must cover N"); return -1; }
-  if (d->C1 % 8 || d->C2 % 8 || (d->C2 && !d->x2)) { es_set_error("es_group_norm: channels must be multiples of 8"); return -1; }
-  if (d->groups < 1 || d->groups > GN_MAX_GROUPS || C % d->groups) { es_set_error("es_group_norm: bad group count"); return -1; }
-  if (C > 8192) { es_set_error("es_group_norm: C too large for the LDS tables"); return -1; }
-  if (d->N < 1 || d->HW < 1) { es_set_error("es_group_norm: empty problem"); return -1; }
-  if ((long long)d->HW * (C / 8) >= (1ll << 30)) { es_set_error("es_group_norm: sample too large for 32-bit chunk indices"); return -1; }
-  if (d->ext_chunks < 0 || (d->ext_chunks > 0 && (d->x2 || d->C2 || d->HW % 64 || d->ext_chunks != 2 * (d->HW / 64)))) {
-    es_set_error("es_group_norm: ext_chunks (statistics from the producer) needs one source, H*W % 64 == 0 and 2 * H*W / 64 entries"); return -1; }
+  if (d->C2 && !d->x2) { es_set_error("es_group_norm: C2 channels without a second source"); return -1; }
+  GnRoute r;
+  if (const char* why = gn_check_geometry(d, &r)) { es_set_error(why); return -1; }
   ES_PLAN_RECORD(ES_OP_GROUP_NORM, d, sizeof(*d));
   hipStream_t st = (hipStream_t)stream;
   es_gn_desc dd = *d;                                  // unused group-table entries must compare false (see es_conv_gemm)
   for (int g = dd.ngroups > 1 ? dd.ngroups : 0; g < 4; ++g) dd.n_end[g] = 0x7FFFFFFF;
-  int rc = dd.dtype == ES_F16 ? launch_gn<f16>(dd, st) : launch_gn<bf16>(dd, st);
+  int rc = dd.dtype == ES_F16 ? launch_gn<f16>(dd, r, st) : launch_gn<bf16>(dd, r, st);
   if (rc) es_set_error("es_group_norm: launch failed");
   return rc;
 }
+
+extern "C" int es_group_norm_route(const es_gn_desc* d, int32_t out[ES_GN_ROUTE_FIELDS]) {
+  GnRoute r;
+  if (const char* why = gn_check_geometry(d, &r)) { es_set_error(why); return -1; }
+  const int32_t v[ES_GN_ROUTE_FIELDS] = {r.slab ? ES_GN_FORM_SLAB : ES_GN_FORM_TWO_LAUNCHES, r.gpb, r.slots, r.cpt_class, r.ppb, r.nchunk, r.ps, r.lanes,
+                                         r.blocks, r.ipt, r.general, (int32_t)(r.slab ? r.lds_slab : d->stats_only ? r.lds_stats : r.lds_apply)};
+  for (int i = 0; i < ES_GN_ROUTE_FIELDS; ++i) out[i] = v[i];
+  return 0;
+}
+
+extern "C" int es_layer_norm_route(int C) { return ln_vpl(C); }
 
 extern "C" int es_layer_norm(const void* x, void* out, const float* gamma, const float* beta, int M, int C,
                              float eps, int dtype, void* stream) {
   if (!x || !out || !gamma || !beta) { es_set_error("es_layer_norm: null pointer"); return -1; }
   if (C % 8 || M < 1) { es_set_error("es_layer_norm: C must be a multiple of 8"); return -1; }
+  if (!ln_vpl(C)) { es_set_error("es_layer_norm: C > 4096 unsupported"); return -1; }
   if (es_plan_recording()) {
     const es_op_layer_norm a{x, out, gamma, beta, M, C, eps, dtype};
     es_plan_record(ES_OP_LAYER_NORM, &a, sizeof(a));
@@ -554,6 +614,7 @@ extern "C" int es_layer_norm_grouped(const es_ln_desc* d, void* stream) {
     if (!grp.gamma[g] || !grp.beta[g]) { es_set_error("es_layer_norm_grouped: null parameter"); return -1; }
   }
   if (d->row_end[d->ngroups - 1] != d->M) { es_set_error("es_layer_norm_grouped: group table must cover M"); return -1; }
+  if (!ln_vpl(d->C)) { es_set_error("es_layer_norm_grouped: C > 4096 unsupported"); return -1; }
   ES_PLAN_RECORD(ES_OP_LAYER_NORM_GROUPED, d, sizeof(*d));
   hipStream_t st = (hipStream_t)stream;
   int rc = d->dtype == ES_F16 ? launch_ln<f16>(d->x, d->out, grp.gamma[0], grp.beta[0], d->M, d->C, d->eps, st, grp)

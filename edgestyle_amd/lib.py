@@ -157,6 +157,8 @@ class LaunchChoice(C.Structure):    # es_launch_choice
 
 
 ROUTE_CONV_GEMM, ROUTE_LINEAR_XS = 0, 1
+GN_FORM_SLAB, GN_FORM_TWO_LAUNCHES = 1, 2        # ES_GN_FORM_*
+GN_ROUTE_FIELDS = ("form", "gpb", "slots", "cpt", "ppb", "nchunk", "ps", "lanes", "blocks", "ipt", "general", "lds")     # ES_GN_ROUTE_*
 
 # every symbol include/edgestyle_hip.h declares: (name, restype, argtypes)
 _P, _I, _F, _L = C.c_void_p, C.c_int, C.c_float, C.c_int64
@@ -176,6 +178,8 @@ SYMBOLS = {
     "es_group_norm_partials_bytes": (C.c_size_t, [_I, _I]),
     "es_group_norm_is_slab": (C.c_int, [_I, _I, _I]),
     "es_group_norm_chunks": (C.c_int, [_I]),
+    "es_group_norm_route": (C.c_int, [C.POINTER(GnDesc), C.POINTER(C.c_int32)]),
+    "es_layer_norm_route": (C.c_int, [_I]),
     "es_layer_norm": (C.c_int, [_P, _P, _P, _P, _I, _I, _F, _I, _P]),
     "es_fusion_block": (C.c_int, [C.POINTER(FusionDesc), _P]),
     "es_fusion_scratch_bytes": (C.c_size_t, [_I]),
@@ -279,3 +283,12 @@ def check(rc: int, what: str = ""):
     if rc != 0:
         msg = load().es_last_error()
         raise EdgeStyleHipError(f"{what} failed (rc={rc}): {msg.decode() if msg else ''}")
+
+
+def group_norm_route(N: int, HW: int, C1: int, C2: int, groups: int, stats_only: bool = False, ext_chunks: int = 0) -> dict:
+    """es_group_norm_route as a dict keyed by GN_ROUTE_FIELDS (raises where es_group_norm would refuse the geometry)"""
+    d = GnDesc()
+    d.N, d.HW, d.C1, d.C2, d.groups, d.stats_only, d.ext_chunks = N, HW, C1, C2, groups, 1 if stats_only else 0, ext_chunks
+    out = (C.c_int32 * len(GN_ROUTE_FIELDS))()
+    check(load().es_group_norm_route(C.byref(d), out), "es_group_norm_route")
+    return dict(zip(GN_ROUTE_FIELDS, out))

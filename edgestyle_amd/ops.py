@@ -786,42 +786,111 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, sca
 _gn_partials = {}
 
 
-def group_norm(x: torch.Tensor, gamma, beta, groups: int, eps: float, silu: bool,
-               x2: Optional[torch.Tensor] = None, group_n: Optional[Sequence[int]] = None) -> torch.Tensor:
-    """x: [N,H,W,C1] (+x2 [N,H,W,C2]) -> normalised [N,H,W,C1+C2].  gamma/beta may be lists (one per group of
-    `group_n` consecutive samples): one launch for several nets' GroupNorms."""
+def _norm_params(what, gamma, beta, Cc, x, nsets=None):
+    """gamma / beta of a normalisation as lists of fp32 [Cc] tensors on x's device (the kernels read Cc floats behind each data_ptr())"""
+    gl = list(gamma) if isinstance(gamma, (list, tuple)) else [gamma]
+    bl = list(beta) if isinstance(beta, (list, tuple)) else [beta]
+    if len(gl) != len(bl) or not gl or len(gl) > 4 or (nsets is not None and len(gl) != nsets):
+        raise L.EdgeStyleHipError(f"{what}: {len(gl)} gamma and {len(bl)} beta sets" + (f" for {nsets} groups" if nsets is not None else " (1 to 4, as many of each)"))
+    for name, ts in (("gamma", gl), ("beta", bl)):
+        for t in ts:
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != x.device or tuple(t.shape) != (Cc,) or not t.is_contiguous():
+                raise L.EdgeStyleHipError(f"{what}: {name} must be a contiguous fp32 [{Cc}] tensor on {x.device}, not "
+                                          f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))} on {getattr(t, 'device', None)}")
+            if t.device.type != "meta" and t.data_ptr() % 16:         # gn_slab_kernel reads gamma / beta as 16-byte vectors
+                raise L.EdgeStyleHipError(f"{what}: {name} must start at a multiple of 16 bytes (a slice at an odd offset of a larger buffer does not)")
+    return gl, bl
+
+
+def _gn_operands(what, x, x2, groups):
+    """(N, H, W, C1, C2) of a GroupNorm launch whose sources the kernels can read as dense NHWC"""
+    def bad(msg):
+        return L.EdgeStyleHipError(f"{what}: {msg}")
+    if x.dim() != 4 or x.dtype not in (torch.float16, torch.bfloat16):
+        raise bad(f"x must be an fp16 or bf16 [N, H, W, C] tensor, not {x.dtype} {tuple(x.shape)}")
     N, H, W, C1 = x.shape
-    C2 = 0 if x2 is None else x2.shape[3]
-    out = torch.empty((N, H, W, C1 + C2), dtype=x.dtype, device=x.device)
-    key = (x.device, N, groups, LANE)
-    part = _gn_partials.get(key)
-    if part is None:
-        part = torch.empty(L.load().es_group_norm_partials_bytes(N, groups) // 4, dtype=torch.float32, device=x.device)
-        _gn_partials[key] = part
+    if not x.is_contiguous():
+        raise bad(f"x must be contiguous (got shape {tuple(x.shape)}, strides {x.stride()})")
+    C2 = 0
+    if x2 is not None:
+        if x2.dtype != x.dtype or x2.device != x.device:
+            raise bad(f"x2 is {x2.dtype} on {x2.device}, x is {x.dtype} on {x.device}")
+        if x2.dim() != 4 or tuple(x2.shape[:3]) != (N, H, W):
+            raise bad(f"x2 {tuple(x2.shape)} does not match x {tuple(x.shape)} in N, H, W")
+        if not x2.is_contiguous():
+            raise bad(f"x2 must be contiguous (got shape {tuple(x2.shape)}, strides {x2.stride()})")
+        C2 = x2.shape[3]
+    for name, t in (("x", x), ("x2", x2)):
+        if t is not None and t.device.type != "meta" and t.data_ptr() % 16:
+            raise bad(f"{name} must start at a multiple of 16 bytes (16-byte vector loads)")
+    if N < 1 or H * W < 1 or C1 < 8 or C1 % 8 or C2 % 8:
+        raise bad(f"channels {C1}+{C2} must be multiples of 8 (16-byte vector loads) and the problem not empty")
+    if groups < 1 or (C1 + C2) % groups:
+        raise bad(f"{C1 + C2} channels do not divide into {groups} groups")
+    return N, H, W, C1, C2
+
+
+def _gn_partials_for(what, x, N, groups, partials=None):
+    if partials is None:
+        key = (x.device, N, groups, LANE)
+        partials = _gn_partials.get(key)
+        if partials is None:
+            partials = torch.empty(L.load().es_group_norm_partials_bytes(N, groups) // 4, dtype=torch.float32, device=x.device)
+            _gn_partials[key] = partials
+        return partials
+    need = L.load().es_group_norm_partials_bytes(N, groups) // 4
+    if partials.dtype != torch.float32 or partials.device != x.device or not partials.is_contiguous() or partials.numel() != need:
+        raise L.EdgeStyleHipError(f"{what}: partials must be a contiguous fp32 tensor of {need} elements ([N][64][groups][2]) on {x.device}, not "
+                                  f"{partials.dtype} {tuple(partials.shape)} on {partials.device}")
+    return partials
+
+
+def _norm_out(what, x, shape, out):
+    if out is None:
+        return torch.empty(shape, dtype=x.dtype, device=x.device)
+    if tuple(out.shape) != tuple(shape) or out.dtype != x.dtype or out.device != x.device or not out.is_contiguous():
+        raise L.EdgeStyleHipError(f"{what}: out must be a contiguous {x.dtype} {tuple(shape)} tensor on {x.device}, not {out.dtype} {tuple(out.shape)} "
+                                  f"(strides {out.stride()}) on {out.device}")
+    if out.data_ptr() % 16:
+        raise L.EdgeStyleHipError(f"{what}: out must start at a multiple of 16 bytes (16-byte vector stores)")
+    return out
+
+
+def group_norm(x: torch.Tensor, gamma, beta, groups: int, eps: float, silu: bool,
+               x2: Optional[torch.Tensor] = None, group_n: Optional[Sequence[int]] = None,
+               out: Optional[torch.Tensor] = None, partials: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x: [N,H,W,C1] (+x2 [N,H,W,C2]) -> normalised [N,H,W,C1+C2].  gamma/beta may be lists (one per group of
+    `group_n` consecutive samples): one launch for several nets' GroupNorms.  out: the tensor to write (contiguous, x's dtype);
+    partials: the statistics scratch (fp32, es_group_norm_partials_bytes(N, groups) bytes) instead of the cached one.  Operands the
+    launch could not read as it is told to are refused here, before anything is recorded or launched."""
+    N, H, W, C1, C2 = _gn_operands("group_norm", x, x2, groups)
+    grouped = isinstance(gamma, (list, tuple)) and len(gamma) > 1
+    if grouped and (len(gamma) > 4 or group_n is None or len(group_n) != len(gamma) or sum(group_n) != N):
+        raise L.EdgeStyleHipError("grouped group_norm: bad group table")
+    gl, bl = _norm_params("group_norm", gamma, beta, C1 + C2, x)
+    out = _norm_out("group_norm", x, (N, H, W, C1 + C2), out)
+    part = _gn_partials_for("group_norm", x, N, groups, partials)
     d = L.GnDesc()
     d.x, d.x2, d.out = x.data_ptr(), (x2.data_ptr() if x2 is not None else None), out.data_ptr()
-    if isinstance(gamma, (list, tuple)) and len(gamma) > 1:
-        if len(gamma) > 4 or len(group_n) != len(gamma) or sum(group_n) != N:
-            raise L.EdgeStyleHipError("grouped group_norm: bad group table")
-        d.ngroups = len(gamma)
+    if grouped:
+        d.ngroups = len(gl)
         acc = 0
         for g, n in enumerate(group_n):
             acc += n
             d.n_end[g] = acc
-            d.gamma_g[g] = gamma[g].data_ptr()
-            d.beta_g[g] = beta[g].data_ptr()
+            d.gamma_g[g] = gl[g].data_ptr()
+            d.beta_g[g] = bl[g].data_ptr()
         d.partials = part.data_ptr()
     else:
-        if isinstance(gamma, (list, tuple)):
-            gamma, beta = gamma[0], beta[0]
-        d.gamma, d.beta, d.partials = gamma.data_ptr(), beta.data_ptr(), part.data_ptr()
+        d.gamma, d.beta, d.partials = gl[0].data_ptr(), bl[0].data_ptr(), part.data_ptr()
     gnp = getattr(x, "_gnp", None)
-    if gnp is not None and x2 is None and gn_handover(H * W, C1, groups) and gnp[1] == groups \
+    if gnp is not None and partials is None and x2 is None and gn_handover(H * W, C1, groups) and gnp[1] == groups \
             and tuple(gnp[0].shape) == (N, 2 * (H * W // 64), groups, 2):
         d.partials, d.ext_chunks = gnp[0].data_ptr(), 2 * (H * W // 64)      # the producer's statistics: one streaming pass
     d.N, d.HW, d.C1, d.C2, d.groups = N, H * W, C1, C2, groups
     d.eps, d.silu, d.dtype = eps, 1 if silu else 0, _dt(x)
     L.check(L.load().es_group_norm(C.byref(d), _stream()), "es_group_norm")
+    _drop_riders(out)
     return out
 
 
@@ -842,55 +911,61 @@ def gn_fold_ok(M: int, hw: int, groups: int, pw: "PackedWeight", pws, group_n) -
 
 def gn_proj_in(x: torch.Tensor, gamma, beta, groups: int, eps: float, pw, group_n: Optional[Sequence[int]] = None) -> torch.Tensor:
     """x [N,H,W,C] -> proj_in(GroupNorm(x)) [N,H,W,Cout] (no activation in between).  gamma / beta / pw: lists for a grouped launch
-    (group_n samples each)."""
-    N, H, W, Cc = x.shape
+    (group_n samples each).  x, gamma and beta are held to what ops.group_norm demands, whichever form runs."""
+    N, H, W, Cc, _ = _gn_operands("gn_proj_in", x, None, groups)
     pws = list(pw) if isinstance(pw, (list, tuple)) and len(pw) > 1 else None
     p0 = pw[0] if isinstance(pw, (list, tuple)) else pw
+    gl, bl = _norm_params("gn_proj_in", gamma, beta, Cc, x, nsets=None if pws is None else len(pws))
     M, hw = N * H * W, H * W
-    if not (x.is_contiguous() and gn_fold_ok(M, hw, groups, p0, pws, group_n)):
+    if not gn_fold_ok(M, hw, groups, p0, pws, group_n):
         kw = {} if group_n is None else dict(group_n=group_n)
         return conv_gemm(group_norm(x, gamma, beta, groups, eps, False, **kw), pw, **kw)
-    key = (x.device, N, groups, LANE)
-    part = _gn_partials.get(key)
-    if part is None:
-        part = torch.empty(L.load().es_group_norm_partials_bytes(N, groups) // 4, dtype=torch.float32, device=x.device)
-        _gn_partials[key] = part
+    part = _gn_partials_for("gn_proj_in", x, N, groups)
     d = L.GnDesc()
     d.x, d.partials = x.data_ptr(), part.data_ptr()
     d.N, d.HW, d.C1, d.C2, d.groups = N, hw, Cc, 0, groups
     d.eps, d.silu, d.dtype, d.stats_only = eps, 0, _dt(x), 1
     L.check(L.load().es_group_norm(C.byref(d), _stream()), "es_group_norm")
     out = torch.empty((N, H, W, p0.cout), dtype=x.dtype, device=x.device)
-    gl = list(gamma) if isinstance(gamma, (list, tuple)) else [gamma]
-    bl = list(beta) if isinstance(beta, (list, tuple)) else [beta]
     linear_xs(x.reshape(M, Cc), pws if pws is not None else p0, M, out.reshape(M, p0.cout),
               None if pws is None else [n * hw for n in group_n],
               gn=dict(part=part, gamma=gl, beta=bl, groups=groups, nchunk=L.load().es_group_norm_chunks(hw), hw=hw, eps=eps))
     return out
 
 
-def layer_norm(x: torch.Tensor, gamma, beta, eps: float = 1e-5, group_rows: Optional[Sequence[int]] = None) -> torch.Tensor:
+def layer_norm(x: torch.Tensor, gamma, beta, eps: float = 1e-5, group_rows: Optional[Sequence[int]] = None,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """LayerNorm over the last dimension of a contiguous x.  gamma / beta: fp32 [C], or lists with `group_rows` rows each.  out: the
+    tensor to write (x's shape and dtype, contiguous).  Refused before anything is recorded or launched: what the launch cannot read."""
+    if x.dim() < 1 or x.dtype not in (torch.float16, torch.bfloat16):
+        raise L.EdgeStyleHipError(f"layer_norm: x must be an fp16 or bf16 [..., C] tensor, not {x.dtype} {tuple(x.shape)}")
     Cc = x.shape[-1]
+    if not x.is_contiguous() or Cc < 8 or Cc % 8 or x.numel() < Cc:
+        raise L.EdgeStyleHipError(f"layer_norm: x must be contiguous, not empty and C a multiple of 8 (got shape {tuple(x.shape)}, strides {x.stride()})")
+    if x.device.type != "meta" and x.data_ptr() % 16:
+        raise L.EdgeStyleHipError("layer_norm: x must start at a multiple of 16 bytes (16-byte vector loads)")
     M = x.numel() // Cc
-    out = torch.empty_like(x)
-    if isinstance(gamma, (list, tuple)) and len(gamma) > 1:
-        if len(gamma) > 4 or len(group_rows) != len(gamma) or sum(group_rows) != M:
-            raise L.EdgeStyleHipError("grouped layer_norm: bad group table")
+    grouped = isinstance(gamma, (list, tuple)) and len(gamma) > 1
+    if grouped and (len(gamma) > 4 or group_rows is None or len(group_rows) != len(gamma) or sum(group_rows) != M):
+        raise L.EdgeStyleHipError("grouped layer_norm: bad group table")
+    gl, bl = _norm_params("layer_norm", gamma, beta, Cc, x)
+    if not L.load().es_layer_norm_route(Cc):
+        raise L.EdgeStyleHipError(f"layer_norm: C = {Cc} > 4096 unsupported")
+    out = _norm_out("layer_norm", x, tuple(x.shape), out)
+    if grouped:
         d = L.LnDesc()
         d.x, d.out = x.data_ptr(), out.data_ptr()
         acc = 0
         for g, n in enumerate(group_rows):
             acc += n
             d.row_end[g] = acc
-            d.gamma_g[g] = gamma[g].data_ptr()
-            d.beta_g[g] = beta[g].data_ptr()
-        d.ngroups, d.M, d.C, d.eps, d.dtype = len(gamma), M, Cc, eps, _dt(x)
+            d.gamma_g[g] = gl[g].data_ptr()
+            d.beta_g[g] = bl[g].data_ptr()
+        d.ngroups, d.M, d.C, d.eps, d.dtype = len(gl), M, Cc, eps, _dt(x)
         L.check(L.load().es_layer_norm_grouped(C.byref(d), _stream()), "es_layer_norm_grouped")
-        return out
-    if isinstance(gamma, (list, tuple)):
-        gamma, beta = gamma[0], beta[0]
-    L.check(L.load().es_layer_norm(_ptr(x), _ptr(out), _ptr(gamma), _ptr(beta), M, Cc, eps, _dt(x), _stream()),
-            "es_layer_norm")
+    else:
+        L.check(L.load().es_layer_norm(_ptr(x), _ptr(out), _ptr(gl[0]), _ptr(bl[0]), M, Cc, eps, _dt(x), _stream()), "es_layer_norm")
+    _drop_riders(out)
     return out
 
 

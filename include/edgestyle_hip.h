@@ -204,7 +204,10 @@ int es_attention_last_kernel(void);
 
 /* GroupNorm (+SiLU) over NHWC with optional channel-concat of two sources.
  * Replaces torch group_norm + silu of ResnetBlock2D.norm1/norm2, conv_norm_out, Transformer2DModel.norm.
- * partials: fp32 scratch [N][nchunk<=32][groups][2]. */
+ * partials: fp32 scratch of es_group_norm_partials_bytes(N, groups) bytes = [N][64][groups][2] floats.  The statistics pass cuts a sample into
+ * chunks of max(16, ceil(HW / 64)) pixels and writes the first es_group_norm_chunks(HW) = ceil(HW / that) <= 64 rows of every sample, densely
+ * ([N][nchunk][groups][2]); the one-launch slab form leaves the buffer untouched.
+ * Refused: C > 8192, groups > 64, and a two-launch geometry with C + groups > 8064 (its scale / shift tables would pass 64 KB of LDS). */
 typedef struct {
   const void* x; const void* x2; void* out;
   const float* gamma; const float* beta; float* partials;
@@ -228,6 +231,26 @@ int es_group_norm(const es_gn_desc* d, void* stream);
 size_t es_group_norm_partials_bytes(int N, int groups);
 int es_group_norm_chunks(int HW);                       /* pixel chunks per sample of the statistics pass */
 int es_group_norm_is_slab(int HW, int C, int groups);   /* 1: this geometry runs as ONE launch (slab form) */
+/* host-only query (tests, tools): the launch es_group_norm would make for this descriptor (N, HW, C1, C2, groups, ext_chunks, stats_only are
+ * read; no pointer is), computed by the launcher's own code.  0, or -1 with es_last_error() where es_group_norm would refuse the geometry.
+ * Fields that do not apply to the form are 0. */
+enum {
+  ES_GN_ROUTE_FORM = 0,          /* ES_GN_FORM_SLAB | ES_GN_FORM_TWO_LAUNCHES */
+  ES_GN_ROUTE_GPB = 1,           /* slab: groups per workgroup (1 | 2 | 4) */
+  ES_GN_ROUTE_SLOTS = 2,         /* slab: pixel slots (pixels in flight per workgroup) */
+  ES_GN_ROUTE_CPT = 3,           /* slab: register class, pixels per thread 8 | 16 | 24 */
+  ES_GN_ROUTE_PPB = 4,           /* statistics pass: pixels per chunk */
+  ES_GN_ROUTE_NCHUNK = 5,        /* ... chunks per sample = rows of `partials` written (ext_chunks where the producer wrote them) */
+  ES_GN_ROUTE_PS = 6,            /* ... pixel slots */
+  ES_GN_ROUTE_LANES = 7,         /* ... lanes that fold one group (8, or 4 for more than 32 groups) */
+  ES_GN_ROUTE_BLOCKS = 8,        /* apply pass: workgroups per sample (0: stats_only) */
+  ES_GN_ROUTE_IPT = 9,           /* ... items per thread the grid was sized for (4 | 8 | 16) */
+  ES_GN_ROUTE_GENERAL = 10,      /* ... 1: the general loop (an index division per item), 0: the fixed-column loop */
+  ES_GN_ROUTE_LDS = 11,          /* dynamic LDS bytes of the (last) launch */
+  ES_GN_ROUTE_FIELDS = 12
+};
+enum { ES_GN_FORM_SLAB = 1, ES_GN_FORM_TWO_LAUNCHES = 2 };
+int es_group_norm_route(const es_gn_desc* d, int32_t out[ES_GN_ROUTE_FIELDS]);
 
 /* LayerNorm over the last dim of [M, C] (BasicTransformerBlock.norm1/2/3), eps 1e-5. */
 int es_layer_norm(const void* x, void* out, const float* gamma, const float* beta, int M, int C, float eps,
@@ -242,6 +265,9 @@ typedef struct {
   int32_t dtype;
 } es_ln_desc;
 int es_layer_norm_grouped(const es_ln_desc* d, void* stream);
+/* host-only query: 16-byte chunks per lane of the kernel instantiation that holds a row of C channels - 1 | 2 | 3 | 4 | 8 (C <= 512 | 1024 |
+ * 1536 | 2048 | 4096); 0 where es_layer_norm refuses C (not a multiple of 8, or above 4096). */
+int es_layer_norm_route(int C);
 
 /* EdgeStyle fusion block: interleave (model/edgestyle_multicontrolnet.py:479-501) + ControlNetBlock
  * (model/edgestyle_multicontrolnet.py:23-63) without materialising the interleaved tensor.

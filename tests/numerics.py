@@ -27,8 +27,9 @@ The implicit-GEMM convolution has a metric of its own, the misrounded share (`mi
 `conv_base_alg`, further down): an extra rounding inside the launch is invisible to row_err and plain to it.
 
 `python -m tests.numerics --report` (GPU) runs the cases of test_numerics_gpu.py and the convolution sweep of test_conv_gpu.py and writes
-the measured tables to tests/NUMERICS.md (`--only conv`: the convolution table alone; `--only fusion`, `--only sampler`, `--only attention`:
-the sweep of test_fusion_gpu.py, the trajectories of test_sampler_gpu.py or the rows of test_attention_gpu.py alone).
+the measured tables to tests/NUMERICS.md (`--only conv`: the convolution table alone; `--only fusion`, `--only sampler`, `--only attention`,
+`--only norm`: the sweep of test_fusion_gpu.py, the trajectories of test_sampler_gpu.py, the rows of test_attention_gpu.py or the rows of
+test_norm_gpu.py alone).
 
 The fusion block (`fusion_case`, `fusion_ref64`, `fusion_base_ref`, `fusion_base_alg`, `fusion_grids`; judged per SAMPLE, `sample_err`) and the
 sampler step (`unipc_apply`, `ddim_apply`, `run_trajectory`, `traj_err`) have sections of their own at the end.
@@ -547,16 +548,22 @@ def xs_group_of_channel_2_16(c: int, cpg: int) -> int:
 GN_MAX_CHUNK = 64               # csrc/norm.hip: pixel chunks per sample of the statistics pass
 
 
+def gn_pixels_per_chunk(HW: int) -> int:
+    """gn_pixels_per_block of csrc/norm.hip: max(16, ceil(HW / 64)) - rounded UP, so that no HW gives more than 64 chunks"""
+    return max(16, (HW + GN_MAX_CHUNK - 1) // GN_MAX_CHUNK)
+
+
 def gn_chunked_stats(xg, eps):
     """GroupNorm statistics of xg [N, HW, groups, cpg] summed the way the kernels sum them - in three short levels, never as one long
-    sum: a channel's pixels inside a chunk of max(16, HW / 64) pixels, the channels of a group, the chunks of a sample
+    sum: a channel's pixels inside a chunk of max(16, ceil(HW / 64)) pixels, the channels of a group, the chunks of a sample
     (gn_stats_kernel + the prologue of gn_apply_kernel; the slab kernel and the producer's epilogue have the same three levels with
     other chunk sizes).  Every level's result is rounded to fp32 once (taken in fp64 inside the level - a little better than the
     kernels' chains of at most a few dozen fp32 additions there).  A flat fp32 sum over a group of 40960 values and more is up to ten
     times noisier than this at |mean| / std = 30, and than the kernels."""
     N, HW, G, cpg = xg.shape
-    ppb = max(16, HW // GN_MAX_CHUNK)
+    ppb = gn_pixels_per_chunk(HW)
     nchunk = (HW + ppb - 1) // ppb
+    assert nchunk <= GN_MAX_CHUNK
     pad = nchunk * ppb - HW
     xd = xg.double()
     if pad:
@@ -573,13 +580,18 @@ def gn_chunked_stats(xg, eps):
     return mean.reshape(N, 1, G, 1), torch.rsqrt(var + eps).reshape(N, 1, G, 1)
 
 
-def gn_base_alg(c, counts=None, defect=None, stats_from=None):
-    """one-pass statistics (fp32 sums in the kernels' chunking: gn_chunked_stats; E[x^2] - mean^2 clamped at 0); x * (rstd gamma) + (beta - mean rstd gamma) (-> SiLU) rounded
+def gn_base_alg(c, counts=None, defect=None, stats_from=None, geom=None):
+    """geom (a route of gn_route / lib.group_norm_route): the norm sweep's form of this function, gn_base_alg_geom - the statistics in the
+    chunk geometry of the form that RUNS (the slab's pixel slots too), two sources, and the planted defects GN_DEFECTS.  Without geom:
+    one-pass statistics (fp32 sums in the kernels' chunking: gn_chunked_stats; E[x^2] - mean^2 clamped at 0); x * (rstd gamma) + (beta - mean rstd gamma) (-> SiLU) rounded
     once; then the projection.  stats_from: another tensor of x's shape from which the STATISTICS are taken (the producer hand-over:
     sums of the fp32 accumulators, while the rounded values are normalised).
     defect "wrong_group_tail": the last three channels are normalised with the statistics of another group - what the 2^16
     reciprocal did to channels 637..639 of K = 640 with one group: they took (rstd, -mean rstd) of a "group 1" that nobody had
     written.  With several groups the stand-in is the first group's pair; with one group it is (0, 0), memory read as zeros."""
+    if geom is not None:
+        assert stats_from is None
+        return gn_base_alg_geom(c, geom, counts, defect)
     dt = c["dtype"]
     G = c["groups"]
 
@@ -610,6 +622,280 @@ def gn_base_alg(c, counts=None, defect=None, stats_from=None):
         return _per_set(c, counts, one)
     assert counts is None
     return one(c["x"], 0, stats_from)
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# csrc/norm.hip on every route (tests/test_norm_gpu.py): GroupNorm in the geometry that runs, plain LayerNorm
+# ----------------------------------------------------------------------------------------------------------------
+GN_UNROLL = 4                   # csrc/norm.hip: loads in flight per thread in the streaming loops
+GN_LDS_LIMIT = 64 * 1024
+GN_FORM_SLAB, GN_FORM_TWO = 1, 2
+GN_DEFECTS = ("pad_pixel_counted", "tail_pixels_dropped", "second_source_stride", "group_by_chunk", "neighbour_sample", "variance_unclamped")
+LN_DEFECTS = ("one_pass_variance", "group_boundary_by_block")
+NORM_KINDS = ("ratio_0", "ratio_30", "dominant", "constant", "zero")
+NORM_CONSTANT = 2.71875         # 87 / 32: exact in bf16 and fp16
+NORM_NAN_BITS_F32 = 0x7FC5A5A5  # the fp32 operands' guard: a quiet NaN with a payload no arithmetic produces (as ATTN_NAN_BITS for the 16-bit types)
+
+
+def gn_route(N, HW, C, groups, stats_only=False):
+    """Python mirror of gn_route() in csrc/norm.hip (chunk rule rounded up), keyed like lib.GN_ROUTE_FIELDS.  The GPU rows assert the
+    LIBRARY's answer (es_group_norm_route); this mirror places the table's rows without a GPU and is held to the library on the CPU."""
+    r = dict.fromkeys(("form", "gpb", "slots", "cpt", "ppb", "nchunk", "ps", "lanes", "blocks", "ipt", "general", "lds"), 0)
+    cpg, CH8 = C // groups, C // 8
+    if not stats_only:
+        for gpb in (1, 2, 4):
+            if groups % gpb or (gpb * cpg) % 8:
+                continue
+            W8 = gpb * cpg // 8
+            if W8 > 256:
+                break
+            PS = 256 // W8
+            cpt = (HW + PS - 1) // PS
+            if cpt <= 24:
+                r.update(form=GN_FORM_SLAB, gpb=gpb, slots=PS, cpt=8 if cpt <= 8 else 16 if cpt <= 16 else 24, lds=(2 * PS * gpb * cpg + 2 * gpb) * 4)
+                return r
+            break
+    ppb = gn_pixels_per_chunk(HW)
+    ps = 256 // CH8 if CH8 <= 256 else 1
+    r.update(form=GN_FORM_TWO, ppb=ppb, nchunk=(HW + ppb - 1) // ppb, ps=ps, lanes=8 if groups <= 32 else 4, lds=2 * ps * C * 4)
+    if stats_only:
+        return r
+    total = HW * CH8
+    ipt = GN_UNROLL
+    for cand in (16, 8):
+        if ((total + 256 * cand - 1) // (256 * cand)) * N >= 1024:
+            ipt = cand
+            break
+    blocks = min(max((total + 256 * ipt - 1) // (256 * ipt), 1), 1024)
+    q = CH8 // math.gcd(CH8, 256)
+    if q <= 64:
+        blocks = q if blocks < q else blocks // q * q
+    r.update(blocks=blocks, ipt=ipt, general=int((blocks * 256) % CH8 != 0), lds=(2 * C + 2 * groups + 256) * 4)
+    return r
+
+
+def gn_sum_chain(route, cpg) -> int:
+    """h of the standard bound |S - S64| <= h 2^-24 sum|x| for one row of `partials`: the longest chain of fp32 additions on the
+    two-launch route - a thread's pixels of one slot, a lane's share of the group's ps * cpg LDS entries, the fold steps"""
+    assert route["form"] == GN_FORM_TWO
+    L = route["lanes"]
+    return -(-route["ppb"] // route["ps"]) + -(-(route["ps"] * cpg) // L) + int(math.log2(L))
+
+
+NORM_TIE_CLEARANCE = 2.0 ** -19        # 32 fp32 ulps: an fp32 SiLU from a hardware exp and reciprocal (about 1 ulp each, two more roundings) is well inside
+
+
+def tie_distance(v64: torch.Tensor, dtype) -> torch.Tensor:
+    """relative distance of |v64| to the nearest rounding boundary of the storage dtype (the midpoint between the value it rounds to and that
+    value's neighbours): below the error of the arithmetic that produced v, WHICH neighbour is stored is a draw, not a property of the kernel"""
+    a = v64.double().abs()
+    bits = a.float().to(dtype).view(torch.int16)
+    assert bool((bits > 0).all()), "tie_distance is for nonzero finite values"
+    r, up, dn = (b.view(dtype).double() for b in (bits, bits + 1, bits - 1))
+    return torch.minimum((a - (r + up) / 2).abs(), (a - (r + dn) / 2).abs()) / a
+
+
+def norm_case(HW, C1, C2, groups, N, kind, dtype, silu=False, counts=None, seed=0, eps=1e-5):
+    """A GroupNorm case of the norm sweep: x [N, HW, 1, C1 + C2] from group_maps (which asserts its own postconditions), split into two
+    sources at C1.  kind: ratio_0 | ratio_30 (|mean| / std per (sample, group)), dominant (one channel holds >= 90 % of a group's
+    variance, ratio 30), constant (sample 0 is NORM_CONSTANT everywhere), zero (sample 0 is 0 everywhere; with SiLU no SiLU(beta) lies
+    within NORM_TIE_CLEARANCE of a rounding boundary of the storage dtype); the other samples of a constant / zero case are ratio_0 maps.  A geometry whose groups hold ONE value (HW * cpg == 1) has no spread to shape: only
+    constant and zero exist there.  Postconditions of the overwritten sample are asserted here."""
+    assert kind in NORM_KINDS
+    C = C1 + C2
+    cpg = C // groups
+    if HW * cpg == 1:
+        assert kind in ("constant", "zero"), "a group of one value is constant"
+        x = rnd(torch.randn(N, HW, 1, C, generator=_gen(seed), dtype=torch.float64), dtype)
+    else:
+        ratio = 30 if kind in ("ratio_30", "dominant") else 0
+        x = group_maps(N, C, HW, groups, ratio, 0.0, peak=4.0, dtype=dtype, seed=seed, dominant_channel=kind == "dominant", W=1)
+    if kind in ("constant", "zero"):
+        x[0] = NORM_CONSTANT if kind == "constant" else 0.0
+        assert float(rnd(x[0], dtype).min()) == float(x[0].max()) == (NORM_CONSTANT if kind == "constant" else 0.0)
+    c = gn_case(x, groups, dtype, silu=silu, eps=eps, seed=seed, ngroups=len(counts) if counts else 1)
+    c.update(C1=C1, C2=C2, kind=kind, counts=list(counts) if counts else None)
+    if kind == "zero" and silu:
+        # a zero sample's output is act(beta), asserted bit for bit: no SiLU(beta) may sit on a rounding boundary of the storage dtype
+        # (to within what an fp32 SiLU can resolve).  About C / 250 of the drawn betas do in fp16; they are moved by steps of 2^-12.
+        for beta in c["beta"]:
+            for _ in range(8):
+                close = tie_distance(F.silu(beta.double()), dtype) < NORM_TIE_CLEARANCE
+                if not bool(close.any()):
+                    break
+                beta[close] += 2.0 ** -12
+            assert float(tie_distance(F.silu(beta.double()), dtype).min()) >= NORM_TIE_CLEARANCE
+    return c
+
+
+def _gn_read_sources(c, x, defect):
+    """x [n, HW, 1, C] as the kernel reads it from its two dense sources; second_source_stride: x2 [n HW, C2] read with C1's row pitch
+    (element (row, cc) <- flat[row * C1 + cc]; addresses behind the buffer wrap, standing in for whatever lies there)"""
+    C1, C2 = c.get("C1", x.shape[-1]), c.get("C2", 0)
+    if defect != "second_source_stride" or not C2:
+        return x
+    n, HW = x.shape[0], x.shape[1]
+    flat = x[..., C1:].reshape(-1)
+    idx = (torch.arange(n * HW)[:, None] * C1 + torch.arange(C2)[None, :]) % flat.numel()
+    return torch.cat([x[..., :C1], flat[idx].reshape(n, HW, 1, C2)], dim=-1)
+
+
+def gn_geom_sums(xg, route, defect=None):
+    """fp32 (S, SS) per (sample, chunk, group) of xg [n, HW, G, cpg] in the chunk geometry of `route`, and the pixel count the geometry
+    covers.  Two launches: chunk k holds pixels [k ppb, (k + 1) ppb), inside it pixel j sits in slot j % ps; level 1 a (slot, channel)'s
+    pixels, level 2 the ps * cpg entries of a group.  Slab: ONE chunk of slots * ceil(HW / slots) pixels; level 1 as above, level 2a the
+    slots of a channel, 2b the channels of a group.  Every level is summed in fp64 and rounded to fp32 once (see gn_chunked_stats).
+    defects: tail_pixels_dropped (a slot's pixels behind its last full round of GN_UNROLL), neighbour_sample (pad pixels read the
+    next sample's first pixels, cyclically, instead of zeros)."""
+    n, HW, G, cpg = xg.shape
+    slab = route["form"] == GN_FORM_SLAB
+    ps = route["slots"] if slab else route["ps"]
+    ppb = ps * (-(-HW // ps)) if slab else route["ppb"]
+    nchunk = 1 if slab else route["nchunk"]
+    assert nchunk * ppb >= HW
+    rounds = -(-ppb // ps)
+    xd = xg.double()
+    pad = nchunk * ppb - HW
+    if pad:
+        if defect == "neighbour_sample":
+            nxt = torch.roll(xd, -1, 0)
+            fill = torch.cat([nxt] * (-(-pad // HW)), 1)[:, :pad]
+        else:
+            fill = torch.zeros(n, pad, G, cpg, dtype=torch.float64)
+        xd = torch.cat([xd, fill], 1)
+    xd = xd.reshape(n, nchunk, ppb, G, cpg)
+    if rounds * ps != ppb:
+        xd = torch.cat([xd, torch.zeros(n, nchunk, rounds * ps - ppb, G, cpg, dtype=torch.float64)], 2)
+    xd = xd.reshape(n, nchunk, rounds, ps, G, cpg)
+    if defect == "tail_pixels_dropped":
+        j = torch.arange(rounds)[:, None] * ps + torch.arange(ps)[None, :]                              # pixel inside the chunk
+        px = torch.arange(nchunk)[:, None, None] * ppb + j[None]
+        valid = (j[None] < ppb) & (px < HW)
+        keep = valid.sum(dim=1, keepdim=True) // GN_UNROLL * GN_UNROLL                                  # [nchunk, 1, ps]
+        mask = (torch.arange(rounds)[None, :, None] < keep).double()
+        xd = xd * mask[None, :, :, :, None, None]
+
+    def levels(t):
+        t = t.sum(dim=2).float()                                    # [n, nchunk, ps, G, cpg]
+        if slab:
+            t = t.double().sum(dim=2).float()                       # slots of a channel
+            return t.double().sum(dim=3).float()                    # channels of a group -> [n, 1, G]
+        return t.double().sum(dim=(2, 4)).float()                   # [n, nchunk, G]
+    return levels(xd), levels(xd * xd), nchunk * ppb
+
+
+def gn_base_alg_geom(c, route, counts=None, defect=None):
+    """The algorithm of csrc/norm.hip on the route that runs: gn_geom_sums, the chunks of a sample added up (rounded once), mean = S / cnt,
+    var = SS / cnt - mean^2 clamped at 0, y = x (rstd gamma) + (beta - mean rstd gamma) (-> SiLU), rounded once.  Defects: GN_DEFECTS."""
+    assert defect is None or defect in GN_DEFECTS, defect
+    dt, G = c["dtype"], c["groups"]
+
+    def one(x, i):
+        n, C = x.shape[0], x.shape[-1]
+        HW, cpg = x[0].numel() // C, C // G
+        xr = _gn_read_sources(c, x.float().reshape(n, HW, 1, C), defect)
+        xg = xr.reshape(n, HW, G, cpg)
+        S, SS, covered = gn_geom_sums(xg, route, defect)
+        S, SS = S.double().sum(dim=1).float(), SS.double().sum(dim=1).float()          # [n, G]
+        cnt = float(cpg) * float(covered if defect == "pad_pixel_counted" else HW)
+        mean = S / cnt
+        var = SS / cnt - mean * mean
+        if defect != "variance_unclamped":
+            var = var.clamp_min(0.0)
+        rstd = torch.rsqrt(var + c["eps"])
+        grp = torch.arange(C) // cpg
+        if defect == "group_by_chunk":
+            grp = (torch.arange(C) // 8 * 8) // cpg
+        a = rstd[:, grp] * c["gamma"][i]                                                # [n, C]
+        b = c["beta"][i] - mean[:, grp] * a
+        y = xr.reshape(n, HW, C) * a[:, None, :] + b[:, None, :]
+        if c["silu"]:
+            y = F.silu(y)
+        return rnd(y, dt).reshape(x.shape)
+    return _per_set(c, counts, one)
+
+
+def ln_plain_case(x, dtype, ngroups=1, seed=0, eps=1e-5):
+    """rows x [M, C] and `ngroups` parameter sets of a plain LayerNorm (es_layer_norm / es_layer_norm_grouped)"""
+    g = _gen(seed + 15485863)
+    C = x.shape[1]
+    return dict(x=x, dtype=dtype, eps=eps, gamma=[1 + 0.2 * torch.randn(C, generator=g) for _ in range(ngroups)],
+                beta=[0.2 * torch.randn(C, generator=g) for _ in range(ngroups)])
+
+
+def _ln_sets(c, rows, by_block=False):
+    """parameter set of every row; by_block (a planted defect): a 4-row block takes its first row's set"""
+    M = c["x"].shape[0]
+    rows = rows or [M]
+    assert sum(rows) == M and len(rows) == len(c["gamma"])
+    r = torch.arange(M)
+    if by_block:
+        r = r // 4 * 4
+    ends = torch.tensor(rows).cumsum(0)
+    return (r[:, None] >= ends[None, :]).sum(dim=1)
+
+
+def ln_plain_ref64(c, rows=None):
+    x = c["x"].double()
+    st = _ln_sets(c, rows)
+    gam, bet = torch.stack(c["gamma"]).double()[st], torch.stack(c["beta"]).double()[st]
+    return (x - x.mean(dim=1, keepdim=True)) / torch.sqrt(x.var(dim=1, unbiased=False, keepdim=True) + c["eps"]) * gam + bet
+
+
+def ln_plain_base_ref(c, rows=None):
+    """the textbook sequence in fp32 with every op's output rounded to the storage dtype: normalise -> round -> scale -> round -> shift -> round"""
+    dt = c["dtype"]
+    x = c["x"].float()
+    st = _ln_sets(c, rows)
+    gam, bet = torch.stack(c["gamma"])[st], torch.stack(c["beta"])[st]
+    mean = x.mean(dim=1, keepdim=True)
+    var = ((x - mean) ** 2).mean(dim=1, keepdim=True)
+    n = rnd((x - mean) * torch.rsqrt(var + c["eps"]), dt)
+    return rnd(rnd(n * gam, dt) + bet, dt)
+
+
+def ln_plain_base_alg(c, rows=None, defect=None):
+    """layer_norm_kernel as designed: one wave per row, lane l holds the 16-byte chunks l, l + 64, ...; EXACT two-pass statistics in fp32 -
+    a lane's values added in order, the 64 lanes folded by wave_sum's tree, mean = s / C, then the squared deviations the same way;
+    (x - mean) rstd gamma + beta rounded once.  Lanes behind the row's end add nothing to either sum.
+    defects: one_pass_variance (E[x^2] - mean^2 clamped at 0), group_boundary_by_block (_ln_sets by_block)."""
+    assert defect is None or defect in LN_DEFECTS, defect
+    x = c["x"].float()
+    M, C = x.shape
+    CH8 = C // 8
+    vpl = -(-CH8 // 64)
+    st = _ln_sets(c, rows, by_block=defect == "group_boundary_by_block")
+    gam, bet = torch.stack(c["gamma"])[st], torch.stack(c["beta"])[st]
+    xp = torch.cat([x, torch.zeros(M, vpl * 512 - C)], 1).reshape(M, vpl, 64, 8)
+    live = (torch.arange(vpl * 64).reshape(vpl, 64) < CH8).float()[None, :, :, None]
+
+    def lanes_then_tree(t):                      # t [M, vpl, 64, 8] -> [M, 1]
+        acc = torch.zeros(M, 64)
+        for i in range(vpl):
+            for e in range(8):
+                acc = acc + t[:, i, :, e]
+        return _wave_tree(acc)[:, None]
+    mean = lanes_then_tree(xp) / float(C)
+    if defect == "one_pass_variance":
+        var = (lanes_then_tree(xp * xp) / float(C) - mean * mean).clamp_min(0.0)
+    else:
+        d = (xp - mean[:, :, None, None]) * live
+        var = lanes_then_tree(d * d) / float(C)
+    rstd = torch.rsqrt(var + c["eps"])
+    return rnd((x - mean) * rstd * gam + bet, c["dtype"])
+
+
+def norm_guarded(t, guard, dtype, device="cpu"):
+    """(whole buffer, recipe of the middle slice) for an operand t: `guard` elements of NaN on each side (fp16 / bf16: the payload NaNs
+    of ATTN_NAN_BITS; fp32: NORM_NAN_BITS_F32), the operand's values in the middle.  guard must keep the slice 16-byte aligned."""
+    assert (guard * torch.empty(0, dtype=dtype).element_size()) % 16 == 0
+    n = t.numel()
+    if dtype == torch.float32:
+        big = torch.full((n + 2 * guard,), NORM_NAN_BITS_F32, dtype=torch.int32).view(torch.float32)
+    else:
+        big = torch.full((n + 2 * guard,), ATTN_NAN_BITS[dtype], dtype=torch.int16).view(dtype)
+    big[guard:guard + n] = t.reshape(-1).to(dtype)
+    return big.to(device), (guard, n)
 
 
 # ----------------------------------------------------------------------------------------------------------------

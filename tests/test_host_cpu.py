@@ -831,3 +831,216 @@ def test_attention_refuses_operands_the_launch_cannot_read(monkeypatch):
             assert dry.size() == 6, kw
         assert L.es_attention(ctypes.byref(desc(ldk=32)), None) == -1 and b"row stride below head_dim" in L.es_last_error()
         assert dry.size() == 6
+
+
+def _gn_two_launch_route(HW):
+    """groups of ONE channel are never eligible for the slab form: the statistics pass's own geometry for this HW"""
+    r = lib.group_norm_route(1, HW, 8, 0, 8)
+    assert r["form"] == lib.GN_FORM_TWO_LAUNCHES
+    return r
+
+
+def test_group_norm_chunks_fit_the_partials_buffer_for_every_size():
+    """The statistics pass writes es_group_norm_chunks(HW) rows of `partials` per sample and both hosts allocate 64
+    (es_group_norm_partials_bytes): 1 <= chunks <= 64 for EVERY HW, the chunks cover HW with none of them empty, and the sizes the models
+    and the goldens use keep the chunking they had.  With the chunk size rounded DOWN (max(16, HW / 64)) every HW > 1024 that is no multiple
+    of 64 gave 65 .. 68 chunks - first at HW = 1025 - and the two launches wrote and read up to N * 4 * groups * 2 floats behind the buffer."""
+    L = lib.load()
+    sizes = list(range(1, 70001)) + [70001 + 7919 * k for k in range(1, 64)] + [(1 << 20) - 1, (1 << 20) + 1, (1 << 24) - 65, (1 << 24) - 1, 1 << 24]
+    for HW in sizes:
+        n = L.es_group_norm_chunks(HW)
+        assert 1 <= n <= 64, (HW, n)
+        if HW <= 2048 or HW % 997 == 0 or HW > 70000:       # the route query is the launcher's own code: same chunk count, and its chunk size covers HW
+            r = _gn_two_launch_route(HW)
+            assert r["nchunk"] == n and r["ppb"] >= 16 and (n - 1) * r["ppb"] < HW <= n * r["ppb"], (HW, r)
+        ppb = max(16, -(-HW // 64))
+        assert (n - 1) * ppb < HW <= n * ppb, (HW, n)
+    for HW, n in {16: 1, 64: 4, 144: 9, 256: 16, 1023: 64, 1024: 64, 4096: 64, 9216: 64, 65536: 64}.items():       # read off the commit before the fix
+        assert L.es_group_norm_chunks(HW) == n, HW
+    for HW, ppb in {1023: 16, 1024: 16, 1025: 17, 4096: 64, 9216: 144}.items():
+        assert _gn_two_launch_route(HW)["ppb"] == ppb
+    assert L.es_group_norm_chunks(0) == 0
+    for N, G in [(1, 1), (3, 32), (14, 64)]:
+        assert L.es_group_norm_partials_bytes(N, G) == N * 64 * G * 2 * 4
+    from tests import numerics as nm
+    for HW in (1, 15, 16, 17, 1023, 1025, 1087, 1225, 1296, 4225, 69999):
+        assert nm.gn_pixels_per_chunk(HW) == _gn_two_launch_route(HW)["ppb"]
+
+
+def test_group_norm_route_is_the_launchers_own_answer():
+    """es_group_norm_route / es_layer_norm_route against the Python mirror of the rule (tests/numerics.py gn_route) on a grid of geometries, the
+    form against es_group_norm_is_slab, and the refusals the launch itself would make."""
+    from tests import numerics as nm
+    L = lib.load()
+    for HW in (1, 7, 24, 25, 64, 408, 409, 816, 817, 1224, 1225, 4096, 9216):
+        for Cc, G in [(8, 1), (8, 8), (24, 8), (64, 64), (120, 40), (128, 64), (320, 32), (640, 32), (1040, 8), (1280, 32), (2048, 1), (2056, 1), (2560, 32)]:
+            for N in (1, 3, 14):
+                r = lib.group_norm_route(N, HW, Cc, 0, G)
+                assert r == nm.gn_route(N, HW, Cc, G), (N, HW, Cc, G, r)
+                assert (r["form"] == lib.GN_FORM_SLAB) == bool(L.es_group_norm_is_slab(HW, Cc, G))
+            s = lib.group_norm_route(3, HW, Cc, 0, G, stats_only=True)
+            assert s == nm.gn_route(3, HW, Cc, G, stats_only=True) and s["form"] == lib.GN_FORM_TWO_LAUNCHES and s["blocks"] == 0
+            assert s["nchunk"] == L.es_group_norm_chunks(HW)
+    r = lib.group_norm_route(2, 4096, 320, 0, 32, ext_chunks=128)          # the producer's statistics: 2 * HW / 64 rows, no slab
+    assert r["form"] == lib.GN_FORM_TWO_LAUNCHES and r["nchunk"] == 128
+    assert lib.group_norm_route(2, 64, 1280, 0, 32)["form"] == lib.GN_FORM_SLAB
+    assert lib.group_norm_route(14, 4096, 320, 0, 32)["ipt"] == 8 and lib.group_norm_route(2, 4096, 320, 0, 32)["ipt"] == 4
+    for kw, msg in [(dict(C1=12), "multiples of 8"), (dict(groups=3), "bad group count"), (dict(groups=65, C1=520), "bad group count"),
+                    (dict(HW=0), "empty problem"), (dict(C1=8200, groups=1), "C too large")]:
+        a = dict(N=1, HW=64, C1=320, C2=0, groups=32)
+        a.update(kw)
+        with pytest.raises(lib.EdgeStyleHipError, match=msg):
+            lib.group_norm_route(**a)
+    for Cc, vpl in {8: 1, 512: 1, 520: 2, 1024: 2, 1032: 3, 1536: 3, 1544: 4, 2048: 4, 2056: 8, 4096: 8, 4104: 0, 12: 0, 0: 0}.items():
+        assert L.es_layer_norm_route(Cc) == vpl, Cc
+
+
+def test_group_norm_refuses_tables_that_do_not_fit_the_lds():
+    """gn_apply_kernel keeps (2 C + 2 groups + 256) floats in dynamic LDS and a launch gets 64 KB: a two-launch geometry with
+    C + groups > 8064 is refused by name, before it is recorded (dry recorder, host buffers) - not left to fail as a launch error.  The slab
+    form and the statistics pass alone need less and stay legal up to C = 8192; so does LayerNorm's limit of 4096 channels."""
+    buf = (ctypes.c_char * 4096)()
+    p = ctypes.addressof(buf)
+
+    def desc(Cc, G, HW=4096, **kw):
+        d = lib.GnDesc()
+        d.x = d.out = d.gamma = d.beta = d.partials = p
+        d.N, d.HW, d.C1, d.C2, d.groups, d.eps, d.dtype = 2, HW, Cc, 0, G, 1e-5, lib.ES_F16
+        for k, v in kw.items():
+            setattr(d, k, v)
+        return d
+
+    with _DryPlan() as dry:
+        L = dry.L
+        assert L.es_group_norm(ctypes.byref(desc(8000, 32)), None) == 0 and dry.size() == 1            # 65 280 bytes
+        assert L.es_group_norm(ctypes.byref(desc(8056, 8)), None) == 0 and dry.size() == 2             # 65 536 bytes: the limit itself
+        for Cc, G in [(8064, 1), (8064, 64), (8192, 1), (8056, 19)]:
+            assert lib.group_norm_route(2, 4096, Cc, 0, G, stats_only=True)["form"] == lib.GN_FORM_TWO_LAUNCHES
+            assert L.es_group_norm(ctypes.byref(desc(Cc, G)), None) == -1, (Cc, G)
+            assert b"es_group_norm: the two-launch form's scale / shift tables exceed 64 KB of LDS" in L.es_last_error(), L.es_last_error()
+            with pytest.raises(lib.EdgeStyleHipError, match="64 KB of LDS"):
+                lib.group_norm_route(2, 4096, Cc, 0, G)
+            assert dry.size() == 2
+        assert L.es_group_norm(ctypes.byref(desc(8192, 1, stats_only=1)), None) == 0 and dry.size() == 3      # the statistics pass alone: 64 KB
+        assert lib.group_norm_route(2, 16, 8192, 0, 64)["form"] == lib.GN_FORM_SLAB
+        assert L.es_group_norm(ctypes.byref(desc(8192, 64, HW=16)), None) == 0 and dry.size() == 4            # slab: 16 KB
+        assert L.es_group_norm(ctypes.byref(desc(8200, 1)), None) == -1 and b"C too large" in L.es_last_error()
+        assert L.es_layer_norm(p, p, p, p, 4, 4096, 1e-5, lib.ES_F16, None) == 0 and dry.size() == 5
+        assert L.es_layer_norm(p, p, p, p, 4, 4104, 1e-5, lib.ES_F16, None) == -1 and b"C > 4096 unsupported" in L.es_last_error()
+        ln = lib.LnDesc()
+        ln.x = ln.out = p
+        ln.ngroups, ln.M, ln.C, ln.eps, ln.dtype = 2, 8, 4104, 1e-5, lib.ES_F16
+        for g in range(2):
+            ln.gamma_g[g] = ln.beta_g[g] = p
+            ln.row_end[g] = 4 * (g + 1)
+        assert L.es_layer_norm_grouped(ctypes.byref(ln), None) == -1 and b"C > 4096 unsupported" in L.es_last_error()
+        assert dry.size() == 5
+
+
+def test_norm_wrappers_refuse_operands_the_launch_cannot_read(monkeypatch):
+    """ops.group_norm, ops.gn_proj_in and ops.layer_norm hand data_ptr()s and one geometry to the library, which reads every operand as dense:
+    a non-contiguous x or x2, x2 of another dtype, device or N, H, W, channel counts that are no multiples of 8 or do not divide into the
+    groups, gamma / beta that are not fp32, not C long or elsewhere, an `out` or `partials` of another shape, and any of x, x2, out, gamma,
+    beta that does not start at a multiple of 16 bytes (all are read or written as 16-byte vectors) - EdgeStyleHipError by name,
+    before anything is recorded or launched (dry recorder, host buffers).  Batch slices and out= / partials= of the right shape stay legal."""
+    monkeypatch.setattr(ops, "_stream", lambda: None)
+    N, H, W, C1, C2, G = 2, 3, 5, 16, 24, 8
+    z = lambda *s: torch.zeros(*s).half()
+    x, x2 = z(N, H, W, C1), z(N, H, W, C2)
+    f = lambda n: torch.ones(n)
+    gn_bad = {
+        "x must be contiguous": dict(x=z(N, H, W, 2 * C1)[..., :C1]),
+        "x must be contiguous#": dict(x=z(N, W, H, C1).transpose(1, 2)),
+        "x must be an fp16 or bf16": dict(x=x.float()),
+        "x must be an fp16 or bf16#": dict(x=x[0]),
+        "x2 must be contiguous": dict(x2=z(N, H, W, 2 * C2)[..., C2:]),
+        "x2 is torch.bfloat16": dict(x2=x2.bfloat16()),
+        "x2 is torch.float16 on meta": dict(x2=x2.to("meta")),
+        "x2 .* does not match x .* in N, H, W": dict(x2=z(N, H, W + 1, C2)),
+        "x2 .* does not match x .* in N, H, W#": dict(x2=z(N + 1, H, W, C2)[:N + 1]),
+        "channels 12.24 must be multiples of 8": dict(x=z(N, H, W, 12), gamma=f(36), beta=f(36), groups=4),
+        "channels 16.20 must be multiples of 8": dict(x2=z(N, H, W, 20), gamma=f(36), beta=f(36), groups=4),
+        "40 channels do not divide into 7 groups": dict(groups=7),
+        "gamma must be a contiguous fp32 .40. tensor": dict(gamma=f(40).half()),
+        "gamma must be a contiguous fp32 .40. tensor#": dict(gamma=f(32)),
+        "gamma must be a contiguous fp32 .40. tensor##": dict(gamma=f(80)[::2]),
+        "beta must be a contiguous fp32 .40. tensor": dict(beta=f(40).double()),
+        "beta must be a contiguous fp32 .40. tensor#": dict(beta=f(48)),
+        "beta must be a contiguous fp32 .40. tensor on cpu": dict(beta=f(40).to("meta")),
+        "gamma must start at a multiple of 16 bytes": dict(gamma=f(41)[1:]),
+        "beta must start at a multiple of 16 bytes": dict(beta=f(42)[2:]),
+        "x must start at a multiple of 16 bytes": dict(x=z(N * H * W * C1 + 4)[4:].view(N, H, W, C1)),
+        "x2 must start at a multiple of 16 bytes": dict(x2=z(N * H * W * C2 + 4)[4:].view(N, H, W, C2)),
+        "out must start at a multiple of 16 bytes": dict(out=z(N * H * W * 40 + 4)[4:].view(N, H, W, 40)),
+        "bad group table": dict(gamma=[f(40), f(40)], beta=[f(40), f(40)], group_n=[1, 2]),
+        "2 gamma and 1 beta sets": dict(gamma=[f(40), f(40)], beta=[f(40)], group_n=[1, 1]),
+        "out must be a contiguous torch.float16 .2, 3, 5, 40.": dict(out=z(N, H, W, C1)),
+        "out must be a contiguous torch.float16 .2, 3, 5, 40.#": dict(out=z(N, H, W, 80)[..., :40]),
+        "out must be a contiguous torch.float16 .2, 3, 5, 40.##": dict(out=torch.zeros(N, H, W, 40)),
+        "out must be a contiguous torch.float16 .2, 3, 5, 40.###": dict(out=z(N * H * W, 40)),
+        "partials must be a contiguous fp32 tensor of 2048 elements": dict(partials=torch.zeros(N * 32 * G * 2)),
+        "partials must be a contiguous fp32 tensor of 2048 elements#": dict(partials=torch.zeros(2048).half()),
+        "partials must be a contiguous fp32 tensor of 2048 elements##": dict(partials=torch.zeros(4096)[::2]),
+    }
+    with _DryPlan() as dry:
+        for msg, kw in gn_bad.items():
+            a = dict(x=x, x2=x2, gamma=f(40), beta=f(40), groups=G, group_n=None, out=None, partials=None)
+            a.update(kw)
+            with pytest.raises(lib.EdgeStyleHipError, match="group_norm: " + msg.rstrip("#")):
+                ops.group_norm(a["x"], a["gamma"], a["beta"], a["groups"], 1e-5, True, x2=a["x2"], group_n=a["group_n"], out=a["out"], partials=a["partials"])
+            assert dry.size() == 0, msg
+        out, part = z(N + 2, H, W, 40), torch.zeros(3 * 2048)
+        y = ops.group_norm(x, f(40), f(40), G, 1e-5, True, x2=x2, out=out[1:N + 1], partials=part[2048:4096])
+        assert dry.size() == 1 and y.data_ptr() == out[1].data_ptr()
+        y = ops.group_norm(z(N + 1, H, W, C1)[1:], [f(40), f(40)], [f(40), f(40)], G, 1e-5, False, x2=x2, group_n=[1, 1])
+        assert dry.size() == 2 and y.shape == (N, H, W, 40) and y.is_contiguous()
+
+        # gn_proj_in: the same demands on x, gamma and beta, whichever form runs
+        g = torch.Generator().manual_seed(0)
+        pw = ops.pack_weight(torch.randn(64, 40, 1, 1, generator=g), torch.randn(64, generator=g), torch.float16, "cpu")
+        xin = z(N, H, W, 40)
+        proj_bad = {
+            "x must be contiguous": dict(x=z(N, H, W, 80)[..., :40]),
+            "x must be an fp16 or bf16": dict(x=xin.float()),
+            "40 channels do not divide into 7 groups": dict(groups=7),
+            "gamma must be a contiguous fp32 .40. tensor": dict(gamma=f(40).half()),
+            "beta must be a contiguous fp32 .40. tensor": dict(beta=f(32)),
+            "channels 36.0 must be multiples of 8": dict(x=z(N, H, W, 36), gamma=f(36), beta=f(36), groups=4),
+        }
+        for msg, kw in proj_bad.items():
+            a = dict(x=xin, gamma=f(40), beta=f(40), groups=G)
+            a.update(kw)
+            with pytest.raises(lib.EdgeStyleHipError, match="gn_proj_in: " + msg):
+                ops.gn_proj_in(a["x"], a["gamma"], a["beta"], a["groups"], 1e-6, pw)
+            assert dry.size() == 2, msg
+        y = ops.gn_proj_in(xin, f(40), f(40), G, 1e-6, pw)
+        assert dry.size() == 4 and y.shape == (N, H, W, 64)              # GroupNorm + projection
+
+        tok = z(6, 40)
+        ln_bad = {
+            "x must be contiguous": dict(x=z(6, 80)[:, :40]),
+            "x must be contiguous, not empty and C a multiple of 8": dict(x=z(6, 36), gamma=f(36), beta=f(36)),
+            "x must be an fp16 or bf16": dict(x=tok.float()),
+            "gamma must be a contiguous fp32 .40. tensor": dict(gamma=f(40).bfloat16()),
+            "beta must be a contiguous fp32 .40. tensor": dict(beta=f(41)),
+            "beta must be a contiguous fp32 .40. tensor on cpu": dict(beta=f(40).to("meta")),
+            "x must start at a multiple of 16 bytes": dict(x=z(6 * 40 + 4)[4:].view(6, 40)),
+            "gamma must start at a multiple of 16 bytes": dict(gamma=f(43)[3:]),
+            "out must start at a multiple of 16 bytes": dict(out=z(6 * 40 + 4)[4:].view(6, 40)),
+            "bad group table": dict(gamma=[f(40)] * 2, beta=[f(40)] * 2, group_rows=[3, 4]),
+            "C = 4104 > 4096 unsupported": dict(x=z(2, 4104), gamma=f(4104), beta=f(4104)),
+            "out must be a contiguous torch.float16 .6, 40.": dict(out=z(6, 48)),
+            "out must be a contiguous torch.float16 .6, 40.#": dict(out=z(6, 80)[:, :40]),
+            "out must be a contiguous torch.float16 .6, 40.##": dict(out=tok.bfloat16()),
+        }
+        for msg, kw in ln_bad.items():
+            a = dict(x=tok, gamma=f(40), beta=f(40), group_rows=None, out=None)
+            a.update(kw)
+            with pytest.raises(lib.EdgeStyleHipError, match="layer_norm: " + msg.rstrip("#")):
+                ops.layer_norm(a["x"], a["gamma"], a["beta"], group_rows=a["group_rows"], out=a["out"])
+            assert dry.size() == 4, msg
+        big = z(8, 40)
+        y = ops.layer_norm(tok.view(2, 3, 40), f(40), f(40), out=big[1:7].view(2, 3, 40))
+        assert dry.size() == 5 and y.data_ptr() == big[1].data_ptr()
+        ops.layer_norm(tok, [f(40)] * 3, [f(40)] * 3, group_rows=[1, 4, 1])
+        assert dry.size() == 6

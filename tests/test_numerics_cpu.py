@@ -716,3 +716,160 @@ def test_ddim_table_applied_as_the_kernel_applies_it_matches_the_oracle():
             worst_t, worst_a = max(worst_t, e_table), max(worst_a, e_alg)
         print(f"numerics: ddim T {T}: worst so far fp32 table {worst_t:.3e}  all fp32 {worst_a:.3e}")
     assert worst_t <= 4 * DDIM_TABLE_ERR and worst_a <= 4 * DDIM_FP32_ERR, (worst_t, worst_a)
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# csrc/norm.hip on every route (tests/test_norm_gpu.py)
+# ----------------------------------------------------------------------------------------------------------------
+def _norm_case(geo, kind, dtype, N=3, silu=False, seed=1):
+    HW, C1, C2, G = geo
+    return nm.norm_case(HW, C1, C2, G, N, kind, dtype, silu=silu, seed=seed), nm.gn_route(N, HW, C1 + C2, G)
+
+
+def _norm_bars(c, route):
+    """(ref64, base_alg's output, the larger of the two baselines' errors): a planted defect is OUTSIDE when its error exceeds MARGIN x that -
+    it then misses both bars of the GPU test, whichever baseline is the better one"""
+    ref = nm.gn_ref64(c)
+    clean = nm.gn_base_alg(c, geom=route)
+    return ref, clean, max(nm.row_err(clean, ref), nm.row_err(nm.gn_base_ref(c), ref))
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_norm_gpu_table_rows_build_and_their_design_is_inside_the_bars(dtype):
+    """every row of test_norm_gpu.GN_TABLE and LN_TABLE: the generator's postconditions hold, the library's route is the mirror's (the table
+    itself is checked against the mirror when that module is imported), both baselines have an error and the design is inside 2 x base_ref"""
+    from tests import test_norm_gpu as NG
+    from edgestyle_amd import lib
+    for row in NG.GN_TABLE:
+        c = nm.norm_case(row["HW"], row["C1"], row["C2"], row["groups"], NG.N_ROW, row["kind"], dtype, silu=row["silu"], seed=row["seed"])
+        route = lib.group_norm_route(NG.N_ROW, row["HW"], row["C1"], row["C2"], row["groups"])
+        NG.assert_route(row, route)
+        ref = nm.gn_ref64(c)
+        e_alg, e_ref = nm.row_err(nm.gn_base_alg(c, geom=route), ref), nm.row_err(nm.gn_base_ref(c), ref)
+        assert 0 < e_alg <= nm.MARGIN * e_ref, (NG.gn_id(row), e_alg, e_ref)
+    for row in NG.LN_TABLE:
+        assert lib.load().es_layer_norm_route(row["C"]) == NG.LN_VPL[row["C"]]
+        c = nm.ln_plain_case(nm.token_rows(row["M"], row["C"], row["ratio"], dtype=dtype, seed=row["M"] + row["C"]), dtype, seed=row["C"])
+        ref = nm.ln_plain_ref64(c)
+        e_alg, e_ref = nm.row_err(nm.ln_plain_base_alg(c), ref), nm.row_err(nm.ln_plain_base_ref(c), ref)
+        assert 0 < e_alg <= nm.MARGIN * e_ref, (NG.ln_id(row), e_alg, e_ref)
+
+
+def test_norm_geometry_sums_agree_with_the_plain_chunking():
+    """gn_base_alg with the route's geometry and without one (gn_chunked_stats, the form the older tests use) are the same algorithm with the
+    levels cut differently: both inside the bar on the same case, and with a geometry of one slot per chunk the sums are the same numbers"""
+    x = nm.group_maps(2, 320, 36, 32, 30, dtype=torch.float16, seed=3)
+    c = nm.gn_case(x, 32, torch.float16, seed=3)
+    route = nm.gn_route(2, 1296, 320, 32)
+    assert (route["ppb"], route["nchunk"], route["ps"]) == (21, 62, 6)
+    ref = nm.gn_ref64(c)
+    a, b = nm.row_err(nm.gn_base_alg(c), ref), nm.row_err(nm.gn_base_alg(c, geom=route), ref)
+    assert max(a, b) <= nm.MARGIN * min(a, b)
+    one_slot = dict(route, ps=1)
+    xg = x.reshape(2, 1296, 32, 10)
+    S, SS, covered = nm.gn_geom_sums(xg, one_slot)
+    assert covered == 62 * 21 and S.shape == (2, 62, 32)
+    mean, rstd = nm.gn_chunked_stats(xg, c["eps"])
+    m2 = S.double().sum(dim=1).float() / (10.0 * 1296.0)
+    assert torch.allclose(m2, mean.reshape(2, 32), rtol=1e-6, atol=0)
+
+
+GN_DEFECT_ROWS = {  # defect -> (rows it is OUTSIDE the bars at, rows it cannot be seen at: (geometry, kind, why))
+    "pad_pixel_counted": ([((1225, 320, 0, 32), "ratio_30"), ((409, 320, 0, 32), "ratio_30"), ((17, 8, 16, 8), "ratio_30")],
+                          [((408, 320, 0, 32), "ratio_30", "8 x 51 pixel slots hold exactly 408 pixels"), ((24, 2048, 0, 1), "ratio_30", "one slot, 24 pixels: no pad")]),
+    "tail_pixels_dropped": ([((1225, 320, 0, 32), "ratio_0"), ((25, 2048, 0, 1), "ratio_30"), ((1087, 8, 16, 8), "ratio_0")],
+                            [((300, 1040, 0, 8), "ratio_30", "one slot, chunks of 16 and a last one of 12 pixels: whole rounds of GN_UNROLL")]),
+    "second_source_stride": ([((409, 104, 216, 32), "ratio_0"), ((17, 8, 16, 8), "ratio_30")],
+                             [((409, 320, 0, 32), "ratio_0", "one source")]),
+    "group_by_chunk": ([((17, 8, 16, 8), "ratio_30"), ((50, 120, 0, 40), "ratio_30"), ((1, 320, 0, 32), "ratio_30"), ((300, 1040, 0, 8), "ratio_30")],
+                       [((9, 1280, 0, 32), "ratio_30", "40 channels per group: a 16-byte chunk never straddles two groups")]),
+    "neighbour_sample": ([((1225, 320, 0, 32), "ratio_30"), ((409, 320, 0, 32), "ratio_30")],
+                         [((408, 320, 0, 32), "ratio_30", "no pad pixels")]),
+}
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("defect", sorted(GN_DEFECT_ROWS))
+def test_norm_planted_group_norm_defects(defect, dtype):
+    """every planted defect of gn_base_alg (geometry form) misses the bars at the rows of the GPU table built for it - by a factor of 8 and
+    more past MARGIN x the worse baseline, in both dtypes - and leaves base_alg's output untouched, bit for bit, where the geometry gives it
+    nothing to act on (the reason is in GN_DEFECT_ROWS)"""
+    from tests import test_norm_gpu as NG
+    table = {(r["HW"], r["C1"], r["C2"], r["groups"]) for r in NG.GN_TABLE}
+    outside, unseen = GN_DEFECT_ROWS[defect]
+    for geo, kind in outside:
+        assert geo in table
+        c, route = _norm_case(geo, kind, dtype)
+        ref, clean, bar = _norm_bars(c, route)
+        e = nm.row_err(nm.gn_base_alg(c, geom=route, defect=defect), ref)
+        assert e > 8 * nm.MARGIN * bar, (defect, geo, kind, e, bar)
+    for geo, kind, why in unseen:
+        assert geo in table
+        c, route = _norm_case(geo, kind, dtype)
+        assert torch.equal(nm.gn_base_alg(c, geom=route, defect=defect), nm.gn_base_alg(c, geom=route)), (defect, geo, why)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_norm_wrong_group_is_invisible_at_ratio_0(dtype):
+    """group_by_chunk hands a channel the statistics of the NEIGHBOURING group.  At |mean| / std = 0 group_maps gives every group a mean
+    near 0 and the same spread, so the neighbour's statistics are as good as the channel's own: inside the bars - which is why every
+    geometry with cpg % 8 != 0 meets ratio_30 or dominant in the GPU table as well"""
+    for geo in [(17, 8, 16, 8), (50, 120, 0, 40), (300, 1040, 0, 8)]:
+        c, route = _norm_case(geo, "ratio_0", dtype)
+        ref, clean, bar = _norm_bars(c, route)
+        assert nm.row_err(nm.gn_base_alg(c, geom=route, defect="group_by_chunk"), ref) <= nm.MARGIN * bar
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_norm_unclamped_variance(dtype):
+    """variance_unclamped on the table's constant samples cannot be seen: the sample holds 87 / 32, k * 87 / 32 is exact in fp32 for every k that
+    occurs, so the mean is exact and E[x^2] - mean^2 is the rounding of ONE fp32 quotient, |var| <= 2^-23 * 7.4 < 1e-6 < eps - var + eps > 0
+    with or without the clamp, and x - mean = 0 wipes out what is left of the difference: inside the bars.  It is seen where the values are
+    large: per (sample, group) one value in 1000 .. 2000 - the rounding of 10^6 * 2^-24 dwarfs eps, some groups come out negative and the
+    unclamped form returns NaN where the clamped one stays finite."""
+    for geo in [(1296, 320, 0, 32), (9, 1280, 0, 32), (49, 8000, 0, 32)]:
+        c, route = _norm_case(geo, "constant", dtype)
+        ref, clean, bar = _norm_bars(c, route)
+        y = nm.gn_base_alg(c, geom=route, defect="variance_unclamped")
+        assert bool(torch.isfinite(y).all()) and nm.row_err(y, ref) <= nm.MARGIN * bar
+    HW, C, G, N = 1296, 320, 32, 3
+    vals = nm.rnd(1000 + 1000 * torch.rand(N, 1, G, 1, generator=torch.Generator().manual_seed(5)), dtype)
+    x = vals.expand(N, HW, G, C // G).reshape(N, HW, 1, C).clone()
+    c = nm.gn_case(x, G, dtype, seed=1)
+    c.update(C1=C, C2=0)
+    route = nm.gn_route(N, HW, C, G)
+    clean, bad = nm.gn_base_alg(c, geom=route), nm.gn_base_alg(c, geom=route, defect="variance_unclamped")
+    assert bool(torch.isfinite(clean).all()) and not bool(torch.isfinite(bad).all())
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_norm_planted_layer_norm_defects(dtype):
+    """group_boundary_by_block: outside the bars on the grouped launch [3, 6, 1, 3] (rows 3, 9 and 10 take another set), nothing to act on with
+    one set.  one_pass_variance: its relative error in the variance is about ratio^2 x 2^-24 x the chain length - at |mean| / std <= 30 under the
+    rounding of the output in either dtype and at 300 still under bf16's (inside the bars, which is why GroupNorm may be built that way);
+    in fp16 at 300 it is outside, and the GPU table carries two such rows.  On a row of ONE value both forms return the rounded beta."""
+    rows = [3, 6, 1, 3]
+    for C in (8, 520, 4096):
+        c = nm.ln_plain_case(nm.token_rows(13, C, 30, dtype=dtype, seed=C), dtype, ngroups=4, seed=C)
+        ref = nm.ln_plain_ref64(c, rows)
+        bar = max(nm.row_err(nm.ln_plain_base_alg(c, rows), ref), nm.row_err(nm.ln_plain_base_ref(c, rows), ref))
+        assert nm.row_err(nm.ln_plain_base_alg(c, rows, defect="group_boundary_by_block"), ref) > 8 * nm.MARGIN * bar
+        one = nm.ln_plain_case(c["x"], dtype, seed=C)
+        assert torch.equal(nm.ln_plain_base_alg(one, defect="group_boundary_by_block"), nm.ln_plain_base_alg(one))
+    for C, M in [(1024, 5), (2056, 4)]:
+        for ratio in (0, 30, 300):
+            c = nm.ln_plain_case(nm.token_rows(M, C, ratio, dtype=dtype, seed=M + C), dtype, seed=C)
+            ref = nm.ln_plain_ref64(c)
+            bar = max(nm.row_err(nm.ln_plain_base_alg(c), ref), nm.row_err(nm.ln_plain_base_ref(c), ref))
+            e = nm.row_err(nm.ln_plain_base_alg(c, defect="one_pass_variance"), ref)
+            if ratio == 300 and dtype == torch.float16:
+                assert e > nm.MARGIN * bar, (C, ratio, e, bar)
+            else:
+                assert e <= nm.MARGIN * bar, (C, ratio, e, bar)
+    x = nm.token_rows(5, 520, 0, dtype=dtype, seed=2)
+    x[1] = nm.NORM_CONSTANT
+    x[3] = 0.0
+    c = nm.ln_plain_case(x, dtype, seed=2)
+    for defect in (None, "one_pass_variance"):
+        y = nm.ln_plain_base_alg(c, defect=defect)
+        assert torch.equal(y[1], nm.rnd(c["beta"][0], dtype)) and torch.equal(y[3], nm.rnd(c["beta"][0], dtype))

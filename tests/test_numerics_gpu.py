@@ -653,7 +653,23 @@ def _attention_section():
     return "\n".join(out), len(rows)
 
 
-_SECTIONS = {"fusion": (_fusion_section, FUSION_MARKERS), "sampler": (_sampler_section, SAMPLER_MARKERS), "attention": (_attention_section, ATTENTION_MARKERS)}
+NORM_MARKERS = ("<!-- norm table begin: written by `python -m tests.numerics --report --only norm` -->", "<!-- norm table end -->")
+
+
+def _norm_section():
+    from tests import test_norm_gpu as NG
+    rows, secs = NG.report_rows()
+    out = [f"GroupNorm and LayerNorm on every route, measured on {torch.cuda.get_device_name(0)}, torch {torch.__version__}; {len(rows)} rows (five launches and "
+           f"more each, guarded operands) in {secs:.1f} s, CPU baselines included.  Error per row (pixel or token): max|y - ref64| / rms(ref64).", "",
+           "| case | route | kernel | base_alg | base_ref | kernel / base_alg | kernel / base_ref | old metric |", "|---|---|---|---|---|---|---|---|"]
+    for r in rows:
+        out.append(f"| {r['case']} | {r['route']} | {r['kernel']:.2e} | {r['base_alg']:.2e} | {r['base_ref']:.2e} | {_div(r['kernel'], r['base_alg']):.2f} | "
+                   f"{_div(r['kernel'], r['base_ref']):.2f} | {r['old_metric']:.1e} |")
+    return "\n".join(out), len(rows)
+
+
+_SECTIONS = {"fusion": (_fusion_section, FUSION_MARKERS), "sampler": (_sampler_section, SAMPLER_MARKERS), "attention": (_attention_section, ATTENTION_MARKERS),
+             "norm": (_norm_section, NORM_MARKERS)}
 
 
 def _write_sections(doc, path, which):
@@ -668,17 +684,17 @@ def _write_sections(doc, path, which):
 
 
 def write_report(path=None, only=None):
-    """python -m tests.numerics --report [--only conv | fusion | sampler | attention]: run every case above and the convolution sweep of
+    """python -m tests.numerics --report [--only conv | fusion | sampler | attention | norm]: run every case above and the convolution sweep of
     tests/test_conv_gpu.py without asserting and write the measured tables (--only conv: the convolution table alone, the other is kept
-    as it is; --only fusion, --only sampler, --only attention: the table of tests/test_fusion_gpu.py, tests/test_sampler_gpu.py or
-    tests/test_attention_gpu.py alone, between its marker lines)"""
+    as it is; --only fusion, --only sampler, --only attention, --only norm: the table of tests/test_fusion_gpu.py, tests/test_sampler_gpu.py,
+    tests/test_attention_gpu.py or tests/test_norm_gpu.py alone, between its marker lines)"""
     global RECORD
     import tempfile
     import pathlib
     assert torch.cuda.is_available(), "the report is measured on the GPU"
     doc = os.path.join(ROOT, "tests", "NUMERICS.md")
     RECORD = []
-    if only in ("fusion", "sampler", "attention"):           # their tables sit between marker lines of their own, above the first measured table
+    if only in _SECTIONS:                                    # their tables sit between marker lines of their own, above the first measured table
         try:
             _write_sections(doc, path or doc, [only])
         finally:
