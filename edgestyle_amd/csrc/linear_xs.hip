@@ -515,8 +515,14 @@ __global__ __launch_bounds__(512, 2) void linear_xs_kernel(const es_xs_desc p) {
 #endif
 }
 
+// which instantiation the last launch of this process went to (es_linear_xs_last_form: tests assert the form they mean to run); written by
+// launch_one from its OWN template arguments, never recomputed from the descriptor
+int xs_last_form = 0;
+
 template <typename T, int KC, bool GEGLU, bool LN, bool RES = false, bool PP = false, bool GN = false>
 int launch_one(const es_xs_desc& d, hipStream_t st) {
+  xs_last_form = KC | (GEGLU ? ES_XS_FORM_GEGLU : 0) | (LN ? ES_XS_FORM_LN : 0) | (RES ? ES_XS_FORM_RES : 0) | (PP ? ES_XS_FORM_PP : 0) |
+                 (GN ? ES_XS_FORM_GN : 0);
   const int rbs = (d.M + XS_ROWS - 1) / XS_ROWS;
   auto kfn = linear_xs_kernel<T, KC, GEGLU, LN, RES, PP, GN>;
   static bool attr_set = false;
@@ -559,6 +565,8 @@ extern unsigned long long es_operand_limit_v;          // gemm_conv.hip: 0x7FFFF
 
 extern "C" int es_linear_xs_set_pp(int on) { const int prev = xs_pp; xs_pp = on; return prev; }
 
+extern "C" int es_linear_xs_last_form(void) { return xs_last_form; }
+
 extern "C" int es_linear_xs(const es_xs_desc* d, void* stream) {
   if (!d->x || !d->out || (d->ngroups <= 1 && (!d->w || !d->bias))) { es_set_error("es_linear_xs: null pointer (bias is required: pass zeros)"); return -1; }
   if (d->K != 320 && d->K != 640) { es_set_error("es_linear_xs: K must be 320 or 640"); return -1; }
@@ -593,8 +601,9 @@ extern "C" int es_linear_xs(const es_xs_desc* d, void* stream) {
   if (d->ngroups > 1) {
     const int tm = (d->M + 127) / 128;
     for (int g = 0; g < d->ngroups; ++g)
-      if (!d->w_g[g] || !d->bias_g[g] || d->mt_end[g] <= (g ? d->mt_end[g - 1] : 0) || (d->mt_end[g] & 1)) {
-        es_set_error("es_linear_xs: groups must be non-empty runs of whole 256-row blocks"); return -1; }
+      // (the LAST run may end anywhere: it ends the launch, and a row block's group is found from its first 128-row tile alone)
+      if (!d->w_g[g] || !d->bias_g[g] || d->mt_end[g] <= (g ? d->mt_end[g - 1] : 0) || (g + 1 < d->ngroups && (d->mt_end[g] & 1))) {
+        es_set_error("es_linear_xs: groups must be non-empty runs of whole 256-row blocks (the last may be ragged)"); return -1; }
     if (d->mt_end[d->ngroups - 1] != tm) { es_set_error("es_linear_xs: groups must cover M"); return -1; }
   }
   for (int g = dd.ngroups > 1 ? dd.ngroups : 0; g < 4; ++g) dd.mt_end[g] = 0x7FFFFFFF;

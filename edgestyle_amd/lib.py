@@ -157,6 +157,8 @@ class LaunchChoice(C.Structure):    # es_launch_choice
 
 
 ROUTE_CONV_GEMM, ROUTE_LINEAR_XS = 0, 1
+# es_linear_xs_last_form: K / 32 in the low byte, then the template flags of the instantiation that ran
+XS_FORM_KC_MASK, XS_FORM_GEGLU, XS_FORM_LN, XS_FORM_RES, XS_FORM_PP, XS_FORM_GN = 0xFF, 0x100, 0x200, 0x400, 0x800, 0x1000
 GN_FORM_SLAB, GN_FORM_TWO_LAUNCHES = 1, 2        # ES_GN_FORM_*
 GN_ROUTE_FIELDS = ("form", "gpb", "slots", "cpt", "ppb", "nchunk", "ps", "lanes", "blocks", "ipt", "general", "lds")     # ES_GN_ROUTE_*
 
@@ -171,6 +173,7 @@ SYMBOLS = {
     "es_conv_gemm_workspace_bytes": (C.c_size_t, [C.POINTER(GemmDesc)]),
     "es_linear_xs": (C.c_int, [C.POINTER(XsDesc), _P]),
     "es_linear_xs_set_pp": (C.c_int, [_I]),
+    "es_linear_xs_last_form": (C.c_int, []),
     "es_attention": (C.c_int, [C.POINTER(AttnDesc), _P]),
     "es_attention_set_kvres": (C.c_int, [_I]),
     "es_attention_last_kernel": (C.c_int, []),

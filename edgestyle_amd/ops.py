@@ -445,12 +445,47 @@ def xs_eligible(M: int, pw: "PackedWeight", pws, group_n, hw: int) -> bool:
 def linear_xs(x: torch.Tensor, pw, M: int, out: torch.Tensor, group_rows=None, residual: Optional[torch.Tensor] = None,
               gn: Optional[dict] = None) -> torch.Tensor:
     """x: [M, K] contiguous; pw (or list of pw for a grouped launch with `group_rows` rows each) -> out [M, cstore]
-    (+ residual [M, cstore] contiguous: K = 320 only).  gn = dict(part, gamma, beta, groups, nchunk, hw, eps): GroupNorm in front
-    (es_xs_desc.gn_part; gamma / beta lists for a grouped launch)."""
+    (+ residual [M, cstore]: K = 320 only).  out (and residual, with the SAME pitch: the kernel reads it with out's) may be row-pitched
+    views: inner stride 1, a row pitch of whole 16-byte vectors >= cstore.  group_rows: runs of whole 256-row blocks, the last may be
+    ragged.  gn = dict(part, gamma, beta, groups, nchunk, hw, eps): GroupNorm in front (es_xs_desc.gn_part; gamma / beta lists for a
+    grouped launch).  The launch takes data_ptr()s, M and one pitch: whatever it would read or write differently from what the tensors
+    hold is refused here, before anything is recorded or launched."""
+    def bad(msg):
+        return L.EdgeStyleHipError("linear_xs: " + msg)
     pws = None
     if isinstance(pw, (list, tuple)):
         pws = list(pw) if len(pw) > 1 else None
         pw = pw[0]
+    cstore = pw.cout // 2 if pw.geglu else pw.cout
+    if x.dtype not in (torch.float16, torch.bfloat16):
+        raise bad(f"x must be fp16 or bf16, not {x.dtype}")
+    for name, t in (("out", out), ("residual", residual)):
+        if t is not None and (t.dtype != x.dtype or t.device != x.device):
+            raise bad(f"{name} is {t.dtype} on {t.device}, x is {x.dtype} on {x.device}")
+    if M < 1 or x.dim() != 2 or tuple(x.shape) != (M, pw.kpad) or not x.is_contiguous():
+        raise bad(f"x must be a contiguous [M, K] = [{M}, {pw.kpad}] (got shape {tuple(x.shape)}, strides {x.stride()})")
+    if x.device.type != "meta" and x.data_ptr() % 16:
+        raise bad("x must start at a multiple of 16 bytes (16-byte vector loads)")
+    for name, t in (("out", out), ("residual", residual)):
+        if t is None:
+            continue
+        if t.dim() != 2 or tuple(t.shape) != (M, cstore):
+            raise bad(f"{name} must be [M, cstore] = [{M}, {cstore}], not {tuple(t.shape)}")
+        if t.stride(1) != 1:
+            raise bad(f"{name}: innermost stride must be 1")
+    ldo = out.stride(0) if M > 1 else cstore                # (one row: its pitch is never used)
+    if ldo < cstore or ldo % 8:
+        raise bad(f"out: row pitch {ldo} must be a multiple of 8 elements and at least the width {cstore}")
+    if residual is not None and M > 1 and residual.stride(0) != ldo:
+        raise bad(f"residual: row pitch {residual.stride(0)} differs from out's {ldo} (the kernel reads it with out's)")
+    for name, t in (("out", out), ("residual", residual)):
+        if t is not None and t.device.type != "meta" and t.data_ptr() % 16:
+            raise bad(f"{name} must start at a multiple of 16 bytes (16-byte vector accesses)")
+    if pws is not None:
+        if group_rows is None or len(group_rows) != len(pws) or sum(group_rows) != M or any(n < 1 for n in group_rows):
+            raise bad(f"group_rows {None if group_rows is None else list(group_rows)} must hold one run of rows per weight set and sum to M = {M}")
+        if any(n % 256 for n in list(group_rows)[:-1]):
+            raise bad(f"group_rows {list(group_rows)}: every run but the last must be whole 256-row blocks")
     K = pw.kpad
     ch = 64 if K == 320 else 32
     pline = 128 // (ch if pw.geglu else 2 * ch)             # chunks per 128-byte output line
@@ -475,7 +510,7 @@ def linear_xs(x: torch.Tensor, pw, M: int, out: torch.Tensor, group_rows=None, r
         return z.data_ptr()
     d.w, d.bias = pw.w.data_ptr(), bias_of(pw)
     d.M, d.K, d.Cout, d.rows_padded = M, K, pw.cout, pw.rows_padded
-    d.ldo = out.shape[-1]
+    d.ldo = ldo
     d.geglu, d.ln, d.ln_eps = int(pw.geglu), int(pw.ln_colsum is not None), pw.ln_eps
     d.nslices, d.chunks_per_slice, d.dtype = nslices, lps * pline, _dt(x)
     d.residual = residual.data_ptr() if residual is not None else None
@@ -497,8 +532,8 @@ def linear_xs(x: torch.Tensor, pw, M: int, out: torch.Tensor, group_rows=None, r
         for g, (q, n) in enumerate(zip(pws, group_rows)):
             if (q.rows_padded, q.kpad, q.cout, q.geglu) != (pw.rows_padded, pw.kpad, pw.cout, pw.geglu):
                 raise L.EdgeStyleHipError("grouped linear_xs: weight geometry differs between groups")
-            acc += n // 128
-            d.mt_end[g] = acc
+            acc += n
+            d.mt_end[g] = (acc + 127) // 128                 # (whole 256-row blocks, checked above; the last run: ceil(M / 128))
             d.w_g[g] = q.w.data_ptr()
             d.bias_g[g] = bias_of(q)
     if PROFILE is not None:
@@ -621,7 +656,8 @@ def conv_gemm(x: torch.Tensor, pw: PackedWeight, *, stride: int = 1, pad: Option
         raise L.EdgeStyleHipError(f"plan_gemm: rows_padded {pw.rows_padded} fits no N tile")
     if ch.route == L.ROUTE_LINEAR_XS:
         linear_xs(x.reshape(M, C1), pws if pws is not None else pw, M, out.reshape(M, cstore),
-                  None if pws is None else [n * Hout * Wout for n in group_n], residual=residual)
+                  None if pws is None else [n * Hout * Wout for n in group_n],
+                  residual=None if residual is None else residual.reshape(M, cstore))
         return out
     bn, splitk = ch.bn, ch.splitk
     d = L.GemmDesc()

@@ -26,7 +26,7 @@ enum { ES_ACT_NONE = 0, ES_ACT_SILU = 1, ES_ACT_GEGLU = 2 };
 /* 7 (round 5): es_gemm_desc.bn = 256; es_xs_desc.gn_* and es_gn_desc.stats_only (both structs grew: GroupNorm in front of a row-stationary
  * projection); es_conv_gemm8p_form_ok, es_ctx_graph_hazard, es_linear_xs_set_pp, es_attention_set_kvres, es_set_operand_limit,
  * es_group_norm_chunks, es_clock_probe.  Context images carry the version and are rebuilt across it.
- * (Host-only helpers that no plan or image records - es_plan_gemm_choice, es_linear_xs_eligible, es_launch_choose and its siblings
+ * (Host-only helpers that no plan or image records - es_plan_gemm_choice, es_linear_xs_eligible, es_linear_xs_last_form, es_launch_choose and its siblings
  * es_launch_route / es_launch_gn_fold / es_launch_gn_handover / es_launch_wide_stream - come and go without a new version.) */
 #define ES_ABI_VERSION 7
 int es_abi_version(void);
@@ -146,7 +146,8 @@ size_t es_conv_gemm_workspace_bytes(const es_gemm_desc* d);
  * [rows_padded] (required); out [M, ldo] dtype, Cout (or Cout / 2 for GEGLU) columns written.
  * Workgroup = 256 rows x one slice of the output columns: grid = ceil(M / 256) * nslices, slice s covers the
  * `chunks_per_slice` column chunks (64 columns at K = 320, 32 at K = 640) starting at s * chunks_per_slice.
- * Grouped launch like es_conv_gemm: rows [mt_end[g-1], mt_end[g]) * 128 use w_g[g] / bias_g[g] (even mt_end only).
+ * Grouped launch like es_conv_gemm: rows [mt_end[g-1], mt_end[g]) * 128 use w_g[g] / bias_g[g] (even mt_end only; the last,
+ * ceil(M / 128), may be odd: a ragged last run).
  * --------------------------------------------------------------------------------------------------------- */
 typedef struct {
   const void* x; void* out;
@@ -180,6 +181,12 @@ int es_linear_xs(const es_xs_desc* d, void* stream);
 /* tool / test knob: the form of the plain (no GEGLU) launches - 1 = two-barrier ping-pong between the wave groups (default; ES_XS_PP=0
  * in the environment turns it off), 0 = the one-barrier form.  Bit-identical outputs.  Returns the previous setting. */
 int es_linear_xs_set_pp(int on);
+/* test query: the kernel instantiation the last es_linear_xs launch of this process went to (of a launch cut into runs: the last run's) -
+ * K / 32 (10 | 20) in the low byte, or'ed with the flags below; 0 before the first launch.  Set by the launcher from the template arguments
+ * it instantiates, not recomputed from the descriptor.  (Host-only, recorded by no plan or image: no new ES_ABI_VERSION.) */
+enum { ES_XS_FORM_KC_MASK = 0xFF, ES_XS_FORM_GEGLU = 0x100, ES_XS_FORM_LN = 0x200, ES_XS_FORM_RES = 0x400, ES_XS_FORM_PP = 0x800,
+       ES_XS_FORM_GN = 0x1000 };
+int es_linear_xs_last_form(void);
 
 /* Fused attention softmax(Q K^T * scale) V (flash-style, online softmax, MFMA).
  * Replaces torch.nn.functional.scaled_dot_product_attention under diffusers Attention (attn1/attn2/VAE attn).

@@ -28,8 +28,8 @@ The implicit-GEMM convolution has a metric of its own, the misrounded share (`mi
 
 `python -m tests.numerics --report` (GPU) runs the cases of test_numerics_gpu.py and the convolution sweep of test_conv_gpu.py and writes
 the measured tables to tests/NUMERICS.md (`--only conv`: the convolution table alone; `--only fusion`, `--only sampler`, `--only attention`,
-`--only norm`: the sweep of test_fusion_gpu.py, the trajectories of test_sampler_gpu.py, the rows of test_attention_gpu.py or the rows of
-test_norm_gpu.py alone).
+`--only norm`, `--only xs`: the sweep of test_fusion_gpu.py, the trajectories of test_sampler_gpu.py, the rows of test_attention_gpu.py, of
+test_norm_gpu.py or of test_linear_xs_gpu.py alone).
 
 The fusion block (`fusion_case`, `fusion_ref64`, `fusion_base_ref`, `fusion_base_alg`, `fusion_grids`; judged per SAMPLE, `sample_err`) and the
 sampler step (`unipc_apply`, `ddim_apply`, `run_trajectory`, `traj_err`) have sections of their own at the end.
@@ -339,12 +339,15 @@ def ln_case(x, Cout, dtype, geglu=False, bias=True, seed=0, eps=1e-5):
 
 
 def ln_ref64(c):
+    """c["ln"] False (the plain forms of es_linear_xs; absent: True): no LayerNorm in front.  c["res"]: a residual added to the result."""
     x = c["x"].double()
-    y = F.layer_norm(x, (x.shape[1],), c["gamma"].double(), c["beta"].double(), c["eps"])
+    y = F.layer_norm(x, (x.shape[1],), c["gamma"].double(), c["beta"].double(), c["eps"]) if c.get("ln", True) else x
     y = F.linear(y, c["W"].double(), None if c["b"] is None else c["b"].double())
     if c["geglu"]:
         h, gate = y.chunk(2, dim=-1)
         y = h * F.gelu(gate)
+    if c.get("res") is not None:
+        y = y + c["res"].double()
     return y
 
 
@@ -365,11 +368,13 @@ def ln_base_ref(c):
     """two-pass LayerNorm -> round -> Linear with fp32 accumulation -> round (-> GELU -> round -> product -> round)"""
     dt = c["dtype"]
     x = c["x"].float()
-    n = rnd(F.layer_norm(x, (x.shape[1],), c["gamma"], c["beta"], c["eps"]), dt)
+    n = rnd(F.layer_norm(x, (x.shape[1],), c["gamma"], c["beta"], c["eps"]), dt) if c.get("ln", True) else x
     y = rnd(F.linear(n, c["W"], c["b"]), dt)
     if c["geglu"]:
         h, gate = y.chunk(2, dim=-1)
         y = rnd(h * rnd(F.gelu(gate), dt), dt)
+    if c.get("res") is not None:
+        y = rnd(y + c["res"].float(), dt)
     return y
 
 
@@ -438,30 +443,46 @@ def fold_weights(c):
     return Wf, colsum, fb.float()
 
 
-def ln_base_alg(c, form="fold", defect=None):
+def ln_base_alg(c, form="fold", defect=None, chain=None):
     """form "fold" (es_conv_gemm, ln_colsum): rstd * (x W'^T - mean * colsum(W')) + (W beta + b), one-pass statistics, rounded once.
     form "xs" (es_linear_xs): the row is normalised in registers, x * rstd + (-mean * rstd) rounded to the storage dtype, then
-    multiplied with W'.
+    multiplied with W'.  With chain = 8 | 32 (form "xs" only) every output is ONE fp32 chain over K that STARTS from the bias (the
+    bias is the C operand of the first MFMA: no separate add), `chain`-wide partial dot products as _chain_dot takes them; c["ln"]
+    False: no LayerNorm (the plain forms: x, W and b as they are); c["res"]: round, + residual in fp32, round again.
     defect: "colsum_unrounded" (colsum taken from W * gamma before rounding), "partial_sums_fp16" (the statistics' partial sums of 64
-    channels rounded to fp16)."""
+    channels rounded to fp16); form "xs" with a chain: "geglu_halves_swapped" (gate * gelu(hidden)), "residual_row_shift" (the residual
+    read one 16-row fragment further down; rows past M read as zeros, as a range-checked buffer load returns them)."""
     dt = c["dtype"]
     x = c["x"].float()
-    Wf, colsum, fb = fold_weights(c)
+    ln = c.get("ln", True)
+    assert form == "xs" or (ln and chain is None and c.get("res") is None)
+    if ln:
+        Wf, colsum, fb = fold_weights(c)
+    else:
+        Wf, fb = c["W"], (c["b"] if c["b"] is not None else torch.zeros(c["W"].shape[0]))
     if defect == "colsum_unrounded":
         colsum = (c["W"].double() * c["gamma"].double()[None, :]).sum(dim=1).float()
-    if defect == "partial_sums_fp16":
+    if not ln:
+        mean = rstd = None
+    elif defect == "partial_sums_fp16":
         mean, rstd = one_pass_stats(x, 1, c["eps"], partial_dtype=torch.float16, chunks=x.shape[1] // 64)
     else:
         mean, rstd = one_pass_stats(x, 1, c["eps"], order="mfma8" if form == "fold" else "xs")
     if form == "fold":
         y = rstd * (x @ Wf.t() - mean * colsum[None, :]) + fb[None, :]
     else:
-        xn = rnd(torch.addcmul(-mean * rstd, x, rstd), dt)
-        y = xn @ Wf.t() + fb[None, :]
+        xn = rnd(torch.addcmul(-mean * rstd, x, rstd), dt) if ln else x
+        y = xn @ Wf.t() + fb[None, :] if chain is None else _chain_dot(xn, Wf, chain, init=fb)
     if c["geglu"]:
         h, gate = y.chunk(2, dim=-1)
-        y = h * F.gelu(gate)
-    return rnd(y, dt)
+        y = gate * F.gelu(h) if defect == "geglu_halves_swapped" else h * F.gelu(gate)
+    y = rnd(y, dt)
+    if c.get("res") is not None:
+        res = c["res"].float()
+        if defect == "residual_row_shift":
+            res = torch.cat([res[16:], torch.zeros(min(16, res.shape[0]), res.shape[1])], 0)
+        y = rnd(y + res, dt)
+    return y
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -580,8 +601,9 @@ def gn_chunked_stats(xg, eps):
     return mean.reshape(N, 1, G, 1), torch.rsqrt(var + eps).reshape(N, 1, G, 1)
 
 
-def gn_base_alg(c, counts=None, defect=None, stats_from=None, geom=None):
-    """geom (a route of gn_route / lib.group_norm_route): the norm sweep's form of this function, gn_base_alg_geom - the statistics in the
+def gn_base_alg(c, counts=None, defect=None, stats_from=None, geom=None, chain=None):
+    """chain = 8 | 32: the projection as es_linear_xs forms it - one fp32 chain per output that starts from the bias (_chain_dot).
+    geom (a route of gn_route / lib.group_norm_route): the norm sweep's form of this function, gn_base_alg_geom - the statistics in the
     chunk geometry of the form that RUNS (the slab's pixel slots too), two sources, and the planted defects GN_DEFECTS.  Without geom:
     one-pass statistics (fp32 sums in the kernels' chunking: gn_chunked_stats; E[x^2] - mean^2 clamped at 0); x * (rstd gamma) + (beta - mean rstd gamma) (-> SiLU) rounded
     once; then the projection.  stats_from: another tensor of x's shape from which the STATISTICS are taken (the producer hand-over:
@@ -615,7 +637,9 @@ def gn_base_alg(c, counts=None, defect=None, stats_from=None, geom=None):
         if c["silu"]:
             y = F.silu(y)
         y = rnd(y, dt).reshape(x.shape)
-        if "W" in c:
+        if "W" in c and chain is not None:
+            y = rnd(_chain_dot(y.reshape(N * HW, -1), c["W"][i], chain, init=c["b"][i]), dt).reshape(*x.shape[:-1], -1)
+        elif "W" in c:
             y = rnd(y @ c["W"][i].t() + c["b"][i], dt)
         return y
     if stats_from is None:
@@ -1174,8 +1198,9 @@ def conv_im2col(c, korder=0, defect=None):
     return A.contiguous(), Wm.contiguous()
 
 
-def _chain_dot(A, Wm, width):
-    """fp32 accumulators of A Wm^T formed as es_conv_gemm's matrix-core chain forms them (see _chain_sums, "mfma8"): one `width`-wide
+def _chain_dot(A, Wm, width, init=None):
+    """init (fp32 [rows of Wm]): the value every chain STARTS from (es_linear_xs: the bias is the C operand of the first MFMA).
+    fp32 accumulators of A Wm^T formed as es_conv_gemm's matrix-core chain forms them (see _chain_sums, "mfma8"): one `width`-wide
     partial dot product after the other, each taken exactly (fp64) and added with one rounding to fp32.  width 8: what a lane
     supplies to a 16x16x32 MFMA; width 32: one rounding per instruction - the other reading of the same hardware."""
     M, K = A.shape
@@ -1185,7 +1210,7 @@ def _chain_dot(A, Wm, width):
     G = (K + pad) // width
     Ad = A.double().reshape(M, G, width).permute(1, 0, 2)
     Wd = Wm.double().reshape(-1, G, width).permute(1, 2, 0)
-    acc = torch.zeros(M, Wm.shape[0], dtype=torch.float32)
+    acc = torch.zeros(M, Wm.shape[0], dtype=torch.float32) if init is None else init.float()[None, :].expand(M, -1).clone()
     for g0 in range(0, G, 64):
         part = torch.bmm(Ad[g0:g0 + 64], Wd[g0:g0 + 64])
         for j in range(part.shape[0]):
@@ -1869,6 +1894,346 @@ def vae_sample_ref(mom, noise, L, scaling, prec, dtype=None):
     mean, logvar = m[..., :L], m[..., L:2 * L].clamp(-30.0, 20.0)
     std = r(torch.exp(r(0.5 * logvar)))
     return r(r(mean + r(std * noise.to(prec).permute(0, 2, 3, 1))) * scaling)
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# es_linear_xs (csrc/linear_xs.hip): every form, stage count and ragged edge (tests/test_linear_xs_gpu.py)
+# ----------------------------------------------------------------------------------------------------------------
+XS_KINDS = ("plain", "ln", "geglu", "geglu_ln", "res", "gn")
+# (K, kind, ping-pong): the 16 instantiations per dtype that launch() of csrc/linear_xs.hip can pick
+XS_FORMS = tuple([(320, k, 0) for k in ("plain", "ln", "geglu", "geglu_ln", "res")] + [(640, k, 0) for k in ("plain", "ln", "geglu", "geglu_ln")] +
+                 [(320, k, 1) for k in ("plain", "ln", "res", "gn")] + [(640, k, 1) for k in ("plain", "ln", "gn")])
+XS_FORM_GEGLU, XS_FORM_LN, XS_FORM_RES, XS_FORM_PP, XS_FORM_GN = 0x100, 0x200, 0x400, 0x800, 0x1000      # include/edgestyle_hip.h
+XS_ROWS = 256                   # rows per workgroup
+XS_GUARD_ROWS = 256             # NaN rows in front of and behind a guarded output
+XS_PAD_COLS = 64                # NaN columns behind every row of one
+XS_DEFECTS = ("stale_stage", "row_dropped", "short_slice_line_dropped", "residual_row_shift", "geglu_halves_swapped", "ln_zero_row_nan")
+
+
+def xs_form_id(K, kind, pp) -> int:
+    """es_linear_xs_last_form of the instantiation (K, kind, pp)"""
+    return K // 32 | (XS_FORM_GEGLU if kind.startswith("geglu") else 0) | (XS_FORM_LN if kind in ("ln", "geglu_ln") else 0) | \
+        (XS_FORM_RES if kind == "res" else 0) | (XS_FORM_PP if pp else 0) | (XS_FORM_GN if kind == "gn" else 0)
+
+
+def xs_geometry(K, kind):
+    """(GEMM columns per stage, stored columns per stage, stages per 128-byte output line) of csrc/linear_xs.hip"""
+    ch = 64 if K == 320 else 32
+    outw = ch // 2 if kind.startswith("geglu") else ch
+    return ch, outw, 64 // outw
+
+
+def xs_split(lines, slices, P):
+    """ops.linear_xs's cut of `lines` output lines into at most `slices` slices: (nslices, chunks_per_slice, stages of the last slice)"""
+    want = max(1, min(lines, slices))
+    lps = -(-lines // want)
+    nslices = -(-lines // lps)
+    return nslices, lps * P, (lines - (nslices - 1) * lps) * P
+
+
+def _xs_clear_ties(final_bias, b, dtype):
+    """moves entries of b (by 2^-13 of the value: a quarter of an fp16 step or less) until no entry of final_bias() - the value a zero row stores - lies within NORM_TIE_CLEARANCE
+    of a rounding boundary of the storage dtype (or below its normal range), as norm_case does for SiLU(beta)"""
+    for _ in range(16):
+        fb = final_bias().double()
+        small = fb.abs() < 2.0 ** -14
+        close = small.clone()
+        close[~small] = tie_distance(fb[~small], dtype) < NORM_TIE_CLEARANCE
+        if not bool(close.any()):
+            return
+        b[close] += torch.where(small, torch.full_like(fb, 2.0 ** -12), fb.abs() * 2.0 ** -13)[close].float()
+    raise AssertionError("a bias stayed on a rounding boundary")
+
+
+def xs_case(M, K, lines, kind, dtype, seed=0, counts=None, ratio=0, hw=None, G=None, N=None, loud=16.0):
+    """One es_linear_xs launch: M rows of K = 320 | 640 channels -> `lines` 128-byte output lines (64 stored columns each; GEGLU kinds: twice
+    as many GEMM columns).  kind: XS_KINDS.  counts: a grouped launch - rows per weight set (kind "gn": SAMPLES per set), the second
+    set's weights and bias `loud` times the others' (a row that took its neighbour's weights is then wrong by that factor).
+    Inputs, seeded and rounded through the storage dtype: token_rows at |mean| / std = `ratio` for the LayerNorm kinds, group_maps [N, hw, 1, K]
+    with G groups at that ratio for "gn" (M == N * hw), randn for the others (the output of an attention or a feed-forward layer, the
+    residual of the same size).  Weights: ln_case's per set (gamma / beta used by the LayerNorm kinds only), gn_case's for "gn"; every bias is
+    kept clear of the storage dtype's rounding boundaries."""
+    assert kind in XS_KINDS and K in (320, 640) and (kind != "res" or K == 320)
+    geglu = kind.startswith("geglu")
+    cstore = 64 * lines
+    Cout = 2 * cstore if geglu else cstore
+    c = dict(M=M, K=K, lines=lines, kind=kind, dtype=dtype, cstore=cstore, counts=list(counts) if counts else None)
+    if kind == "gn":
+        assert M == N * hw and (counts is None or sum(counts) == N)
+        x = group_maps(N, K, hw, G, ratio, dtype=dtype, seed=seed, W=1)
+        g = gn_case(x, G, dtype, eps=1e-6, seed=seed, Cout=Cout, ngroups=len(counts) if counts else 1)
+        for i in range(len(g["W"])):
+            if i == 1:
+                g["W"][i], g["b"][i] = g["W"][i] * loud, g["b"][i] * loud
+            _xs_clear_ties(lambda: g["b"][i], g["b"][i], dtype)
+        c.update(gn=g, hw=hw, G=G, N=N, x=x.reshape(M, K))
+        return c
+    assert counts is None or sum(counts) == M
+    if kind in ("ln", "geglu_ln"):
+        x = token_rows(M, K, ratio, dtype=dtype, seed=seed)
+    else:
+        x = rnd(torch.randn(M, K, generator=_gen(seed), dtype=torch.float64), dtype)
+    res = rnd(torch.randn(M, cstore, generator=_gen(seed + 31), dtype=torch.float64), dtype) if kind == "res" else None
+    sets, a = [], 0
+    for i, n in enumerate(counts or [M]):
+        q = ln_case(x[a:a + n], Cout, dtype, geglu=geglu, bias=True, seed=seed + 13 * i)
+        q["ln"] = kind in ("ln", "geglu_ln")
+        q["res"] = None if res is None else res[a:a + n]
+        if i == 1:
+            q["W"], q["b"] = q["W"] * loud, q["b"] * loud
+        _xs_clear_ties((lambda: fold_weights(q)[2]) if q["ln"] else (lambda: q["b"]), q["b"], dtype)
+        sets.append(q)
+        a += n
+    c.update(sets=sets, x=x, res=res)
+    return c
+
+
+def xs_ref64(c):
+    """the plain operation in fp64 on the rounded inputs and the UNFOLDED rounded weights"""
+    if c["kind"] == "gn":
+        return gn_ref64(c["gn"], c["counts"]).reshape(c["M"], -1)
+    return torch.cat([ln_ref64(q) for q in c["sets"]], 0)
+
+
+def xs_base_ref(c):
+    """the per-op-rounded fp32 sequence (ln_base_ref / gn_base_ref)"""
+    if c["kind"] == "gn":
+        return gn_base_ref(c["gn"], c["counts"]).reshape(c["M"], -1)
+    return torch.cat([ln_base_ref(q) for q in c["sets"]], 0)
+
+
+def _xs_stale(W, b, c, stage):
+    """W, b with the rows of `stage` replaced by those of the stage three earlier (the LDS ring has three slots: a stage's slot last held
+    stage - 3).  Stages are runs of stored columns; a GEGLU stage holds its hidden AND its gate rows."""
+    ch, outw, _ = xs_geometry(c["K"], c["kind"])
+    assert stage >= 3 and (stage + 1) * outw <= c["cstore"]
+    W, b = W.clone(), b.clone()
+    for off in ((0, c["cstore"]) if c["kind"].startswith("geglu") else (0,)):
+        d0, s0 = off + stage * outw, off + (stage - 3) * outw
+        W[d0:d0 + outw], b[d0:d0 + outw] = W[s0:s0 + outw].clone(), b[s0:s0 + outw].clone()
+    return W, b
+
+
+def xs_base_alg(c, chain=8, defect=None, stage=3):
+    """The launch as designed (ln_base_alg form "xs" / gn_base_alg with a chain): LayerNorm or GroupNorm rounded to the storage dtype in
+    registers, every output one fp32 chain over K that starts from the bias, `chain`-wide partial dot products, GEGLU in fp32 with one
+    rounding, the residual kinds round, + residual, round.  chain None: torch's fp32 matmul and a separate bias add (a third, independent
+    reading for the misrounded bar).  Planted defects (XS_DEFECTS):
+      "stale_stage"               the output columns of `stage` computed with the weights and bias of the stage three earlier - what a counted
+                                  wait one group too loose lets the MFMAs read
+      "row_dropped"               row M - 1 never stored (NaN, as a sentinel-filled output shows it)
+      "short_slice_line_dropped"  the last 128-byte line - the last line of the last, short slice - never stored
+      "residual_row_shift"        the residual read one 16-row fragment off
+      "geglu_halves_swapped"      gate * gelu(hidden)
+      "ln_zero_row_nan"           an arithmetic NaN stored into row M (returned as an extra row): an out-of-range row's statistics leaking out"""
+    assert defect is None or defect in XS_DEFECTS
+    inner = defect if defect in ("residual_row_shift", "geglu_halves_swapped") else None
+    if c["kind"] == "gn":
+        g = c["gn"]
+        if defect == "stale_stage":
+            Wb = [_xs_stale(W, b, c, stage) for W, b in zip(g["W"], g["b"])]
+            g = dict(g, W=[w for w, _ in Wb], b=[b for _, b in Wb])
+        y = gn_base_alg(g, c["counts"], chain=chain).reshape(c["M"], -1)
+    else:
+        outs = []
+        for q in c["sets"]:
+            if defect == "stale_stage":
+                W, b = _xs_stale(q["W"], q["b"], c, stage)
+                q = dict(q, W=W, b=b)
+            outs.append(ln_base_alg(q, "xs", defect=inner, chain=chain))
+        y = torch.cat(outs, 0)
+    if defect == "row_dropped":
+        y[-1] = float("nan")
+    if defect == "short_slice_line_dropped":
+        y[:, -64:] = float("nan")
+    if defect == "ln_zero_row_nan":
+        y = torch.cat([y, torch.full((1, y.shape[1]), float("nan"))], 0)
+    return y
+
+
+# ---- the counted waits of csrc/linear_xs.hip: a walk of one wave's vector-memory queue (tests/test_numerics_cpu.py) ----
+# ASSUMPTION (the kernel's own, not checked here): s_waitcnt vmcnt(N) returns when all but the N YOUNGEST vector-memory operations of the
+# wave - loads, LDS-DMA loads and stores alike - have completed, i.e. they retire in issue order.
+XS_NDMA, XS_ST, XS_RS = 6, 4, 4         # VMEM operations per wave: per weight stage, per finished 128-byte line, residual loads per stage
+# every wait_vm<...> of the source in source order: (site, template argument as written)
+XS_WAIT_SITES = (
+    ("top_last", "0"), ("top_first", "NDMA"), ("top_p1", "NDMA + 8 + (RES ? 4 : 0)"), ("top_p2", "NDMA + 4"), ("top_p4_store", "NDMA + 4"),
+    ("top_p4", "NDMA"),
+    ("res_early", "NDMA"), ("res_early_end", "0"), ("res_late", "NDMA + 4 + 4 + NDMA"), ("res_late_end", "0"),
+    ("pp_open", "NDMA"), ("pp_open_one", "0"),
+    ("pp_late_first", "RS"), ("pp_late_store", "ST + RS"), ("pp_late", "RS"),
+    ("pp_early_store", "NDMA + ST"), ("pp_early", "NDMA"), ("pp_early_end_store", "ST"), ("pp_early_end", "0"))
+
+
+def xs_wait_count(site, res):
+    env = dict(NDMA=XS_NDMA, ST=XS_ST, RS=XS_RS if res else 0)
+    expr = dict(XS_WAIT_SITES)[site].replace("(RES ? 4 : 0)", "4" if res else "0")
+    return eval(expr, {"__builtins__": {}}, env)
+
+
+def xs_wave_walk(pp, late, P, res, nch, loosen=None):
+    """One wave's program (the order of csrc/linear_xs.hip; one-barrier form: pp False) as a walk of its VMEM queue.  Returns
+    dict(barriers, arrive: per barrier the stages whose own DMAs were still in flight when the wave ARRIVED at it, compute: stage ->
+    barriers passed when its MFMAs run, issue: stage -> barriers passed when its DMAs are issued, problems: residual loads still in flight
+    in the epilogue that adds them).  loosen: {site: extra operations} added to that wait's count (the planted defects)."""
+    loosen = loosen or {}
+    q, out = [], dict(barriers=0, arrive=[], compute={}, issue={}, problems=[])
+
+    def wait(site):
+        n = xs_wait_count(site, res) + loosen.get(site, 0)
+        del q[:max(0, len(q) - n)]
+
+    def barrier():
+        out["arrive"].append(sorted({s for kind, s in q if kind == "dma"}))
+        out["barriers"] += 1
+
+    def issue(s):
+        out["issue"][s] = out["barriers"]
+        q.extend([("dma", s)] * XS_NDMA)
+
+    def load_res(s):
+        if res:
+            q.extend([("res", s)] * XS_RS)
+
+    def compute(s):
+        out["compute"][s] = out["barriers"]
+
+    def line_done(t):
+        return t >= 0 and t % P == P - 1
+
+    def stores(s):
+        if line_done(s):
+            q.extend([("st", s)] * XS_ST)
+
+    def used(s):
+        if any(kind == "res" and st == s for kind, st in q):
+            out["problems"].append(f"residual of stage {s} still in flight in its epilogue")
+
+    q.extend([("x", 0)] * 20)                           # the activation loads (their number does not matter: they are the oldest)
+    if nch > 0:
+        issue(0)
+    if nch > 1:
+        issue(1)
+    if pp:
+        wait("pp_open" if nch > 1 else "pp_open_one")
+        if late:
+            barrier()
+        for t in range(nch):
+            barrier()
+            load_res(t)
+            compute(t)
+            if late and t + 1 < nch:
+                wait("pp_late_first" if (t + 2 >= nch and t == 0) else "pp_late_store" if line_done(t - 1) else "pp_late")
+            if not late or t + 1 < nch:
+                barrier()
+            if t + 2 < nch:
+                issue(t + 2)
+            if res:
+                wait("res_early" if t + 2 < nch else "res_early_end")
+                used(t)
+            stores(t)
+            if not late and t + 1 < nch:
+                if t + 2 < nch:
+                    wait("pp_early_store" if line_done(t) else "pp_early")
+                else:
+                    wait("pp_early_end_store" if line_done(t) else "pp_early_end")
+        return out
+
+    def top(ci):
+        cio = ci - (1 if late else 0)
+        if ci + 1 >= nch:
+            wait("top_last")
+        elif ci < (3 if late else 2):
+            wait("top_first")
+        elif P == 1:
+            wait("top_p1")
+        elif P == 2:
+            wait("top_p2")
+        else:
+            wait("top_p4_store" if (cio & 3) < 2 else "top_p4")
+        barrier()
+        load_res(ci)
+        if ci + 2 < nch:
+            issue(ci + 2)
+
+    def epilogue(ci):
+        if res:
+            if not late:
+                wait("res_early" if ci + 2 < nch else "res_early_end")
+            else:
+                wait("res_late" if (ci >= 1 and ci + 3 < nch) else "res_late_end")
+            used(ci)
+        stores(ci)
+
+    for ci in range(nch):                               # (the late waves' loop is unrolled by two in the source: the same order, two register sets)
+        top(ci)
+        if late and ci > 0:
+            epilogue(ci - 1)
+        compute(ci)
+        if not late:
+            epilogue(ci)
+    if late and nch > 0:
+        epilogue(nch - 1)
+    return out
+
+
+def xs_wait_audit(pp, P, res, nch, loosen=None, late_only=None):
+    """The walks of an early and a late wave held against each other: the problems found (empty: the counts are safe).
+      * when a wave ARRIVES at the barrier that opens compute(s) for any wave, its own DMAs of stage s are retired;
+      * every residual load is retired in the epilogue that adds it;
+      * both groups pass the same number of barriers;
+      * the DMAs of stage s (s >= 3) are issued after the barrier that follows the last compute(s - 3) of either group (the ring slot's
+        last readers).
+    late_only: apply `loosen` to the late (True) / early (False) wave alone; None: to both."""
+    w = {late: xs_wave_walk(pp, late, P, res, nch, loosen if late_only in (None, late) else None) for late in (False, True)}
+    bad = [f"{'late' if late else 'early'}: {p}" for late in w for p in w[late]["problems"]]
+    if w[False]["barriers"] != w[True]["barriers"]:
+        bad.append(f"barriers: early {w[False]['barriers']}, late {w[True]['barriers']}")
+    for who in w:
+        for s, passed in w[who]["compute"].items():
+            b = passed - 1                              # the barrier that opened this compute
+            for other in w:
+                if b < len(w[other]["arrive"]) and s in w[other]["arrive"][b]:
+                    bad.append(f"{'late' if other else 'early'} wave reaches barrier {b} (opens compute({s}) of the {'late' if who else 'early'} "
+                               f"waves) with its DMAs of stage {s} in flight")
+    for who in w:
+        for s, passed in w[who]["issue"].items():
+            for other in w:
+                if s >= 3 and passed < w[other]["compute"][s - 3] + 1:
+                    bad.append(f"{'late' if who else 'early'} wave issues stage {s} before the barrier behind compute({s - 3}) of the "
+                               f"{'late' if other else 'early'} waves")
+    return bad
+
+
+def xs_wait_programs():
+    """(pp, P, res) of every wave program pair the kernel instantiates: a residual exists at P = 1 only (static_assert), ping-pong at
+    P = 1 | 2 (no GEGLU)"""
+    return [(False, P, False) for P in (1, 2, 4)] + [(False, 1, True)] + [(True, P, False) for P in (1, 2)] + [(True, 1, True)]
+
+
+def xs_rounds_once(kind) -> bool:
+    """plain and GEGLU-without-LayerNorm launches round ONCE after the fp32 accumulation: judged by the misrounded share too"""
+    return kind in ("plain", "geglu")
+
+
+def xs_baselines(c):
+    """the independent fp32 implementations of one launch that set the misrounded bar: chains of 8, chains of 32, torch's fp32 matmul"""
+    return {"alg8": xs_base_alg(c, 8), "alg32": xs_base_alg(c, 32), "torch32": xs_base_alg(c, None)}
+
+
+def xs_out_guarded(M, cstore, dtype, device="cpu"):
+    """(buffer, payload view) of an output with pitch cstore + XS_PAD_COLS and XS_GUARD_ROWS rows on either side, every element the payload
+    NaN of ATTN_NAN_BITS (which no arithmetic produces)"""
+    big = torch.full((M + 2 * XS_GUARD_ROWS, cstore + XS_PAD_COLS), ATTN_NAN_BITS[dtype], dtype=torch.int16).view(dtype).to(device)
+    return big, big[XS_GUARD_ROWS:XS_GUARD_ROWS + M, :cstore]
+
+
+def xs_guards_intact(big, M, cstore) -> bool:
+    """every guard row and guard column still holds the NaN bits it was filled with"""
+    bits = big.detach().cpu().view(torch.int16).clone()
+    want = bits[0, 0].item()
+    bits[XS_GUARD_ROWS:XS_GUARD_ROWS + M, :cstore] = want
+    return bool((bits == want).all())
 
 
 if __name__ == "__main__":

@@ -1044,3 +1044,100 @@ def test_norm_wrappers_refuse_operands_the_launch_cannot_read(monkeypatch):
         assert dry.size() == 5 and y.data_ptr() == big[1].data_ptr()
         ops.layer_norm(tok, [f(40)] * 3, [f(40)] * 3, group_rows=[1, 4, 1])
         assert dry.size() == 6
+
+
+# one refusal of ops.linear_xs per entry: message -> what to change in a legal call (M = 512 rows of K = 320 -> 128 columns, fp16)
+_XS_M, _XS_K, _XS_C = 512, 320, 128
+_xs_z = lambda *s: torch.zeros(*s).half()
+_XS_REFUSALS = {
+    "x must be fp16 or bf16": lambda a: a.update(x=a["x"].float(), out=a["out"].float()),
+    "out is torch.bfloat16": lambda a: a.update(out=a["out"].bfloat16()),
+    "residual is torch.float32": lambda a: a.update(residual=torch.zeros(_XS_M, _XS_C)),
+    "out is torch.float16 on meta": lambda a: a.update(out=a["out"].to("meta")),
+    r"x must be a contiguous \[M, K\] = \[512, 320\]": lambda a: a.update(x=_xs_z(_XS_M, 2 * _XS_K)[:, :_XS_K]),
+    r"x must be a contiguous \[M, K\] = \[512, 320\]#": lambda a: a.update(x=_xs_z(_XS_M, 1, 1, _XS_K)),
+    r"x must be a contiguous \[M, K\] = \[512, 320\]##": lambda a: a.update(x=_xs_z(_XS_M + 1, _XS_K)),
+    "x must start at a multiple of 16 bytes": lambda a: a.update(x=_xs_z(_XS_M * _XS_K + 4)[4:].view(_XS_M, _XS_K)),
+    r"out must be \[M, cstore\] = \[512, 128\]": lambda a: a.update(out=_xs_z(_XS_M, 1, 1, _XS_C)),
+    r"out must be \[M, cstore\] = \[512, 128\]#": lambda a: a.update(out=_xs_z(_XS_M, _XS_C + 64)),
+    r"residual must be \[M, cstore\] = \[512, 128\]": lambda a: a.update(residual=_xs_z(_XS_M, 1, 1, _XS_C)),
+    "out: innermost stride must be 1": lambda a: a.update(out=_xs_z(_XS_C, _XS_M).t()),
+    "residual: innermost stride must be 1": lambda a: a.update(residual=_xs_z(_XS_C, _XS_M).t()),
+    "out: row pitch 132 must be a multiple of 8 elements": lambda a: a.update(out=_xs_z(_XS_M, _XS_C + 4)[:, :_XS_C]),
+    "out: row pitch 64 must be a multiple of 8 elements and at least the width 128": lambda a: a.update(out=torch.as_strided(_xs_z(_XS_M * _XS_C), (_XS_M, _XS_C), (64, 1))),
+    "residual: row pitch 128 differs from out's 192": lambda a: a.update(out=_xs_z(_XS_M, _XS_C + 64)[:, :_XS_C]),
+    "out must start at a multiple of 16 bytes": lambda a: a.update(out=_xs_z(_XS_M * _XS_C + 4)[4:].view(_XS_M, _XS_C)),
+    "residual must start at a multiple of 16 bytes": lambda a: a.update(residual=_xs_z(_XS_M * _XS_C + 4)[4:].view(_XS_M, _XS_C)),
+    "group_rows None must hold one run of rows per weight set": lambda a: a.update(pw=[a["pw"], a["pw"]]),
+    r"group_rows \[256\] must hold one run of rows per weight set": lambda a: a.update(pw=[a["pw"], a["pw"]], group_rows=[256]),
+    r"group_rows \[256, 255\] must hold one run of rows per weight set and sum to M = 512": lambda a: a.update(pw=[a["pw"], a["pw"]], group_rows=[256, 255]),
+    r"group_rows \[128, 384\]: every run but the last must be whole 256-row blocks": lambda a: a.update(pw=[a["pw"], a["pw"]], group_rows=[128, 384]),
+}
+
+
+@pytest.mark.parametrize("msg", list(_XS_REFUSALS), ids=lambda m: re.sub(r"[^A-Za-z0-9#]+", "_", m)[:60])
+def test_linear_xs_wrapper_refuses_what_the_launch_cannot_address(msg, monkeypatch):
+    """ops.linear_xs hands data_ptr()s, M and ONE row pitch to es_linear_xs: operands of another dtype, device, shape, inner stride,
+    pitch or alignment than that launch addresses, and group tables that do not cover M in whole 256-row blocks, raise EdgeStyleHipError
+    before anything is recorded or launched (dry recorder, host buffers)."""
+    monkeypatch.setattr(ops, "_stream", lambda: None)
+    pw = ops.pack_weight(torch.zeros(_XS_C, _XS_K), torch.zeros(_XS_C), torch.float16, "cpu")
+    a = dict(x=_xs_z(_XS_M, _XS_K), pw=pw, out=_xs_z(_XS_M, _XS_C), residual=_xs_z(_XS_M, _XS_C), group_rows=None)
+    _XS_REFUSALS[msg](a)
+    with _DryPlan() as dry:
+        with pytest.raises(lib.EdgeStyleHipError, match="linear_xs: " + msg.rstrip("#")):
+            ops.linear_xs(a["x"], a["pw"], _XS_M, a["out"], a["group_rows"], residual=a["residual"])
+        assert dry.size() == 0
+
+
+def test_linear_xs_wrapper_passes_the_pitch_and_keeps_a_ragged_last_group(monkeypatch):
+    """What stays legal: dense operands (ldo = cstore, as before), `out` and `residual` as column / row slices of ONE pitch (ldo = that
+    pitch, read back from the recorded descriptor), a single row whose stride is never used - and a grouped launch whose LAST run is
+    ragged, with ceil(rows / 128) odd: the choice is to SUPPORT it (mt_end of the last group = ceil(M / 128); es_linear_xs demands whole
+    256-row blocks of every group but the last), while an earlier ragged run stays refused by the library as well."""
+    monkeypatch.setattr(ops, "_stream", lambda: None)
+    pw = ops.pack_weight(torch.zeros(_XS_C, _XS_K), torch.zeros(_XS_C), torch.float16, "cpu")
+    M = _XS_M
+
+    class Rec:
+        descs = []
+        next = staticmethod(lambda meta: None)
+    monkeypatch.setattr(ops, "PROFILE", Rec)
+    with _DryPlan() as dry:
+        ops.linear_xs(_xs_z(M, _XS_K), pw, M, _xs_z(M, _XS_C), residual=_xs_z(M, _XS_C))
+        assert dry.size() == 1 and Rec.descs[-1].ldo == _XS_C
+        big, rbig = _xs_z(M + 8, _XS_C + 64), _xs_z(M + 2, _XS_C + 64)
+        ops.linear_xs(_xs_z(M + 4, _XS_K)[2:M + 2], pw, M, big[4:M + 4, :_XS_C], residual=rbig[1:M + 1, :_XS_C])
+        assert dry.size() == 2 and Rec.descs[-1].ldo == _XS_C + 64 and Rec.descs[-1].out == big[4].data_ptr()
+        ops.linear_xs(_xs_z(1, _XS_K), pw, 1, torch.as_strided(_xs_z(1024), (1, _XS_C), (3, 1)))
+        assert dry.size() == 3 and Rec.descs[-1].ldo == _XS_C
+        # ragged last groups: 256 + 100 rows (ceil(356 / 128) = 3, odd), 512 + 256 + 1
+        for rows in ([256, 100], [512, 256, 1], [256, 256]):
+            m = sum(rows)
+            ops.linear_xs(_xs_z(m, _XS_K), [pw] * len(rows), m, _xs_z(m, _XS_C), rows)
+            d = Rec.descs[-1]
+            ends = [d.mt_end[g] for g in range(len(rows))]
+            assert d.ngroups == len(rows) and ends[-1] == (m + 127) // 128 and all(e % 2 == 0 for e in ends[:-1]), (rows, ends)
+        assert dry.size() == 6 and [Rec.descs[-3].mt_end[g] for g in range(2)] == [2, 3]
+        # the library itself: an odd boundary anywhere but at the end is refused, nothing recorded
+        d = Rec.descs[-2]
+        d.mt_end[0], d.mt_end[1] = 3, 6
+        assert dry.L.es_linear_xs(ctypes.byref(d), None) == -1 and b"the last may be ragged" in dry.L.es_last_error() and dry.size() == 6
+
+
+def test_linear_xs_last_form_is_set_by_launches_only(monkeypatch):
+    """es_linear_xs_last_form: written by the launcher alone - a dry (recording) call leaves it as it was, and it is 0 in a process that
+    has launched nothing (no GPU: this one); the flags are the header's"""
+    monkeypatch.setattr(ops, "_stream", lambda: None)
+    L = lib.load()
+    before = L.es_linear_xs_last_form()
+    if not torch.cuda.is_available():
+        assert before == 0
+    pw = ops.pack_weight(torch.zeros(_XS_C, _XS_K), torch.zeros(_XS_C), torch.float16, "cpu")
+    with _DryPlan() as dry:
+        ops.linear_xs(_xs_z(_XS_M, _XS_K), pw, _XS_M, _xs_z(_XS_M, _XS_C))
+        assert dry.size() == 1 and L.es_linear_xs_last_form() == before
+    hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "edgestyle_hip.h")).read()
+    for name in ("GEGLU", "LN", "RES", "PP", "GN"):
+        m = re.search(rf"ES_XS_FORM_{name} = (0x[0-9A-Fa-f]+)", hdr)
+        assert m and int(m.group(1), 16) == getattr(lib, f"XS_FORM_{name}")

@@ -873,3 +873,160 @@ def test_norm_planted_layer_norm_defects(dtype):
     for defect in (None, "one_pass_variance"):
         y = nm.ln_plain_base_alg(c, defect=defect)
         assert torch.equal(y[1], nm.rnd(c["beta"][0], dtype)) and torch.equal(y[3], nm.rnd(c["beta"][0], dtype))
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# es_linear_xs: the table of tests/test_linear_xs_gpu.py on the CPU, the planted defects, the counted waits
+# ----------------------------------------------------------------------------------------------------------------
+def _xs_row_case(r, dtype):
+    kw = dict(hw=r["hw"], G=r["G"], N=r["N"]) if r["kind"] == "gn" else {}
+    return nm.xs_case(r["M"], r["K"], r["lines"], r["kind"], dtype, seed=r["seed"], counts=r["counts"], ratio=r["ratio"], **kw)
+
+
+def _xs_verdict(c, y, ref, alg8, e_ref):
+    """what tests/test_linear_xs_gpu.py would hold against an output y of case c (a y with more rows than M: stored through a guarded
+    buffer, as the GPU test launches): the list of bars missed"""
+    M, cstore, dt = c["M"], c["cstore"], c["dtype"]
+    bad = []
+    big, view = nm.xs_out_guarded(M, cstore, dt)
+    rows = y.shape[0]
+    big[nm.XS_GUARD_ROWS:nm.XS_GUARD_ROWS + rows, :cstore] = y.to(dt)
+    if not nm.xs_guards_intact(big, M, cstore):
+        bad.append("guard")
+    y = view.float()
+    if bool(torch.isnan(y).any()):
+        bad.append("nan in the payload")
+    e, e_alg = nm.row_err(y, ref), nm.row_err(alg8, ref)
+    if not e <= nm.MARGIN * e_alg:
+        bad.append(f"base_alg bar: {e:.3e} > 2 x {e_alg:.3e}")
+    if not e <= nm.MARGIN * e_ref:
+        bad.append(f"base_ref bar: {e:.3e} > 2 x {e_ref:.3e}")
+    if nm.xs_rounds_once(c["kind"]):
+        base = dict(alg8=alg8, alg32=nm.xs_base_alg(c, 32), torch32=nm.xs_base_alg(c, None))
+        bar = nm.misrounded_bar([nm.misrounded(v, ref, dt, count=True) for v in base.values()])
+        n = nm.misrounded(y, ref, dt, count=True)
+        if n > bar:
+            bad.append(f"misrounded: {n} > {bar}")
+    if c["kind"] == "res":
+        bar = nm.misrounded_bar([nm.differs(nm.xs_base_alg(c, k), alg8, count=True) for k in (32, None)])
+        n = nm.differs(y, alg8, count=True)
+        if n > bar:
+            bad.append(f"differs from base_alg: {n} > {bar}")
+    return bad
+
+
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=["fp16", "bf16"])
+def test_xs_gpu_table_rows_build_and_their_design_is_inside_the_bars(dtype):
+    """every row of the GPU table builds its case (the generators assert their postconditions, every bias is clear of the rounding
+    boundaries) and the design - xs_base_alg with chains of 8 - passes every check the GPU test makes of the kernel.  Every other row per
+    dtype (the even rows in fp16, the odd ones in bf16: each row is walked once here; on the GPU every row runs in both)"""
+    from tests import test_linear_xs_gpu as X
+    for r in X.TABLE[(0 if dtype == torch.float16 else 1)::2]:
+        c = _xs_row_case(r, dtype)
+        ref = nm.xs_ref64(c)
+        assert ref.shape == (r["M"], 64 * r["lines"])
+        alg8 = nm.xs_base_alg(c, 8)
+        bad = _xs_verdict(c, alg8, ref, alg8, nm.row_err(nm.xs_base_ref(c), ref))
+        assert not bad, (X.row_id(r), bad)
+
+
+def _xs_smallest(pred):
+    from tests import test_linear_xs_gpu as X
+    rows = [r for r in X.TABLE if pred(r)]
+    return min(rows, key=lambda r: (r["M"] * r["lines"], r["K"], r["pp"]))
+
+
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=["fp16", "bf16"])
+@pytest.mark.parametrize("defect", nm.XS_DEFECTS)
+def test_xs_planted_defects_land_outside_the_bars(defect, dtype):
+    """each planted defect of nm.xs_base_alg, at the smallest row of the GPU table where it applies, misses a check the GPU test makes -
+    while the design passes all of them on the same row"""
+    from tests import test_linear_xs_gpu as X
+    P = lambda r: nm.xs_geometry(r["K"], r["kind"])[2]
+    pred = {
+        "stale_stage": lambda r: X.row_split(r)[1] >= 4,                               # a fourth stage in the first slice
+        "row_dropped": lambda r: True,
+        "short_slice_line_dropped": lambda r: X.row_split(r)[0] > 1 and X.row_split(r)[2] < X.row_split(r)[1],
+        "residual_row_shift": lambda r: r["kind"] == "res",
+        "geglu_halves_swapped": lambda r: r["kind"].startswith("geglu"),
+        "ln_zero_row_nan": lambda r: r["kind"] in ("ln", "geglu_ln"),
+    }[defect]
+    r = _xs_smallest(pred)
+    c = _xs_row_case(r, dtype)
+    ref, alg8 = nm.xs_ref64(c), nm.xs_base_alg(c, 8)
+    e_ref = nm.row_err(nm.xs_base_ref(c), ref)
+    assert not _xs_verdict(c, alg8, ref, alg8, e_ref), X.row_id(r)
+    bad = _xs_verdict(c, nm.xs_base_alg(c, 8, defect=defect), ref, alg8, e_ref)
+    print(f"xs defect {defect} at {X.row_id(r)}: {bad}")
+    assert bad, (defect, X.row_id(r))
+    want = {"row_dropped": "nan in the payload", "short_slice_line_dropped": "nan in the payload", "ln_zero_row_nan": "guard"}.get(defect)
+    assert want is None or want in bad
+
+
+def test_xs_stale_stage_is_seen_in_every_stage_of_every_form():
+    """the stale stage (a wait one group too loose) at EVERY stage index >= 3 of one long row per kind: always outside the base_alg bar"""
+    for K, kind in ((320, "plain"), (320, "geglu_ln"), (640, "ln"), (640, "geglu"), (320, "res"), (640, "gn")):
+        kw = dict(hw=256, G=32, N=1) if kind == "gn" else {}
+        c = nm.xs_case(256 if kind == "gn" else 17, K, 3, kind, torch.float16, seed=5, ratio=30, **kw)
+        ref, alg8 = nm.xs_ref64(c), nm.xs_base_alg(c, 8)
+        e_alg = nm.row_err(alg8, ref)
+        outw = nm.xs_geometry(K, kind)[1]
+        for stage in range(3, 3 * 64 // outw):
+            e = nm.row_err(nm.xs_base_alg(c, 8, defect="stale_stage", stage=stage), ref)
+            assert e > 100 * e_alg, (K, kind, stage, e, e_alg)
+
+
+def _xs_source():
+    import os
+    return open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "edgestyle_amd", "csrc", "linear_xs.hip")).read()
+
+
+def test_xs_wait_model_is_the_source():
+    """the walk of nm.xs_wave_walk is tied to csrc/linear_xs.hip by its TEXT: the ordered list of wait_vm<...> arguments, NDMA, ST, RS and
+    the static_assert that keeps a residual at P = 1.  An edit to any of them fails here until the model is updated with it."""
+    import re
+    src = _xs_source()
+    args = [a.strip() for a in re.findall(r"wait_vm<([^>]*)>\(\)", src)]
+    assert args == [a for _, a in nm.XS_WAIT_SITES], args
+    assert int(re.search(r"constexpr int NDMA = (\d+);", src).group(1)) == nm.XS_NDMA
+    assert int(re.search(r"constexpr int ST = (\d+);", src).group(1)) == nm.XS_ST
+    assert int(re.search(r"constexpr int RS = RES \? (\d+) : 0;", src).group(1)) == nm.XS_RS
+    assert "static_assert(!RES || (P == 1 && !GEGLU && !LN)" in src and "constexpr int XS_STAGES = 3;" in src
+    # five weight pieces and one bias load per wave per stage; four residual loads, four stores per line
+    assert src.count("for (int i = 0; i < 5; ++i)") == 1 and src.count("__builtin_amdgcn_raw_ptr_buffer_load_lds(") == 2
+    assert src.count("for (int i = 0; i < 4; ++i)") == 2
+    # the conditions under which each count is chosen, as the walk spells them
+    for text in ("} else if (ci + 1 >= nch) {", "} else if (ci < (late ? 3 : 2)) {", "if ((cio & 3) < 2) wait_vm<NDMA + 4>(); else wait_vm<NDMA>();",
+                 "if (PP || !late) { if (ci + 2 < nch) wait_vm<NDMA>(); else wait_vm<0>(); }",
+                 "else { if (ci >= 1 && ci + 3 < nch) wait_vm<NDMA + 4 + 4 + NDMA>(); else wait_vm<0>(); }",
+                 "if (nch > 1) wait_vm<NDMA>(); else wait_vm<0>();", "if (late) __builtin_amdgcn_s_barrier();",
+                 "if (t + 2 >= nch && t == 0) wait_vm<RS>();", "else if (line_done(t - 1)) wait_vm<ST + RS>(); else wait_vm<RS>();",
+                 "if (!late || t + 1 < nch) __builtin_amdgcn_s_barrier();",
+                 "if (t + 2 < nch) { if (line_done(t)) wait_vm<NDMA + ST>(); else wait_vm<NDMA>(); }",
+                 "else { if (line_done(t)) wait_vm<ST>(); else wait_vm<0>(); }"):
+        assert text in src, text
+
+
+def test_xs_counted_waits_are_safe_and_every_loosened_count_is_caught():
+    """One wave's vector-memory queue walked through both forms, both wave groups, every P, with and without a residual, nch = P .. 12:
+    whenever a wave arrives at a barrier that opens compute(s) for any wave its own DMAs of stage s are retired, every residual load
+    is retired in its epilogue, both groups pass the same number of barriers, and a ring slot is refilled only behind the barrier that
+    follows its last readers.  Then every wait of the source, one at a time, is loosened by one store group (4) and by one DMA group (6):
+    each such kernel is caught in at least one program - also when only the early or only the late waves run the loose count."""
+    walked = 0
+    for pp, P, res in nm.xs_wait_programs():
+        for nch in range(P, 13, P):
+            assert not nm.xs_wait_audit(pp, P, res, nch), (pp, P, res, nch, nm.xs_wait_audit(pp, P, res, nch))
+            a, b = nm.xs_wave_walk(pp, False, P, res, nch), nm.xs_wave_walk(pp, True, P, res, nch)
+            assert a["barriers"] == b["barriers"] == (2 * nch if pp else nch)
+            assert sorted(a["compute"]) == sorted(b["compute"]) == list(range(nch)) == sorted(a["issue"])
+            walked += 2
+    assert walked == 2 * sum(12 // P for _, P, _ in nm.xs_wait_programs())
+    for site, _ in nm.XS_WAIT_SITES:
+        for extra in (nm.XS_ST, nm.XS_NDMA):
+            caught = [(pp, P, res, nch) for pp, P, res in nm.xs_wait_programs() for nch in range(P, 13, P) if nm.xs_wait_audit(pp, P, res, nch, {site: extra})]
+            assert caught, f"wait {site} loosened by {extra} passes the audit"
+    # a count one group TIGHTER is safe (the audit is no equality test of the counts)
+    assert not nm.xs_wait_audit(False, 1, False, 7, {"top_p1": -4}) and not nm.xs_wait_audit(True, 2, False, 8, {"pp_early_store": -4})
+    # the steady-state counts are exact where the issue says so: one more operation than they allow is already too loose
+    assert nm.xs_wait_audit(False, 1, False, 7, {"top_p1": 1}) and nm.xs_wait_audit(True, 1, True, 7, {"pp_late_store": 1})

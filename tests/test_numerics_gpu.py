@@ -668,8 +668,25 @@ def _norm_section():
     return "\n".join(out), len(rows)
 
 
+XS_MARKERS = ("<!-- xs table begin: written by `python -m tests.numerics --report --only xs` -->", "<!-- xs table end -->")
+
+
+def _xs_section():
+    from tests import test_linear_xs_gpu as XG
+    rows, secs = XG.report_rows()
+    out = [f"es_linear_xs in every form, measured on {torch.cuda.get_device_name(0)}, torch {torch.__version__}; {len(rows)} rows (four or five launches each: dense, "
+           f"guarded views, dense again, the other ping-pong setting) in {secs:.1f} s, CPU baselines included.  Error per row: max|y - ref64| / rms(ref64).  "
+           "`differs`: elements that differ from the correctly rounded fp64 result (plain and GEGLU rows) or from `base_alg` (residual rows), and the bar.", "",
+           "| case | form | kernel | base_alg | base_ref | kernel / base_alg | kernel / base_ref | differs / bar (elements) | old metric |", "|---|---|---|---|---|---|---|---|---|"]
+    for r in rows:
+        share = "-" if r["differs"] is None else f"{r['differs']} / {r['bar']} ({r['numel']})"
+        out.append(f"| {r['case']} | {r['form']} | {r['kernel']:.2e} | {r['base_alg']:.2e} | {r['base_ref']:.2e} | {_div(r['kernel'], r['base_alg']):.2f} | "
+                   f"{_div(r['kernel'], r['base_ref']):.2f} | {share} | {r['old_metric']:.1e} |")
+    return "\n".join(out), len(rows)
+
+
 _SECTIONS = {"fusion": (_fusion_section, FUSION_MARKERS), "sampler": (_sampler_section, SAMPLER_MARKERS), "attention": (_attention_section, ATTENTION_MARKERS),
-             "norm": (_norm_section, NORM_MARKERS)}
+             "norm": (_norm_section, NORM_MARKERS), "xs": (_xs_section, XS_MARKERS)}
 
 
 def _write_sections(doc, path, which):
@@ -684,10 +701,10 @@ def _write_sections(doc, path, which):
 
 
 def write_report(path=None, only=None):
-    """python -m tests.numerics --report [--only conv | fusion | sampler | attention | norm]: run every case above and the convolution sweep of
+    """python -m tests.numerics --report [--only conv | fusion | sampler | attention | norm | xs]: run every case above and the convolution sweep of
     tests/test_conv_gpu.py without asserting and write the measured tables (--only conv: the convolution table alone, the other is kept
-    as it is; --only fusion, --only sampler, --only attention, --only norm: the table of tests/test_fusion_gpu.py, tests/test_sampler_gpu.py,
-    tests/test_attention_gpu.py or tests/test_norm_gpu.py alone, between its marker lines)"""
+    as it is; --only fusion, --only sampler, --only attention, --only norm, --only xs: the table of tests/test_fusion_gpu.py,
+    tests/test_sampler_gpu.py, tests/test_attention_gpu.py, tests/test_norm_gpu.py or tests/test_linear_xs_gpu.py alone, between its marker lines)"""
     global RECORD
     import tempfile
     import pathlib
