@@ -53,6 +53,9 @@ def parse_args(argv: Optional[List[str]] = None):
     p.add_argument("--scheduler", type=str, default="unipc", choices=["unipc", "ddim"])
     p.add_argument("--seed", type=int, default=42)
     p.add_argument("--random_init", type=str, default=None, help="write seeded random-init model dirs here and use them")
+    p.add_argument("--device_preprocess", action="store_true",
+                   help="resize, crop and convert the condition images on the GPU (Pillow-exact kernels with torchvision's size and "
+                        "crop rules, TT:29-48) instead of with PIL on the host: the files are only decoded with PIL, their bytes uploaded")
     p.add_argument("--tiny", action="store_true", help="with --random_init: width-reduced 128x128 config (plumbing demo)")
     return p.parse_args(argv)
 
@@ -146,9 +149,14 @@ def main(args):
     res = unet.cfg.sample_size * vae.cfg.scale
     tp2 = args.target_path2 or args.target_path
 
-    def img(root, kind, name, normalize):
-        return load_image(os.path.join(root, kind, name), res, normalize)
     from PIL import Image
+
+    def img(root, kind, name, normalize):
+        path = os.path.join(root, kind, name)
+        if args.device_preprocess:
+            pixels = np.asarray(Image.open(path).convert("RGB"))
+            return pipeline.preprocess_images([pixels], res, [normalize])[0]
+        return load_image(path, res, normalize)
     shown = [Image.open(os.path.join(args.source_path, "subject", args.source_image_name)).convert("RGB").resize((res, res)),
              Image.open(os.path.join(args.target_path, "subject", args.target_image_name)).convert("RGB").resize((res, res)),
              Image.open(os.path.join(tp2, "subject", args.target_image_name2)).convert("RGB").resize((res, res))]

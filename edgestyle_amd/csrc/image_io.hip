@@ -1,0 +1,343 @@
+// Byte images at the edge of the C ABI (gfx950): Pillow-exact bilinear resize + centre crop of uint8 HWC images of any size,
+// uint8 HWC -> fp32 NCHW network input, fp32 NCHW network output -> uint8 HWC.
+//
+// The reference's callers prepare every condition image with torchvision's Resize(R, BILINEAR) -> CenterCrop(R) -> ToTensor
+// (-> Normalize(.5, .5)) on a PIL image (test_text2image_pretrained_openpose.py:29-48).  On a PIL image that resize is Pillow's
+// ImagingResample: separable (horizontal pass, then vertical pass, a uint8 image in between), antialiased (the triangle filter
+// is stretched by the scale when shrinking), with double-precision weights normalised per output pixel and then quantised to
+// 22 fractional bits; everything after the quantisation is integer arithmetic.  The kernels below redo exactly that, so their
+// bytes EQUAL Pillow's.  The coefficient code is written once (resize_axis, __host__ __device__): es_image_resize_coeffs hands
+// the host build of it to the CPU tests, the kernels run the device build.  Built with -ffp-contract=off (csrc/Makefile): a
+// fused multiply-add in the weight arithmetic would round differently from Pillow's C.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdio.h>
+#include <vector>
+
+#include "../../include/edgestyle_hip.h"
+#include "plan.h"
+
+extern "C" void es_set_error(const char* msg);
+
+namespace {
+
+constexpr int kPrecisionBits = 32 - 8 - 2;      // Pillow's PRECISION_BITS for 8-bit channels
+
+// One output pixel `xx` of an axis resampled from `in` to `out` pixels (Pillow precompute_coeffs + normalize_coeffs_8bpc with
+// the bilinear filter, box = the whole axis): calls sink(xmin, x, k) for every tap - source index xmin + x, 22-bit
+// fixed-point weight k - in index order, returns the tap count and the first source index.
+template <typename Sink>
+__host__ __device__ inline int resize_axis(int in, int out, int xx, int* xmin_out, Sink&& sink) {
+  const double scale = (double)in / (double)out;
+  const double fs = scale < 1.0 ? 1.0 : scale;
+  const double support = 1.0 * fs;
+  const double ss = 1.0 / fs;
+  const double center = (xx + 0.5) * scale;
+  int xmin = (int)(center - support + 0.5);
+  if (xmin < 0) xmin = 0;
+  int xmax = (int)(center + support + 0.5);
+  if (xmax > in) xmax = in;
+  const int n = xmax - xmin;
+  auto weight = [&](int x) {
+    double a = (x + xmin - center + 0.5) * ss;
+    if (a < 0.0) a = -a;
+    return a < 1.0 ? 1.0 - a : 0.0;
+  };
+  double ww = 0.0;
+  for (int x = 0; x < n; ++x) ww += weight(x);
+  for (int x = 0; x < n; ++x) {
+    double w = weight(x);
+    if (ww != 0.0) w /= ww;
+    sink(xmin, x, (int)(0.5 + w * (double)(1 << kPrecisionBits)));     // bilinear weights are never negative
+  }
+  *xmin_out = xmin;
+  return n;
+}
+
+__host__ __device__ inline uint8_t clip8(int v) {
+  v >>= kPrecisionBits;
+  return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
+}
+
+// ToTensor (-> Normalize(.5, .5)): both divisions correctly rounded, as numpy / torch compute them on the host
+__device__ inline float u8_to_unit(uint8_t v, int normalize) {
+  float y = __fdiv_rn((float)v, 255.0f);
+  if (normalize) y = __fdiv_rn(y - 0.5f, 0.5f);
+  return y;
+}
+
+// torchvision's Resize(R) (shorter side -> R, longer side truncated) and CenterCrop(R) (round-half-to-even offsets)
+void fit(int height, int width, int R, int32_t out[4]) {
+  int rh, rw;
+  if (width <= height) { rw = R; rh = (int)((double)((long long)R * height) / (double)width); }
+  else { rh = R; rw = (int)((double)((long long)R * width) / (double)height); }
+  out[0] = rh; out[1] = rw;
+  out[2] = (int)rint((rh - R) / 2.0);
+  out[3] = (int)rint((rw - R) / 2.0);
+}
+
+struct ImgDesc {
+  const uint8_t* src;     // [in_h][stride bytes], ch bytes per pixel
+  long long stride;
+  uint8_t* tmp;           // horizontal pass result: source rows [y0, y0 + nrows) x the R kept columns x 3 (need_h only)
+  uint8_t* out;           // [R, R, 3] or null
+  float* fout;            // [3, R, R] or null
+  int32_t in_h, in_w, ch;
+  int32_t rh, rw, top, left;
+  int32_t y0, nrows;
+  int32_t need_h, need_v, normalize;
+};
+constexpr int kImgPerLaunch = 16;
+struct Batch { ImgDesc d[kImgPerLaunch]; int32_t R; };
+
+// Horizontal pass.  grid.y = image; consecutive threads take consecutive (x * 3 + c) bytes of a row of the intermediate image,
+// so the stores coalesce and the loads of a wave fall into a few neighbouring lines of one source row.  Only the columns the
+// crop keeps and the source rows the kept output rows read are produced.
+__global__ __launch_bounds__(256) void resize_h_kernel(const Batch b) {
+  const ImgDesc& d = b.d[blockIdx.y];
+  if (!d.need_h) return;
+  const int row3 = 3 * b.R;
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (long long)d.nrows * row3) return;
+  const int r = (int)(idx / row3), j = (int)(idx - (long long)r * row3);
+  const int xx = d.left + j / 3, c = j % 3;
+  const uint8_t* row = d.src + (size_t)(d.y0 + r) * (size_t)d.stride + c;
+  int acc = 1 << (kPrecisionBits - 1), xmin;
+  const int ch = d.ch;
+  resize_axis(d.in_w, d.rw, xx, &xmin, [&](int x0, int x, int k) { acc += k * (int)row[(size_t)(x0 + x) * ch]; });
+  d.tmp[idx] = clip8(acc);
+}
+
+// Vertical pass + crop (+ ToTensor / Normalize).  grid.y = image; consecutive threads take consecutive (x * 3 + c) bytes of an
+// output row: every tap is one coalesced row segment of the intermediate image (or of the source, when the horizontal pass was
+// skipped).  An axis whose size does not change is skipped as Pillow skips it: the kept bytes are copied.
+__global__ __launch_bounds__(256) void resize_v_kernel(const Batch b) {
+  const ImgDesc& d = b.d[blockIdx.y];
+  const int R = b.R, row3 = 3 * R;
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (long long)R * row3) return;
+  const int yy = (int)(idx / row3), j = (int)(idx - (long long)yy * row3);
+  const int x = j / 3, c = j - 3 * x;
+  const uint8_t* base;
+  size_t pitch;
+  if (d.need_h) { base = d.tmp + j - (size_t)d.y0 * row3; pitch = (size_t)row3; }          // row y of the source is row y - y0 of tmp
+  else { base = d.src + (size_t)(d.left + x) * d.ch + c; pitch = (size_t)d.stride; }
+  uint8_t v;
+  if (d.need_v) {
+    int acc = 1 << (kPrecisionBits - 1), ymin;
+    resize_axis(d.in_h, d.rh, d.top + yy, &ymin, [&](int y0, int y, int k) { acc += k * (int)base[(size_t)(y0 + y) * pitch]; });
+    v = clip8(acc);
+  } else {
+    v = base[(size_t)(d.top + yy) * pitch];
+  }
+  if (d.out) d.out[idx] = v;
+  if (d.fout) d.fout[((size_t)c * R + yy) * R + x] = u8_to_unit(v, d.normalize);
+}
+
+__global__ __launch_bounds__(256) void u8_to_f32_kernel(const uint8_t* __restrict__ in, float* __restrict__ out, long long count, long long HW, int normalize) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= count * 3 * HW) return;
+  const long long p = i % HW, nc = i / HW;
+  const long long n = nc / 3;
+  const int c = (int)(nc - 3 * n);
+  out[i] = u8_to_unit(in[(n * HW + p) * 3 + c], normalize);
+}
+
+__device__ inline unsigned unit_to_u8(float x) {
+  float y = x * 255.0f;                       // the file is built with -ffp-contract=off: a plain product, then the rounding
+  y = rintf(y);
+  y = y < 0.0f ? 0.0f : (y > 255.0f ? 255.0f : y);
+  return (unsigned)y;
+}
+
+// Four pixels per thread: one float4 per colour plane in, three dwords out.  The planes of an image are contiguous over H*W and
+// so are its HWC bytes, so the pixels are taken in runs of four over H*W whatever W is; `vec` (uniform) says that every run of
+// four is whole and aligned (H*W % 4 == 0, 16-byte aligned input, 4-byte aligned output); without it, and for nothing else,
+// pixels are moved one by one.
+__global__ __launch_bounds__(256) void f32_to_u8_kernel(const float* __restrict__ in, uint8_t* __restrict__ out, long long B, long long HW, int vec) {
+  const long long groups = (HW + 3) / 4;
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= B * groups) return;
+  const long long n = i / groups, p0 = (i - n * groups) * 4;
+  const float* src = in + n * 3 * HW + p0;
+  uint8_t* dst = out + (n * HW + p0) * 3;
+  if (vec) {
+    const float4 r = *(const float4*)src, g = *(const float4*)(src + HW), bl = *(const float4*)(src + 2 * HW);
+    const unsigned r0 = unit_to_u8(r.x), r1 = unit_to_u8(r.y), r2 = unit_to_u8(r.z), r3 = unit_to_u8(r.w);
+    const unsigned g0 = unit_to_u8(g.x), g1 = unit_to_u8(g.y), g2 = unit_to_u8(g.z), g3 = unit_to_u8(g.w);
+    const unsigned b0 = unit_to_u8(bl.x), b1 = unit_to_u8(bl.y), b2 = unit_to_u8(bl.z), b3 = unit_to_u8(bl.w);
+    unsigned* d32 = (unsigned*)dst;
+    d32[0] = r0 | (g0 << 8) | (b0 << 16) | (r1 << 24);
+    d32[1] = g1 | (b1 << 8) | (r2 << 16) | (g2 << 24);
+    d32[2] = b2 | (r3 << 8) | (g3 << 16) | (b3 << 24);
+  } else {
+    const int m = (int)(HW - p0 < 4 ? HW - p0 : 4);
+    for (int q = 0; q < m; ++q)
+      for (int c = 0; c < 3; ++c) dst[q * 3 + c] = (uint8_t)unit_to_u8(src[(long long)c * HW + q]);
+  }
+}
+
+thread_local char g_msg[224];
+int fail(const char* who, const char* what) {
+  snprintf(g_msg, sizeof(g_msg), "%s: %s", who, what);
+  es_set_error(g_msg);
+  return -1;
+}
+int fail_img(const char* who, int i, const char* what) {
+  snprintf(g_msg, sizeof(g_msg), "%s: image %d: %s", who, i, what);
+  es_set_error(g_msg);
+  return -1;
+}
+
+// argument checks shared by the size query and the launcher: everything that can be judged without a GPU
+int check_images(const char* who, const es_image_u8* imgs, int count, int R) {
+  if (!imgs) return fail(who, "null pointer (imgs)");
+  if (count < 1) return fail(who, "count < 1");
+  if (R < 1) return fail(who, "R < 1");
+  if (R > 16384) return fail(who, "R > 16384");
+  for (int i = 0; i < count; ++i) {
+    const es_image_u8& im = imgs[i];
+    if (!im.data) return fail_img(who, i, "null pointer (data)");
+    if (im.height < 1 || im.width < 1) return fail_img(who, i, "height or width < 1");
+    if (im.channels != 3 && im.channels != 4) return fail_img(who, i, "channels must be 3 or 4");
+    if (im.row_stride < (int64_t)im.width * im.channels) return fail_img(who, i, "row_stride < width*channels");
+    const long long lng = im.height > im.width ? im.height : im.width, sht = im.height > im.width ? im.width : im.height;
+    if ((long long)R * lng / sht > (1 << 24)) return fail_img(who, i, "the resized longer side would pass 2^24 pixels");
+  }
+  return 0;
+}
+
+// geometry of one image: resized size, crop, which passes run, and the source rows the kept output rows read
+void plan_image(const es_image_u8& im, int R, ImgDesc& d) {
+  int32_t f[4];
+  fit(im.height, im.width, R, f);
+  d.src = im.data; d.stride = im.row_stride;
+  d.in_h = im.height; d.in_w = im.width; d.ch = im.channels;
+  d.rh = f[0]; d.rw = f[1]; d.top = f[2]; d.left = f[3];
+  d.need_h = d.rw != d.in_w;
+  d.need_v = d.rh != d.in_h;
+  d.y0 = d.top; d.nrows = R;
+  if (d.need_v) {
+    int lo = d.in_h, hi = 0;
+    for (int yy = d.top; yy < d.top + R; ++yy) {
+      int ymin;
+      const int n = resize_axis(d.in_h, d.rh, yy, &ymin, [](int, int, int) {});
+      lo = ymin < lo ? ymin : lo;
+      hi = ymin + n > hi ? ymin + n : hi;
+    }
+    d.y0 = lo; d.nrows = hi - lo;
+  }
+  d.tmp = nullptr; d.out = nullptr; d.fout = nullptr; d.normalize = 0;
+}
+size_t tmp_bytes(const ImgDesc& d, int R) { return d.need_h ? (size_t)d.nrows * 3 * (size_t)R : 0; }
+
+}  // namespace
+
+// library-internal (plan.hip: es_prepare_conds_u8): the resize with a uint8 [count,R,R,3] result (out_u8), an fp32 [3,R,R]
+// result per image (out_f32[i], ToTensor (+ Normalize where normalize[i])), or both
+int es_image_resize_impl(const char* who, const es_image_u8* imgs, int count, uint8_t* out_u8, float* const* out_f32,
+                         const int32_t* normalize, int R, void* workspace, size_t workspace_bytes, void* stream) {
+  if (check_images(who, imgs, count, R)) return -1;
+  if (!out_u8 && !out_f32) return fail(who, "null pointer (out)");
+  if (es_plan_recording()) return fail(who, "a plan is recording on this thread; the byte-image calls are never part of a plan");
+  std::vector<ImgDesc> ds((size_t)count);
+  size_t need = 0;
+  for (int i = 0; i < count; ++i) {
+    plan_image(imgs[i], R, ds[i]);
+    ds[i].tmp = (uint8_t*)workspace + need;
+    need += tmp_bytes(ds[i], R);
+    if (out_u8) ds[i].out = out_u8 + (size_t)i * 3 * R * R;
+    if (out_f32) {
+      if (!out_f32[i]) return fail_img(who, i, "null pointer (fp32 output)");
+      ds[i].fout = out_f32[i];
+      ds[i].normalize = normalize ? normalize[i] != 0 : 0;
+    }
+  }
+  if (need && !workspace) return fail(who, "null pointer (workspace)");
+  if (workspace_bytes < need) {
+    snprintf(g_msg, sizeof(g_msg), "%s: workspace too small: %zu bytes given, %zu needed (es_image_resize_workspace_bytes)", who, workspace_bytes, need);
+    es_set_error(g_msg);
+    return -1;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const long long row3 = 3ll * R;
+  for (int first = 0; first < count; first += kImgPerLaunch) {
+    Batch b = {};
+    b.R = R;
+    const int n = count - first < kImgPerLaunch ? count - first : kImgPerLaunch;
+    long long hmax = 0;
+    for (int i = 0; i < n; ++i) {
+      b.d[i] = ds[first + i];
+      if (b.d[i].need_h && b.d[i].nrows * row3 > hmax) hmax = b.d[i].nrows * row3;
+    }
+    if (hmax) hipLaunchKernelGGL(resize_h_kernel, dim3((unsigned)((hmax + 255) / 256), n), dim3(256), 0, st, b);
+    hipLaunchKernelGGL(resize_v_kernel, dim3((unsigned)((R * row3 + 255) / 256), n), dim3(256), 0, st, b);
+  }
+  if (hipGetLastError() != hipSuccess) { fail(who, "launch failed"); return -2; }
+  return 0;
+}
+
+extern "C" int es_image_fit(int height, int width, int R, int32_t out[4]) {
+  if (!out) return fail("es_image_fit", "null pointer (out)");
+  if (height < 1 || width < 1) return fail("es_image_fit", "height or width < 1");
+  if (R < 1) return fail("es_image_fit", "R < 1");
+  fit(height, width, R, out);
+  return 0;
+}
+
+extern "C" int es_image_resize_coeffs(int in, int out, int32_t* xmin, int32_t* ntaps, int32_t* k, int cap) {
+  if (in < 1 || out < 1) return fail("es_image_resize_coeffs", "in or out < 1");
+  int most = 0;
+  for (int xx = 0; xx < out; ++xx) {
+    int x0;
+    const int n = resize_axis(in, out, xx, &x0, [&](int, int x, int kk) { if (k && x < cap) k[(size_t)xx * cap + x] = kk; });
+    if (xmin) xmin[xx] = x0;
+    if (ntaps) ntaps[xx] = n;
+    most = n > most ? n : most;
+  }
+  if (k && cap < most) return fail("es_image_resize_coeffs", "cap is smaller than the longest run of taps (ask with k = NULL first)");
+  return most;
+}
+
+extern "C" size_t es_image_resize_workspace_bytes(const es_image_u8* imgs, int count, int R) {
+  if (!imgs || count < 1 || R < 1) { fail("es_image_resize_workspace_bytes", "null pointer (imgs), count < 1 or R < 1"); return 0; }
+  size_t need = 0;
+  for (int i = 0; i < count; ++i) {
+    if (imgs[i].height < 1 || imgs[i].width < 1) { fail_img("es_image_resize_workspace_bytes", i, "height or width < 1"); return 0; }
+    ImgDesc d;
+    plan_image(imgs[i], R, d);
+    need += tmp_bytes(d, R);
+  }
+  return need;
+}
+
+extern "C" int es_image_resize_u8(const es_image_u8* imgs, int count, uint8_t* out, int R, void* workspace, size_t workspace_bytes,
+                                  void* stream) {
+  if (!out) return fail("es_image_resize_u8", "null pointer (out)");
+  return es_image_resize_impl("es_image_resize_u8", imgs, count, out, nullptr, nullptr, R, workspace, workspace_bytes, stream);
+}
+
+extern "C" int es_image_u8_to_f32(const uint8_t* in, float* out_nchw, int count, int H, int W, int normalize, void* stream) {
+  if (!in || !out_nchw) return fail("es_image_u8_to_f32", "null pointer");
+  if (count < 1) return fail("es_image_u8_to_f32", "count < 1");
+  if (H < 1 || W < 1) return fail("es_image_u8_to_f32", "height or width < 1");
+  if (es_plan_recording()) return fail("es_image_u8_to_f32", "a plan is recording on this thread; the byte-image calls are never part of a plan");
+  const long long HW = (long long)H * W, n = (long long)count * 3 * HW;
+  if ((n + 255) / 256 > 0x7fffffffll) return fail("es_image_u8_to_f32", "too many elements for one launch");
+  hipLaunchKernelGGL(u8_to_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, in, out_nchw, (long long)count, HW, normalize != 0);
+  if (hipGetLastError() != hipSuccess) { fail("es_image_u8_to_f32", "launch failed"); return -2; }
+  return 0;
+}
+
+extern "C" int es_image_f32_to_u8(const float* in_nchw, uint8_t* out_hwc, int B, int H, int W, void* stream) {
+  if (!in_nchw || !out_hwc) return fail("es_image_f32_to_u8", "null pointer");
+  if (B < 1) return fail("es_image_f32_to_u8", "count < 1 (B)");
+  if (H < 1 || W < 1) return fail("es_image_f32_to_u8", "height or width < 1");
+  if (es_plan_recording()) return fail("es_image_f32_to_u8", "a plan is recording on this thread; the byte-image calls are never part of a plan");
+  const long long HW = (long long)H * W, n = (long long)B * ((HW + 3) / 4);
+  if ((n + 255) / 256 > 0x7fffffffll) return fail("es_image_f32_to_u8", "too many elements for one launch");
+  const int vec = HW % 4 == 0 && (uintptr_t)in_nchw % 16 == 0 && (uintptr_t)out_hwc % 4 == 0;
+  hipLaunchKernelGGL(f32_to_u8_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, in_nchw, out_hwc, (long long)B, HW, vec);
+  if (hipGetLastError() != hipSuccess) { fail("es_image_f32_to_u8", "launch failed"); return -2; }
+  return 0;
+}

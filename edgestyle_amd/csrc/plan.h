@@ -45,3 +45,8 @@ struct es_ctx;
 int es_plan_relocate(es_plan* p, unsigned long long (*map)(unsigned long long addr, int use, void* user), void* user);
 void es_ctx_adopt_arena(es_ctx* c, void* arena, size_t bytes, bool on_host);
 void es_ctx_add_extent(es_ctx* c, unsigned long long off, unsigned long long bytes);   // persistent data inside the arena (es_ctx_save)
+
+// library-internal (image_io.hip): the byte-image resize with a uint8 [count,R,R,3] result (out_u8), an fp32 [3,R,R] result per
+// image (out_f32[i]: ToTensor, + Normalize(.5, .5) where normalize[i]), or both; `who` prefixes the error text
+int es_image_resize_impl(const char* who, const es_image_u8* imgs, int count, uint8_t* out_u8, float* const* out_f32,
+                         const int32_t* normalize, int R, void* workspace, size_t workspace_bytes, void* stream);

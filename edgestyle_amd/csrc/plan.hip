@@ -967,3 +967,64 @@ extern "C" int es_vae_decode(es_ctx* c, const float* latents, float* out_img, vo
   if ((rc = run(c, ES_PLAN_DECODE, (hipStream_t)stream, nullptr))) return rc;
   return d2d(out_img, c->buf[ES_BUF_IMAGE], c->bytes[ES_BUF_IMAGE], (hipStream_t)stream);
 }
+
+namespace {
+// the pixel size of an fp32 [B,3,H,W] image slot of a context whose latents are h x w: H = s * h, W = s * w (s = the VAE's scale)
+int slot_image_size(const es_ctx* c, int slot, int* H, int* W) {
+  const es_ctx_geometry& g = c->g;
+  const size_t per = (size_t)g.B * 3 * sizeof(float) * (size_t)g.h * g.w;
+  if (!c->buf[slot] || !per || c->bytes[slot] % per) return -1;
+  const size_t s2 = c->bytes[slot] / per;
+  for (size_t s = 1; s * s <= s2; ++s)
+    if (s * s == s2) { *H = (int)s * g.h; *W = (int)s * g.w; return 0; }
+  return -1;
+}
+}  // namespace
+
+// == es_prepare_conds from decoded photos: TT:29-48's Resize -> CenterCrop -> ToTensor (-> Normalize) on the device, straight into
+// the slots ES_PLAN_CONDS reads
+extern "C" int es_prepare_conds_u8(es_ctx* c, const es_image_u8* images, const int32_t* normalize, const float* const* noise,
+                                   void* workspace, size_t workspace_bytes, void* stream) {
+  if (!c || !images || !normalize) { es_set_error("es_prepare_conds_u8: null pointer (context, images or normalize)"); return -1; }
+  if (g_rec) { es_set_error("es_prepare_conds_u8: a plan is recording on this thread; the byte-image calls are never part of a plan"); return -1; }
+  if (can_launch(c, "es_prepare_conds_u8")) return -1;
+  if (!c->plan[ES_PLAN_CONDS]) { es_set_error("es_prepare_conds_u8: the context has no ES_PLAN_CONDS (built from pre-embedded conditions)"); return -1; }
+  const int nc = c->g.n_conds, B = c->g.B;
+  int H = 0, W = 0;
+  std::vector<float*> outs((size_t)nc * B);
+  std::vector<int32_t> norm((size_t)nc * B);
+  for (int i = 0; i < nc; ++i) {
+    int Hi, Wi;
+    if (slot_image_size(c, ES_BUF_COND_IMG0 + i, &Hi, &Wi)) { es_set_error("es_prepare_conds_u8: ES_BUF_COND_IMG not bound as fp32 [B,3,8h,8w]"); return -1; }
+    if (Hi != Wi) { es_set_error("es_prepare_conds_u8: the context's images are not square (8h != 8w); the reference's transform (Resize -> CenterCrop) is"); return -1; }
+    if (i && (Hi != H)) { es_set_error("es_prepare_conds_u8: the ES_BUF_COND_IMG slots differ in size"); return -1; }
+    H = Hi; W = Wi;
+    if (c->buf[ES_BUF_COND_NOISE0 + i] && (!noise || !noise[i])) { es_set_error("es_prepare_conds_u8: a VAE-conditioned net needs its latent sampling noise"); return -1; }
+    for (int b = 0; b < B; ++b) {
+      outs[(size_t)i * B + b] = (float*)c->buf[ES_BUF_COND_IMG0 + i] + (size_t)b * 3 * H * W;
+      norm[(size_t)i * B + b] = normalize[i];
+    }
+  }
+  hipStream_t st = (hipStream_t)stream;
+  int rc;
+  if ((rc = es_image_resize_impl("es_prepare_conds_u8", images, nc * B, nullptr, outs.data(), norm.data(), H, workspace, workspace_bytes, stream))) return rc;
+  for (int i = 0; i < nc; ++i)
+    if (c->buf[ES_BUF_COND_NOISE0 + i] && (rc = d2d(c->buf[ES_BUF_COND_NOISE0 + i], noise[i], c->bytes[ES_BUF_COND_NOISE0 + i], st))) return rc;
+  return run(c, ES_PLAN_CONDS, st, nullptr);
+}
+
+// == es_vae_decode + the rounding of image_processor.postprocess(output_type "pil") (PL:570-572) on the device:
+// latents fp32 [B,h,w,L] NHWC -> uint8 [B,8h,8w,3]
+extern "C" int es_vae_decode_u8(es_ctx* c, const float* latents, uint8_t* out_hwc, void* stream) {
+  if (!c || !latents || !out_hwc) { es_set_error("es_vae_decode_u8: null pointer"); return -1; }
+  if (g_rec) { es_set_error("es_vae_decode_u8: a plan is recording on this thread; the byte-image calls are never part of a plan"); return -1; }
+  if (can_launch(c, "es_vae_decode_u8")) return -1;
+  if (need(c, ES_BUF_SAMPLE, "es_vae_decode_u8: ES_BUF_SAMPLE not bound") || need(c, ES_BUF_IMAGE, "es_vae_decode_u8: ES_BUF_IMAGE not bound")) return -1;
+  int H, W;
+  if (slot_image_size(c, ES_BUF_IMAGE, &H, &W)) { es_set_error("es_vae_decode_u8: ES_BUF_IMAGE is not bound as fp32 [B,3,8h,8w]"); return -1; }
+  const es_ctx_geometry& g = c->g;
+  int rc;
+  if ((rc = es_latents_to_input(latents, c->buf[ES_BUF_SAMPLE], g.B, g.h * g.w, g.latent_channels, g.latent_pad, g.cfg, g.dtype, stream))) return rc;
+  if ((rc = run(c, ES_PLAN_DECODE, (hipStream_t)stream, nullptr))) return rc;
+  return es_image_f32_to_u8((const float*)c->buf[ES_BUF_IMAGE], out_hwc, g.B, H, W, stream);
+}

@@ -109,6 +109,10 @@ class FusionDesc(C.Structure):
     ]
 
 
+class ImageU8(C.Structure):         # es_image_u8
+    _fields_ = [("data", C.c_void_p), ("height", C.c_int32), ("width", C.c_int32), ("channels", C.c_int32), ("row_stride", C.c_int64)]
+
+
 class Tensor(C.Structure):          # es_tensor
     _fields_ = [("key", C.c_char_p), ("data", C.c_void_p), ("shape", C.c_int64 * 4), ("ndim", C.c_int32), ("dtype", C.c_int32)]
 
@@ -246,6 +250,14 @@ SYMBOLS = {
     "es_conv_gemm8p_form_ok": (C.c_int, [_I, _I, _I, C.c_longlong, _I]),
     "es_ctx_graph_hazard": (C.c_int, []),
     "es_plan_set_dry": (C.c_int, [_I]),
+    "es_image_fit": (C.c_int, [_I, _I, _I, C.POINTER(C.c_int32)]),
+    "es_image_resize_coeffs": (C.c_int, [_I, _I, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _I]),
+    "es_image_resize_workspace_bytes": (C.c_size_t, [C.POINTER(ImageU8), _I, _I]),
+    "es_image_resize_u8": (C.c_int, [C.POINTER(ImageU8), _I, _P, _I, _P, C.c_size_t, _P]),
+    "es_image_u8_to_f32": (C.c_int, [_P, _P, _I, _I, _I, _I, _P]),
+    "es_image_f32_to_u8": (C.c_int, [_P, _P, _I, _I, _I, _P]),
+    "es_prepare_conds_u8": (C.c_int, [_P, C.POINTER(ImageU8), C.POINTER(C.c_int32), C.POINTER(_P), _P, C.c_size_t, _P]),
+    "es_vae_decode_u8": (C.c_int, [_P, _P, _P, _P]),
 }
 
 _lib = None

@@ -28,6 +28,25 @@ def _p(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def _prepare_conds_u8(self, images, normalize, noise, nn: int, B: int, R: int, device):
+    """es_prepare_conds_u8 for either context class: images is nn x B uint8 HWC device tensors (net-major: a flat list, or one
+    list per net; any sizes), normalize one flag per net, noise per net None or device fp32 [N,L,h,w]."""
+    if len(images) == nn and not torch.is_tensor(images[0]):
+        images = [im for per_net in images for im in per_net]
+    if len(images) != nn * B:
+        raise EdgeStyleHipError(f"prepare_conds_u8: {nn} nets x batch {B} = {nn * B} images, got {len(images)}")
+    if len(normalize) != nn:
+        raise EdgeStyleHipError(f"prepare_conds_u8: one normalize flag per net ({nn}), got {len(normalize)}")
+    descs = ops.image_descriptors(images, "prepare_conds_u8")
+    need = ops.image_resize_workspace_bytes(descs, R)
+    ws = torch.empty((max(need, 1),), dtype=torch.uint8, device=device)
+    nz = [None if (noise is None or noise[i] is None) else noise[i].to(device, torch.float32).contiguous() for i in range(nn)]
+    npz = (C.c_void_p * nn)(*[None if z is None else z.data_ptr() for z in nz])
+    nrm = (C.c_int32 * nn)(*[1 if f else 0 for f in normalize])
+    L.check(self.lib.es_prepare_conds_u8(self.ctx, descs, nrm, npz, _p(ws), ws.numel(), self._stream()), "es_prepare_conds_u8")
+    self._live = (list(images), nz, ws)       # asynchronous: keep the sources and the scratch until the next call
+
+
 class NativeEngine:
     def __init__(self, pipe, batch_size: int = 1, guidance: bool = True, num_inference_steps: int = 50,
                  height: Optional[int] = None, width: Optional[int] = None, use_graphs: bool = True,
@@ -297,10 +316,25 @@ class NativeEngine:
         L.check(self.lib.es_prepare_conds(self.ctx, ip, npz, self._stream()), "es_prepare_conds")
         self._live = (imgs, nz)               # the copies are asynchronous: keep the sources until the next call
 
+    def prepare_conds_u8(self, images, normalize: Sequence[bool], noise: Optional[Sequence[Optional[torch.Tensor]]] = None):
+        """prepare_conds from decoded photos: n x B uint8 HWC device tensors of any sizes (net-major), resized, cropped and
+        converted on the device (TT:29-48); normalize[i]: net i takes [-1,1] (the VAE-conditioned nets)."""
+        if L.PLAN_CONDS not in self.plan_sizes:
+            raise EdgeStyleHipError("this context was built without ES_PLAN_CONDS")
+        _prepare_conds_u8(self, images, normalize, noise, self.nn, self.B, self.cond_img[0].shape[-1], self.pipe.device)
+
     def vae_decode(self, latents: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         if out is None:
             out = torch.empty_like(self.image)
         L.check(self.lib.es_vae_decode(self.ctx, _p(latents), _p(out), self._stream()), "es_vae_decode")
+        return out
+
+    def vae_decode_u8(self, latents: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """vae_decode with the bytes of output_type "pil" as the result: uint8 [B,H,W,3] on the device."""
+        if out is None:
+            B, _, H, W = self.image.shape
+            out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=self.image.device)
+        L.check(self.lib.es_vae_decode_u8(self.ctx, _p(latents), _p(out), self._stream()), "es_vae_decode_u8")
         return out
 
     # -- context image: everything es_ctx_load needs to run this context without Python ---------------------------------
@@ -622,6 +656,19 @@ class NativeContext:
             s = self.vcfg.scale
             out = torch.empty((self.B, 3, self.h * s, self.w * s), dtype=torch.float32, device=latents.device)
         L.check(self.lib.es_vae_decode(self.ctx, _p(latents), _p(out), self._stream()), "es_vae_decode")
+        return out
+
+    def prepare_conds_u8(self, images, normalize, noise=None):
+        """images: 6 x B uint8 HWC device tensors of any sizes (net-major); normalize: one flag per slot (the VAE-conditioned
+        nets take [-1,1], TT:29-48); noise as in prepare_conds"""
+        dev = images[0][0].device if not torch.is_tensor(images[0]) else images[0].device
+        _prepare_conds_u8(self, images, normalize, noise, self.nn, self.B, self.h * self.vcfg.scale, dev)
+
+    def vae_decode_u8(self, latents, out=None):
+        if out is None:
+            s = self.vcfg.scale
+            out = torch.empty((self.B, self.h * s, self.w * s, 3), dtype=torch.uint8, device=latents.device)
+        L.check(self.lib.es_vae_decode_u8(self.ctx, _p(latents), _p(out), self._stream()), "es_vae_decode_u8")
         return out
 
     def close(self):

@@ -1243,3 +1243,97 @@ def pack_fusion_params(sd: dict, prefix: str, dtype, device) -> dict:
         "b3": sd[f"{prefix}.third_conv.bias"].float().contiguous(),
     }
     return {k: v.to(device) for k, v in p.items()}
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# byte images (csrc/image_io.hip): Pillow-exact resize + centre crop, bytes -> network input, network output -> bytes
+# ----------------------------------------------------------------------------------------------------------------
+def image_descriptors(images: Sequence[torch.Tensor], what: str = "image_resize_u8"):
+    """uint8 HWC device tensors ([H,W,3|4]; rows may be pitched: stride(0) >= W * channels bytes) -> an es_image_u8 array.
+    The library gets data_ptr(), height, width, channels and the row stride: whatever it would read differently from what the
+    tensors hold is refused here."""
+    def bad(msg):
+        return L.EdgeStyleHipError(f"{what}: {msg}")
+    if len(images) < 1:
+        raise bad("no images")
+    arr = (L.ImageU8 * len(images))()
+    dev = images[0].device
+    for i, t in enumerate(images):
+        if not torch.is_tensor(t) or t.dtype != torch.uint8:
+            raise bad(f"image {i} must be a uint8 tensor")
+        if not t.is_cuda or t.device != dev:
+            raise bad(f"image {i} is on {t.device}: all images must be on one GPU")
+        if t.dim() != 3 or t.shape[2] not in (3, 4) or t.shape[0] < 1 or t.shape[1] < 1:
+            raise bad(f"image {i} must be [H, W, 3 | 4] (HWC), got {tuple(t.shape)}")
+        H, W, ch = t.shape
+        if t.stride(2) != 1 or t.stride(1) != ch or (H > 1 and t.stride(0) < W * ch):
+            raise bad(f"image {i}: pixels must be dense and the row stride at least width * channels (strides {t.stride()})")
+        arr[i].data, arr[i].height, arr[i].width, arr[i].channels = t.data_ptr(), H, W, ch
+        arr[i].row_stride = t.stride(0) if H > 1 else W * ch
+    return arr
+
+
+def image_resize_workspace_bytes(descs, R: int) -> int:
+    return int(L.load().es_image_resize_workspace_bytes(descs, len(descs), int(R)))
+
+
+def image_resize_u8(images: Sequence[torch.Tensor], R: int, out: Optional[torch.Tensor] = None,
+                    workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """torchvision Resize(R, BILINEAR) on a PIL image -> CenterCrop(R) for a list of uint8 HWC device tensors of any sizes,
+    as ONE call: -> uint8 [count, R, R, 3], byte for byte Pillow's pixels (TT:29-48)."""
+    def bad(msg):
+        return L.EdgeStyleHipError("image_resize_u8: " + msg)
+    if int(R) < 1:
+        raise bad("R < 1")
+    R = int(R)
+    descs = image_descriptors(images)
+    n, dev = len(images), images[0].device
+    if out is None:
+        out = torch.empty((n, R, R, 3), dtype=torch.uint8, device=dev)
+    elif out.dtype != torch.uint8 or out.device != dev or tuple(out.shape) != (n, R, R, 3) or not out.is_contiguous():
+        raise bad(f"out must be a contiguous uint8 [{n}, {R}, {R}, 3] tensor on {dev}")
+    need = image_resize_workspace_bytes(descs, R)
+    if workspace is None:
+        workspace = torch.empty((max(need, 1),), dtype=torch.uint8, device=dev)
+    elif workspace.dtype != torch.uint8 or workspace.device != dev or not workspace.is_contiguous() or workspace.numel() < need:
+        raise bad(f"workspace must be a contiguous uint8 tensor of at least {need} bytes on {dev}")
+    L.check(L.load().es_image_resize_u8(descs, n, _ptr(out), R, _ptr(workspace), workspace.numel(), _stream()), "es_image_resize_u8")
+    return out
+
+
+def image_u8_to_f32(x: torch.Tensor, normalize: bool, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ToTensor (+ Normalize(.5, .5)): uint8 HWC [count,H,W,3] -> fp32 NCHW [count,3,H,W] in [0,1] ([-1,1] if normalize)."""
+    def bad(msg):
+        return L.EdgeStyleHipError("image_u8_to_f32: " + msg)
+    if x.dtype != torch.uint8 or not x.is_cuda:
+        raise bad(f"x must be a uint8 device tensor, not {x.dtype} on {x.device}")
+    if x.dim() != 4 or x.shape[3] != 3 or min(x.shape) < 1:
+        raise bad(f"x must be [count, H, W, 3], got {tuple(x.shape)}")
+    if not x.is_contiguous():
+        raise bad("x must be dense")
+    n, H, W, _ = x.shape
+    if out is None:
+        out = torch.empty((n, 3, H, W), dtype=torch.float32, device=x.device)
+    elif out.dtype != torch.float32 or out.device != x.device or tuple(out.shape) != (n, 3, H, W) or not out.is_contiguous():
+        raise bad(f"out must be a contiguous fp32 [{n}, 3, {H}, {W}] tensor on {x.device}")
+    L.check(L.load().es_image_u8_to_f32(_ptr(x), _ptr(out), n, H, W, 1 if normalize else 0, _stream()), "es_image_u8_to_f32")
+    return out
+
+
+def image_f32_to_u8(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp32 NCHW [B,3,H,W] in [0,1] -> uint8 HWC [B,H,W,3] = (x * 255).round() clamped to 0..255 (PL:570-572's "pil" rounding)."""
+    def bad(msg):
+        return L.EdgeStyleHipError("image_f32_to_u8: " + msg)
+    if x.dtype != torch.float32 or not x.is_cuda:
+        raise bad(f"x must be an fp32 device tensor, not {x.dtype} on {x.device}")
+    if x.dim() != 4 or x.shape[1] != 3 or min(x.shape) < 1:
+        raise bad(f"x must be [B, 3, H, W], got {tuple(x.shape)}")
+    if not x.is_contiguous():
+        raise bad("x must be dense")
+    B, _, H, W = x.shape
+    if out is None:
+        out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=x.device)
+    elif out.dtype != torch.uint8 or out.device != x.device or tuple(out.shape) != (B, H, W, 3) or not out.is_contiguous():
+        raise bad(f"out must be a contiguous uint8 [{B}, {H}, {W}, 3] tensor on {x.device}")
+    L.check(L.load().es_image_f32_to_u8(_ptr(x), _ptr(out), B, H, W, _stream()), "es_image_f32_to_u8")
+    return out

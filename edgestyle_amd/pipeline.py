@@ -107,6 +107,8 @@ class _Loop:
         self.prep_graph = None           # text K/V projections + condition slots + time table, captured like the step
         self.decode_graph = None         # VAE decode + [0,1] post-process
         self.image = None                # the decode graph's output buffer
+        self.decode_graph_u8 = None      # output_type "u8": the same decode + the float -> byte rounding, one graph
+        self.image_u8 = None
         self.ts_dev = None               # fp32 [T] timesteps the time table is built from
         self.sig = None
         self.captures = 0                # how often this loop's graph was (re)captured (tests)
@@ -310,6 +312,49 @@ class StableDiffusionControlNetPipeline:
         else:
             emb = image                                                 # already embedded [N,C0,h,w]
         return _as_nhwc(emb, self.dtype, self.device)
+
+    def preprocess_images(self, images, resolution: Optional[int] = None, normalize=None) -> List[torch.Tensor]:
+        """Decoded photos -> the tensors `image=` takes, on the device: TT:29-48's Resize(resolution, BILINEAR) on a PIL image
+        -> CenterCrop(resolution) -> ToTensor (-> Normalize(.5, .5)), byte for byte Pillow's pixels (csrc/image_io.hip).
+        images: uint8 HWC tensors, numpy arrays or PIL images of any sizes; -> one fp32 [1,3,R,R] device tensor each.
+        normalize: one flag per image, one for all, or None = per net "is VAE-conditioned" (those take [-1,1], the pose nets
+        [0,1]; needs one image per net); resolution: None = 8 x the UNet's sample size."""
+        from .models import ControlLoRAModel
+        if self.device.type != "cuda":
+            raise EdgeStyleHipError("preprocess_images runs only on an MI355X: call .to('cuda') first")
+        images = list(images)
+        if normalize is None:
+            nets = self._nets
+            if len(images) != len(nets):
+                raise ValueError(f"normalize=None takes one image per ControlNet ({len(nets)}), got {len(images)}")
+            normalize = [isinstance(net, ControlLoRAModel) and bool(net.config.uses_vae) for net in nets]
+        elif isinstance(normalize, (bool, int)):
+            normalize = [bool(normalize)] * len(images)
+        if len(normalize) != len(images):
+            raise ValueError("`normalize` must have one entry per image")
+        R = int(resolution) if resolution is not None else self.vae_scale_factor * self.unet.cfg.sample_size
+        dev_imgs = []
+        for img in images:
+            if not torch.is_tensor(img):
+                if hasattr(img, "convert"):
+                    img = img.convert("RGB")             # PIL
+                arr = np.asarray(img)
+                if arr.dtype != np.uint8:
+                    raise ValueError(f"preprocess_images takes uint8 pixels, got {arr.dtype}")
+                if not arr.flags.writeable or not arr.flags.c_contiguous:
+                    arr = np.array(arr, order="C")       # PIL hands out a read-only view
+                img = torch.from_numpy(arr)
+            dev_imgs.append(img.to(self.device))
+        u8 = ops.image_resize_u8(dev_imgs, R)
+        out = [None] * len(images)
+        for flag in (False, True):
+            idx = [i for i, f in enumerate(normalize) if bool(f) == flag]
+            if idx:
+                sel = u8 if len(idx) == len(images) else u8[torch.tensor(idx, device=self.device)]
+                x = ops.image_u8_to_f32(sel.contiguous(), flag)
+                for k, i in enumerate(idx):
+                    out[i] = x[k:k + 1]
+        return out
 
     def prepare_images(self, images, batch_size, do_cfg, cond_noise=None, generator=None, num_images_per_prompt: int = 1):
         """The six one-time condition embeddings (PL:352-377, 629-664) with the redundant work removed: the reference
@@ -617,7 +662,7 @@ class StableDiffusionControlNetPipeline:
                 gp = torch.cuda.CUDAGraph()           # the per-call preparation replays from the next call on
                 with torch.cuda.graph(gp):
                     prep()
-                loop.prep_graph, loop.decode_graph = gp, None
+                loop.prep_graph, loop.decode_graph, loop.decode_graph_u8 = gp, None, None
                 loop.loop_graph = None
                 loop.sig = loop.signature()
                 loop.captures += 1
@@ -649,7 +694,23 @@ class StableDiffusionControlNetPipeline:
             def decode():
                 dec = self.vae.decode_nhwc(loop.model_in[:B], unscaled_latents=True)
                 return ops.nhwc_to_nchw(dec, channels=3, scale=0.5, shift=0.5, clamp01=True)
-            if graphs:
+            if output_type == "u8":
+                # the bytes of output_type "pil" without the trip through host floats: rounded on the device, inside the decode graph
+                def decode_u8():
+                    return ops.image_f32_to_u8(decode())
+                if graphs:
+                    if loop.decode_graph_u8 is None:
+                        decode_u8()
+                        torch.cuda.synchronize()
+                        gd = torch.cuda.CUDAGraph()
+                        with torch.cuda.graph(gd):
+                            loop.image_u8 = decode_u8()
+                        loop.decode_graph_u8 = gd
+                    loop.decode_graph_u8.replay()
+                    img = loop.image_u8.clone()
+                else:
+                    img = decode_u8()
+            elif graphs:
                 if loop.decode_graph is None:
                     decode()                          # eager once: kernels warm, scratch sized outside the capture
                     torch.cuda.synchronize()
@@ -668,7 +729,7 @@ class StableDiffusionControlNetPipeline:
                     img = [Image.fromarray((a * 255).round().astype("uint8")) for a in arr]
                 else:
                     img = arr
-            elif output_type != "pt":
+            elif output_type not in ("pt", "u8"):
                 raise ValueError(f"unknown output_type {output_type}")
         mark("decode")
         if ev:

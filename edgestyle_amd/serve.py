@@ -26,7 +26,9 @@ import torch
 @dataclass
 class TryOnRequest:
     """One `try_on` call (app.py:151-182).  `images`: the six conditioning tensors [1,3,H,W] in the reference's order
-    (agnostic, subject pose, clothes 1, pose 1, clothes 2, pose 2; images in [-1,1], poses in [0,1], TT:29-48)."""
+    (agnostic, subject pose, clothes 1, pose 1, clothes 2, pose 2; images in [-1,1], poses in [0,1], TT:29-48) - or six decoded
+    photos of any sizes (uint8 HWC tensors, numpy arrays or PIL images): the worker turns those into the tensors with
+    `pipeline.preprocess_images` (resize, crop and conversion on the device) when it takes the request off the queue."""
     images: Sequence[torch.Tensor]
     prompt_embeds: torch.Tensor                 # [1,77,768]  (or pass `prompt` and let the pipeline's CLIP encode it)
     negative_prompt_embeds: torch.Tensor
@@ -62,7 +64,7 @@ class TryOnService:
 
     def __init__(self, pipeline: Callable[..., Any], max_batch: int = 8, max_wait_s: float = 0.02,
                  batch_sizes: Sequence[int] = (1, 2, 4, 8), latent_channels: int = 4, vae_scale: int = 8,
-                 cond_noise_fn: Optional[Callable[[int, List[int]], Any]] = None):
+                 cond_noise_fn: Optional[Callable[[int, List[int]], Any]] = None, output_u8: bool = False):
         if max_batch < 1 or not batch_sizes or min(batch_sizes) != 1:
             raise ValueError("max_batch >= 1 and batch_sizes must contain 1")
         self.pipeline = pipeline
@@ -71,6 +73,7 @@ class TryOnService:
         self.batch_sizes = sorted(b for b in set(batch_sizes) if b <= max_batch)
         self.latent_channels, self.vae_scale = latent_channels, vae_scale
         self.cond_noise_fn = cond_noise_fn
+        self.output_u8 = bool(output_u8)         # ask the pipeline for output_type "u8": uint8 [B,H,W,3] device tensors
         self._q: "queue.Queue[Optional[TryOnRequest]]" = queue.Queue()
         self._pending: List[TryOnRequest] = []
         self._stop = threading.Event()
@@ -99,6 +102,22 @@ class TryOnService:
             self._worker.join()
 
     # ------------------------------------------------------------------ worker side
+    @staticmethod
+    def _is_prepared(img) -> bool:
+        return torch.is_tensor(img) and img.is_floating_point() and img.dim() == 4
+
+    def _admit(self, r: TryOnRequest) -> bool:
+        """A request that carries decoded photos gets its tensors here, BEFORE its key() is looked at, so that photos of
+        different sizes batch like tensors of one size.  A request whose images cannot be prepared fails alone."""
+        if all(self._is_prepared(i) for i in r.images):
+            return True
+        try:
+            r.images = self.pipeline.preprocess_images(list(r.images))
+            return True
+        except Exception as e:
+            r.future.set_exception(e)
+            return False
+
     def _take_batch(self) -> List[TryOnRequest]:
         """Oldest request first; everything compatible with it that is already queued or arrives within max_wait_s
         of the moment it reached the head of the line joins its batch (up to max_batch), the rest keeps its order."""
@@ -106,7 +125,8 @@ class TryOnService:
             r = self._q.get()
             if r is None:
                 return []
-            self._pending.append(r)
+            if self._admit(r):
+                self._pending.append(r)
         head = self._pending[0]
         deadline = time.perf_counter() + self.max_wait_s
 
@@ -121,7 +141,8 @@ class TryOnService:
             if r is None:
                 self._stop.set()
                 break
-            self._pending.append(r)
+            if self._admit(r):
+                self._pending.append(r)
         batch = compatible()[: self.max_batch]
         n = max(b for b in self.batch_sizes if b <= len(batch))
         batch = batch[:n]
@@ -139,7 +160,7 @@ class TryOnService:
             image=[torch.cat([r.images[k] for r in batch], 0) for k in range(6)],
             latents=lat, guidance_scale=r0.guidance_scale, num_inference_steps=r0.num_inference_steps,
             control_guidance_start=r0.control_guidance_start, control_guidance_end=r0.control_guidance_end,
-            output_type="pt")
+            output_type="u8" if self.output_u8 else "pt")
         if self.cond_noise_fn is not None:       # per-request VAE-condition sampling noise (CL:38-42), keyed by seed
             kwargs["cond_noise"] = self.cond_noise_fn(len(batch), [r.seed for r in batch])
         return self.pipeline(**kwargs).images

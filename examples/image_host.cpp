@@ -1,0 +1,131 @@
+// The try-on path from decoded photos to bytes, in plain C++ against the C ABI (include/edgestyle_hip.h) and the HIP runtime: no
+// Python, no torch, no model code, and no float image ever crosses the bus.  It loads a context image (es_ctx_save /
+// edgestyle_amd/native.py NativeEngine.save), uploads six binary PPM files of ANY size, has the library resize, crop and convert
+// them on the device exactly as the reference's transforms would (test_text2image_pretrained_openpose.py:29-48), runs the
+// 6-ControlNet denoising loop and the VAE decode, and writes the result as a PPM.
+//
+//   hipcc -O2 -Iinclude examples/image_host.cpp -Ledgestyle_amd/lib -ledgestyle_hip -Wl,-rpath,$PWD/edgestyle_amd/lib -o image_host
+//   ./image_host ctx.esctx cond0.ppm cond1.ppm cond2.ppm cond3.ppm cond4.ppm cond5.ppm inputs.bin out.ppm
+//
+// cond<i>.ppm: binary PPM (P6, maxval 255), the condition image of net i in the reference's order (agnostic, subject pose,
+// clothes 1, pose 1, clothes 2, pose 2); a context of batch B > 1 takes the same six photos for every image of the batch.
+// inputs.bin (little endian, written by tests/test_image_io_gpu.py):
+//   int32 B, h, w, L, D, n_conds, n_steps, has_noise[n_conds], normalize[n_conds]; float guidance_scale; float timesteps[n_steps];
+//   float latents[B*h*w*L] (NHWC); uint16 ehs[2B*77*D] (fp16 bits, negative prompt rows first);
+//   per net with has_noise: float noise[2B*L*h*w]      (the library has no RNG: latents and sampling noise are the caller's)
+// out.ppm: image 0 of the batch, 8h x 8w
+//
+// What each call replaces in the reference: es_prepare_conds_u8 = the transforms of TT:29-48 + prepare_image + preprocess_image
+// (PL:629-664, CL:289-290), es_denoise_loop = the loop of PL:435-543, es_vae_decode_u8 = PL:552-572 with output_type "pil".
+#include <hip/hip_runtime.h>
+#include <cstdint>
+#include <cstdio>
+#include <vector>
+
+#include "edgestyle_hip.h"
+
+#define HIP_OK(x) do { if ((x) != hipSuccess) { fprintf(stderr, "HIP error at %s:%d\n", __FILE__, __LINE__); return 2; } } while (0)
+#define ES_OK(x) do { if ((x) != 0) { fprintf(stderr, "%s: %s\n", #x, es_last_error()); return 3; } } while (0)
+
+template <typename T>
+static bool rd(FILE* f, std::vector<T>& v, size_t n) { v.resize(n); return fread(v.data(), sizeof(T), n, f) == n; }
+
+// one header token of a PPM: digits (or the magic) after whitespace and # comments
+static bool ppm_int(FILE* f, int* v) {
+  int c = fgetc(f);
+  while (c == ' ' || c == '\t' || c == '\n' || c == '\r' || c == '#') {
+    if (c == '#') while (c != '\n' && c != EOF) c = fgetc(f);
+    c = fgetc(f);
+  }
+  if (c < '0' || c > '9') return false;
+  long n = 0;
+  while (c >= '0' && c <= '9') { n = n * 10 + (c - '0'); if (n > (1 << 24)) return false; c = fgetc(f); }
+  *v = (int)n;
+  return c == ' ' || c == '\t' || c == '\n' || c == '\r';      // exactly one whitespace byte ends the header
+}
+static bool read_ppm(const char* path, std::vector<uint8_t>& px, int* H, int* W) {
+  FILE* f = fopen(path, "rb");
+  if (!f) { perror(path); return false; }
+  int maxval = 0;
+  const bool ok = fgetc(f) == 'P' && fgetc(f) == '6' && ppm_int(f, W) && ppm_int(f, H) && ppm_int(f, &maxval) && maxval == 255 &&
+                  *H > 0 && *W > 0 && rd(f, px, (size_t)*H * *W * 3);
+  fclose(f);
+  if (!ok) fprintf(stderr, "%s: not a binary PPM (P6, maxval 255)\n", path);
+  return ok;
+}
+
+int main(int argc, char** argv) {
+  if (argc != 10) { fprintf(stderr, "usage: %s ctx.esctx cond0.ppm .. cond5.ppm inputs.bin out.ppm\n", argv[0]); return 1; }
+  FILE* f = fopen(argv[8], "rb");
+  if (!f) { perror(argv[8]); return 1; }
+  int32_t hd[7];
+  if (fread(hd, 4, 7, f) != 7) return 1;
+  const int B = hd[0], h = hd[1], w = hd[2], L = hd[3], D = hd[4], nc = hd[5], T = hd[6];
+  if (nc != 6 || B < 1) { fprintf(stderr, "this host feeds six condition images\n"); return 1; }
+  std::vector<int32_t> has_noise, normalize;
+  float gs;
+  std::vector<float> ts, lat;
+  std::vector<uint16_t> ehs;
+  if (!rd(f, has_noise, nc) || !rd(f, normalize, nc) || fread(&gs, 4, 1, f) != 1 || !rd(f, ts, T) || !rd(f, lat, (size_t)B * h * w * L) ||
+      !rd(f, ehs, (size_t)2 * B * 77 * D)) return 1;
+  const size_t noise_n = (size_t)2 * B * L * h * w;
+
+  es_ctx* ctx = nullptr;
+  ES_OK(es_ctx_load(argv[1], 0, &ctx));
+
+  std::vector<const float*> d_noise(nc, nullptr);
+  std::vector<float> tmp;
+  for (int i = 0; i < nc; ++i)
+    if (has_noise[i]) {
+      float* p = nullptr;
+      if (!rd(f, tmp, noise_n)) return 1;
+      HIP_OK(hipMalloc(&p, noise_n * 4));
+      HIP_OK(hipMemcpy(p, tmp.data(), noise_n * 4, hipMemcpyHostToDevice));
+      d_noise[i] = p;
+    }
+  fclose(f);
+
+  // the photos: bytes up, as they are (any size, dense rows)
+  std::vector<es_image_u8> imgs((size_t)nc * B);
+  std::vector<uint8_t> px;
+  for (int i = 0; i < nc; ++i) {
+    int H = 0, W = 0;
+    if (!read_ppm(argv[2 + i], px, &H, &W)) return 1;
+    uint8_t* p = nullptr;
+    HIP_OK(hipMalloc(&p, px.size()));
+    HIP_OK(hipMemcpy(p, px.data(), px.size(), hipMemcpyHostToDevice));
+    for (int b = 0; b < B; ++b) imgs[(size_t)i * B + b] = es_image_u8{p, H, W, 3, (int64_t)W * 3};
+  }
+  const int R = 8 * h;
+  const size_t ws_bytes = es_image_resize_workspace_bytes(imgs.data(), nc * B, R);
+  void* d_ws = nullptr;
+  HIP_OK(hipMalloc(&d_ws, ws_bytes ? ws_bytes : 1));
+
+  float* d_lat = nullptr;
+  void* d_ehs = nullptr;
+  uint8_t* d_out = nullptr;
+  const size_t out_n = (size_t)B * 8 * h * 8 * w * 3;
+  HIP_OK(hipMalloc(&d_lat, lat.size() * 4));
+  HIP_OK(hipMemcpy(d_lat, lat.data(), lat.size() * 4, hipMemcpyHostToDevice));
+  HIP_OK(hipMalloc(&d_ehs, ehs.size() * 2));
+  HIP_OK(hipMemcpy(d_ehs, ehs.data(), ehs.size() * 2, hipMemcpyHostToDevice));
+  HIP_OK(hipMalloc(&d_out, out_n));
+
+  hipStream_t st;
+  HIP_OK(hipStreamCreate(&st));
+  ES_OK(es_prepare_conds_u8(ctx, imgs.data(), normalize.data(), d_noise.data(), d_ws, ws_bytes, st));
+  ES_OK(es_denoise_loop(ctx, d_lat, d_ehs, gs, ts.data(), T, st));
+  ES_OK(es_vae_decode_u8(ctx, d_lat, d_out, st));
+  HIP_OK(hipStreamSynchronize(st));
+
+  std::vector<uint8_t> out((size_t)8 * h * 8 * w * 3);
+  HIP_OK(hipMemcpy(out.data(), d_out, out.size(), hipMemcpyDeviceToHost));
+  FILE* o = fopen(argv[9], "wb");
+  if (!o) { perror(argv[9]); return 1; }
+  fprintf(o, "P6\n%d %d\n255\n", 8 * w, 8 * h);
+  fwrite(out.data(), 1, out.size(), o);
+  fclose(o);
+  es_ctx_destroy(ctx);
+  printf("ok\n");
+  return 0;
+}

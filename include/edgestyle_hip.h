@@ -617,6 +617,56 @@ int es_vae_decode(es_ctx* c, const float* latents, float* out_img, void* stream)
  * nets; results land in ES_BUF_COND0.. as [N,h,w,C0], ready for es_denoise_loop / es_ctx_launch_plan. */
 int es_prepare_conds(es_ctx* c, const float* const* images, const float* const* noise, void* stream);
 
+/* =========================================================================================================
+ * Byte images (csrc/image_io.hip): what a caller holds is a decoded photo - uint8, HWC, any size - and what it wants back is
+ * bytes.  Replaces, on the input side, the transforms the reference's callers apply to every condition image
+ * (test_text2image_pretrained_openpose.py:29-48): torchvision Resize(R, BILINEAR) on a PIL image -> CenterCrop(R) -> ToTensor
+ * (-> Normalize(.5, .5) for the VAE-conditioned nets); on the output side image_processor.postprocess(output_type "pil")'s
+ * (x * 255).round().astype(uint8) (model/edgestyle_pipeline.py:570-572).  The resize is Pillow's ImagingResample restated:
+ * horizontal pass, then vertical pass, a uint8 image after each, per-pixel weights derived in double and quantised to 22 bits,
+ * integer accumulation - the bytes EQUAL Pillow's.  A pass whose size does not change is skipped, as Pillow skips it.
+ * Output size and crop are torchvision's: the shorter side becomes R, the longer (int)(R * long / short); the crop starts at
+ * (int)rint((rh - R) / 2.0) (round half to even) and likewise for the columns.
+ * None of these calls is ever part of a plan: while a plan records on the calling thread they return -1.  No new
+ * ES_ABI_VERSION: no plan or context image records them.
+ * ========================================================================================================= */
+typedef struct {
+  const uint8_t* data;             /* DEVICE memory: height rows of row_stride bytes, `channels` bytes per pixel (R, G, B[, A]) */
+  int32_t height, width;
+  int32_t channels;                /* 3 | 4 (the fourth byte is ignored) */
+  int64_t row_stride;              /* bytes, >= width * channels */
+} es_image_u8;
+/* host-only: out = {rh, rw, top, left} - the size Resize(R) gives a height x width image and where CenterCrop(R) starts */
+int es_image_fit(int height, int width, int R, int32_t out[4]);
+/* host-only: the taps of one axis resampled from `in` to `out` pixels, computed by THE SAME code the kernels run (one
+ * __host__ __device__ function): output pixel i reads source pixels xmin[i] .. xmin[i] + ntaps[i] - 1 with the 22-bit fixed-point
+ * weights k[i * cap + 0 ..]; result = clip8(((1 << 21) + sum k * src) >> 22).  xmin / ntaps: [out] or NULL; k: [out][cap] or NULL.
+ * Returns the longest run of taps (ask with k = NULL to size cap), -1 on bad arguments or a cap smaller than that. */
+int es_image_resize_coeffs(int in, int out, int32_t* xmin, int32_t* ntaps, int32_t* k, int cap);
+/* host-only: bytes of device scratch es_image_resize_u8 / es_prepare_conds_u8 need for these images (the uint8 image between
+ * the two passes: the source rows the kept output rows read x the R kept columns, for every image whose width changes; may be
+ * 0).  Only height / width of the descriptors are read.  0 with es_last_error() set on bad arguments. */
+size_t es_image_resize_workspace_bytes(const es_image_u8* imgs, int count, int R);
+/* imgs: HOST array of `count` descriptors (images of different sizes in one call: two launches per 16 images);
+ * out: device uint8 [count, R, R, 3].  Asynchronous on `stream`, nothing is allocated: capturable. */
+int es_image_resize_u8(const es_image_u8* imgs, int count, uint8_t* out, int R, void* workspace, size_t workspace_bytes, void* stream);
+/* ToTensor (+ Normalize(.5, .5) if normalize): uint8 HWC [count,H,W,3] -> fp32 NCHW [count,3,H,W], y = x / 255.0f (correctly
+ * rounded), then y = (y - 0.5f) / 0.5f - bitwise what numpy / torch compute on the host for the same bytes */
+int es_image_u8_to_f32(const uint8_t* in, float* out_nchw, int count, int H, int W, int normalize, void* stream);
+/* fp32 NCHW [B,3,H,W] in [0,1] -> uint8 HWC [B,H,W,3]: b = (uint8) clamp(rintf(x * 255.0f), 0, 255), no fused multiply-add ahead
+ * of the rounding; four pixels per thread */
+int es_image_f32_to_u8(const float* in_nchw, uint8_t* out_hwc, int B, int H, int W, void* stream);
+/* es_prepare_conds from bytes: images[n_conds * B] (HOST array, net-major: image b of net i is images[i * B + b]) are resized,
+ * cropped and converted straight into the bound ES_BUF_COND_IMG* slots (format unchanged: fp32 NCHW [B,3,8h,8w]; normalize[i] != 0
+ * for the nets that take [-1,1], TT:29-48), the noise is copied and the unchanged ES_PLAN_CONDS runs, as in es_prepare_conds.
+ * workspace: es_image_resize_workspace_bytes(images, n_conds * B, 8h) bytes.  The reference's transform is square: a context with
+ * 8h != 8w is refused.  Capturable like es_prepare_conds. */
+int es_prepare_conds_u8(es_ctx* c, const es_image_u8* images, const int32_t* normalize, const float* const* noise,
+                        void* workspace, size_t workspace_bytes, void* stream);
+/* es_vae_decode to bytes: the unchanged decode plan into ES_BUF_IMAGE, then es_image_f32_to_u8 from there;
+ * out_hwc device uint8 [B,8h,8w,3].  Capturable like es_vae_decode. */
+int es_vae_decode_u8(es_ctx* c, const float* latents, uint8_t* out_hwc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
