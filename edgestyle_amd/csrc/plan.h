@@ -50,3 +50,6 @@ void es_ctx_add_extent(es_ctx* c, unsigned long long off, unsigned long long byt
 // image (out_f32[i]: ToTensor, + Normalize(.5, .5) where normalize[i]), or both; `who` prefixes the error text
 int es_image_resize_impl(const char* who, const es_image_u8* imgs, int count, uint8_t* out_u8, float* const* out_f32,
                          const int32_t* normalize, int R, void* workspace, size_t workspace_bytes, void* stream);
+
+// library-internal (rng.hip): es_randn with `who` prefixing the error text; *advance (may be null) = the offset increment of the draw
+int es_randn_impl(const char* who, float* out, const es_randn_desc* d, void* stream, unsigned long long* advance);

@@ -275,6 +275,7 @@ struct es_ctx {
   int loop_steps = 0;
   float loop_guidance = 0.f;
   float loop_window[2] = {0.f, 1.f};   // the control-guidance window the loop graph was captured for (it decides which steps are UNet-only)
+  bool noise_drawn[6] = {};            // es_ctx_draw_cond_noise filled ES_BUF_COND_NOISE0 + i: a NULL noise pointer keeps it (es_prepare_conds*)
 };
 
 namespace {
@@ -575,6 +576,7 @@ extern "C" int es_ctx_bind(es_ctx* c, int slot, void* dev, size_t nbytes) {
   if (!c || slot < 0 || slot >= ES_BUF_COUNT || !dev || !nbytes) { es_set_error("es_ctx_bind: bad arguments"); return -1; }
   c->buf[slot] = dev;
   c->bytes[slot] = nbytes;
+  if (slot >= ES_BUF_COND_NOISE0 && slot < ES_BUF_COND_NOISE0 + 6) c->noise_drawn[slot - ES_BUF_COND_NOISE0] = false;
   return 0;
 }
 extern "C" void* es_ctx_buffer(const es_ctx* c, int slot, size_t* bytes) {      // borrowed: the slot's device memory
@@ -948,8 +950,8 @@ extern "C" int es_prepare_conds(es_ctx* c, const float* const* images, const flo
     if (!images[i] || !c->buf[ES_BUF_COND_IMG0 + i]) { es_set_error("es_prepare_conds: condition image missing / ES_BUF_COND_IMG not bound"); return -1; }
     if ((rc = d2d(c->buf[ES_BUF_COND_IMG0 + i], images[i], c->bytes[ES_BUF_COND_IMG0 + i], st))) return rc;
     if (c->buf[ES_BUF_COND_NOISE0 + i]) {
-      if (!noise || !noise[i]) { es_set_error("es_prepare_conds: a VAE-conditioned net needs its latent sampling noise"); return -1; }
-      if ((rc = d2d(c->buf[ES_BUF_COND_NOISE0 + i], noise[i], c->bytes[ES_BUF_COND_NOISE0 + i], st))) return rc;
+      if (noise && noise[i]) { if ((rc = d2d(c->buf[ES_BUF_COND_NOISE0 + i], noise[i], c->bytes[ES_BUF_COND_NOISE0 + i], st))) return rc; }
+      else if (!c->noise_drawn[i]) { es_set_error("es_prepare_conds: a VAE-conditioned net needs its latent sampling noise (pass it, or draw it with es_ctx_draw_cond_noise)"); return -1; }
     }
   }
   return run(c, ES_PLAN_CONDS, st, nullptr);
@@ -999,7 +1001,7 @@ extern "C" int es_prepare_conds_u8(es_ctx* c, const es_image_u8* images, const i
     if (Hi != Wi) { es_set_error("es_prepare_conds_u8: the context's images are not square (8h != 8w); the reference's transform (Resize -> CenterCrop) is"); return -1; }
     if (i && (Hi != H)) { es_set_error("es_prepare_conds_u8: the ES_BUF_COND_IMG slots differ in size"); return -1; }
     H = Hi; W = Wi;
-    if (c->buf[ES_BUF_COND_NOISE0 + i] && (!noise || !noise[i])) { es_set_error("es_prepare_conds_u8: a VAE-conditioned net needs its latent sampling noise"); return -1; }
+    if (c->buf[ES_BUF_COND_NOISE0 + i] && (!noise || !noise[i]) && !c->noise_drawn[i]) { es_set_error("es_prepare_conds_u8: a VAE-conditioned net needs its latent sampling noise (pass it, or draw it with es_ctx_draw_cond_noise)"); return -1; }
     for (int b = 0; b < B; ++b) {
       outs[(size_t)i * B + b] = (float*)c->buf[ES_BUF_COND_IMG0 + i] + (size_t)b * 3 * H * W;
       norm[(size_t)i * B + b] = normalize[i];
@@ -1009,7 +1011,7 @@ extern "C" int es_prepare_conds_u8(es_ctx* c, const es_image_u8* images, const i
   int rc;
   if ((rc = es_image_resize_impl("es_prepare_conds_u8", images, nc * B, nullptr, outs.data(), norm.data(), H, workspace, workspace_bytes, stream))) return rc;
   for (int i = 0; i < nc; ++i)
-    if (c->buf[ES_BUF_COND_NOISE0 + i] && (rc = d2d(c->buf[ES_BUF_COND_NOISE0 + i], noise[i], c->bytes[ES_BUF_COND_NOISE0 + i], st))) return rc;
+    if (c->buf[ES_BUF_COND_NOISE0 + i] && noise && noise[i] && (rc = d2d(c->buf[ES_BUF_COND_NOISE0 + i], noise[i], c->bytes[ES_BUF_COND_NOISE0 + i], st))) return rc;
   return run(c, ES_PLAN_CONDS, st, nullptr);
 }
 
@@ -1027,4 +1029,51 @@ extern "C" int es_vae_decode_u8(es_ctx* c, const float* latents, uint8_t* out_hw
   if ((rc = es_latents_to_input(latents, c->buf[ES_BUF_SAMPLE], g.B, g.h * g.w, g.latent_channels, g.latent_pad, g.cfg, g.dtype, stream))) return rc;
   if ((rc = run(c, ES_PLAN_DECODE, (hipStream_t)stream, nullptr))) return rc;
   return es_image_f32_to_u8((const float*)c->buf[ES_BUF_IMAGE], out_hwc, g.B, H, W, stream);
+}
+
+// == prepare_latents (PL:585-627) with torch's device generator restated (rng.hip): randn_tensor([B,L,h,w], generator) * sigma,
+// written as the fp32 [B,h,w,L] es_denoise_loop takes; a list of generators draws [1,L,h,w] per image (randn_tensor's list case)
+extern "C" int es_ctx_draw_latents(es_ctx* c, es_philox* gens, int n_gens, float sigma, int round_dtype, float* latents_out, void* stream) {
+  if (!c || !gens || !latents_out) { es_set_error("es_ctx_draw_latents: null pointer (context, gens or latents_out)"); return -1; }
+  if (g_rec) { es_set_error("es_ctx_draw_latents: a plan is recording on this thread; the noise calls are never part of a plan"); return -1; }
+  const es_ctx_geometry& g = c->g;
+  if (g.B < 1 || g.h < 1 || g.w < 1 || g.latent_channels < 1) { es_set_error("es_ctx_draw_latents: the context has no geometry (es_ctx_set_geometry)"); return -1; }
+  if (n_gens != 1 && n_gens != g.B) { es_set_error("es_ctx_draw_latents: n_gens must be 1 or the context's batch size B"); return -1; }
+  const int per = n_gens == 1 ? g.B : 1;                 // images per draw
+  const int64_t HW = (int64_t)g.h * g.w, L = g.latent_channels;
+  for (int i = 0; i < n_gens; ++i)
+    if (gens[i].offset % 4) { es_set_error("es_ctx_draw_latents: a generator's offset is not a multiple of 4"); return -1; }
+  for (int i = 0; i < n_gens; ++i) {
+    es_randn_desc d = {};
+    d.seed = gens[i].seed; d.offset = gens[i].offset;
+    d.numel = per * L * HW;
+    d.scale = sigma; d.round_dtype = round_dtype;
+    d.N = per; d.C = L; d.HW = HW; d.Cstride = L;
+    unsigned long long adv = 0;
+    const int rc = es_randn_impl("es_ctx_draw_latents", latents_out + (size_t)i * per * HW * L, &d, stream, &adv);
+    if (rc) return rc;
+    gens[i].offset += adv;
+  }
+  return 0;
+}
+
+// == latent_dist.sample() of every VAE-conditioned net (CL:39: the device's default generator, one draw of [N,L,h,w] per net in net
+// order), straight into the slots ES_PLAN_CONDS reads
+extern "C" int es_ctx_draw_cond_noise(es_ctx* c, es_philox* gen, int round_dtype, void* stream) {
+  if (!c || !gen) { es_set_error("es_ctx_draw_cond_noise: null pointer (context or gen)"); return -1; }
+  if (g_rec) { es_set_error("es_ctx_draw_cond_noise: a plan is recording on this thread; the noise calls are never part of a plan"); return -1; }
+  if (can_launch(c, "es_ctx_draw_cond_noise")) return -1;
+  for (int i = 0; i < c->g.n_conds; ++i) {
+    if (!c->buf[ES_BUF_COND_NOISE0 + i]) continue;
+    es_randn_desc d = {};
+    d.seed = gen->seed; d.offset = gen->offset;
+    d.numel = (int64_t)(c->bytes[ES_BUF_COND_NOISE0 + i] / sizeof(float));
+    d.scale = 1.0f; d.round_dtype = round_dtype;
+    unsigned long long adv = 0;
+    const int rc = es_randn_impl("es_ctx_draw_cond_noise", (float*)c->buf[ES_BUF_COND_NOISE0 + i], &d, stream, &adv);
+    if (rc) return rc;
+    gen->offset += adv;
+    c->noise_drawn[i] = true;
+  }
+  return 0;
 }

@@ -113,6 +113,15 @@ class ImageU8(C.Structure):         # es_image_u8
     _fields_ = [("data", C.c_void_p), ("height", C.c_int32), ("width", C.c_int32), ("channels", C.c_int32), ("row_stride", C.c_int64)]
 
 
+class Philox(C.Structure):          # es_philox
+    _fields_ = [("seed", C.c_uint64), ("offset", C.c_uint64)]
+
+
+class RandnDesc(C.Structure):       # es_randn_desc
+    _fields_ = [("seed", C.c_uint64), ("offset", C.c_uint64), ("numel", C.c_int64), ("blocks", C.c_int32), ("scale", C.c_float),
+                ("round_dtype", C.c_int32), ("N", C.c_int64), ("C", C.c_int64), ("HW", C.c_int64), ("Cstride", C.c_int64)]
+
+
 class Tensor(C.Structure):          # es_tensor
     _fields_ = [("key", C.c_char_p), ("data", C.c_void_p), ("shape", C.c_int64 * 4), ("ndim", C.c_int32), ("dtype", C.c_int32)]
 
@@ -258,6 +267,14 @@ SYMBOLS = {
     "es_image_f32_to_u8": (C.c_int, [_P, _P, _I, _I, _I, _P]),
     "es_prepare_conds_u8": (C.c_int, [_P, C.POINTER(ImageU8), C.POINTER(C.c_int32), C.POINTER(_P), _P, C.c_size_t, _P]),
     "es_vae_decode_u8": (C.c_int, [_P, _P, _P, _P]),
+    "es_philox4x32_10": (C.c_int, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "es_philox_block_cap": (C.c_int, [_I]),
+    "es_philox_blocks": (C.c_int, [_L, _I]),
+    "es_philox_advance": (_L, [_L, _I]),
+    "es_randn": (C.c_int, [_P, C.POINTER(RandnDesc), _P]),
+    "es_randn_host": (C.c_int, [_P, C.POINTER(RandnDesc)]),
+    "es_ctx_draw_latents": (C.c_int, [_P, C.POINTER(Philox), _I, _F, _I, _P, _P]),
+    "es_ctx_draw_cond_noise": (C.c_int, [_P, C.POINTER(Philox), _I, _P]),
 }
 
 _lib = None

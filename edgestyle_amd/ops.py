@@ -1337,3 +1337,55 @@ def image_f32_to_u8(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torc
         raise bad(f"out must be a contiguous uint8 [{B}, {H}, {W}, 3] tensor on {x.device}")
     L.check(L.load().es_image_f32_to_u8(_ptr(x), _ptr(out), B, H, W, _stream()), "es_image_f32_to_u8")
     return out
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# seeded noise: torch's device Philox stream restated (csrc/rng.hip)
+_ROUND = {None: L.ES_F32, torch.float32: L.ES_F32, torch.float16: L.ES_F16, torch.bfloat16: L.ES_BF16}
+
+
+def philox_blocks(numel: int, device=None) -> int:
+    """The grid torch's generator kernel takes for a draw of `numel` floats on `device` (it decides layout and advance)."""
+    lib = L.load()
+    dev = torch.device("cuda" if device is None else device)
+    cap = lib.es_philox_block_cap(torch.cuda.current_device() if dev.index is None else dev.index)
+    if cap < 1:
+        L.check(cap, "es_philox_block_cap")
+    return lib.es_philox_blocks(numel, cap)
+
+
+def randn(shape, seed: int, offset: int, *, blocks: int = 0, scale: float = 1.0, round_dtype=None, nhwc=None,
+          device=None, out: Optional[torch.Tensor] = None):
+    """torch.randn(shape, device=device, generator=g) for a device generator g with initial_seed() == seed and get_offset() ==
+    offset, as fp32, and the offset g has afterwards: (tensor, advanced offset).
+
+    blocks: torch's grid for the draw, 0 = this device's (philox_blocks).  round_dtype: None | torch.float16 | torch.bfloat16 -
+    the values of a draw in that dtype, widened to fp32.  scale multiplies the result after that rounding.  nhwc: None = the
+    tensor has `shape`; True or a channel stride >= C = shape is [N, C, ...], drawn in that order and returned as
+    [N, ..., stride] (channels-last; channels C.. of a padded result are zero, or keep what `out` held)."""
+    lib = L.load()
+    shape = tuple(int(v) for v in shape)
+    numel = math.prod(shape)
+    if round_dtype not in _ROUND:
+        raise L.EdgeStyleHipError(f"randn: round_dtype must be None, torch.float16 or torch.bfloat16, not {round_dtype}")
+    dev = torch.device("cuda" if device is None else device) if out is None else out.device
+    if dev.type != "cuda":
+        raise L.EdgeStyleHipError(f"randn: draws on the GPU, not on {dev} (lib.es_randn_host is the CPU form)")
+    d = L.RandnDesc(seed=int(seed) & (2 ** 64 - 1), offset=int(offset), numel=numel, blocks=int(blocks), scale=float(scale),
+                    round_dtype=_ROUND[round_dtype])
+    out_shape = shape
+    if nhwc is not None and nhwc is not False:
+        if len(shape) < 3:
+            raise L.EdgeStyleHipError(f"randn: nhwc needs a shape [N, C, ...], got {shape}")
+        d.N, d.C, d.HW = shape[0], shape[1], math.prod(shape[2:])
+        d.Cstride = shape[1] if nhwc is True else int(nhwc)
+        out_shape = (shape[0],) + shape[2:] + (int(d.Cstride),)
+    with torch.cuda.device(dev):
+        if not d.blocks:
+            d.blocks = philox_blocks(max(numel, 1), dev)
+        if out is None:
+            out = (torch.zeros if d.Cstride > d.C else torch.empty)(out_shape, dtype=torch.float32, device=dev)
+        elif out.dtype != torch.float32 or tuple(out.shape) != out_shape or not out.is_contiguous():
+            raise L.EdgeStyleHipError(f"randn: out must be a contiguous fp32 {out_shape} tensor")
+        L.check(lib.es_randn(_ptr(out), C.byref(d), _stream()), "es_randn")
+    return out, int(offset) + lib.es_philox_advance(numel, d.blocks)

@@ -191,7 +191,8 @@ class StableDiffusionControlNetPipeline:
 
     def __init__(self, vae: AutoencoderKL, text_encoder=None, tokenizer=None, unet: UNet2DConditionModel = None,
                  controlnet: Union[EdgeStyleMultiControlNetModel, ControlNetModel] = None, scheduler=None,
-                 safety_checker=None, feature_extractor=None, image_encoder=None, requires_safety_checker: bool = False):
+                 safety_checker=None, feature_extractor=None, image_encoder=None, requires_safety_checker: bool = False,
+                 noise_source: str = "host", noise_dtype=None):
         if unet is None or controlnet is None or vae is None:
             raise ValueError("vae, unet and controlnet are required")
         if isinstance(controlnet, (list, tuple)):
@@ -211,6 +212,16 @@ class StableDiffusionControlNetPipeline:
         self._last_loop: Optional[_Loop] = None
         self.collect_timing = False      # tools: HIP events at the phase boundaries of a call -> self.timing (ms)
         self.timing: Dict[str, float] = {}
+        # Where latents and the VAE-sample noise come from when the caller passes neither `latents=` nor `cond_noise=`:
+        #   "host" (default): the CPU generator stream (_host_generator) - independent of the device, and the CPU oracle can
+        #                     reproduce it;
+        #   "device":         torch's DEVICE Philox stream, drawn by ops.randn straight into device memory - what the reference's
+        #                     callers get: latents from `generator` (a device generator, TT:274), the VAE sample from the device's
+        #                     default generator (CL:39).  noise_dtype: None (fp32) | torch.float16 | torch.bfloat16 - the dtype
+        #                     the reference's pipeline would have drawn in (values are rounded to it, then widened).
+        if noise_source not in ("host", "device"):
+            raise ValueError(f'noise_source must be "host" or "device", not {noise_source!r}')
+        self.noise_source, self.noise_dtype = noise_source, noise_dtype
 
     @classmethod
     def from_pretrained(cls, path=None, **components):
@@ -219,7 +230,7 @@ class StableDiffusionControlNetPipeline:
             components["scheduler"] = DDIMScheduler()
         return cls(**{k: v for k, v in components.items() if k in (
             "vae", "text_encoder", "tokenizer", "unet", "controlnet", "scheduler", "safety_checker",
-            "feature_extractor", "image_encoder", "requires_safety_checker")})
+            "feature_extractor", "image_encoder", "requires_safety_checker", "noise_source", "noise_dtype")})
 
     def to(self, device):
         self.device = torch.device(device)
@@ -231,6 +242,32 @@ class StableDiffusionControlNetPipeline:
         self._loops.clear()
         self._last_loop = None
         return self
+
+    @property
+    def _device_noise(self) -> bool:
+        if self.noise_source not in ("host", "device"):
+            raise ValueError(f'noise_source must be "host" or "device", not {self.noise_source!r}')
+        return self.noise_source == "device"
+
+    def _device_generator(self, generator):
+        """noise_source "device": the generator a draw comes from - the caller's device generator, or the device's default one."""
+        if generator is None:
+            torch.cuda.init()
+            return torch.cuda.default_generators[self.device.index if self.device.index is not None else torch.cuda.current_device()]
+        if generator.device.type != "cuda":
+            raise ValueError(f'noise_source="device" draws torch\'s device stream: pass torch.Generator("{self.device}").manual_seed(seed) '
+                             f"(or None for the device's default generator), not a generator on {generator.device}; "
+                             'CPU generators belong to noise_source="host"')
+        return generator
+
+    def _draw_device(self, shape, generator, scale: float = 1.0, out=None):
+        """One torch.randn(shape, generator=generator, device=...) restated on the device (ops.randn); the generator is left
+        where torch's own draw would have left it."""
+        g = self._device_generator(generator)
+        t, offset = ops.randn(shape, g.initial_seed(), g.get_offset(), scale=scale, round_dtype=self.noise_dtype,
+                              device=self.device, out=out)
+        g.set_offset(offset)
+        return t
 
     @property
     def _execution_device(self):
@@ -307,8 +344,12 @@ class StableDiffusionControlNetPipeline:
                 raise ValueError("condition image batch must be 1 or equal to the prompt batch")
         if do_cfg:
             image = torch.cat([image] * 2)                              # PL:657-658
+        if tuple(image.shape[1:2]) == (3,) and noise is None and self._device_noise and getattr(net.config, "uses_vae", False):
+            sc, lc = net._vae.cfg.scale, net._vae.cfg.latent_channels
+            noise = self._draw_device((image.shape[0], lc, image.shape[2] // sc, image.shape[3] // sc), None)     # CL:39
         if tuple(image.shape[1:2]) == (3,):
-            emb = net.preprocess_image(image.to(self.device), noise=noise, generator=_host_generator(generator))
+            emb = net.preprocess_image(image.to(self.device), noise=noise,
+                                       generator=None if self._device_noise else _host_generator(generator))
         else:
             emb = image                                                 # already embedded [N,C0,h,w]
         return _as_nhwc(emb, self.dtype, self.device)
@@ -365,7 +406,9 @@ class StableDiffusionControlNetPipeline:
         prepare_image for anything that is not an RGB image tensor handled by the known net classes."""
         from .models import ControlLoRAModel
         nets = self._nets
-        generator = _host_generator(generator)
+        device_noise = self._device_noise
+        if not device_noise:
+            generator = _host_generator(generator)
         rgb = []
         for img in images:
             if not torch.is_tensor(img):
@@ -398,7 +441,9 @@ class StableDiffusionControlNetPipeline:
                 nz = None if cond_noise is None else cond_noise[i]
                 if nz is not None and nz.dim() == 5:
                     nz = nz[0]                               # a per-step table: the embedding made here is step 0's
-                if nz is None:
+                if nz is None and device_noise:
+                    nz = self._draw_device((N, vae.cfg.latent_channels, hh, ww), None)       # the device's default generator (CL:39)
+                elif nz is None:
                     nz = torch.randn((N, vae.cfg.latent_channels, hh, ww), generator=generator, dtype=torch.float32)
                 noise[i] = nz
         for (kind, _), idx in groups.items():
@@ -427,7 +472,18 @@ class StableDiffusionControlNetPipeline:
     def prepare_latents(self, batch_size, channels, h, w, generator, latents=None):
         """PL:585-627.  Latents are always drawn on the HOST RNG stream (results then do not depend on the device's
         Philox stream, and the CPU oracle can reproduce them): a device generator, as TT:274 passes
-        (`torch.Generator(device).manual_seed(42)`), is re-seated as a CPU generator with the same initial seed."""
+        (`torch.Generator(device).manual_seed(42)`), is re-seated as a CPU generator with the same initial seed.
+        noise_source "device" instead draws the device generator's own stream (a device generator, a list of them, or None =
+        the device's default generator) and leaves each generator where torch's draw would have."""
+        if latents is None and self._device_noise:
+            shape = (batch_size, channels, h, w)
+            sigma = float(self.scheduler.init_noise_sigma)
+            if isinstance(generator, (list, tuple)):
+                if len(generator) != batch_size:
+                    raise ValueError(f"You have passed a list of generators of length {len(generator)}, but requested an "
+                                     f"effective batch size of {batch_size}.")
+                return torch.cat([self._draw_device((1,) + shape[1:], g, sigma) for g in generator])
+            return self._draw_device(shape, generator, sigma)
         generator = _host_generator(generator)
         shape = (batch_size, channels, h, w)
         if isinstance(generator, list) and len(generator) != batch_size:
@@ -522,7 +578,8 @@ class StableDiffusionControlNetPipeline:
         if want_rs and not guess and isinstance(image, (list, tuple)):
             from .models import ControlLoRAModel
             Nn = B * (2 if do_cfg else 1)
-            gen_h = _host_generator(generator)
+            device_noise = self._device_noise
+            gen_h = None if device_noise else _host_generator(generator)
             cand = [i for i, (img, net) in enumerate(zip(image, self._nets))
                     if isinstance(net, ControlLoRAModel) and net.config.uses_vae and torch.is_tensor(img) and img.dim() == 4
                     and img.shape[1] == 3 and (cond_noise is None or cond_noise[i] is None or cond_noise[i].dim() == 5)]
@@ -535,10 +592,16 @@ class StableDiffusionControlNetPipeline:
                         raise ValueError(f"cond_noise[{i}]: a per-step table must be [num_inference_steps, N, L, h, w] = "
                                          f"{(num_inference_steps,) + shapes[i]}, got {tuple(tb.shape)}")
                 drawn = {i: [] for i in cand if i not in given}
-                for _ in range(num_inference_steps if drawn else 0):          # the reference's draw order: step by step, net by net
+                tables = {}
+                if device_noise:                        # same order, each draw straight into its row of a device table
+                    tables = {i: torch.empty((num_inference_steps,) + shapes[i], dtype=torch.float32, device=self.device) for i in drawn}
+                    for t_i in range(num_inference_steps):
+                        for i in drawn:
+                            self._draw_device(shapes[i], None, out=tables[i][t_i])
+                for _ in range(num_inference_steps if drawn and not device_noise else 0):     # the reference's draw order: step by step, net by net
                     for i in drawn:
                         drawn[i].append(torch.randn(shapes[i], generator=gen_h, dtype=torch.float32))
-                rs_tables = {i: (given[i].float() if i in given else torch.stack(drawn[i])) for i in cand}
+                rs_tables = {i: (given[i].float() if i in given else tables[i] if i in tables else torch.stack(drawn[i])) for i in cand}
                 cond_noise = [rs_tables.get(i, None if cond_noise is None else cond_noise[i]) for i in range(len(image))]
         conds = self.prepare_images(image, B, do_cfg and not guess, cond_noise, generator,
                                     num_images_per_prompt)                                      # PL:352-377, 657-658

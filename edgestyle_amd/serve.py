@@ -54,6 +54,13 @@ def latents_for(seed: int, channels: int, h: int, w: int) -> torch.Tensor:
     return torch.randn((1, channels, h, w), generator=g, dtype=torch.float32)
 
 
+def device_latents_for(seed: int, channels: int, h: int, w: int) -> torch.Tensor:
+    """Initial latents of ONE request as torch.Generator("cuda").manual_seed(seed) would draw them at offset 0 - the
+    reference's own stream (app.py:119) - drawn on the device (ops.randn)."""
+    from . import ops
+    return ops.randn((1, channels, h, w), int(seed), 0)[0]
+
+
 class TryOnService:
     """Batches `TryOnRequest`s into pipeline calls on a worker thread.
 
@@ -64,7 +71,8 @@ class TryOnService:
 
     def __init__(self, pipeline: Callable[..., Any], max_batch: int = 8, max_wait_s: float = 0.02,
                  batch_sizes: Sequence[int] = (1, 2, 4, 8), latent_channels: int = 4, vae_scale: int = 8,
-                 cond_noise_fn: Optional[Callable[[int, List[int]], Any]] = None, output_u8: bool = False):
+                 cond_noise_fn: Optional[Callable[[int, List[int]], Any]] = None, output_u8: bool = False,
+                 noise_source: str = "host"):
         if max_batch < 1 or not batch_sizes or min(batch_sizes) != 1:
             raise ValueError("max_batch >= 1 and batch_sizes must contain 1")
         self.pipeline = pipeline
@@ -73,6 +81,11 @@ class TryOnService:
         self.batch_sizes = sorted(b for b in set(batch_sizes) if b <= max_batch)
         self.latent_channels, self.vae_scale = latent_channels, vae_scale
         self.cond_noise_fn = cond_noise_fn
+        if noise_source not in ("host", "device"):
+            raise ValueError(f'noise_source must be "host" or "device", not {noise_source!r}')
+        # "host" (default): each request's latents from its own CPU generator (the CPU oracle can reproduce them);
+        # "device": from torch's device Philox stream for the request's seed at offset 0, drawn on the device
+        self.noise_source = noise_source
         self.output_u8 = bool(output_u8)         # ask the pipeline for output_type "u8": uint8 [B,H,W,3] device tensors
         self._q: "queue.Queue[Optional[TryOnRequest]]" = queue.Queue()
         self._pending: List[TryOnRequest] = []
@@ -153,7 +166,8 @@ class TryOnService:
     def _call(self, batch: List[TryOnRequest]):
         r0 = batch[0]
         h, w = r0.images[0].shape[-2:]
-        lat = torch.cat([latents_for(r.seed, self.latent_channels, h // self.vae_scale, w // self.vae_scale) for r in batch], 0)
+        draw = device_latents_for if self.noise_source == "device" else latents_for
+        lat = torch.cat([draw(r.seed, self.latent_channels, h // self.vae_scale, w // self.vae_scale) for r in batch], 0)
         kwargs = dict(
             prompt_embeds=torch.cat([r.prompt_embeds for r in batch], 0),
             negative_prompt_embeds=torch.cat([r.negative_prompt_embeds for r in batch], 0),

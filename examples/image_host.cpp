@@ -5,14 +5,19 @@
 // 6-ControlNet denoising loop and the VAE decode, and writes the result as a PPM.
 //
 //   hipcc -O2 -Iinclude examples/image_host.cpp -Ledgestyle_amd/lib -ledgestyle_hip -Wl,-rpath,$PWD/edgestyle_amd/lib -o image_host
-//   ./image_host ctx.esctx cond0.ppm cond1.ppm cond2.ppm cond3.ppm cond4.ppm cond5.ppm inputs.bin out.ppm
+//   ./image_host ctx.esctx cond0.ppm cond1.ppm cond2.ppm cond3.ppm cond4.ppm cond5.ppm inputs.bin out.ppm [--seed S [--cond-seed S2]]
 //
 // cond<i>.ppm: binary PPM (P6, maxval 255), the condition image of net i in the reference's order (agnostic, subject pose,
 // clothes 1, pose 1, clothes 2, pose 2); a context of batch B > 1 takes the same six photos for every image of the batch.
 // inputs.bin (little endian, written by tests/test_image_io_gpu.py):
 //   int32 B, h, w, L, D, n_conds, n_steps, has_noise[n_conds], normalize[n_conds]; float guidance_scale; float timesteps[n_steps];
 //   float latents[B*h*w*L] (NHWC); uint16 ehs[2B*77*D] (fp16 bits, negative prompt rows first);
-//   per net with has_noise: float noise[2B*L*h*w]      (the library has no RNG: latents and sampling noise are the caller's)
+//   per net with has_noise: float noise[2B*L*h*w]      (host noise, the default: the caller's own arrays, which the CPU oracle
+//                                                       can reproduce)
+// --seed S: the latents and noise records of inputs.bin are ignored and the library draws both from torch's device Philox stream
+//   (csrc/rng.hip) - the latents as torch.Generator("cuda").manual_seed(S) would (TT:274, app.py:119), the VAE-sample noise as the
+//   device's default generator would after torch.manual_seed(S2) (CL:39); --cond-seed S2 defaults to S.  Both schedulers the
+//   library implements start from init_noise_sigma 1.
 // out.ppm: image 0 of the batch, 8h x 8w
 //
 // What each call replaces in the reference: es_prepare_conds_u8 = the transforms of TT:29-48 + prepare_image + preprocess_image
@@ -20,6 +25,8 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #include "edgestyle_hip.h"
@@ -55,7 +62,20 @@ static bool read_ppm(const char* path, std::vector<uint8_t>& px, int* H, int* W)
 }
 
 int main(int argc, char** argv) {
-  if (argc != 10) { fprintf(stderr, "usage: %s ctx.esctx cond0.ppm .. cond5.ppm inputs.bin out.ppm\n", argv[0]); return 1; }
+  bool seeded = false, usage = argc < 10 || (argc - 10) % 2 != 0;
+  es_philox lat_gen = {0, 0}, cond_gen = {0, 0};
+  bool cond_given = false;
+  for (int a = 10; a + 1 < argc && !usage; a += 2) {
+    char* end = nullptr;
+    const unsigned long long v = strtoull(argv[a + 1], &end, 10);
+    if (!*argv[a + 1] || *end) usage = true;
+    else if (!strcmp(argv[a], "--seed")) { lat_gen.seed = v; seeded = true; }
+    else if (!strcmp(argv[a], "--cond-seed")) { cond_gen.seed = v; cond_given = true; }
+    else usage = true;
+  }
+  if (cond_given && !seeded) usage = true;
+  if (usage) { fprintf(stderr, "usage: %s ctx.esctx cond0.ppm .. cond5.ppm inputs.bin out.ppm [--seed S [--cond-seed S2]]\n", argv[0]); return 1; }
+  if (!cond_given) cond_gen.seed = lat_gen.seed;
   FILE* f = fopen(argv[8], "rb");
   if (!f) { perror(argv[8]); return 1; }
   int32_t hd[7];
@@ -79,6 +99,7 @@ int main(int argc, char** argv) {
     if (has_noise[i]) {
       float* p = nullptr;
       if (!rd(f, tmp, noise_n)) return 1;
+      if (seeded) continue;                     // drawn on the device instead (es_ctx_draw_cond_noise)
       HIP_OK(hipMalloc(&p, noise_n * 4));
       HIP_OK(hipMemcpy(p, tmp.data(), noise_n * 4, hipMemcpyHostToDevice));
       d_noise[i] = p;
@@ -113,6 +134,10 @@ int main(int argc, char** argv) {
 
   hipStream_t st;
   HIP_OK(hipStreamCreate(&st));
+  if (seeded) {
+    ES_OK(es_ctx_draw_cond_noise(ctx, &cond_gen, ES_F32, st));          // NULL noise pointers below keep what this drew
+    ES_OK(es_ctx_draw_latents(ctx, &lat_gen, 1, 1.0f, ES_F32, d_lat, st));
+  }
   ES_OK(es_prepare_conds_u8(ctx, imgs.data(), normalize.data(), d_noise.data(), d_ws, ws_bytes, st));
   ES_OK(es_denoise_loop(ctx, d_lat, d_ehs, gs, ts.data(), T, st));
   ES_OK(es_vae_decode_u8(ctx, d_lat, d_out, st));

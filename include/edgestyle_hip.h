@@ -611,8 +611,9 @@ int es_denoise_loop(es_ctx* c, float* latents_inout, const void* ehs, float guid
 int es_vae_decode(es_ctx* c, const float* latents, float* out_img, void* stream);
 /* == prepare_image + the one-time conditioning embedding (model/edgestyle_pipeline.py:352-377, 629-664;
  * model/controllora.py:28-42, 289-290): images[n_conds] device fp32 NCHW [B,3,8h,8w]; noise[n_conds] device fp32
- * [N,latent_channels,h,w] for the nets whose ES_BUF_COND_NOISE slot is bound (the VAE-conditioned ones: the library has no
- * RNG, the host draws what the reference's global generator would), ignored (may be NULL) for the others.  Each shared
+ * [N,latent_channels,h,w] for the nets whose ES_BUF_COND_NOISE slot is bound (the VAE-conditioned ones: the caller's own
+ * noise, what the reference's global generator would draw; NULL for such a net keeps what es_ctx_draw_cond_noise last drew
+ * into the slot and is refused where nothing was drawn), ignored (may be NULL) for the others.  Each shared
  * encoder (the VAE of the LoRA nets, the conv stack of the pose net) runs once over the un-duplicated images of all its
  * nets; results land in ES_BUF_COND0.. as [N,h,w,C0], ready for es_denoise_loop / es_ctx_launch_plan. */
 int es_prepare_conds(es_ctx* c, const float* const* images, const float* const* noise, void* stream);
@@ -666,6 +667,57 @@ int es_prepare_conds_u8(es_ctx* c, const es_image_u8* images, const int32_t* nor
 /* es_vae_decode to bytes: the unchanged decode plan into ES_BUF_IMAGE, then es_image_f32_to_u8 from there;
  * out_hwc device uint8 [B,8h,8w,3].  Capturable like es_vae_decode. */
 int es_vae_decode_u8(es_ctx* c, const float* latents, uint8_t* out_hwc, void* stream);
+
+/* =========================================================================================================
+ * Seeded noise (csrc/rng.hip): the normal stream of torch's DEVICE generator, restated, so that a host without Python can take
+ * "seed 42" as an input and get the latents torch.randn(shape, generator=torch.Generator(device).manual_seed(42), device=device)
+ * gives the reference's callers (test_text2image_pretrained_openpose.py:274, app.py:119).  The generator is Philox4x32-10 (ten
+ * rounds, multipliers D2511F53 / CD9E8D57, Weyl constants 9E3779B9 / BB67AE85, key {seed lo, seed hi}, counter {offset / 4 lo,
+ * offset / 4 hi, subsequence lo, subsequence hi}); a draw of numel floats is laid out as torch's grid-stride kernel lays it out:
+ * blocks = min(block_cap, ceil(numel / 256)), T = 256 * blocks; element li is component (li % 4T) / T of the four normals (two
+ * Box-Muller pairs: words x, y -> 0, 1; z, w -> 2, 3) of counter offset / 4 + li / 4T in subsequence li % T, and the generator
+ * moves on by ((numel - 1) / 4T + 1) * 4.  block_cap = multiProcessorCount * (maxThreadsPerMultiProcessor / 256) of the device,
+ * so the values of draws longer than 256 * block_cap elements depend on the device, as torch's do.
+ * Host noise - the caller's own arrays, as before - stays the default everywhere: the CPU oracle can reproduce it, a device
+ * stream it cannot.  None of these calls is ever part of a plan: while a plan records on the calling thread they return -1.
+ * No new ES_ABI_VERSION: no plan or context image records them.
+ * ========================================================================================================= */
+typedef struct { uint64_t seed, offset; } es_philox;      /* a generator: manual_seed(seed), get_offset() / set_offset(offset) */
+typedef struct {
+  uint64_t seed;
+  uint64_t offset;                 /* the generator's offset before the draw: a multiple of 4 */
+  int64_t numel;
+  int32_t blocks;                  /* torch's grid for this draw (es_philox_blocks); 0 = derive it from the current device */
+  float scale;                     /* the result is multiplied by it after any rounding (the scheduler's init_noise_sigma) */
+  int32_t round_dtype;             /* ES_F32: none.  ES_F16 | ES_BF16: rounded to that type and widened again, as torch draws a
+                                      half tensor (in float, then cast) */
+  /* optional permutation, all four 0 = a plain linear write: the draw index runs over NCHW [N, C, HW] (N * C * HW == numel) and
+   * the value lands at [n, p, c] of an [N, HW, Cstride] array (Cstride >= C; channels C .. Cstride - 1 are left untouched) */
+  int64_t N, C, HW, Cstride;
+} es_randn_desc;
+/* host-only: one Philox4x32-10 block */
+int es_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
+/* block_cap of a device (needs a GPU; -2 without one) */
+int es_philox_block_cap(int device);
+/* host-only: min(block_cap, ceil(numel / 256)) */
+int es_philox_blocks(int64_t numel, int block_cap);
+/* host-only: by how much a draw of numel elements on `blocks` blocks advances the generator's offset */
+int64_t es_philox_advance(int64_t numel, int blocks);
+/* out: device fp32, numel elements (or the [N, HW, Cstride] array of the permutation).  Asynchronous on `stream`, nothing is
+ * allocated: capturable.  Bit-equal to torch.randn on the same device for the same (seed, offset). */
+int es_randn(float* out, const es_randn_desc* d, void* stream);
+/* the same draw on the CPU (out: host memory; `blocks` must be given).  Integer layer, layout, rounding and scatter are the
+ * kernel's own code; the float step uses the host's libm and no fused multiply-add, so values agree with the device's to a few
+ * ulp, not bit for bit. */
+int es_randn_host(float* out, const es_randn_desc* d);
+/* == prepare_latents (model/edgestyle_pipeline.py: randn_tensor(shape, generator) * init_noise_sigma): fills latents_out, device
+ * fp32 [B,h,w,L] - the layout es_denoise_loop takes.  n_gens == 1: one draw of [B,L,h,w]; n_gens == B: one draw of [1,L,h,w] per
+ * image from its own generator (the reference's list of generators).  Every gens[i] is advanced in place.  Capturable. */
+int es_ctx_draw_latents(es_ctx* c, es_philox* gens, int n_gens, float sigma, int round_dtype, float* latents_out, void* stream);
+/* == latent_dist.sample() of the VAE-conditioned nets (model/controllora.py:39, the device's default generator): fills every bound
+ * ES_BUF_COND_NOISE* slot, in net order, each with one draw of [N,L,h,w]; `gen` is advanced after each draw.  es_prepare_conds /
+ * es_prepare_conds_u8 called afterwards with a NULL noise pointer for such a net keep what the slot holds. */
+int es_ctx_draw_cond_noise(es_ctx* c, es_philox* gen, int round_dtype, void* stream);
 
 #ifdef __cplusplus
 }
