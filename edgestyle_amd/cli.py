@@ -56,6 +56,9 @@ def parse_args(argv: Optional[List[str]] = None):
     p.add_argument("--device_preprocess", action="store_true",
                    help="resize, crop and convert the condition images on the GPU (Pillow-exact kernels with torchvision's size and "
                         "crop rules, TT:29-48) instead of with PIL on the host: the files are only decoded with PIL, their bytes uploaded")
+    p.add_argument("--native_text_encoder", action="store_true",
+                   help="encode the prompts on the GPU with the library's own CLIP text encoder (edgestyle_amd/text.py) instead of "
+                        "with transformers on the host; needs the tokenizer/ and text_encoder/ directories")
     p.add_argument("--tiny", action="store_true", help="with --random_init: width-reduced 128x128 config (plumbing demo)")
     return p.parse_args(argv)
 
@@ -128,6 +131,11 @@ def main(args):
         from transformers import AutoTokenizer, CLIPTextModel
         tokenizer = AutoTokenizer.from_pretrained(args.pretrained_model_name_or_path, subfolder="tokenizer", use_fast=False)
         text_encoder = CLIPTextModel.from_pretrained(args.pretrained_model_name_or_path, subfolder="text_encoder")
+        if args.native_text_encoder:
+            from .text import NativeCLIPTextEncoder
+            text_encoder = NativeCLIPTextEncoder.from_module(text_encoder, dtype=weight_dtype, device=device, max_n=2)
+    elif args.native_text_encoder:
+        raise SystemExit("--native_text_encoder needs tokenizer/ and text_encoder/ under --pretrained_model_name_or_path")
     vae = AutoencoderKL.from_pretrained(args.pretrained_vae_name_or_path or os.path.join(args.pretrained_model_name_or_path, "vae"))
     unet = UNet2DConditionModel.from_pretrained(args.pretrained_model_name_or_path, subfolder="unet", torch_dtype=weight_dtype)
     openpose = ControlNetModel.from_pretrained(args.pretrained_openpose_name_or_path, torch_dtype=weight_dtype)

@@ -122,6 +122,11 @@ class RandnDesc(C.Structure):       # es_randn_desc
                 ("round_dtype", C.c_int32), ("N", C.c_int64), ("C", C.c_int64), ("HW", C.c_int64), ("Cstride", C.c_int64)]
 
 
+class TextConfig(C.Structure):      # es_text_config
+    _fields_ = [(n, C.c_int32) for n in ("vocab_size", "hidden", "heads", "layers", "intermediate", "max_positions")] + \
+        [("ln_eps", C.c_float), ("act", C.c_int32)]
+
+
 class Tensor(C.Structure):          # es_tensor
     _fields_ = [("key", C.c_char_p), ("data", C.c_void_p), ("shape", C.c_int64 * 4), ("ndim", C.c_int32), ("dtype", C.c_int32)]
 
@@ -275,6 +280,12 @@ SYMBOLS = {
     "es_randn_host": (C.c_int, [_P, C.POINTER(RandnDesc)]),
     "es_ctx_draw_latents": (C.c_int, [_P, C.POINTER(Philox), _I, _F, _I, _P, _P]),
     "es_ctx_draw_cond_noise": (C.c_int, [_P, C.POINTER(Philox), _I, _P]),
+    "es_attention_causal": (C.c_int, [C.POINTER(AttnDesc), _P]),
+    "es_text_embed": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "es_text_encoder_create": (C.c_int, [C.POINTER(StateDict), C.POINTER(TextConfig), _I, _I, _I, C.POINTER(_P)]),
+    "es_text_encoder_destroy": (None, [_P]),
+    "es_text_encoder_arena_bytes": (C.c_size_t, [_P]),
+    "es_text_encode": (C.c_int, [_P, _P, _I, _P, _P]),
 }
 
 _lib = None

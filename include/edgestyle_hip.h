@@ -719,6 +719,49 @@ int es_ctx_draw_latents(es_ctx* c, es_philox* gens, int n_gens, float sigma, int
  * es_prepare_conds_u8 called afterwards with a NULL noise pointer for such a net keep what the slot holds. */
 int es_ctx_draw_cond_noise(es_ctx* c, es_philox* gen, int round_dtype, void* stream);
 
+/* =========================================================================================================
+ * Text encoder (csrc/text.hip): token ids in, the text states `ehs` of es_denoise_step / es_denoise_loop out - CLIPTextModel's
+ * last_hidden_state, which the reference computes per request with transformers (app.py:163-176: the prompt and the negative
+ * prompt; model/edgestyle_pipeline.py encode_prompt).  Tokenisation (BPE, vocabulary files) stays with the caller.
+ * A self-contained object beside es_ctx: it owns one arena (fp32 embedding tables, packed weights, activations for max_n prompts)
+ * and runs on the library's own kernels - es_conv_gemm through the launch policy (es_launch_choose; LayerNorm1 / LayerNorm2 folded
+ * into q|k|v and fc1, residual adds in the epilogues of out_proj and fc2), the two kernels below and es_layer_norm.
+ * None of these calls is ever part of a plan: while a plan records on the calling thread they return -1.  No new
+ * ES_ABI_VERSION: no plan or context image records them.
+ * ========================================================================================================= */
+/* Causal self-attention O[n, i, h] = softmax over j <= i of (Q_i . K_j * scale) V_j, same descriptor as es_attention.  Scope: Sq == Skv
+ * in 1..128 (all keys of a head stay on chip: no online softmax), head_dim 32 | 64, fp16 | bf16 with fp32 accumulation, any row and
+ * batch strides that are multiples of 8 elements (Q, K, V may be column slices of one fused [M, 3C] projection output).  The mask is
+ * applied before the row maximum and the row sum; masked probabilities are exactly 0.  Anything else is refused before a launch. */
+int es_attention_causal(const es_attn_desc* d, void* stream);
+/* out[r, :] = round_dtype(tok[ids[r], :] + pos[r % S, :]): ids device int32 [rows] (clamped to [0, vocab) by the kernel), tok fp32
+ * [vocab, hidden], pos fp32 [S, hidden] (nn.Embedding stays fp32 under autocast), summed in fp32, rounded once; out dtype [rows, hidden];
+ * hidden a multiple of 8. */
+int es_text_embed(const int32_t* ids, const float* tok, const float* pos, void* out, int rows, int S, int hidden, int vocab, int dtype,
+                  void* stream);
+typedef struct {                   /* config.json of a text_encoder/ directory (CLIPTextConfig) */
+  int32_t vocab_size, hidden, heads, layers, intermediate, max_positions;
+  float ln_eps;
+  int32_t act;                     /* 0 = quick_gelu (SD1.5's CLIP ViT-L/14); anything else is refused */
+} es_text_config;
+typedef struct es_text_encoder es_text_encoder;
+/* sd: CLIPTextModel's state dict as es_tensor descriptors (host or device memory, ES_F32 | ES_F16 | ES_BF16), keys
+ * embeddings.{token,position}_embedding.weight, encoder.layers.{i}.{layer_norm1,layer_norm2}.{weight,bias},
+ * encoder.layers.{i}.self_attn.{q,k,v,out}_proj.{weight,bias}, encoder.layers.{i}.mlp.{fc1,fc2}.{weight,bias},
+ * final_layer_norm.{weight,bias} - bare, as transformers 5 spells them, or with the `text_model.` prefix of the SD1.5 checkpoints
+ * (test_text2image_pretrained_openpose.py:224-232).  Other keys are ignored; a missing key or a wrong shape is an error naming the key.
+ * quick_gelu rides on the SiLU epilogue: fc1 is packed as 1.702 W, 1.702 b and launched with ES_ACT_SILU and out_scale 1 / 1.702.
+ * Refused: hidden % 64 != 0 or above 4096, hidden / heads not 32 | 64, max_positions > 128, intermediate % 64 != 0, act != 0.
+ * device -1: dry build - everything but the allocation and the upload; es_text_encoder_arena_bytes reports the size and
+ * es_text_encode returns an error that says so. */
+int es_text_encoder_create(const es_state_dict* sd, const es_text_config* cfg, int dtype, int max_n, int device, es_text_encoder** out);
+void es_text_encoder_destroy(es_text_encoder* e);
+size_t es_text_encoder_arena_bytes(const es_text_encoder* e);
+/* ids_host: HOST int32 [n, max_positions], n <= max_n, every id in [0, vocab_size) (else -1 naming the position); rows in the order of
+ * the `ehs` operand - under CFG the negative prompts first, then the prompts.  out_ehs: device dtype [n, max_positions, hidden].
+ * The ids are staged through pinned memory: a capturing stream is refused, as es_denoise_step refuses it.  Asynchronous on `stream`. */
+int es_text_encode(es_text_encoder* e, const int32_t* ids_host, int n, void* out_ehs, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
