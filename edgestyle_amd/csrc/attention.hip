@@ -665,14 +665,6 @@ __global__ __launch_bounds__(256, 2) void attention32_kernel(const es_attn_desc 
   }
 }
 
-template <typename T, int KS, int DF, bool ONES, int QB = 1>
-int launch_attn32(const es_attn_desc& d, hipStream_t st) {
-  constexpr int lds = 2 * (64 * (16 * KS * 2 + 16) + 64 * (16 * DF * 2 + 16));
-  auto kfn = attention32_kernel<T, KS, DF, ONES, QB>;
-  dim3 grid((d.Sq + 128 * QB - 1) / (128 * QB), d.heads, d.N);
-  hipLaunchKernelGGL(kfn, grid, dim3(256), lds, st, d);
-  return hipGetLastError() == hipSuccess ? 0 : -2;
-}
 
 // ---------------------------------------------------------------------------------------------------------------
 // head_dim 40 self-attention, PING-PONG between the two waves of a SIMD (the structure of gemm_conv8p.hip applied to
@@ -1150,119 +1142,232 @@ __global__ __launch_bounds__(512, 2) void attention_kvres_kernel(const es_attn_d
   }
 }
 
-template <typename T, int KS, int DF, bool ONES>
-int launch_attn_kvres(const es_attn_desc& d, hipStream_t st) {
-  // strips of queries, whole 32-query blocks: ONE round of workgroups (eight heads each, one wave per head; one workgroup per CU) - at
-  // most 256 of them; a part-filled second round (308 workgroups in the first grid rule) cost a third of the launch
-  const int per_strip = (d.heads + 7) / 8 * d.N;
-  int strips = 256 / per_strip;
-  const int blocks32 = (d.Sq + 31) / 32;
-  strips = strips < 1 ? 1 : (strips > blocks32 ? blocks32 : strips);
-  const int qper = ((blocks32 + strips - 1) / strips) * 32;
-  strips = (d.Sq + qper - 1) / qper;
-  const int nh = d.heads < 8 ? d.heads : 8;
-  const size_t lds = (size_t)3 * 32 * (nh * d.d * 2 + 16);
-  auto kfn = attention_kvres_kernel<T, KS, DF, ONES>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 32 * (8 * 80 * 2 + 16));
-    attr_set = true;
-  }
-  dim3 grid(strips, (d.heads + 7) / 8, d.N);
-  hipLaunchKernelGGL(kfn, grid, dim3(512), lds, st, d, qper);
-  return hipGetLastError() == hipSuccess ? 0 : -2;
+// ---------------------------------------------------------------------------------------------------------------
+// Host side.  A launch is DECIDED first (attn_route: a pure function of the descriptor's geometry and the knobs - kernel, grid,
+// LDS bytes, strip length) and only then MADE (dispatch: a switch on the route's kernel id; the launchers take every number from
+// the route).  es_attention_route reports the same AttnRoute without a GPU.
+// ---------------------------------------------------------------------------------------------------------------
+
+// The tuning switches, read from the environment ONCE per process, on first use (the first launch, route query or
+// es_attention_set_kvres - ES_ATTN_KVRES too, which earlier versions read when the library was loaded):
+//   ES_ATTN_KVRES  1   0: no launch goes to the K/V-resident kernel, 1: those that fill one round of its workgroups, 2: every eligible one
+//   ES_ATTN_BIG    512 blocks of 128 (256) queries from which a launch counts as big: 32 (64) queries per wave
+//   ES_ATTN32      on  0: 16x16 score tiles only, 2: the 32x32 tile also for head_dim 80 (A/B switch: tools, tests)
+//   ES_ATTN_QB     2   1: one query block per wave in the 32x32-tile kernel
+//   ES_ATTN_PP     -1  head_dim-40 ping-pong kernel: 0 off, 1 | 2: 32 | 64 queries per wave, -1: 32 from 256 blocks of 256 queries on
+typedef es_attn_knobs AttnKnobs;
+
+AttnKnobs& attn_knobs() {
+  static AttnKnobs knobs = [] {
+    AttnKnobs k{};
+    const char* e;
+    k.kvres = (e = getenv("ES_ATTN_KVRES")) ? atoi(e) : 1;
+    k.big_thr = (e = getenv("ES_ATTN_BIG")) ? atoll(e) : 512;
+    k.attn32 = (e = getenv("ES_ATTN32")) ? atoi(e) : 1;
+    k.qb = (e = getenv("ES_ATTN_QB")) ? atoi(e) : 2;
+    k.pp = (e = getenv("ES_ATTN_PP")) ? atoi(e) : -1;
+    return k;
+  }();
+  return knobs;
 }
 
-template <typename T, int QB>
-int launch_attn40pp(const es_attn_desc& d, hipStream_t st) {
-  constexpr int lds = 2 * (64 * (16 * 3 * 2 + 16) + 64 * (16 * 3 * 2 + 16));
-  dim3 grid((d.Sq + 256 * QB - 1) / (256 * QB), d.heads, d.N);
-  hipLaunchKernelGGL((attention40pp_kernel<T, QB>), grid, dim3(512), lds, st, d);
-  return hipGetLastError() == hipSuccess ? 0 : -2;
-}
-
-template <typename T, int KS, int DF, int QF, int KVT, bool ONES = false>
-int launch_attn(const es_attn_desc& d, hipStream_t st) {
-  constexpr int lds = (KS <= 5 ? 2 : 1) * (KVT * (32 * KS * 2 + 16) + KVT * (16 * DF * 2 + 16));
-  auto kfn = attention_kernel<T, KS, DF, QF, KVT, ONES>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_set = true;
-  }
-  dim3 grid((d.Sq + 64 * QF - 1) / (64 * QF), d.heads, d.N);
-  hipLaunchKernelGGL(kfn, grid, dim3(256), lds, st, d);
-  return hipGetLastError() == hipSuccess ? 0 : -2;
-}
-
-// 1 (default; ES_ATTN_KVRES=0 turns it off, 2 forces it for every eligible shape): launches of enough samples to fill one round of its
-// workgroups - where it wins (profiles/r05_xattn_bench.txt: 1.13-1.45x at head_dim 40 from 14 samples up, 1.21x at head_dim 80 with 112
-// samples; it LOSES on the two-sample decoder launches and at head_dim 80 with 14-16 samples: 0.5-0.9x, those stay on the tiled kernels).
-// Two earlier versions (Q / O in fragment-shaped accesses; a grid of 1.2 rounds) lost everywhere: what matters for this kernel is whole-row
-// Q / O tiles AND exactly one round of workgroups.  It remains bound by its eight waves moving in lockstep (2.5-3 us per 32-query block
-// against ~1.2 us of vector issue).
-int attn_kvres = [] { const char* e = getenv("ES_ATTN_KVRES"); return e ? atoi(e) : 1; }();
-
-// which kernel the last es_attention launch of this process went to (es_attention_last_kernel: tests assert the variant they mean to run)
+// es_attention_last_kernel / AttnRoute::kernel
 enum { ATTN_K_NONE = 0, ATTN_K_GENERIC16 = 1, ATTN_K_GENERIC32 = 2, ATTN_K_TILE32 = 3, ATTN_K_TILE32_2BLOCKS = 4, ATTN_K_PP32 = 5, ATTN_K_PP64 = 6,
        ATTN_K_KVRES = 7 };
-int attn_last_kernel = ATTN_K_NONE;
 
-template <typename T>
-int dispatch(const es_attn_desc& d, hipStream_t st) {
-  // 32 queries per wave (128 per block) only when that still yields >= 2 blocks per CU; else 16 per wave
-  static const long long big_thr = getenv("ES_ATTN_BIG") ? atoll(getenv("ES_ATTN_BIG")) : 512;
-  const bool big = (long long)((d.Sq + 127) / 128) * d.heads * d.N >= big_thr;
-  // the text-token cross-attention (77 keys) of the 64 x 64 and 32 x 32 levels: K / V resident in registers
-  if (attn_kvres && d.Skv <= 96 && d.Sq >= 64 && (d.d == 40 || d.d == 80)) {
-    const long long groups = (long long)((d.heads + 7) / 8) * d.N;           // workgroups per strip of queries
-    if (attn_kvres == 2 || groups >= (d.d == 40 ? 12 : 64)) {
-      attn_last_kernel = ATTN_K_KVRES;
-      return d.d == 40 ? launch_attn_kvres<T, 3, 3, true>(d, st) : launch_attn_kvres<T, 5, 5, false>(d, st);
+// attention_kernel's instantiation per head width: X(d, KS, DF, QF of a big launch, QF otherwise, KVT, ONES).  The one table the
+// width check, the route and dispatch() are written from.  (64 queries per wave was measured slower: 309 registers -> one wave per SIMD.)
+#define ATTN_GENERIC_TABLE(X)    \
+  X(8, 1, 1, 2, 2, 64, true)     \
+  X(16, 1, 1, 2, 2, 64, false)   \
+  X(24, 1, 2, 2, 2, 64, true)    \
+  X(32, 1, 2, 2, 2, 64, false)   \
+  X(40, 2, 3, 2, 1, 64, true)    \
+  X(48, 2, 3, 2, 1, 64, false)   \
+  X(64, 2, 4, 2, 2, 64, false)   \
+  X(80, 3, 5, 2, 1, 64, false)   \
+  X(128, 4, 8, 2, 2, 64, false)  \
+  X(160, 5, 10, 2, 2, 64, false) \
+  X(512, 16, 32, 1, 1, 32, false)
+
+// dynamic LDS of attention_kernel<KS, DF, ., KVT> (its TILE_BYTES, twice where it double-buffers) and of the 64-key ring of two that
+// attention32_kernel<KS, DF> and attention40pp_kernel (KS = DF = 3) keep
+constexpr int attn_generic_lds(int KS, int DF, int KVT) { return (KS <= 5 ? 2 : 1) * (KVT * (32 * KS * 2 + 16) + KVT * (16 * DF * 2 + 16)); }
+constexpr int attn_tile32_lds(int KS, int DF) { return 2 * (64 * (16 * KS * 2 + 16) + 64 * (16 * DF * 2 + 16)); }
+constexpr int ATTN_KVRES_LDS_MAX = 3 * 32 * (8 * 80 * 2 + 16);      // attention_kvres_kernel's three 32-row tiles of eight heads at head_dim 80
+
+// ATTN_K_GENERIC32 names the 32-queries-per-wave form of a width that also has a 16-query one (40 | 48 | 80); every other instantiation
+// of attention_kernel reports ATTN_K_GENERIC16, whatever its QF (the ids are older than this table and tests pin them)
+constexpr int attn_generic_id(int ks, int df, int qf) {
+#define X(D, KS, DF, QFB, QFS, KVT, ONES) \
+  if (ks == KS && df == DF && qf == QFB && QFB != QFS) return ATTN_K_GENERIC32;
+  ATTN_GENERIC_TABLE(X)
+#undef X
+  return ATTN_K_GENERIC16;
+}
+
+// Everything es_attention decides, as numbers
+struct AttnRoute {
+  int kernel;                         // ATTN_K_*
+  int q_per_wg, q_per_wave;           // queries a workgroup covers / a wave holds at a time (K/V-resident: the strip / its 32-query blocks)
+  int grid_x, grid_y, grid_z, threads;
+  int lds;                            // dynamic LDS bytes
+  int qper;                           // K/V-resident kernel: queries per strip (its second argument); 0 otherwise
+};
+
+AttnRoute attn_route(const es_attn_desc& d, const AttnKnobs& k) {
+  AttnRoute r{};
+  const auto tiled = [&](int kernel, int q_per_wg, int q_per_wave, int threads, int lds) {
+    r.kernel = kernel; r.q_per_wg = q_per_wg; r.q_per_wave = q_per_wave; r.threads = threads; r.lds = lds;
+    r.grid_x = (d.Sq + q_per_wg - 1) / q_per_wg; r.grid_y = d.heads; r.grid_z = d.N;
+    return r;
+  };
+  // 1. the text-token cross-attention (77 keys) of the 64 x 64 and 32 x 32 levels: K / V resident in registers - for launches of enough
+  // samples to fill one round of its workgroups, where it wins (profiles/r05_xattn_bench.txt: 1.13-1.45x at head_dim 40 from 14 samples up,
+  // 1.21x at head_dim 80 with 112 samples; it LOSES on the two-sample decoder launches and at head_dim 80 with 14-16 samples: 0.5-0.9x,
+  // those stay on the tiled kernels).  Two earlier versions (Q / O in fragment-shaped accesses; a grid of 1.2 rounds) lost everywhere: what
+  // matters for this kernel is whole-row Q / O tiles AND exactly one round of workgroups.  It remains bound by its eight waves moving in
+  // lockstep (2.5-3 us per 32-query block against ~1.2 us of vector issue).
+  if (k.kvres && d.Skv <= 96 && d.Sq >= 64 && (d.d == 40 || d.d == 80)) {
+    const int head_groups = (d.heads + 7) / 8;
+    const long long groups = (long long)head_groups * d.N;                    // workgroups per strip of queries
+    if (k.kvres == 2 || groups >= (d.d == 40 ? 12 : 64)) {
+      // strips of queries, whole 32-query blocks: ONE round of workgroups (eight heads each, one wave per head; one workgroup per CU) - at
+      // most 256 of them; a part-filled second round (308 workgroups in the first grid rule) cost a third of the launch
+      const int per_strip = head_groups * d.N;
+      int strips = 256 / per_strip;
+      const int blocks32 = (d.Sq + 31) / 32;
+      strips = strips < 1 ? 1 : (strips > blocks32 ? blocks32 : strips);
+      const int nh = d.heads < 8 ? d.heads : 8;
+      r.kernel = ATTN_K_KVRES;
+      r.qper = ((blocks32 + strips - 1) / strips) * 32;
+      r.q_per_wg = r.qper; r.q_per_wave = 32; r.threads = 512;
+      r.grid_x = (d.Sq + r.qper - 1) / r.qper; r.grid_y = head_groups; r.grid_z = d.N;
+      r.lds = 3 * 32 * (nh * d.d * 2 + 16);
+      return r;
     }
   }
-  static const bool tile32 = !(getenv("ES_ATTN32") && atoi(getenv("ES_ATTN32")) == 0);   // A/B switch (tools)
-  if (big && tile32) {
-    // measured (tools/attn_bench.py, 14 x 8 x 4096^2): head_dim 40 476 -> 449 us; head_dim 80 is no faster (189 VGPRs,
-    // two waves per SIMD instead of three) and stays on the 16x16 kernel unless asked for (ES_ATTN32=2, tests)
-    static const bool tile32_80 = getenv("ES_ATTN32") && atoi(getenv("ES_ATTN32")) == 2;
-    // 64 queries per wave where that still leaves two 256-query blocks per CU: the kernel is bound by LDS reads of the K / V
-    // fragments (tool build with MFMAs, v_exp and row max removed: 265 of 448 us), and a fragment then serves two blocks
-    static const int qb2 = getenv("ES_ATTN_QB") ? atoi(getenv("ES_ATTN_QB")) : 2;
-    // the ping-pong kernel (8 waves, two groups one barrier out of phase): ES_ATTN_PP = 0 off, 1 = 32 queries per wave,
-    // 2 = 64 queries per wave, unset (-1) = 32 queries per wave from 256 blocks of 256 queries on.
+  // 2. 32 queries per wave (128 per block) only when that still yields >= 2 blocks per CU; else 16 per wave
+  const bool big = (long long)((d.Sq + 127) / 128) * d.heads * d.N >= k.big_thr;
+  if (big && k.attn32) {
+    const long long wg256 = (long long)((d.Sq + 255) / 256) * d.heads * d.N;
+    // the ping-pong kernel (8 waves, two groups one barrier out of phase).
     // (Rounds 3-4 ran 64 queries per wave from 4096 blocks on: per tile it is the faster form in isolation (tools/attn_bench.py; stamps: 1730
     //  cycles per 64-query tile against 2 x 1050) - inside the pipeline it is the slower one, -0.6 % per batch-8 call and -1.1 % per 768 x 768
     //  call with 32: profiles/r05_pipeline_ab.txt.  The step runs at the package power limit there; the denser form buys clock it then loses.)
-    static const int pp = getenv("ES_ATTN_PP") ? atoi(getenv("ES_ATTN_PP")) : -1;
-    if (d.d == 40 && pp != 0 && d.Skv % 64 == 0 && d.Skv >= 128) {
-      const long long wg256 = (long long)((d.Sq + 255) / 256) * d.heads * d.N;
-      if (pp == 2) { attn_last_kernel = ATTN_K_PP64; return launch_attn40pp<T, 2>(d, st); }
-      if (pp == 1 || (pp == -1 && wg256 >= 256)) { attn_last_kernel = ATTN_K_PP32; return launch_attn40pp<T, 1>(d, st); }
+    if (d.d == 40 && k.pp != 0 && d.Skv % 64 == 0 && d.Skv >= 128) {
+      if (k.pp == 2) return tiled(ATTN_K_PP64, 512, 64, 512, attn_tile32_lds(3, 3));
+      if (k.pp == 1 || (k.pp == -1 && wg256 >= 256)) return tiled(ATTN_K_PP32, 256, 32, 512, attn_tile32_lds(3, 3));
     }
-    if (d.d == 40 && qb2 == 2 && (long long)((d.Sq + 255) / 256) * d.heads * d.N >= big_thr) {
-      attn_last_kernel = ATTN_K_TILE32_2BLOCKS;
-      return launch_attn32<T, 3, 3, true, 2>(d, st);
-    }
-    if (d.d == 40) { attn_last_kernel = ATTN_K_TILE32; return launch_attn32<T, 3, 3, true>(d, st); }
-    if (d.d == 80 && tile32_80) { attn_last_kernel = ATTN_K_TILE32; return launch_attn32<T, 5, 5, false>(d, st); }
+    // 64 queries per wave where that still leaves two 256-query blocks per CU: the kernel is bound by LDS reads of the K / V
+    // fragments (tool build with MFMAs, v_exp and row max removed: 265 of 448 us), and a fragment then serves two blocks
+    if (d.d == 40 && k.qb == 2 && wg256 >= k.big_thr) return tiled(ATTN_K_TILE32_2BLOCKS, 256, 64, 256, attn_tile32_lds(3, 3));
+    // measured (tools/attn_bench.py, 14 x 8 x 4096^2): head_dim 40 476 -> 449 us; head_dim 80 is no faster (189 VGPRs,
+    // two waves per SIMD instead of three) and stays on the 16x16 kernel unless asked for (ES_ATTN32=2, tests)
+    if (d.d == 40) return tiled(ATTN_K_TILE32, 128, 32, 256, attn_tile32_lds(3, 3));
+    if (d.d == 80 && k.attn32 == 2) return tiled(ATTN_K_TILE32, 128, 32, 256, attn_tile32_lds(5, 5));
   }
-  // (64 queries per wave was measured slower: 309 registers -> one wave per SIMD)
-  attn_last_kernel = big && (d.d == 40 || d.d == 48 || d.d == 80) ? ATTN_K_GENERIC32 : ATTN_K_GENERIC16;    // QF = 2 | 1 below
+  // 3. the generic kernel: four waves of 16 * QF queries
   switch (d.d) {
-    case 8: return launch_attn<T, 1, 1, 2, 64, true>(d, st);
-    case 16: return launch_attn<T, 1, 1, 2, 64>(d, st);
-    case 24: return launch_attn<T, 1, 2, 2, 64, true>(d, st);
-    case 32: return launch_attn<T, 1, 2, 2, 64>(d, st);
-    case 40: return big ? launch_attn<T, 2, 3, 2, 64, true>(d, st) : launch_attn<T, 2, 3, 1, 64, true>(d, st);
-    case 48: return big ? launch_attn<T, 2, 3, 2, 64>(d, st) : launch_attn<T, 2, 3, 1, 64>(d, st);
-    case 64: return launch_attn<T, 2, 4, 2, 64>(d, st);
-    case 80: return big ? launch_attn<T, 3, 5, 2, 64>(d, st) : launch_attn<T, 3, 5, 1, 64>(d, st);
-    case 128: return launch_attn<T, 4, 8, 2, 64>(d, st);
-    case 160: return launch_attn<T, 5, 10, 2, 64>(d, st);
-    case 512: return launch_attn<T, 16, 32, 1, 32>(d, st);
-    default: return -3;
+#define X(D, KS, DF, QFB, QFS, KVT, ONES) \
+  case D: { const int qf = big ? QFB : QFS; return tiled(attn_generic_id(KS, DF, qf), 64 * qf, 16 * qf, 256, attn_generic_lds(KS, DF, KVT)); }
+    ATTN_GENERIC_TABLE(X)
+#undef X
   }
+  return r;                           // a width without a kernel: ATTN_K_NONE (attn_check_geometry refuses it)
+}
+
+// which kernel the last es_attention launch of this process went to (es_attention_last_kernel: tests assert the variant they mean to run);
+// written by the launchers from their OWN template arguments, never copied from the route
+int attn_last_kernel = ATTN_K_NONE;
+
+int attn_launched() { return hipGetLastError() == hipSuccess ? 0 : -2; }
+
+template <typename T, int KS, int DF, bool ONES>
+int launch_attn_kvres(const es_attn_desc& d, const AttnRoute& r, hipStream_t st) {
+  attn_last_kernel = ATTN_K_KVRES;
+  auto kfn = attention_kvres_kernel<T, KS, DF, ONES>;
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, ATTN_KVRES_LDS_MAX);
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(kfn, dim3(r.grid_x, r.grid_y, r.grid_z), dim3(r.threads), r.lds, st, d, r.qper);
+  return attn_launched();
+}
+
+template <typename T, int QB>
+int launch_attn40pp(const es_attn_desc& d, const AttnRoute& r, hipStream_t st) {
+  attn_last_kernel = QB == 2 ? ATTN_K_PP64 : ATTN_K_PP32;
+  hipLaunchKernelGGL((attention40pp_kernel<T, QB>), dim3(r.grid_x, r.grid_y, r.grid_z), dim3(r.threads), r.lds, st, d);
+  return attn_launched();
+}
+
+template <typename T, int KS, int DF, bool ONES, int QB = 1>
+int launch_attn32(const es_attn_desc& d, const AttnRoute& r, hipStream_t st) {
+  attn_last_kernel = QB == 2 ? ATTN_K_TILE32_2BLOCKS : ATTN_K_TILE32;
+  auto kfn = attention32_kernel<T, KS, DF, ONES, QB>;
+  hipLaunchKernelGGL(kfn, dim3(r.grid_x, r.grid_y, r.grid_z), dim3(r.threads), r.lds, st, d);
+  return attn_launched();
+}
+
+template <typename T, int KS, int DF, int QF, int KVT, bool ONES>
+int launch_attn(const es_attn_desc& d, const AttnRoute& r, hipStream_t st) {
+  attn_last_kernel = attn_generic_id(KS, DF, QF);
+  auto kfn = attention_kernel<T, KS, DF, QF, KVT, ONES>;
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, r.lds);
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(kfn, dim3(r.grid_x, r.grid_y, r.grid_z), dim3(r.threads), r.lds, st, d);
+  return attn_launched();
+}
+
+template <typename T>
+int dispatch(const es_attn_desc& d, hipStream_t st) {
+  const AttnRoute r = attn_route(d, attn_knobs());
+  switch (r.kernel) {
+    case ATTN_K_KVRES: return d.d == 40 ? launch_attn_kvres<T, 3, 3, true>(d, r, st) : launch_attn_kvres<T, 5, 5, false>(d, r, st);
+    case ATTN_K_PP64: return launch_attn40pp<T, 2>(d, r, st);
+    case ATTN_K_PP32: return launch_attn40pp<T, 1>(d, r, st);
+    case ATTN_K_TILE32_2BLOCKS: return launch_attn32<T, 3, 3, true, 2>(d, r, st);
+    case ATTN_K_TILE32: return d.d == 40 ? launch_attn32<T, 3, 3, true>(d, r, st) : launch_attn32<T, 5, 5, false>(d, r, st);
+    case ATTN_K_GENERIC32:
+    case ATTN_K_GENERIC16:
+      switch (d.d) {
+#define X(D, KS, DF, QFB, QFS, KVT, ONES) \
+  case D: return r.q_per_wave == 16 * QFB ? launch_attn<T, KS, DF, QFB, KVT, ONES>(d, r, st) : launch_attn<T, KS, DF, QFS, KVT, ONES>(d, r, st);
+        ATTN_GENERIC_TABLE(X)
+#undef X
+      }
+  }
+  return -3;
+}
+
+// the checks of es_attention that need no pointer: null = the geometry can be launched, else the refusal's text
+const char ATTN_BAD_HEAD_DIM[] = "es_attention: unsupported head_dim (8,16,24,32,40,48,64,80,128,160,512)";
+
+const char* attn_check_geometry(const es_attn_desc* d) {
+  if (d->d % 8 || d->ldq % 8 || d->ldk % 8 || d->ldv % 8 || d->ldo % 4) return "es_attention: d and strides must be multiples of 8";
+  if (d->Sq < 1 || d->Skv < 1 || d->N < 1 || d->heads < 1) return "es_attention: empty problem";
+  {   // the head widths dispatch() has a kernel for - checked HERE so that a dry recording (es_load_weights) rejects what a launch would
+    bool ok = false;
+#define X(D, KS, DF, QFB, QFS, KVT, ONES) ok = ok || d->d == D;
+    ATTN_GENERIC_TABLE(X)
+#undef X
+    if (!ok) return ATTN_BAD_HEAD_DIM;
+  }
+  // the kernels address K and V through buffer resources with a 32-bit byte range ((Skv - 1) * ld + d) * 2 and step their 32-bit tile
+  // offsets up to two 64-key tiles past the last key: both must stay below 2^31
+  const long long ldkv[2] = {d->ldk, d->ldv};
+  for (long long ld : ldkv) {
+    if (ld < d->d) return "es_attention: a k / v row stride below head_dim";
+    const long long range = ((long long)(d->Skv - 1) * ld + d->d) * 2, steps = ((long long)d->Skv + 2 * 64) * ld * 2;
+    if (range >= (1ll << 31) || steps >= (1ll << 31))
+      return "es_attention: k / v too long for 32-bit buffer offsets ((Skv + 128) * ld * 2 must stay below 2^31)";
+  }
+  return nullptr;
 }
 
 }  // namespace
@@ -1277,34 +1382,25 @@ extern "C" int es_attn_debug_read(unsigned long long* host16) {
 
 extern "C" int es_attention_last_kernel(void) { return attn_last_kernel; }
 
-extern "C" int es_attention_set_kvres(int on) { const int prev = attn_kvres; attn_kvres = on; return prev; }
+extern "C" int es_attention_set_kvres(int on) { const int prev = attn_knobs().kvres; attn_knobs().kvres = on; return prev; }
+
+extern "C" void es_attention_knobs(es_attn_knobs* out) { *out = attn_knobs(); }
+
+extern "C" int es_attention_route(const es_attn_desc* d, const es_attn_knobs* knobs, int32_t out[ES_ATTN_ROUTE_FIELDS]) {
+  if (const char* why = attn_check_geometry(d)) { es_set_error(why); return -1; }
+  const AttnRoute r = attn_route(*d, knobs ? *knobs : attn_knobs());
+  const int32_t v[ES_ATTN_ROUTE_FIELDS] = {r.kernel, r.q_per_wg, r.q_per_wave, r.grid_x, r.grid_y, r.grid_z, r.threads, r.lds, r.qper};
+  for (int i = 0; i < ES_ATTN_ROUTE_FIELDS; ++i) out[i] = v[i];
+  return 0;
+}
 
 extern "C" int es_attention(const es_attn_desc* d, void* stream) {
   if (!d->q || !d->k || !d->v || !d->o) { es_set_error("es_attention: null pointer"); return -1; }
-  if (d->d % 8 || d->ldq % 8 || d->ldk % 8 || d->ldv % 8 || d->ldo % 4) { es_set_error("es_attention: d and strides must be multiples of 8"); return -1; }
-  if (d->Sq < 1 || d->Skv < 1 || d->N < 1 || d->heads < 1) { es_set_error("es_attention: empty problem"); return -1; }
-  {   // the head widths dispatch() has a kernel for - checked HERE so that a dry recording (es_load_weights) rejects what a launch would
-    static const int ok_d[] = {8, 16, 24, 32, 40, 48, 64, 80, 128, 160, 512};
-    bool ok = false;
-    for (int v : ok_d) ok = ok || d->d == v;
-    if (!ok) { es_set_error("es_attention: unsupported head_dim (8,16,24,32,40,48,64,80,128,160,512)"); return -3; }
-  }
-  {   // the kernels address K and V through buffer resources with a 32-bit byte range ((Skv - 1) * ld + d) * 2 and step their 32-bit tile
-      // offsets up to two 64-key tiles past the last key: both must stay below 2^31
-    const long long ldkv[2] = {d->ldk, d->ldv};
-    for (long long ld : ldkv) {
-      if (ld < d->d) { es_set_error("es_attention: a k / v row stride below head_dim"); return -1; }
-      const long long range = ((long long)(d->Skv - 1) * ld + d->d) * 2, steps = ((long long)d->Skv + 2 * 64) * ld * 2;
-      if (range >= (1ll << 31) || steps >= (1ll << 31)) {
-        es_set_error("es_attention: k / v too long for 32-bit buffer offsets ((Skv + 128) * ld * 2 must stay below 2^31)");
-        return -1;
-      }
-    }
-  }
+  if (const char* why = attn_check_geometry(d)) { es_set_error(why); return why == ATTN_BAD_HEAD_DIM ? -3 : -1; }
   ES_PLAN_RECORD(ES_OP_ATTENTION, d, sizeof(*d));       // after validation: a rejected call never enters a recording plan
   hipStream_t st = (hipStream_t)stream;
   int rc = d->dtype == ES_F16 ? dispatch<f16>(*d, st) : dispatch<bf16>(*d, st);
-  if (rc == -3) es_set_error("es_attention: unsupported head_dim (8,16,24,32,40,48,64,80,128,160,512)");
+  if (rc == -3) es_set_error(ATTN_BAD_HEAD_DIM);
   else if (rc) es_set_error("es_attention: launch failed");
   return rc;
 }

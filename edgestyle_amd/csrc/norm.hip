@@ -424,12 +424,26 @@ struct GnRoute {
   size_t lds_slab, lds_stats, lds_apply;
 };
 
+// the two switches of the route, read from the environment once per process, on first use
+struct GnKnobs {
+  bool slab;                                  // ES_GN_SLAB=0 (tuning switch): the two-launch form everywhere
+  bool legacy;                                // ES_GN_LEGACY=1 (tool switch): the apply pass in its round-2 geometry
+};
+
+const GnKnobs& gn_knobs() {
+  static const GnKnobs knobs = [] {
+    const char* slab = getenv("ES_GN_SLAB");
+    const char* legacy = getenv("ES_GN_LEGACY");
+    return GnKnobs{!(slab && slab[0] == '0'), legacy && legacy[0] == '1'};
+  }();
+  return knobs;
+}
+
 GnRoute gn_route(const es_gn_desc& d) {
   GnRoute r{};
   const int C = d.C1 + d.C2;
   int cpt = 0;
-  static const bool slab_on = !(getenv("ES_GN_SLAB") && getenv("ES_GN_SLAB")[0] == '0');   // tuning switch
-  const int gpb = (slab_on && d.ext_chunks <= 0 && !d.stats_only) ? gn_slab_gpb(d, cpt) : 0;
+  const int gpb = (gn_knobs().slab && d.ext_chunks <= 0 && !d.stats_only) ? gn_slab_gpb(d, cpt) : 0;
   if (gpb) {
     const int W = gpb * (C / d.groups);
     r.slab = 1;
@@ -452,7 +466,7 @@ GnRoute gn_route(const es_gn_desc& d) {
   // workgroups per sample: every workgroup first reduces the partials and builds the scale / shift tables (~2 us), so a thread
   // should stream more than one round of loads behind that prologue - 16 items where that still leaves >= 1024 workgroups for the
   // chip, else 8, else 4 (tools/norm_bench.py, 14 x 64^2 x 320: 32.1 / 27.7 / 28.5 us for 4 / 8 / 16; 112 samples: 215 / 188 / 180)
-  static const bool legacy = getenv("ES_GN_LEGACY") && getenv("ES_GN_LEGACY")[0] == '1';     // tool switch: the round-2 geometry
+  const bool legacy = gn_knobs().legacy;
   int ipt = GNU;
   if (!legacy)
     for (int cand : {16, 8}) if (((total + 256 * cand - 1) / (256 * cand)) * d.N >= 1024) { ipt = cand; break; }
@@ -527,11 +541,10 @@ extern "C" int es_group_norm_chunks(int HW) {          // pixel chunks per sampl
 
 extern "C" int es_group_norm_is_slab(int HW, int C, int groups) {
   if (HW < 1 || C < 8 || groups < 1 || C % groups) return 0;
-  static const bool slab_on = !(getenv("ES_GN_SLAB") && getenv("ES_GN_SLAB")[0] == '0');
   es_gn_desc d{};
   d.HW = HW; d.C1 = C; d.groups = groups;
   int cpt = 0;
-  return slab_on && gn_slab_gpb(d, cpt) ? 1 : 0;
+  return gn_knobs().slab && gn_slab_gpb(d, cpt) ? 1 : 0;
 }
 
 // the checks of es_group_norm that need no pointer: null = the geometry can be launched, *r then holds its route

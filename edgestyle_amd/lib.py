@@ -76,6 +76,10 @@ class AttnDesc(C.Structure):
     ]
 
 
+class AttnKnobs(C.Structure):       # es_attn_knobs
+    _fields_ = [("big_thr", C.c_int64), ("kvres", C.c_int32), ("attn32", C.c_int32), ("qb", C.c_int32), ("pp", C.c_int32)]
+
+
 class GnDesc(C.Structure):
     _fields_ = [
         ("x", C.c_void_p), ("x2", C.c_void_p), ("out", C.c_void_p),
@@ -179,6 +183,7 @@ ROUTE_CONV_GEMM, ROUTE_LINEAR_XS = 0, 1
 XS_FORM_KC_MASK, XS_FORM_GEGLU, XS_FORM_LN, XS_FORM_RES, XS_FORM_PP, XS_FORM_GN = 0xFF, 0x100, 0x200, 0x400, 0x800, 0x1000
 GN_FORM_SLAB, GN_FORM_TWO_LAUNCHES = 1, 2        # ES_GN_FORM_*
 GN_ROUTE_FIELDS = ("form", "gpb", "slots", "cpt", "ppb", "nchunk", "ps", "lanes", "blocks", "ipt", "general", "lds")     # ES_GN_ROUTE_*
+ATTN_ROUTE_FIELDS = ("kernel", "q_per_wg", "q_per_wave", "grid_x", "grid_y", "grid_z", "threads", "lds", "qper")               # ES_ATTN_ROUTE_*
 
 # every symbol include/edgestyle_hip.h declares: (name, restype, argtypes)
 _P, _I, _F, _L = C.c_void_p, C.c_int, C.c_float, C.c_int64
@@ -195,6 +200,8 @@ SYMBOLS = {
     "es_attention": (C.c_int, [C.POINTER(AttnDesc), _P]),
     "es_attention_set_kvres": (C.c_int, [_I]),
     "es_attention_last_kernel": (C.c_int, []),
+    "es_attention_knobs": (None, [C.POINTER(AttnKnobs)]),
+    "es_attention_route": (C.c_int, [C.POINTER(AttnDesc), C.POINTER(AttnKnobs), C.POINTER(C.c_int32)]),
     "es_group_norm": (C.c_int, [C.POINTER(GnDesc), _P]),
     "es_group_norm_partials_bytes": (C.c_size_t, [_I, _I]),
     "es_group_norm_is_slab": (C.c_int, [_I, _I, _I]),
@@ -335,3 +342,14 @@ def group_norm_route(N: int, HW: int, C1: int, C2: int, groups: int, stats_only:
     out = (C.c_int32 * len(GN_ROUTE_FIELDS))()
     check(load().es_group_norm_route(C.byref(d), out), "es_group_norm_route")
     return dict(zip(GN_ROUTE_FIELDS, out))
+
+
+def attention_route(N: int, heads: int, Sq: int, Skv: int, d: int, *, dtype: int = ES_F16, knobs: "AttnKnobs | None" = None, ld=None) -> dict:
+    """es_attention_route as a dict keyed by ATTN_ROUTE_FIELDS (raises where es_attention would refuse the geometry).  knobs None: the
+    process's own (environment and es_attention_set_kvres).  ld None: dense rows of heads * d elements, else the row stride of q | k | v | o."""
+    a = AttnDesc()
+    a.N, a.heads, a.Sq, a.Skv, a.d, a.dtype = N, heads, Sq, Skv, d, dtype
+    a.ldq = a.ldk = a.ldv = a.ldo = heads * d if ld is None else ld
+    out = (C.c_int32 * len(ATTN_ROUTE_FIELDS))()
+    check(load().es_attention_route(C.byref(a), None if knobs is None else C.byref(knobs), out), "es_attention_route")
+    return dict(zip(ATTN_ROUTE_FIELDS, out))

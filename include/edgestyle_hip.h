@@ -27,7 +27,8 @@ enum { ES_ACT_NONE = 0, ES_ACT_SILU = 1, ES_ACT_GEGLU = 2 };
  * projection); es_conv_gemm8p_form_ok, es_ctx_graph_hazard, es_linear_xs_set_pp, es_attention_set_kvres, es_set_operand_limit,
  * es_group_norm_chunks, es_clock_probe.  Context images carry the version and are rebuilt across it.
  * (Host-only helpers that no plan or image records - es_plan_gemm_choice, es_linear_xs_eligible, es_linear_xs_last_form, es_launch_choose and its siblings
- * es_launch_route / es_launch_gn_fold / es_launch_gn_handover / es_launch_wide_stream - come and go without a new version.) */
+ * es_launch_route / es_launch_gn_fold / es_launch_gn_handover / es_launch_wide_stream, es_attention_route, es_attention_knobs - come and go
+ * without a new version.) */
 #define ES_ABI_VERSION 7
 int es_abi_version(void);
 /* sizeof the descriptor structs as compiled (0 gemm, 1 attn, 2 gn, 3 fusion, 4 ln, 5 xs): lets a binding verify its mirror */
@@ -202,12 +203,40 @@ typedef struct {
 int es_attention(const es_attn_desc* d, void* stream);
 /* tool / test knob: launches with Skv <= 96 and head_dim 40 | 80 (the text-token cross-attention of the two shallow UNet levels) on the
  * K/V-resident kernel - 0 never, 1 (default; ES_ATTN_KVRES in the environment) where it wins (>= 12 samples at head_dim 40, >= 64 at 80:
- * profiles/r05_xattn_bench.txt), 2 every eligible launch.  Returns the previous setting. */
+ * profiles/r05_xattn_bench.txt), 2 every eligible launch.  Returns the previous setting.  It edits `kvres` of the process's knobs below. */
 int es_attention_set_kvres(int on);
-/* test query: the kernel the last es_attention launch of this process went to - 1 generic tile (16 queries per wave), 2 generic tile
- * (32 queries per wave: head_dim 40 | 48 | 80 in large launches), 3 32x32 score tile, 4 32x32 score tile with two query blocks per wave,
- * 5 | 6 head_dim-40 ping-pong kernel with 32 | 64 queries per wave, 7 K/V-resident; 0 before the first launch. */
+/* test query: the kernel the last es_attention launch of this process went to - 1 generic tile, 2 generic tile with 32 queries per wave at
+ * head_dim 40 | 48 | 80 in large launches (1 also names the widths that ALWAYS run 32 per wave - 8-32, 64, 128, 160: ES_ATTN_ROUTE_Q_PER_WAVE
+ * states the geometry), 3 32x32 score tile, 4 32x32 score tile with two query blocks per wave, 5 | 6 head_dim-40 ping-pong kernel with
+ * 32 | 64 queries per wave, 7 K/V-resident; 0 before the first launch.  Set by the launcher from the template arguments it instantiates. */
 int es_attention_last_kernel(void);
+/* The switches that bend the choice of kernel (tools, tests).  The process's own are read from the environment once, on first use - the
+ * first launch, route query or es_attention_set_kvres (ES_ATTN_KVRES too: earlier versions read that one when the library was loaded). */
+typedef struct {
+  int64_t big_thr;   /* ES_ATTN_BIG, 512: blocks of 128 (256) queries from which a launch runs 32 (64) queries per wave */
+  int32_t kvres;     /* ES_ATTN_KVRES, 1: see es_attention_set_kvres */
+  int32_t attn32;    /* ES_ATTN32, 1: 0 = no 32x32 score tile (nor what builds on it: 4 - 6), 2 = also for head_dim 80 */
+  int32_t qb;        /* ES_ATTN_QB, 2: 1 = never two query blocks per wave (kernel 4) */
+  int32_t pp;        /* ES_ATTN_PP, -1: ping-pong kernel 0 = off, 1 | 2 = 32 | 64 queries per wave, -1 = 32 from 256 blocks of 256 queries on */
+} es_attn_knobs;
+void es_attention_knobs(es_attn_knobs* out);      /* host-only: a copy of the process's knobs */
+/* host-only query (tests, tools): the launch es_attention would make for this descriptor (N, heads, Sq, Skv, d and the row strides are read;
+ * no pointer is, and NULL pointers are accepted), computed by the launcher's own code: es_attention switches on this kernel id and launches
+ * with this grid, block, LDS size and strip length.  knobs NULL: the process's own; else used as given.  0, or -1 with es_last_error()
+ * where es_attention would refuse the geometry (same texts). */
+enum {
+  ES_ATTN_ROUTE_KERNEL = 0,      /* the ids of es_attention_last_kernel */
+  ES_ATTN_ROUTE_Q_PER_WG = 1,    /* queries a workgroup covers (K/V-resident: its strip, = ES_ATTN_ROUTE_QPER) */
+  ES_ATTN_ROUTE_Q_PER_WAVE = 2,  /* queries a wave holds at a time: 16 | 32 | 64 (K/V-resident: the 32-query blocks it walks its strip in) */
+  ES_ATTN_ROUTE_GRID_X = 3,
+  ES_ATTN_ROUTE_GRID_Y = 4,
+  ES_ATTN_ROUTE_GRID_Z = 5,
+  ES_ATTN_ROUTE_THREADS = 6,     /* threads per workgroup */
+  ES_ATTN_ROUTE_LDS = 7,         /* dynamic LDS bytes */
+  ES_ATTN_ROUTE_QPER = 8,        /* K/V-resident kernel: queries per strip; 0 otherwise */
+  ES_ATTN_ROUTE_FIELDS = 9
+};
+int es_attention_route(const es_attn_desc* d, const es_attn_knobs* knobs, int32_t out[ES_ATTN_ROUTE_FIELDS]);
 
 /* GroupNorm (+SiLU) over NHWC with optional channel-concat of two sources.
  * Replaces torch group_norm + silu of ResnetBlock2D.norm1/norm2, conv_norm_out, Transformer2DModel.norm.

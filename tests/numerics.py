@@ -1384,6 +1384,53 @@ def attn_design_err(q, k, v, heads, dtype, ref64, scale=None, rowsum="fp32"):
     return max(row_err(attn_base_alg(q, k, v, heads, dtype, scale, offset=o, rowsum=rowsum), ref64) for o in (0.0, LAZY))
 
 
+ATTN_WIDTHS = (8, 16, 24, 32, 40, 48, 64, 80, 128, 160, 512)            # the head widths es_attention has a kernel for
+ATTN_KNOBS = dict(kvres=1, big_thr=512, attn32=1, qb=2, pp=-1)          # ES_ATTN_KVRES | _BIG | ATTN32 | _QB | _PP unset
+ATTN_ROUTE_KEYS = ("kernel", "q_per_wg", "q_per_wave", "grid_x", "grid_y", "grid_z", "threads", "lds", "qper")
+
+
+def attn_route(N, heads, Sq, Skv, d, knobs=None):
+    """Python mirror of attn_route() in csrc/attention.hip, keyed like lib.ATTN_ROUTE_FIELDS: which kernel (es_attention_last_kernel's ids)
+    a launch goes to under `knobs` (a dict like ATTN_KNOBS; None: the defaults), with which grid, LDS size and - K/V-resident kernel -
+    strip length.  Written from the rules, not from the library's table (the generic kernel's tile is a formula of d here); the tables of
+    tests/test_attention_gpu.py are placed with it without a GPU, and tests/test_host_cpu.py holds it to es_attention_route."""
+    k = ATTN_KNOBS if knobs is None else knobs
+    assert d in ATTN_WIDTHS and min(N, heads, Sq, Skv) >= 1
+    cdiv = lambda a, b: (a + b - 1) // b
+
+    def tiled(kernel, q_per_wg, q_per_wave, threads, lds):
+        return dict(kernel=kernel, q_per_wg=q_per_wg, q_per_wave=q_per_wave, grid_x=cdiv(Sq, q_per_wg), grid_y=heads, grid_z=N, threads=threads,
+                    lds=lds, qper=0)
+
+    if k["kvres"] != 0 and Skv <= 96 and Sq >= 64 and d in (40, 80):
+        groups = cdiv(heads, 8) * N
+        if k["kvres"] == 2 or groups >= (12 if d == 40 else 64):
+            blocks32 = cdiv(Sq, 32)
+            strips = max(1, min(256 // groups, blocks32))
+            qper = cdiv(blocks32, strips) * 32
+            return dict(kernel=7, q_per_wg=qper, q_per_wave=32, grid_x=cdiv(Sq, qper), grid_y=cdiv(heads, 8), grid_z=N, threads=512,
+                        lds=3 * 32 * (min(heads, 8) * d * 2 + 16), qper=qper)          # three tiles of 32 whole rows (+ 16 B): Q twice, O
+    big = cdiv(Sq, 128) * heads * N >= k["big_thr"]
+    ring32 = lambda: 2 * 2 * 64 * (16 * cdiv(d, 16) * 2 + 16)           # two slots of a 64-key K tile and V tile, rows of d padded to 16 (+ 16 B)
+    if big and k["attn32"] != 0:
+        wg256 = cdiv(Sq, 256) * heads * N
+        if d == 40 and k["pp"] != 0 and Skv % 64 == 0 and Skv >= 128:
+            if k["pp"] == 2:
+                return tiled(6, 512, 64, 512, ring32())
+            if k["pp"] == 1 or (k["pp"] == -1 and wg256 >= 256):
+                return tiled(5, 256, 32, 512, ring32())
+        if d == 40 and k["qb"] == 2 and wg256 >= k["big_thr"]:
+            return tiled(4, 256, 64, 256, ring32())
+        if d == 40 or (d == 80 and k["attn32"] == 2):
+            return tiled(3, 128, 32, 256, ring32())
+    # the generic kernel: four waves; 16 queries per wave only at 40 | 48 | 80 in launches that are not big, and at 512
+    two_forms = d in (40, 48, 80)
+    w = 16 if d == 512 or (two_forms and not big) else 32
+    kvt, ks, df = (32 if d == 512 else 64), cdiv(d, 32), cdiv(d, 16)
+    lds = (2 if ks <= 5 else 1) * kvt * ((32 * ks * 2 + 16) + (16 * df * 2 + 16))
+    return tiled(2 if (big and two_forms) else 1, 4 * w, w, 256, lds)
+
+
 ATTN_INPUT_KINDS = ("randn", "shift-300", "shift+300", "last_key_decides", "one_loud_query", "loud_values_2e4")
 
 

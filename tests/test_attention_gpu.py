@@ -16,7 +16,9 @@ with one key, the output IS v[:, 0].
 
 TABLE is no cross product: REQUIRED lists, per variant, the classes it has to meet (query raggedness against its workgroup and wave
 sizes, key raggedness against its tile, input classes, dtypes, head widths, dispatcher edges); `coverage()` checks that, is asserted at
-import and prints the matrix.  A variant's precondition shapes its rows, nothing is skipped at run time."""
+import and prints the matrix.  A variant's precondition shapes its rows, nothing is skipped at run time.  Which kernel a row goes to, and the
+K/V-resident kernel's strips, are asked of nm.attn_route (the Python mirror of the library's route, held to it in tests/test_host_cpu.py);
+test_attention_route_is_the_launch checks in this process that the kernel the library's route names is the kernel that then runs."""
 import os
 import subprocess
 import sys
@@ -53,13 +55,20 @@ KVRES_QUERIES = (64, 65, 95, 97)
 KVRES_HEADS = (1, 6, 8, 9, 12)                          # 9: the second workgroup of eight heads has a single one
 
 
+ENV_KNOB = dict(ES_ATTN32="attn32", ES_ATTN_BIG="big_thr", ES_ATTN_PP="pp", ES_ATTN_QB="qb")
+
+
+def row_knobs(r, **kw):
+    """the knobs a row's child runs under: its variant's environment and its own es_attention_set_kvres, as nm.attn_route takes them"""
+    k = dict(nm.ATTN_KNOBS, kvres=r["kvres"], **{ENV_KNOB[name]: int(val) for name, val in ATTN_KERNELS[r["variant"]][0].items()})
+    return dict(k, **kw)
+
+
 def kvres_strips(N, heads, Sq):
-    """launch_attn_kvres' rule: (queries per strip, strips)"""
-    per_strip = (heads + 7) // 8 * N
-    blocks32 = (Sq + 31) // 32
-    strips = max(1, min(256 // per_strip, blocks32))
-    qper = (blocks32 + strips - 1) // strips * 32
-    return qper, (Sq + qper - 1) // qper
+    """the K/V-resident kernel's strip rule (nm.attn_route, the mirror of csrc/attention.hip's): (queries per strip, strips)"""
+    route = nm.attn_route(N, heads, Sq, 77, 40, dict(nm.ATTN_KNOBS, kvres=2))
+    assert route["kernel"] == ATTN_KERNEL_ID["kv_resident"]
+    return route["qper"], route["grid_x"]
 
 
 def _row(variant, Sq, Skv, kind, d=40, bf=False, N=2, heads=2, scale=None, kvres=None, expect=None, batch_slice=False, tag=()):
@@ -154,21 +163,24 @@ def row_id(r):
 
 
 def validate(r):
-    """a row is eligible for the kernel it names (the dispatcher's rules, restated) and stays inside the size limits"""
+    """a row goes to the kernel it names - by the dispatcher's rules as nm.attn_route restates them, under the knobs its child runs with - for
+    the reason it is in the table for, with that kernel's geometry, and stays inside the size limits"""
     ex, d, Sq, Skv = r["expect"], r["d"], r["Sq"], r["Skv"]
     assert Sq <= 600 and Skv <= 320 and r["heads"] <= 12, row_id(r)
     assert r["N"] <= 3 or (r["heads"] == 1 and r["variant"] == "kv_resident" and (r["kvres"] == 1 or "qper" in r["tag"])), row_id(r)
     assert d in ALL_WIDTHS and (Skv >= 2 or r["kind"] == "randn") and (not r["batch_slice"] or r["N"] == 3), row_id(r)
-    if ex == "kv_resident":
-        groups = (r["heads"] + 7) // 8 * r["N"]
-        assert Skv <= 96 and Sq >= 64 and d in (40, 80) and (r["kvres"] == 2 or (r["kvres"] == 1 and groups >= (12 if d == 40 else 64))), row_id(r)
-    elif r["variant"] == "kv_resident":
-        groups = (r["heads"] + 7) // 8 * r["N"]
-        assert Skv > 96 or Sq < 64 or (r["kvres"] == 1 and groups < (12 if d == 40 else 64)), row_id(r)
-    if ex.startswith("attention40pp"):
-        assert d == 40 and Skv % 64 == 0 and Skv >= 128, row_id(r)
+    shape = (r["N"], r["heads"], Sq, Skv, d)
+    route = nm.attn_route(*shape, row_knobs(r))
+    assert route["kernel"] == ATTN_KERNEL_ID[ex], (row_id(r), route)
+    g = GEOMETRY[ex]        # (kernel id 1 runs 32 queries per wave at the widths that have no 16-query form: GEOMETRY states the 16-query one)
+    assert g["B"] is None or (ex == "generic" and route["q_per_wave"] == 32) or (route["q_per_wg"], route["q_per_wave"]) == (g["B"], g["w"]), (row_id(r), route)
+    if r["variant"] == "kv_resident" and ex != "kv_resident":
+        # an edge row of the K/V-resident rule: a shape it never takes (key or query count), or one it takes only when forced and the row asks for 1
+        forced = nm.attn_route(*shape, row_knobs(r, kvres=2))["kernel"] == ATTN_KERNEL_ID["kv_resident"]
+        assert d in ATTN_KERNELS["kv_resident"][1] and (r["kvres"] == 1 or not forced), row_id(r)
     if r["variant"].startswith("attention40pp") and ex == "tile32_2blocks":
-        assert d == 40 and (Skv % 64 != 0 or Skv < 128), row_id(r)
+        # a fallback row: only the key count keeps it off the ping-pong kernel
+        assert nm.attn_route(r["N"], r["heads"], Sq, 128, d, row_knobs(r))["kernel"] == ATTN_KERNEL_ID[r["variant"]], row_id(r)
     if ex in ("generic", "generic_32q", "tile32") and r["variant"] == ex:
         assert d in ATTN_KERNELS[ex][1] or "width" in r["tag"], row_id(r)
     if "qper" in r["tag"]:
@@ -375,6 +387,43 @@ def test_attention_table_covers_every_class():
     matrix, missing = coverage()
     print(f"test_attention_gpu: {len(TABLE)} rows\n{matrix}")
     assert not missing
+
+
+# (N, heads, Sq, Skv, d), bf16, the kernel id under default knobs: the smallest shapes across the 512-block and 256-workgroup thresholds (kernel 6
+# is reachable through ES_ATTN_PP=2 alone: the children above)
+ROUTE_ROWS = [((1, 1, 17, 31, 8), False, 1), ((2, 8, 4096, 100, 80), False, 2), ((2, 8, 4096, 100, 40), False, 3), ((4, 8, 4096, 100, 40), False, 4),
+              ((2, 8, 4096, 128, 40), False, 5), ((2, 8, 4096, 128, 40), True, 5), ((12, 8, 64, 77, 40), False, 7)]
+
+
+def test_attention_route_is_the_launch():
+    """In this process, under its own knobs: what es_attention_route answers for a shape is what es_attention then launches
+    (es_attention_last_kernel is written by the launcher from its template arguments, the route is asked BEFORE the launch), the id is the one
+    the rules give under default knobs, and the output meets the required-tier bar against fp64."""
+    from edgestyle_amd import ops, lib
+    L = lib.load()
+    own = lib.AttnKnobs()
+    L.es_attention_knobs(own)
+    own = {name: getattr(own, name) for name in nm.ATTN_KNOBS}
+    if own != nm.ATTN_KNOBS:
+        print(f"test_attention_gpu: this process runs with knobs {own}, not the defaults: the literal kernel ids are not asserted")
+    fails = []
+    for shape, bf, want in ROUTE_ROWS:
+        N, heads, Sq, Skv, d = shape
+        dtype = torch.bfloat16 if bf else torch.float16
+        name = f"route N={N} heads={heads} Sq={Sq} Skv={Skv} d={d} {'bf16' if bf else 'fp16'}"
+        route = lib.attention_route(*shape, dtype=lib.ES_BF16 if bf else lib.ES_F16)
+        assert route == nm.attn_route(*shape, own), (name, route)
+        assert own != nm.ATTN_KNOBS or route["kernel"] == want, (name, route)
+        q, k, v = nm.attn_inputs("randn", N, heads, Sq, Skv, d, dtype, seed=11 * Sq + Skv + d)
+        y = ops.attention(q.to(dtype).to(DEV), k.to(dtype).to(DEV), v.to(dtype).to(DEV), heads).cpu()
+        ran = L.es_attention_last_kernel()
+        if ran != route["kernel"]:
+            fails.append(f"{name}: kernel {ran} ran, the route said {route['kernel']}")
+        ref = nm.attn_ref64(q, k, v, heads)
+        e_ref = nm.row_err(nm.attn_base_ref(q, k, v, heads, dtype), ref)
+        e_alg = nm.attn_design_err(q, k, v, heads, dtype, ref, rowsum="rounded" if nm.attn_ones(d) else "fp32")
+        judge(fails, f"attention {name}", y, ref, e_alg, e_ref, dtype)
+    done(fails)
 
 
 def report_rows():

@@ -833,6 +833,163 @@ def test_attention_refuses_operands_the_launch_cannot_read(monkeypatch):
         assert dry.size() == 6
 
 
+def _attn_knobs(**kw):
+    k = lib.AttnKnobs()
+    for name, val in kw.items():
+        setattr(k, name, val)
+    return k
+
+
+def _own_attn_knobs_are_the_defaults():
+    """the knobs of this process against the documented defaults; with an ES_ATTN_* variable set, nothing is asserted (and why is printed)"""
+    from tests import numerics as nm
+    own = lib.AttnKnobs()
+    lib.load().es_attention_knobs(own)
+    own = {name: getattr(own, name) for name in nm.ATTN_KNOBS}
+    set_here = sorted(v for v in ("ES_ATTN_KVRES", "ES_ATTN_BIG", "ES_ATTN32", "ES_ATTN_QB", "ES_ATTN_PP") if v in os.environ)
+    if set_here:
+        print(f"attention knobs: {set_here} set in this process's environment - its knobs {own} are not held to the defaults")
+        return False
+    assert own == nm.ATTN_KNOBS == dict(kvres=1, big_thr=512, attn32=1, qb=2, pp=-1), own
+    return True
+
+
+def test_attention_route_is_the_mirrors_answer_under_every_knob():
+    """es_attention_route (attn_route of csrc/attention.hip, which es_attention launches from) against the Python restatement of the rules
+    (tests/numerics.py attn_route) in every field, on a grid of geometries that brackets every threshold, under every setting of the five
+    switches - passed in, so the process's own knobs play no part."""
+    from tests import numerics as nm
+    L = lib.load()
+    assert lib.ATTN_ROUTE_FIELDS == nm.ATTN_ROUTE_KEYS
+    a, out = lib.AttnDesc(), (ctypes.c_int32 * len(lib.ATTN_ROUTE_FIELDS))()
+    knob_grid = [dict(kvres=kv, attn32=a32, pp=pp, qb=qb, big_thr=big)
+                 for kv in (0, 1, 2) for a32 in (0, 1, 2) for pp in (-1, 0, 1, 2) for qb in (1, 2) for big in (1, 512)]
+    knob_grid = [(k, _attn_knobs(**k)) for k in knob_grid]
+    kernels = set()
+    for N, heads in [(1, 1), (2, 8), (11, 1), (12, 1), (63, 1), (64, 1), (14, 8), (112, 8)]:
+        for d in nm.ATTN_WIDTHS:
+            for Sq in (1, 63, 64, 65, 127, 129, 255, 257, 4096):
+                for Skv in (1, 64, 77, 96, 97, 127, 128, 192, 4096):
+                    a.N, a.heads, a.Sq, a.Skv, a.d = N, heads, Sq, Skv, d
+                    a.ldq = a.ldk = a.ldv = a.ldo = heads * d
+                    for k, ck in knob_grid:
+                        assert L.es_attention_route(ctypes.byref(a), ctypes.byref(ck), out) == 0, (N, heads, Sq, Skv, d, L.es_last_error())
+                        want = nm.attn_route(N, heads, Sq, Skv, d, k)
+                        assert tuple(out) == tuple(want[f] for f in lib.ATTN_ROUTE_FIELDS), (N, heads, Sq, Skv, d, k, list(out), want)
+                        kernels.add(out[0])
+    assert kernels == {1, 2, 3, 4, 5, 6, 7}
+    # the helper and a NULL knobs pointer: the process's own knobs
+    own = lib.AttnKnobs()
+    L.es_attention_knobs(own)
+    own = {name: getattr(own, name) for name in nm.ATTN_KNOBS}
+    for shape in [(14, 8, 4096, 77, 40), (2, 8, 4096, 4096, 40), (2, 8, 1024, 1024, 80)]:
+        assert lib.attention_route(*shape) == nm.attn_route(*shape, own)
+        assert lib.attention_route(*shape, knobs=_attn_knobs(**dict(nm.ATTN_KNOBS, kvres=0))) == nm.attn_route(*shape, dict(nm.ATTN_KNOBS, kvres=0))
+
+
+def test_attention_knobs_default_and_follow_set_kvres():
+    """es_attention_knobs returns the documented defaults (ES_ATTN_* unset here), and es_attention_set_kvres edits that struct"""
+    L = lib.load()
+    _own_attn_knobs_are_the_defaults()
+    k = lib.AttnKnobs()
+    L.es_attention_knobs(k)
+    first = k.kvres
+    assert L.es_attention_set_kvres(2) == first
+    try:
+        L.es_attention_knobs(k)
+        assert k.kvres == 2 and lib.attention_route(2, 8, 4096, 77, 40)["kernel"] == 7
+        assert L.es_attention_set_kvres(0) == 2 and lib.attention_route(14, 8, 4096, 77, 40)["kernel"] != 7
+    finally:
+        L.es_attention_set_kvres(first)
+    L.es_attention_knobs(k)
+    assert k.kvres == first
+
+
+def test_attention_production_dispatch_table():
+    """Which kernel, on which grid, every attention launch of a 512 x 512 step goes to under default knobs, as both hosts issue them: 14
+    samples (batch 1: the grouped encoder pass) and 2 (the decoder), 112 and 16 at batch 8; self-attention at 64^2 / 32^2 / 16^2 / 8^2 tokens
+    with 8 heads of 40 / 80 / 160 / 160, the text cross-attention (77 keys) at the same levels, and the VAE's one head of 512 over 4096
+    tokens.  The literals are worked out from the rules in the header of csrc/attention.hip's host section, not read off the library;
+    DESIGN section 4 names the same choices: the ping-pong kernel (5) for the level-0 self-attention, K/V-resident (7) from 14 samples at
+    head_dim 40 and from 112 at head_dim 80, tiled kernels for the 2-sample decoder's cross-attention."""
+    if not _own_attn_knobs_are_the_defaults():
+        return
+    levels = [(4096, 40), (1024, 80), (256, 160), (64, 160)]
+    # self-attention: (kernel, grid x, threads) per level; grid y = 8 heads, grid z = N
+    self_attn = {
+        14: [(5, 16, 512), (2, 8, 256), (1, 2, 256), (1, 1, 256)],
+        2: [(5, 16, 512), (1, 16, 256), (1, 2, 256), (1, 1, 256)],          # 16 x 8 x 2 = 256 workgroups of 256 queries: still the ping-pong kernel
+        112: [(5, 16, 512), (2, 8, 256), (1, 2, 256), (1, 1, 256)],
+        16: [(5, 16, 512), (2, 8, 256), (1, 2, 256), (1, 1, 256)],
+    }
+    # cross-attention, 77 keys: (kernel, grid x, grid y, threads, queries per strip)
+    cross_attn = {
+        14: [(7, 16, 1, 512, 256), (2, 8, 8, 256, 0), (1, 2, 8, 256, 0), (1, 1, 8, 256, 0)],
+        2: [(3, 32, 8, 256, 0), (1, 16, 8, 256, 0), (1, 2, 8, 256, 0), (1, 1, 8, 256, 0)],
+        112: [(7, 2, 1, 512, 2048), (7, 2, 1, 512, 512), (1, 2, 8, 256, 0), (1, 1, 8, 256, 0)],
+        16: [(7, 16, 1, 512, 256), (2, 8, 8, 256, 0), (1, 2, 8, 256, 0), (1, 1, 8, 256, 0)],
+    }
+    for N in (14, 2, 112, 16):
+        for (S, d), (kernel, gx, threads), (xkernel, xgx, xgy, xthreads, qper) in zip(levels, self_attn[N], cross_attn[N]):
+            r = lib.attention_route(N, 8, S, S, d)
+            assert (r["kernel"], r["grid_x"], r["grid_y"], r["grid_z"], r["threads"], r["qper"]) == (kernel, gx, 8, N, threads, 0), (N, S, d, r)
+            r = lib.attention_route(N, 8, S, 77, d)
+            assert (r["kernel"], r["grid_x"], r["grid_y"], r["grid_z"], r["threads"], r["qper"]) == (xkernel, xgx, xgy, N, xthreads, qper), (N, S, d, r)
+    for N in (1, 8):        # the VAE's mid-block attention: 16 queries per wave, one K/V buffer of 32 keys
+        r = lib.attention_route(N, 1, 4096, 4096, 512)
+        assert (r["kernel"], r["q_per_wave"], r["grid_x"], r["grid_y"], r["grid_z"], r["threads"]) == (1, 16, 64, 1, N, 256), r
+        assert r["lds"] == 32 * (1024 + 16) + 32 * (1024 + 16)
+
+
+def test_attention_route_refuses_what_the_launch_refuses():
+    """es_attention_route and es_attention (dry recorder, host buffers) refuse the same geometries with the same texts - an unsupported
+    head_dim, strides that are no multiples of 8 or below head_dim, an empty problem, a K/V range past 2^31 - and the query reads no
+    pointer: NULL ones are fine."""
+    out = (ctypes.c_int32 * len(lib.ATTN_ROUTE_FIELDS))()
+    hostbuf = (ctypes.c_char * 4096)()
+
+    def desc(ptr, **kw):
+        a = lib.AttnDesc()
+        a.q = a.k = a.v = a.o = ptr
+        a.N, a.heads, a.Sq, a.Skv, a.d = 1, 1, 64, 4096, 40
+        a.ldq = a.ldk = a.ldv = a.ldo = 40
+        a.scale, a.dtype = 1.0, lib.ES_F16
+        for name, val in kw.items():
+            setattr(a, name, val)
+        return a
+    refused = [(dict(d=56, ldq=56, ldk=56, ldv=56, ldo=56), b"es_attention: unsupported head_dim (8,16,24,32,40,48,64,80,128,160,512)", -3),
+               (dict(d=44), b"es_attention: d and strides must be multiples of 8", -1),
+               (dict(ldk=44), b"es_attention: d and strides must be multiples of 8", -1),
+               (dict(ldk=32), b"es_attention: a k / v row stride below head_dim", -1),
+               (dict(ldv=32), b"es_attention: a k / v row stride below head_dim", -1),
+               (dict(Sq=0), b"es_attention: empty problem", -1), (dict(Skv=0), b"es_attention: empty problem", -1),
+               (dict(N=0), b"es_attention: empty problem", -1), (dict(heads=0), b"es_attention: empty problem", -1),
+               (dict(Skv=1 << 26), b"es_attention: k / v too long for 32-bit buffer offsets ((Skv + 128) * ld * 2 must stay below 2^31)", -1),
+               (dict(ldv=(1 << 30) // (4096 + 128) + 8), b"es_attention: k / v too long for 32-bit buffer offsets ((Skv + 128) * ld * 2 must stay below 2^31)", -1)]
+    with _DryPlan() as dry:
+        L = dry.L
+        assert L.es_attention_route(ctypes.byref(desc(None)), None, out) == 0 and out[0] != 0
+        assert L.es_attention(ctypes.byref(desc(None)), None) == -1 and L.es_last_error() == b"es_attention: null pointer"
+        assert L.es_attention(ctypes.byref(desc(ctypes.addressof(hostbuf))), None) == 0 and dry.size() == 1
+        for kw, text, rc in refused:
+            assert L.es_attention_route(ctypes.byref(desc(None, **kw)), None, out) == -1 and L.es_last_error() == text, (kw, L.es_last_error())
+            assert L.es_attention(ctypes.byref(desc(ctypes.addressof(hostbuf), **kw)), None) == rc and L.es_last_error() == text, (kw, L.es_last_error())
+            assert dry.size() == 1, kw
+        with pytest.raises(lib.EdgeStyleHipError, match="unsupported head_dim"):
+            lib.attention_route(1, 1, 64, 64, 56)
+        assert dry.size() == 1              # the query records nothing
+
+
+def test_attention_route_states_the_geometry_the_kernel_id_leaves_open():
+    """Kernel id 1 ("generic, 16 queries per wave") is also what head widths 8-32, 64, 128 and 160 report, which always run 32 queries per
+    wave: the route says which.  Default knobs, a launch far below the 512-block threshold."""
+    if not _own_attn_knobs_are_the_defaults():
+        return
+    r64, r40 = lib.attention_route(1, 1, 70, 77, 64), lib.attention_route(1, 1, 70, 77, 40)
+    assert (r64["kernel"], r64["q_per_wave"], r64["q_per_wg"], r64["grid_x"]) == (1, 32, 128, 1), r64
+    assert (r40["kernel"], r40["q_per_wave"], r40["q_per_wg"], r40["grid_x"]) == (1, 16, 64, 2), r40
+
+
 def _gn_two_launch_route(HW):
     """groups of ONE channel are never eligible for the slab form: the statistics pass's own geometry for this HW"""
     r = lib.group_norm_route(1, HW, 8, 0, 8)
