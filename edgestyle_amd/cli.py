@@ -59,6 +59,9 @@ def parse_args(argv: Optional[List[str]] = None):
     p.add_argument("--native_text_encoder", action="store_true",
                    help="encode the prompts on the GPU with the library's own CLIP text encoder (edgestyle_amd/text.py) instead of "
                         "with transformers on the host; needs the tokenizer/ and text_encoder/ directories")
+    p.add_argument("--native_prompt_picker", action="store_true",
+                   help="with --clip_model_name_or_path: pick the prompt on the GPU with the library's own CLIP image tower and scorer "
+                        "(edgestyle_amd/clip.py) - the directory's weights are read, transformers' forward is not run")
     p.add_argument("--tiny", action="store_true", help="with --random_init: width-reduced 128x128 config (plumbing demo)")
     return p.parse_args(argv)
 
@@ -182,14 +185,22 @@ def main(args):
         kw = dict(prompt_embeds=torch.randn(1, 77, d, generator=g) * 0.5, negative_prompt_embeds=torch.randn(1, 77, d, generator=g) * 0.5)
     else:
         prompt = args.prompt
-        if args.clip_model_name_or_path:                                                          # TT:52-55, TT:316
+        garment = os.path.join(args.target_path, "clothes", args.target_image_name)
+        if args.native_prompt_picker:
+            if not args.clip_model_name_or_path:
+                raise SystemExit("--native_prompt_picker needs --clip_model_name_or_path")
+            from .clip import NativeBestEmbeddings
+            be = NativeBestEmbeddings.from_pretrained(args.clip_model_name_or_path, vocab_file=args.prompt_vocab, dtype=weight_dtype, device=device)
+            prompt = be([Image.open(garment).convert("RGB")])[0]
+            be.close()
+        elif args.clip_model_name_or_path:                                                        # TT:52-55, TT:316
             from transformers import CLIPModel, CLIPProcessor
             from .prompts import BestEmbeddings
             clip = CLIPModel.from_pretrained(args.clip_model_name_or_path).eval()
             proc = CLIPProcessor.from_pretrained(args.clip_model_name_or_path)
             be = (BestEmbeddings.from_vocab_file(clip, proc, args.prompt_vocab) if args.prompt_vocab
                   else BestEmbeddings(clip, proc))
-            prompt = be([Image.open(os.path.join(args.target_path, "clothes", args.target_image_name)).convert("RGB")])[0]
+            prompt = be([Image.open(garment).convert("RGB")])[0]
         kw = dict(prompt=prompt + " " + args.prompt_text_to_add, negative_prompt=args.negative_prompt)
     for gs in np.linspace(1.0, 7.0, NUM_IMAGES):                                                  # TT:318, 326-359
         out = pipeline(guidance_scale=float(gs), image=conds, num_inference_steps=args.num_inference_steps,

@@ -23,14 +23,27 @@ namespace {
 
 constexpr int kPrecisionBits = 32 - 8 - 2;      // Pillow's PRECISION_BITS for 8-bit channels
 
+// Pillow's filters (Resample.c): the triangle of BILINEAR (support 1) and the Keys cubic of BICUBIC (a = -0.5, support 2)
+__host__ __device__ inline double filter_support(int filter) { return filter == ES_FILTER_BICUBIC ? 2.0 : 1.0; }
+__host__ __device__ inline double filter_weight(int filter, double x) {
+  if (x < 0.0) x = -x;
+  if (filter == ES_FILTER_BICUBIC) {
+    const double a = -0.5;
+    if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
+    if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
+    return 0.0;
+  }
+  return x < 1.0 ? 1.0 - x : 0.0;
+}
+
 // One output pixel `xx` of an axis resampled from `in` to `out` pixels (Pillow precompute_coeffs + normalize_coeffs_8bpc with
-// the bilinear filter, box = the whole axis): calls sink(xmin, x, k) for every tap - source index xmin + x, 22-bit
-// fixed-point weight k - in index order, returns the tap count and the first source index.
+// `filter`, box = the whole axis): calls sink(xmin, x, k) for every tap - source index xmin + x, 22-bit fixed-point weight k
+// (negative for the outer lobes of the cubic) - in index order, returns the tap count and the first source index.
 template <typename Sink>
-__host__ __device__ inline int resize_axis(int in, int out, int xx, int* xmin_out, Sink&& sink) {
+__host__ __device__ inline int resize_axis(int filter, int in, int out, int xx, int* xmin_out, Sink&& sink) {
   const double scale = (double)in / (double)out;
   const double fs = scale < 1.0 ? 1.0 : scale;
-  const double support = 1.0 * fs;
+  const double support = filter_support(filter) * fs;
   const double ss = 1.0 / fs;
   const double center = (xx + 0.5) * scale;
   int xmin = (int)(center - support + 0.5);
@@ -38,17 +51,13 @@ __host__ __device__ inline int resize_axis(int in, int out, int xx, int* xmin_ou
   int xmax = (int)(center + support + 0.5);
   if (xmax > in) xmax = in;
   const int n = xmax - xmin;
-  auto weight = [&](int x) {
-    double a = (x + xmin - center + 0.5) * ss;
-    if (a < 0.0) a = -a;
-    return a < 1.0 ? 1.0 - a : 0.0;
-  };
+  auto weight = [&](int x) { return filter_weight(filter, (x + xmin - center + 0.5) * ss); };
   double ww = 0.0;
   for (int x = 0; x < n; ++x) ww += weight(x);
   for (int x = 0; x < n; ++x) {
     double w = weight(x);
     if (ww != 0.0) w /= ww;
-    sink(xmin, x, (int)(0.5 + w * (double)(1 << kPrecisionBits)));     // bilinear weights are never negative
+    sink(xmin, x, w < 0.0 ? (int)(-0.5 + w * (double)(1 << kPrecisionBits)) : (int)(0.5 + w * (double)(1 << kPrecisionBits)));
   }
   *xmin_out = xmin;
   return n;
@@ -66,14 +75,15 @@ __device__ inline float u8_to_unit(uint8_t v, int normalize) {
   return y;
 }
 
-// torchvision's Resize(R) (shorter side -> R, longer side truncated) and CenterCrop(R) (round-half-to-even offsets)
-void fit(int height, int width, int R, int32_t out[4]) {
+// torchvision's Resize(R) = transformers' resize(shortest_edge = R) (shorter side -> R, longer side truncated), then the centre crop:
+// torchvision's CenterCrop(R) (round-half-to-even offsets) or transformers' center_crop ((size - R) // 2: the half is dropped)
+void fit(int height, int width, int R, int crop, int32_t out[4]) {
   int rh, rw;
   if (width <= height) { rw = R; rh = (int)((double)((long long)R * height) / (double)width); }
   else { rh = R; rw = (int)((double)((long long)R * width) / (double)height); }
   out[0] = rh; out[1] = rw;
-  out[2] = (int)rint((rh - R) / 2.0);
-  out[3] = (int)rint((rw - R) / 2.0);
+  if (crop == ES_CROP_TRANSFORMERS) { out[2] = (rh - R) / 2; out[3] = (rw - R) / 2; }      // rh, rw >= R: no negative operand
+  else { out[2] = (int)rint((rh - R) / 2.0); out[3] = (int)rint((rw - R) / 2.0); }
 }
 
 struct ImgDesc {
@@ -88,7 +98,7 @@ struct ImgDesc {
   int32_t need_h, need_v, normalize;
 };
 constexpr int kImgPerLaunch = 16;
-struct Batch { ImgDesc d[kImgPerLaunch]; int32_t R; };
+struct Batch { ImgDesc d[kImgPerLaunch]; int32_t R, filter; };
 
 // Horizontal pass.  grid.y = image; consecutive threads take consecutive (x * 3 + c) bytes of a row of the intermediate image,
 // so the stores coalesce and the loads of a wave fall into a few neighbouring lines of one source row.  Only the columns the
@@ -104,7 +114,7 @@ __global__ __launch_bounds__(256) void resize_h_kernel(const Batch b) {
   const uint8_t* row = d.src + (size_t)(d.y0 + r) * (size_t)d.stride + c;
   int acc = 1 << (kPrecisionBits - 1), xmin;
   const int ch = d.ch;
-  resize_axis(d.in_w, d.rw, xx, &xmin, [&](int x0, int x, int k) { acc += k * (int)row[(size_t)(x0 + x) * ch]; });
+  resize_axis(b.filter, d.in_w, d.rw, xx, &xmin, [&](int x0, int x, int k) { acc += k * (int)row[(size_t)(x0 + x) * ch]; });
   d.tmp[idx] = clip8(acc);
 }
 
@@ -125,7 +135,7 @@ __global__ __launch_bounds__(256) void resize_v_kernel(const Batch b) {
   uint8_t v;
   if (d.need_v) {
     int acc = 1 << (kPrecisionBits - 1), ymin;
-    resize_axis(d.in_h, d.rh, d.top + yy, &ymin, [&](int y0, int y, int k) { acc += k * (int)base[(size_t)(y0 + y) * pitch]; });
+    resize_axis(b.filter, d.in_h, d.rh, d.top + yy, &ymin, [&](int y0, int y, int k) { acc += k * (int)base[(size_t)(y0 + y) * pitch]; });
     v = clip8(acc);
   } else {
     v = base[(size_t)(d.top + yy) * pitch];
@@ -207,10 +217,11 @@ int check_images(const char* who, const es_image_u8* imgs, int count, int R) {
   return 0;
 }
 
-// geometry of one image: resized size, crop, which passes run, and the source rows the kept output rows read
-void plan_image(const es_image_u8& im, int R, ImgDesc& d) {
+// geometry of one image: resized size, crop, which passes run, and the source rows the kept output rows read (their range follows
+// the filter's support: the cubic reaches twice as far as the triangle)
+void plan_image(const es_image_u8& im, int R, int filter, int crop, ImgDesc& d) {
   int32_t f[4];
-  fit(im.height, im.width, R, f);
+  fit(im.height, im.width, R, crop, f);
   d.src = im.data; d.stride = im.row_stride;
   d.in_h = im.height; d.in_w = im.width; d.ch = im.channels;
   d.rh = f[0]; d.rw = f[1]; d.top = f[2]; d.left = f[3];
@@ -221,7 +232,7 @@ void plan_image(const es_image_u8& im, int R, ImgDesc& d) {
     int lo = d.in_h, hi = 0;
     for (int yy = d.top; yy < d.top + R; ++yy) {
       int ymin;
-      const int n = resize_axis(d.in_h, d.rh, yy, &ymin, [](int, int, int) {});
+      const int n = resize_axis(filter, d.in_h, d.rh, yy, &ymin, [](int, int, int) {});
       lo = ymin < lo ? ymin : lo;
       hi = ymin + n > hi ? ymin + n : hi;
     }
@@ -231,19 +242,52 @@ void plan_image(const es_image_u8& im, int R, ImgDesc& d) {
 }
 size_t tmp_bytes(const ImgDesc& d, int R) { return d.need_h ? (size_t)d.nrows * 3 * (size_t)R : 0; }
 
+bool known_rules(const char* who, int filter, int crop) {
+  if (filter != ES_FILTER_BILINEAR && filter != ES_FILTER_BICUBIC) { fail(who, "filter must be ES_FILTER_BILINEAR or ES_FILTER_BICUBIC"); return false; }
+  if (crop != ES_CROP_TORCHVISION && crop != ES_CROP_TRANSFORMERS) { fail(who, "crop rule must be ES_CROP_TORCHVISION or ES_CROP_TRANSFORMERS"); return false; }
+  return true;
+}
+
+int resize_coeffs(const char* who, int filter, int in, int out, int32_t* xmin, int32_t* ntaps, int32_t* k, int cap) {
+  if (in < 1 || out < 1) return fail(who, "in or out < 1");
+  int most = 0;
+  for (int xx = 0; xx < out; ++xx) {
+    int x0;
+    const int n = resize_axis(filter, in, out, xx, &x0, [&](int, int x, int kk) { if (k && x < cap) k[(size_t)xx * cap + x] = kk; });
+    if (xmin) xmin[xx] = x0;
+    if (ntaps) ntaps[xx] = n;
+    most = n > most ? n : most;
+  }
+  if (k && cap < most) return fail(who, "cap is smaller than the longest run of taps (ask with k = NULL first)");
+  return most;
+}
+
+size_t workspace_bytes(const char* who, const es_image_u8* imgs, int count, int R, int filter, int crop) {
+  if (!imgs || count < 1 || R < 1) { fail(who, "null pointer (imgs), count < 1 or R < 1"); return 0; }
+  size_t need = 0;
+  for (int i = 0; i < count; ++i) {
+    if (imgs[i].height < 1 || imgs[i].width < 1) { fail_img(who, i, "height or width < 1"); return 0; }
+    ImgDesc d;
+    plan_image(imgs[i], R, filter, crop, d);
+    need += tmp_bytes(d, R);
+  }
+  return need;
+}
+
 }  // namespace
 
-// library-internal (plan.hip: es_prepare_conds_u8): the resize with a uint8 [count,R,R,3] result (out_u8), an fp32 [3,R,R]
-// result per image (out_f32[i], ToTensor (+ Normalize where normalize[i])), or both
-int es_image_resize_impl(const char* who, const es_image_u8* imgs, int count, uint8_t* out_u8, float* const* out_f32,
-                         const int32_t* normalize, int R, void* workspace, size_t workspace_bytes, void* stream) {
+// library-internal (plan.hip: es_prepare_conds_u8; clip.hip: es_clip_pick): the resize with a uint8 [count,R,R,3] result (out_u8), an
+// fp32 [3,R,R] result per image (out_f32[i], ToTensor (+ Normalize where normalize[i])), or both
+int es_image_resize_impl_ex(const char* who, const es_image_u8* imgs, int count, uint8_t* out_u8, float* const* out_f32,
+                            const int32_t* normalize, int R, int filter, int crop, void* workspace, size_t workspace_bytes, void* stream) {
   if (check_images(who, imgs, count, R)) return -1;
+  if (!known_rules(who, filter, crop)) return -1;
   if (!out_u8 && !out_f32) return fail(who, "null pointer (out)");
   if (es_plan_recording()) return fail(who, "a plan is recording on this thread; the byte-image calls are never part of a plan");
   std::vector<ImgDesc> ds((size_t)count);
   size_t need = 0;
   for (int i = 0; i < count; ++i) {
-    plan_image(imgs[i], R, ds[i]);
+    plan_image(imgs[i], R, filter, crop, ds[i]);
     ds[i].tmp = (uint8_t*)workspace + need;
     need += tmp_bytes(ds[i], R);
     if (out_u8) ds[i].out = out_u8 + (size_t)i * 3 * R * R;
@@ -263,7 +307,7 @@ int es_image_resize_impl(const char* who, const es_image_u8* imgs, int count, ui
   const long long row3 = 3ll * R;
   for (int first = 0; first < count; first += kImgPerLaunch) {
     Batch b = {};
-    b.R = R;
+    b.R = R; b.filter = filter;
     const int n = count - first < kImgPerLaunch ? count - first : kImgPerLaunch;
     long long hmax = 0;
     for (int i = 0; i < n; ++i) {
@@ -277,44 +321,50 @@ int es_image_resize_impl(const char* who, const es_image_u8* imgs, int count, ui
   return 0;
 }
 
-extern "C" int es_image_fit(int height, int width, int R, int32_t out[4]) {
-  if (!out) return fail("es_image_fit", "null pointer (out)");
-  if (height < 1 || width < 1) return fail("es_image_fit", "height or width < 1");
-  if (R < 1) return fail("es_image_fit", "R < 1");
-  fit(height, width, R, out);
-  return 0;
+int es_image_resize_impl(const char* who, const es_image_u8* imgs, int count, uint8_t* out_u8, float* const* out_f32,
+                         const int32_t* normalize, int R, void* workspace, size_t workspace_bytes, void* stream) {
+  return es_image_resize_impl_ex(who, imgs, count, out_u8, out_f32, normalize, R, ES_FILTER_BILINEAR, ES_CROP_TORCHVISION, workspace, workspace_bytes, stream);
 }
 
+static int image_fit(const char* who, int height, int width, int R, int crop, int32_t out[4]) {
+  if (!out) return fail(who, "null pointer (out)");
+  if (height < 1 || width < 1) return fail(who, "height or width < 1");
+  if (R < 1) return fail(who, "R < 1");
+  if (!known_rules(who, ES_FILTER_BILINEAR, crop)) return -1;
+  fit(height, width, R, crop, out);
+  return 0;
+}
+extern "C" int es_image_fit(int height, int width, int R, int32_t out[4]) { return image_fit("es_image_fit", height, width, R, ES_CROP_TORCHVISION, out); }
+extern "C" int es_image_fit_ex(int height, int width, int R, int crop, int32_t out[4]) { return image_fit("es_image_fit_ex", height, width, R, crop, out); }
+
 extern "C" int es_image_resize_coeffs(int in, int out, int32_t* xmin, int32_t* ntaps, int32_t* k, int cap) {
-  if (in < 1 || out < 1) return fail("es_image_resize_coeffs", "in or out < 1");
-  int most = 0;
-  for (int xx = 0; xx < out; ++xx) {
-    int x0;
-    const int n = resize_axis(in, out, xx, &x0, [&](int, int x, int kk) { if (k && x < cap) k[(size_t)xx * cap + x] = kk; });
-    if (xmin) xmin[xx] = x0;
-    if (ntaps) ntaps[xx] = n;
-    most = n > most ? n : most;
-  }
-  if (k && cap < most) return fail("es_image_resize_coeffs", "cap is smaller than the longest run of taps (ask with k = NULL first)");
-  return most;
+  return resize_coeffs("es_image_resize_coeffs", ES_FILTER_BILINEAR, in, out, xmin, ntaps, k, cap);
+}
+
+extern "C" int es_image_resize_coeffs_ex(int filter, int in, int out, int32_t* xmin, int32_t* ntaps, int32_t* k, int cap) {
+  if (!known_rules("es_image_resize_coeffs_ex", filter, ES_CROP_TORCHVISION)) return -1;
+  return resize_coeffs("es_image_resize_coeffs_ex", filter, in, out, xmin, ntaps, k, cap);
 }
 
 extern "C" size_t es_image_resize_workspace_bytes(const es_image_u8* imgs, int count, int R) {
-  if (!imgs || count < 1 || R < 1) { fail("es_image_resize_workspace_bytes", "null pointer (imgs), count < 1 or R < 1"); return 0; }
-  size_t need = 0;
-  for (int i = 0; i < count; ++i) {
-    if (imgs[i].height < 1 || imgs[i].width < 1) { fail_img("es_image_resize_workspace_bytes", i, "height or width < 1"); return 0; }
-    ImgDesc d;
-    plan_image(imgs[i], R, d);
-    need += tmp_bytes(d, R);
-  }
-  return need;
+  return workspace_bytes("es_image_resize_workspace_bytes", imgs, count, R, ES_FILTER_BILINEAR, ES_CROP_TORCHVISION);
+}
+
+extern "C" size_t es_image_resize_workspace_bytes_ex(const es_image_u8* imgs, int count, int R, int filter, int crop) {
+  if (!known_rules("es_image_resize_workspace_bytes_ex", filter, crop)) return 0;
+  return workspace_bytes("es_image_resize_workspace_bytes_ex", imgs, count, R, filter, crop);
 }
 
 extern "C" int es_image_resize_u8(const es_image_u8* imgs, int count, uint8_t* out, int R, void* workspace, size_t workspace_bytes,
                                   void* stream) {
   if (!out) return fail("es_image_resize_u8", "null pointer (out)");
   return es_image_resize_impl("es_image_resize_u8", imgs, count, out, nullptr, nullptr, R, workspace, workspace_bytes, stream);
+}
+
+extern "C" int es_image_resize_u8_ex(const es_image_u8* imgs, int count, uint8_t* out, int R, int filter, int crop, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+  if (!out) return fail("es_image_resize_u8_ex", "null pointer (out)");
+  return es_image_resize_impl_ex("es_image_resize_u8_ex", imgs, count, out, nullptr, nullptr, R, filter, crop, workspace, workspace_bytes, stream);
 }
 
 extern "C" int es_image_u8_to_f32(const uint8_t* in, float* out_nchw, int count, int H, int W, int normalize, void* stream) {

@@ -50,6 +50,9 @@ void es_ctx_add_extent(es_ctx* c, unsigned long long off, unsigned long long byt
 // image (out_f32[i]: ToTensor, + Normalize(.5, .5) where normalize[i]), or both; `who` prefixes the error text
 int es_image_resize_impl(const char* who, const es_image_u8* imgs, int count, uint8_t* out_u8, float* const* out_f32,
                          const int32_t* normalize, int R, void* workspace, size_t workspace_bytes, void* stream);
+// ... with the filter (ES_FILTER_*) and the crop rule (ES_CROP_*) chosen; the call above is bilinear with torchvision's crop
+int es_image_resize_impl_ex(const char* who, const es_image_u8* imgs, int count, uint8_t* out_u8, float* const* out_f32,
+                            const int32_t* normalize, int R, int filter, int crop, void* workspace, size_t workspace_bytes, void* stream);
 
 // library-internal (rng.hip): es_randn with `who` prefixing the error text; *advance (may be null) = the offset increment of the draw
 int es_randn_impl(const char* who, float* out, const es_randn_desc* d, void* stream, unsigned long long* advance);

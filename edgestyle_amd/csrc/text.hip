@@ -12,32 +12,20 @@
 //                        query column, its accumulators are keys; P^T is the B operand of O^T = V^T P^T; V is read with the transposed
 //                        LDS read).  A wave only computes the 16-key fragments at or below its 16 queries.
 //   es_text_embed        out[r] = round(tok[ids[r]] + pos[r % S]), both tables fp32 (nn.Embedding stays fp32 under autocast), one rounding.
-//   es_text_encoder      the builder (state dict -> packed weights in one arena) and the forward, on the kernels the library already has:
+//   es_text_encoder      the builder (state dict -> packed weights in one arena; its pieces are encoder.h's, shared with clip.hip) and the
+//                        forward, on the kernels the library already has:
 //                        es_conv_gemm through the shared launch policy (es_launch_choose) for the four GEMMs of a layer - q|k|v as one
 //                        GEMM of 3C columns with LayerNorm1 folded in (ln_colsum), out_proj and fc2 with the residual add in the epilogue,
 //                        fc1 with LayerNorm2 folded in - and es_layer_norm for the final norm.
 // quick_gelu without a new GEMM epilogue: x sigmoid(1.702 x) = silu(1.702 x) / 1.702, so fc1 is packed as 1.702 W, 1.702 b and launched with
 // ES_ACT_SILU and out_scale = 1 / 1.702.
 // None of these calls is ever part of a plan: while a plan records on the calling thread they return -1.
-#include <math.h>
-#include <stdio.h>
-#include <string.h>
+#include "encoder.h"
 
-#include <algorithm>
-#include <memory>
-#include <string>
-#include <unordered_map>
-#include <vector>
-
-#include "common.h"
-#include "../../include/edgestyle_hip.h"
-#include "plan.h"
-
-extern "C" void es_set_error(const char* msg);
+using namespace es_enc;
 
 namespace {
 
-constexpr int BK = 64;
 constexpr int S_MAX = 128;
 constexpr float NEG = -3.0e38f;
 
@@ -188,37 +176,7 @@ __global__ __launch_bounds__(256) void text_embed_kernel(const int32_t* __restri
   *(u32x4*)(out + (size_t)i * 8) = __builtin_bit_cast(u32x4, v);
 }
 
-thread_local char g_msg[320];
-int fail(int rc, const char* who, const std::string& what) {
-  snprintf(g_msg, sizeof(g_msg), "%s: %s", who, what.c_str());
-  es_set_error(g_msg);
-  return rc;
-}
 const char* const kRecording = "a plan is recording on this thread; the text-encoder calls are never part of a plan";
-
-bool capturing(hipStream_t st) {
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  return hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
-}
-
-// ---- 16-bit storage types, round to nearest even like torch's .to(dtype) ----
-inline uint16_t f32_to_f16(float f) { _Float16 h = (_Float16)f; uint16_t u; memcpy(&u, &h, 2); return u; }
-inline float f16_to_f32(uint16_t u) { _Float16 h; memcpy(&h, &u, 2); return (float)h; }
-inline uint16_t f32_to_bf16(float f) {
-  uint32_t u; memcpy(&u, &f, 4);
-  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (uint16_t)((u >> 16) | 0x40);
-  return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
-}
-inline float bf16_to_f32(uint16_t h) { uint32_t u = (uint32_t)h << 16; float f; memcpy(&f, &u, 4); return f; }
-inline int round_up(int a, int b) { return (a + b - 1) / b * b; }
-
-struct Lin {                      // one packed linear layer: [rows_padded][kpad] dtype, bias fp32 [rows_padded], optional LayerNorm fold
-  size_t w = 0, bias = 0, colsum = 0;
-  bool ln = false;
-  int cout = 0, cin = 0, rows_padded = 0, kpad = 0;
-};
-struct Layer { Lin qkv, out, fc1, fc2; };
-constexpr float QUICK_GELU = 1.702f;
 
 }  // namespace
 
@@ -234,138 +192,6 @@ struct es_text_encoder {
   size_t ids = 0, xa = 0, xb = 0, qkv = 0, att = 0, hid = 0, ws = 0;
   es_launch_knobs knobs;
 };
-
-namespace {
-
-struct Upload { size_t off; const void* src; size_t bytes; std::vector<char> own; };
-
-struct TextBuilder {
-  const char* who = "es_text_encoder_create";
-  std::unordered_map<std::string, const es_tensor*> m;
-  std::vector<Upload> uploads;
-  size_t top = 0;
-  int dt = ES_F16;
-  std::string err;
-
-  size_t alloc(size_t bytes) { const size_t off = top; top += (bytes + 255) & ~(size_t)255; return off; }
-  char* staged(size_t off, size_t bytes) {
-    uploads.push_back(Upload{off, nullptr, bytes, std::vector<char>(bytes, 0)});
-    return uploads.back().own.data();
-  }
-  uint16_t enc(float f) const { return dt == ES_F16 ? f32_to_f16(f) : f32_to_bf16(f); }
-  float dec(uint16_t u) const { return dt == ES_F16 ? f16_to_f32(u) : bf16_to_f32(u); }
-
-  bool init(const es_state_dict* sd) {
-    if (!sd || sd->count < 0 || (sd->count > 0 && !sd->tensors)) { err = "the state dict has a count but no tensors"; return false; }
-    for (int i = 0; i < sd->count; ++i) {
-      const es_tensor& t = sd->tensors[i];
-      if (!t.key || !t.data || t.ndim < 1 || t.ndim > 4 || t.dtype < 0 || t.dtype > ES_F32) { err = "malformed tensor descriptor #" + std::to_string(i); return false; }
-      std::string k = t.key;
-      if (k.compare(0, 11, "text_model.") == 0) k = k.substr(11);      // SD1.5 checkpoints spell the keys with this prefix, transformers 5 without
-      m[k] = &t;
-    }
-    return true;
-  }
-  // fp32 copy of tensor `key` with exactly this shape; empty (and err set) otherwise
-  std::vector<float> get(const std::string& key, long long d0, long long d1 = -1) {
-    auto it = m.find(key);
-    if (it == m.end()) { err = "missing key '" + key + "'"; return {}; }
-    const es_tensor* t = it->second;
-    const int nd = d1 < 0 ? 1 : 2;
-    if (t->ndim != nd || t->shape[0] != d0 || (nd == 2 && t->shape[1] != d1)) {
-      std::string s = "size mismatch for '" + key + "': (";
-      for (int j = 0; j < t->ndim; ++j) s += std::to_string(t->shape[j]) + (j + 1 < t->ndim ? "," : "");
-      err = s + ") vs (" + std::to_string(d0) + (nd == 2 ? "," + std::to_string(d1) : std::string()) + ")";
-      return {};
-    }
-    const size_t n = (size_t)d0 * (size_t)(nd == 2 ? d1 : 1);
-    std::vector<float> v(n);
-    const void* src = t->data;
-    std::vector<char> tmp;
-    hipPointerAttribute_t a;
-    const bool dev = hipPointerGetAttributes(&a, src) == hipSuccess && a.type == hipMemoryTypeDevice;
-    (void)hipGetLastError();
-    if (dev) {
-      tmp.resize(n * (t->dtype == ES_F32 ? 4 : 2));
-      if (hipMemcpy(tmp.data(), src, tmp.size(), hipMemcpyDeviceToHost) != hipSuccess) { err = "cannot read '" + key + "' from the device"; return {}; }
-      src = tmp.data();
-    }
-    if (t->dtype == ES_F32) memcpy(v.data(), src, n * 4);
-    else if (t->dtype == ES_F16) { const uint16_t* s = (const uint16_t*)src; for (size_t i = 0; i < n; ++i) v[i] = f16_to_f32(s[i]); }
-    else { const uint16_t* s = (const uint16_t*)src; for (size_t i = 0; i < n; ++i) v[i] = bf16_to_f32(s[i]); }
-    return v;
-  }
-  size_t upload_f32(std::vector<float>&& v) {
-    const size_t off = alloc(v.size() * 4);
-    memcpy(staged(off, v.size() * 4), v.data(), v.size() * 4);
-    return off;
-  }
-  // w [cout][cin], b [cout]; gamma / beta: the LayerNorm in front, folded in as es_gemm_desc.ln_colsum asks (w gamma, W beta + b, column sums of
-  // the ROUNDED weights); `mul` scales weights and bias (quick_gelu's 1.702)
-  Lin pack(const std::vector<float>& w, const std::vector<float>& b, int cout, int cin, const std::vector<float>* gamma, const std::vector<float>* beta, double mul) {
-    Lin L;
-    L.cout = cout; L.cin = cin;
-    const int bn = (cout % 160 == 0 && cout % 128 != 0) ? 160 : 128;
-    L.rows_padded = round_up(cout, bn); L.kpad = round_up(cin, BK);
-    L.w = alloc((size_t)L.rows_padded * L.kpad * 2);
-    uint16_t* dw = (uint16_t*)staged(L.w, (size_t)L.rows_padded * L.kpad * 2);
-    L.bias = alloc((size_t)L.rows_padded * 4);
-    float* db = (float*)staged(L.bias, (size_t)L.rows_padded * 4);
-    std::vector<float> cs;
-    if (gamma) { L.ln = true; cs.assign((size_t)L.rows_padded, 0.f); }
-    for (int r = 0; r < cout; ++r) {
-      double acc = (double)b[r], sum = 0.0;
-      for (int j = 0; j < cin; ++j) {
-        const double wv = (double)w[(size_t)r * cin + j];
-        const uint16_t q = enc((float)(wv * (gamma ? (double)(*gamma)[j] : 1.0) * mul));
-        dw[(size_t)r * L.kpad + j] = q;
-        if (gamma) { acc += wv * (double)(*beta)[j]; sum += (double)dec(q); }
-      }
-      db[r] = (float)(acc * mul);
-      if (gamma) cs[r] = (float)sum;
-    }
-    if (gamma) L.colsum = upload_f32(std::move(cs));
-    return L;
-  }
-};
-
-es_gemm_desc gemm_desc(const es_text_encoder* e, const Lin& L, int M, int act, float out_scale, const es_launch_choice& ch) {
-  es_gemm_desc d;
-  memset(&d, 0, sizeof(d));
-  d.N = M; d.Hsrc = 1; d.Wsrc = 1; d.C1 = L.cin; d.Hout = 1; d.Wout = 1; d.Cout = L.cout;
-  d.rows_padded = L.rows_padded; d.Kpad = L.kpad; d.ksize = 1; d.stride = 1; d.pad = 0;
-  d.act = act; d.splitk = ch.splitk; d.bn = ch.bn; d.dtype = e->dtype; d.out_scale = out_scale; d.stages = ch.stages;
-  d.waves = ch.waves; d.xcd_m_fastest = ch.xcd_m_fastest;
-  d.ln_eps = e->cfg.ln_eps;
-  return d;
-}
-// the launch policy's answer for one linear layer over M rows (the questions Builder::conv_gemm of builder.hip asks)
-bool choose(const es_text_encoder* e, const Lin& L, int M, int act, float out_scale, bool residual, es_launch_choice* ch) {
-  es_launch_query q;
-  memset(&q, 0, sizeof(q));
-  q.M = M; q.hw = 1; q.w_numel = (long long)L.rows_padded * L.kpad; q.src_numel = (long long)M * L.cin;
-  q.ksize = 1; q.stride = 1; q.C1 = L.cin; q.rows_padded = L.rows_padded; q.kpad = L.kpad; q.cin = L.cin; q.cout = L.cout;
-  q.has_ln = L.ln; q.act = act; q.has_residual = residual; q.residual_dense = 1; q.unit_scale = out_scale == 1.f; q.x_rep = 1; q.dtype = e->dtype;
-  es_launch_knobs k = e->knobs;
-  if (act != ES_ACT_NONE) k.big_tile_256 = 0;       // the 256 x 256 tile has no SiLU epilogue form
-  return es_launch_choose(&q, &k, ch) == 0;
-}
-
-int linear(es_text_encoder* e, const Lin& L, const void* x, void* out, const void* residual, int M, int act, float out_scale, hipStream_t st) {
-  es_launch_choice ch;
-  if (!choose(e, L, M, act, out_scale, residual != nullptr, &ch)) return -1;
-  es_gemm_desc d = gemm_desc(e, L, M, act, out_scale, ch);
-  d.x = x; d.out = out; d.residual = residual;
-  d.w = e->arena + L.w; d.bias = (const float*)(e->arena + L.bias);
-  if (L.ln) d.ln_colsum = (const float*)(e->arena + L.colsum);
-  if (ch.splitk > 1) {
-    if (es_conv_gemm_workspace_bytes(&d) > e->ws_bytes) return fail(-1, "es_text_encode", "split-K workspace smaller than the launch needs");
-    d.workspace = (float*)(e->arena + e->ws);
-  }
-  return es_conv_gemm(&d, st);
-}
-
-}  // namespace
 
 extern "C" int es_attention_causal(const es_attn_desc* d, void* stream) {
   const char* who = "es_attention_causal";
@@ -433,16 +259,12 @@ extern "C" int es_text_encoder_create(const es_state_dict* sd, const es_text_con
   if (max_n < 1 || (long long)max_n * S > (1 << 24)) return fail(-1, who, "max_n must be >= 1 (and max_n * max_positions <= 2^24)");
   if (!(cfg->ln_eps > 0.f)) return fail(-1, who, "ln_eps must be positive");
 
-  TextBuilder b;
+  EncBuilder b;
   b.dt = dtype;
-  if (!b.init(sd)) return fail(-1, who, b.err);
+  if (!b.init(sd, "text_model.")) return fail(-1, who, b.err);
   std::unique_ptr<es_text_encoder, void (*)(es_text_encoder*)> e(new es_text_encoder, es_text_encoder_destroy);
   e->cfg = *cfg; e->dtype = dtype; e->max_n = max_n; e->device = device;
-  // the policy's defaults (builder.hip read_build_env) with es_linear_xs off: that kernel serves K = 320 | 640 from 8192 rows on, and a text
-  // batch is max_n * max_positions rows of K = hidden
-  memset(&e->knobs, 0, sizeof(e->knobs));
-  e->knobs.big_tile = e->knobs.big_tile_256 = e->knobs.small_tile = e->knobs.eight_waves = e->knobs.deep_ring = 1;
-  e->knobs.xcd_order = -1; e->knobs.wide_stream = 0;
+  default_knobs(&e->knobs);
 
 #define ES_GET(var, ...) std::vector<float> var = b.get(__VA_ARGS__); if (var.empty()) return fail(-1, who, b.err)
   {
@@ -454,20 +276,7 @@ extern "C" int es_text_encoder_create(const es_state_dict* sd, const es_text_con
   for (int li = 0; li < NL; ++li) {
     const std::string p = "encoder.layers." + std::to_string(li) + ".";
     Layer L;
-    ES_GET(g1, p + "layer_norm1.weight", C); ES_GET(b1, p + "layer_norm1.bias", C);
-    ES_GET(g2, p + "layer_norm2.weight", C); ES_GET(b2, p + "layer_norm2.bias", C);
-    std::vector<float> w, bias;
-    for (const char* nm : {"q_proj", "k_proj", "v_proj"}) {
-      ES_GET(wi, p + "self_attn." + nm + ".weight", C, C); ES_GET(bi, p + "self_attn." + nm + ".bias", C);
-      w.insert(w.end(), wi.begin(), wi.end()); bias.insert(bias.end(), bi.begin(), bi.end());
-    }
-    L.qkv = b.pack(w, bias, 3 * C, C, &g1, &b1, 1.0);
-    ES_GET(wo, p + "self_attn.out_proj.weight", C, C); ES_GET(bo, p + "self_attn.out_proj.bias", C);
-    L.out = b.pack(wo, bo, C, C, nullptr, nullptr, 1.0);
-    ES_GET(w1, p + "mlp.fc1.weight", I, C); ES_GET(bb1, p + "mlp.fc1.bias", I);
-    L.fc1 = b.pack(w1, bb1, I, C, &g2, &b2, (double)QUICK_GELU);
-    ES_GET(w2, p + "mlp.fc2.weight", C, I); ES_GET(bb2, p + "mlp.fc2.bias", C);
-    L.fc2 = b.pack(w2, bb2, C, I, nullptr, nullptr, 1.0);
+    if (!b.pack_layer(p, C, I, &L)) return fail(-1, who, b.err);
     e->layers.push_back(L);
   }
   {
@@ -486,12 +295,8 @@ extern "C" int es_text_encoder_create(const es_state_dict* sd, const es_text_con
     const int M = n * S;
     struct { const Lin* L; int act; float sc; bool res; } g[4] = {{&L0.qkv, ES_ACT_NONE, 1.f, false}, {&L0.out, ES_ACT_NONE, 1.f, true},
                                                                    {&L0.fc1, ES_ACT_SILU, 1.f / QUICK_GELU, false}, {&L0.fc2, ES_ACT_NONE, 1.f, true}};
-    for (auto& x : g) {
-      es_launch_choice ch;
-      if (!choose(e.get(), *x.L, M, x.act, x.sc, x.res, &ch)) return fail(-1, who, std::string("the launch policy has no tile for a projection: ") + es_last_error());
-      if (ch.route != ES_ROUTE_CONV_GEMM) return fail(-1, who, "the launch policy routed a projection away from es_conv_gemm");
-      if (ch.splitk > 1) e->ws_bytes = std::max(e->ws_bytes, (size_t)ch.splitk * M * x.L->rows_padded * 4);
-    }
+    for (auto& x : g)
+      if (!size_workspace(who, e.get(), *x.L, M, x.act, x.sc, x.res)) return -1;
   }
   e->ws = b.alloc(e->ws_bytes);
   e->arena_bytes = b.top;
@@ -499,9 +304,7 @@ extern "C" int es_text_encoder_create(const es_state_dict* sd, const es_text_con
 
   int prev = 0;
   if (hipGetDevice(&prev) != hipSuccess || hipSetDevice(device) != hipSuccess) return fail(-2, who, "cannot select the device");
-  bool ok = hipMalloc((void**)&e->arena, e->arena_bytes) == hipSuccess;
-  ok = ok && hipMemset(e->arena, 0, e->arena_bytes) == hipSuccess;
-  for (const Upload& u : b.uploads) ok = ok && hipMemcpy(e->arena + u.off, u.own.data(), u.bytes, hipMemcpyHostToDevice) == hipSuccess;
+  bool ok = upload_arena(b, &e->arena, e->arena_bytes);
   ok = ok && hipHostMalloc((void**)&e->ids_pinned, Mmax * 4, hipHostMallocDefault) == hipSuccess;
   ok = ok && hipEventCreateWithFlags(&e->staged, hipEventDisableTiming) == hipSuccess;
   ok = ok && hipDeviceSynchronize() == hipSuccess;
@@ -542,11 +345,11 @@ extern "C" int es_text_encode(es_text_encoder* e, const int32_t* ids_host, int n
   a.bsq = a.bsk = a.bsv = (int64_t)S * 3 * C; a.bso = (int64_t)S * C;
   a.scale = (float)(1.0 / sqrt((double)dh)); a.dtype = e->dtype;
   for (const Layer& L : e->layers) {      // the stream lives in xa at the top of every layer
-    if ((rc = linear(e, L.qkv, A + e->xa, A + e->qkv, nullptr, M, ES_ACT_NONE, 1.f, st))) return rc;
+    if ((rc = linear(who, e, L.qkv, A + e->xa, A + e->qkv, nullptr, M, ES_ACT_NONE, 1.f, st))) return rc;
     if ((rc = es_attention_causal(&a, stream))) return rc;
-    if ((rc = linear(e, L.out, A + e->att, A + e->xb, A + e->xa, M, ES_ACT_NONE, 1.f, st))) return rc;
-    if ((rc = linear(e, L.fc1, A + e->xb, A + e->hid, nullptr, M, ES_ACT_SILU, 1.f / QUICK_GELU, st))) return rc;
-    if ((rc = linear(e, L.fc2, A + e->hid, A + e->xa, A + e->xb, M, ES_ACT_NONE, 1.f, st))) return rc;
+    if ((rc = linear(who, e, L.out, A + e->att, A + e->xb, A + e->xa, M, ES_ACT_NONE, 1.f, st))) return rc;
+    if ((rc = linear(who, e, L.fc1, A + e->xb, A + e->hid, nullptr, M, ES_ACT_SILU, 1.f / QUICK_GELU, st))) return rc;
+    if ((rc = linear(who, e, L.fc2, A + e->hid, A + e->xa, A + e->xb, M, ES_ACT_NONE, 1.f, st))) return rc;
   }
   return es_layer_norm(A + e->xa, out_ehs, (const float*)(A + e->fln_g), (const float*)(A + e->fln_b), M, C, e->cfg.ln_eps, e->dtype, stream);
 }

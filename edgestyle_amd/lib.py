@@ -131,6 +131,15 @@ class TextConfig(C.Structure):      # es_text_config
         [("ln_eps", C.c_float), ("act", C.c_int32)]
 
 
+class ClipVisionConfig(C.Structure):    # es_clip_vision_config
+    _fields_ = [(n, C.c_int32) for n in ("image_size", "patch_size", "hidden", "heads", "layers", "intermediate", "projection_dim")] + \
+        [("ln_eps", C.c_float), ("act", C.c_int32), ("image_mean", C.c_float * 3), ("image_std", C.c_float * 3)]
+
+
+FILTER_BILINEAR, FILTER_BICUBIC = 0, 1           # ES_FILTER_*
+CROP_TORCHVISION, CROP_TRANSFORMERS = 0, 1       # ES_CROP_*
+
+
 class Tensor(C.Structure):          # es_tensor
     _fields_ = [("key", C.c_char_p), ("data", C.c_void_p), ("shape", C.c_int64 * 4), ("ndim", C.c_int32), ("dtype", C.c_int32)]
 
@@ -293,6 +302,25 @@ SYMBOLS = {
     "es_text_encoder_destroy": (None, [_P]),
     "es_text_encoder_arena_bytes": (C.c_size_t, [_P]),
     "es_text_encode": (C.c_int, [_P, _P, _I, _P, _P]),
+    "es_image_fit_ex": (C.c_int, [_I, _I, _I, _I, C.POINTER(C.c_int32)]),
+    "es_image_resize_coeffs_ex": (C.c_int, [_I, _I, _I, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _I]),
+    "es_image_resize_workspace_bytes_ex": (C.c_size_t, [C.POINTER(ImageU8), _I, _I, _I, _I]),
+    "es_image_resize_u8_ex": (C.c_int, [C.POINTER(ImageU8), _I, _P, _I, _I, _I, _P, C.c_size_t, _P]),
+    "es_clip_patchify": (C.c_int, [_P, _P, _P, _I, _I, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _I, _P]),
+    "es_clip_embed": (C.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _I, _P]),
+    "es_clip_score": (C.c_int, [_P, _I, _P, _I, _I, _I, _F, C.POINTER(C.c_int32), _I, _I, _P, _P, _P, _P]),
+    "es_clip_bank_create": (C.c_int, [C.POINTER(StateDict), _I, _I, _I, _I, _I, _I, C.POINTER(_P)]),
+    "es_clip_bank_destroy": (None, [_P]),
+    "es_clip_bank_rows": (C.c_int, [_P]),
+    "es_clip_bank_data": (_P, [_P]),
+    "es_clip_bank_append": (C.c_int, [_P, _P, _I, _P]),
+    "es_clip_text_pool": (C.c_int, [_P, _P, C.POINTER(C.c_int32), _I, _I, _P]),
+    "es_clip_vision_create": (C.c_int, [C.POINTER(StateDict), C.POINTER(ClipVisionConfig), _I, _I, _I, C.POINTER(_P)]),
+    "es_clip_vision_destroy": (None, [_P]),
+    "es_clip_vision_arena_bytes": (C.c_size_t, [_P]),
+    "es_clip_vision_encode": (C.c_int, [_P, _P, _I, _P, _P]),
+    "es_clip_pick_workspace_bytes": (C.c_size_t, [_P, C.POINTER(ImageU8), _I]),
+    "es_clip_pick": (C.c_int, [_P, _P, C.POINTER(ImageU8), _I, _F, C.POINTER(C.c_int32), _I, _I, _P, _P, _P, _P, C.c_size_t, _P]),
 }
 
 _lib = None

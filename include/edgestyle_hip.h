@@ -686,6 +686,19 @@ int es_image_u8_to_f32(const uint8_t* in, float* out_nchw, int count, int H, int
 /* fp32 NCHW [B,3,H,W] in [0,1] -> uint8 HWC [B,H,W,3]: b = (uint8) clamp(rintf(x * 255.0f), 0, 255), no fused multiply-add ahead
  * of the rounding; four pixels per thread */
 int es_image_f32_to_u8(const float* in_nchw, uint8_t* out_hwc, int B, int H, int W, void* stream);
+/* The same four calls with the FILTER and the CROP RULE chosen (the calls above are ES_FILTER_BILINEAR with ES_CROP_TORCHVISION and keep
+ * their bytes).  ES_FILTER_BICUBIC is Pillow's BICUBIC - the Keys cubic with a = -0.5, support 2.0 (stretched by the scale when shrinking),
+ * negative weights quantised as (int)(-0.5 + w * (1 << 22)) - which transformers' CLIPImageProcessor resizes with (model/utils.py:647-684
+ * through CLIPProcessor); its wider support widens the range of source rows the horizontal pass keeps for the vertical one.
+ * ES_CROP_TRANSFORMERS is transformers.image_transforms.center_crop: top = (rh - R) // 2, left = (rw - R) // 2 (the half is dropped,
+ * where torchvision rounds it to even).  The size rule is the same for both: shortest edge -> R, the other (int)(R * long / short). */
+enum { ES_FILTER_BILINEAR = 0, ES_FILTER_BICUBIC = 1 };
+enum { ES_CROP_TORCHVISION = 0, ES_CROP_TRANSFORMERS = 1 };
+int es_image_fit_ex(int height, int width, int R, int crop, int32_t out[4]);
+int es_image_resize_coeffs_ex(int filter, int in, int out, int32_t* xmin, int32_t* ntaps, int32_t* k, int cap);
+size_t es_image_resize_workspace_bytes_ex(const es_image_u8* imgs, int count, int R, int filter, int crop);
+int es_image_resize_u8_ex(const es_image_u8* imgs, int count, uint8_t* out, int R, int filter, int crop, void* workspace,
+                          size_t workspace_bytes, void* stream);
 /* es_prepare_conds from bytes: images[n_conds * B] (HOST array, net-major: image b of net i is images[i * B + b]) are resized,
  * cropped and converted straight into the bound ES_BUF_COND_IMG* slots (format unchanged: fp32 NCHW [B,3,8h,8w]; normalize[i] != 0
  * for the nets that take [-1,1], TT:29-48), the noise is copied and the unchanged ES_PLAN_CONDS runs, as in es_prepare_conds.
@@ -790,6 +803,88 @@ size_t es_text_encoder_arena_bytes(const es_text_encoder* e);
  * the `ehs` operand - under CFG the negative prompts first, then the prompts.  out_ehs: device dtype [n, max_positions, hidden].
  * The ids are staged through pinned memory: a capturing stream is refused, as es_denoise_step refuses it.  Asynchronous on `stream`. */
 int es_text_encode(es_text_encoder* e, const int32_t* ids_host, int n, void* out_ehs, void* stream);
+
+/* =========================================================================================================
+ * CLIP prompt picker (csrc/clip.hip): garment bytes in, the best words of the caller's vocabularies out.  Replaces BestEmbeddings
+ * (model/utils.py:647-684), which the reference's try_on runs inside every request (app.py:161-165): CLIPProcessor (bicubic resize,
+ * centre crop, normalise), CLIPModel's image tower, its text tower over the colour and garment words, logits_per_image, softmax and the
+ * two best words of each list.  The word side is computed ONCE per vocabulary into an es_clip_bank; a request is es_clip_pick.
+ * The transformer layers are the text encoder's (csrc/encoder.h) without the causal mask: es_conv_gemm through the launch policy with
+ * LayerNorm1 / LayerNorm2 folded into q|k|v and fc1, es_attention over Q, K, V as column slices of the [M, 3C] projection, residual adds
+ * in the epilogues of out_proj and fc2, quick_gelu on the SiLU epilogue.  Tokenisation stays with the caller.
+ * None of these calls is ever part of a plan: while a plan records on the calling thread they return -1.  No new
+ * ES_ABI_VERSION: no plan or context image records them.
+ * ========================================================================================================= */
+/* CLIPImageProcessor's rescale + normalize and the unfold of the patch convolution (CLIPVisionEmbeddings.patch_embedding, a Conv2d with
+ * kernel = stride = p): in device uint8 HWC [n, R, R, 3] -> out_rows dtype [n * (R/p)^2, Kpad], Kpad = roundup(3 p^2, 64), row = (image, patch
+ * row, patch column), column = c * p^2 + ky * p + kx - the order of the flattened weight [hidden, 3, p, p]; columns 3 p^2 .. Kpad - 1 are
+ * WRITTEN as zero (the GEMM multiplies them).  Value: ((b / 255) - mean[c]) / std[c] in fp32, both divisions correctly rounded, rounded
+ * once to dtype.  out_nchw (may be NULL): the same fp32 values before that rounding as [n, 3, R, R], the processor's pixel_values.
+ * out_rows may be NULL when out_nchw is given.  mean / std: host float[3]. */
+int es_clip_patchify(const uint8_t* in, void* out_rows, float* out_nchw, int n, int R, int p, const float* mean, const float* std, int dtype,
+                     void* stream);
+/* CLIPVisionEmbeddings' class token + position embedding and CLIPVisionTransformer.pre_layrnorm (transformers spells it so) in one launch:
+ * patch dtype [n * P, hidden] (the patch GEMM's output), cls fp32 [hidden], pos fp32 [1 + P, hidden]; x[n, 0] = cls + pos[0],
+ * x[n, 1 + j] = patch[n, j] + pos[1 + j], summed in fp32 and rounded once to dtype; out[n, t] = LayerNorm(x[n, t]) (two-pass statistics
+ * in fp32 over the rounded row, gamma / beta fp32), rounded once; out dtype [n, 1 + P, hidden].  hidden a multiple of 8, at most 4096. */
+int es_clip_embed(const void* patch, const float* cls, const float* pos, const float* gamma, const float* beta, void* out, int n, int P,
+                  int hidden, float eps, int dtype, void* stream);
+/* logits_per_image, its softmax per vocabulary and the best words (model/utils.py:666-684): pooled [n, proj] in pooled_dtype (ES_F16 |
+ * ES_BF16 | ES_F32: the projection GEMM's output), bank fp32 [W, proj] of unit rows, logit_scale_exp = exp(logit_scale); seg_ends: HOST
+ * int32[nseg], increasing, the last == W - the vocabularies bank rows [seg_ends[s - 1], seg_ends[s]) (nseg <= 4).  Per image: the
+ * embedding is L2-normalised in fp32; logits[n, W] = logit_scale_exp * <e, bank[w]>; probs[n, W] = softmax inside each segment;
+ * topk[n, nseg, k] (int32, k <= 8) = segment-relative indices by descending logit, equal logits resolving to the lower index; entries
+ * past the end of a segment shorter than k are -1.  fp32 throughout.  logits / probs / topk: device, any may be NULL.  proj % 4 == 0, proj <= 4096, W <= 4096. */
+int es_clip_score(const void* pooled, int pooled_dtype, const float* bank, int n, int W, int proj, float logit_scale_exp,
+                  const int32_t* seg_ends, int nseg, int k, float* logits, float* probs, int32_t* topk, void* stream);
+/* es_clip_bank: a device array of up to `capacity` fp32 unit rows [proj] - the normalised text_embeds of the caller's words.  Rows come
+ * from the host as raw fp32 (es_clip_bank_append: copied, then L2-normalised by the row-norm code es_clip_score runs on its embeddings),
+ * or from the text side (es_clip_text_pool below; text_sd then holds `text_projection.weight` [proj, text_hidden], packed at create time;
+ * text_sd NULL: a bank of raw rows only).  max_n: the most rows one es_clip_text_pool call appends.  dtype: the compute dtype of that
+ * projection.  device -1 is refused: a bank is device memory. */
+typedef struct es_clip_bank es_clip_bank;
+int es_clip_bank_create(const es_state_dict* text_sd, int text_hidden, int proj, int capacity, int max_n, int dtype, int device,
+                        es_clip_bank** out);
+void es_clip_bank_destroy(es_clip_bank* b);
+int es_clip_bank_rows(const es_clip_bank* b);                 /* rows appended so far */
+const float* es_clip_bank_data(const es_clip_bank* b);        /* device fp32 [capacity, proj] (borrowed) */
+int es_clip_bank_append(es_clip_bank* b, const float* rows_host, int count, void* stream);
+/* CLIPModel.get_text_features behind es_text_encode: ehs device dtype [n, S, text_hidden] (an es_text_encoder's output, final_layer_norm
+ * applied), eos_pos HOST int32[n] - the pooled position of every row as transformers picks it (the argmax of the ids where the config has
+ * the legacy eos_token_id == 2, else the first occurrence of eos_token_id; the caller computes it).  Gathers those rows, applies
+ * text_projection (no bias), L2-normalises in fp32 and appends n rows to the bank.  Once per vocabulary, not per request. */
+int es_clip_text_pool(es_clip_bank* b, const void* ehs, const int32_t* eos_pos, int n, int S, void* stream);
+typedef struct {                   /* vision_config of a CLIPModel's config.json + its preprocessor_config.json */
+  int32_t image_size, patch_size, hidden, heads, layers, intermediate, projection_dim;
+  float ln_eps;
+  int32_t act;                     /* 0 = quick_gelu; anything else is refused */
+  float image_mean[3], image_std[3];
+} es_clip_vision_config;
+typedef struct es_clip_vision es_clip_vision;
+/* sd: CLIPModel's state dict as es_tensor descriptors, keys vision_model.embeddings.{class_embedding, patch_embedding.weight,
+ * position_embedding.weight}, vision_model.pre_layrnorm.{weight,bias}, vision_model.encoder.layers.{i}.* (the text tower's names),
+ * vision_model.post_layernorm.{weight,bias}, visual_projection.weight - or the vision_model.* ones without that prefix, as a bare
+ * CLIPVisionModel spells them.  Other keys are ignored; a missing key or a wrong shape is an error naming the key.
+ * Forward (es_clip_vision_encode): es_clip_patchify -> patch embedding (es_conv_gemm, ksize 1, K = Kpad, no bias) -> es_clip_embed -> the
+ * layers -> class-token rows (es_memcpy2d) -> es_layer_norm (post_layernorm) -> visual_projection (no bias) -> pooled dtype [n, proj].
+ * Refused: hidden % 64 != 0 or above 4096, hidden / heads not 32 | 64, image_size % patch_size != 0, more than 1025 tokens,
+ * intermediate % 64 != 0, act != 0.  device -1: dry build - es_clip_vision_arena_bytes reports the size, es_clip_vision_encode and
+ * es_clip_pick return an error that says so. */
+int es_clip_vision_create(const es_state_dict* sd, const es_clip_vision_config* cfg, int dtype, int max_n, int device, es_clip_vision** out);
+void es_clip_vision_destroy(es_clip_vision* e);
+size_t es_clip_vision_arena_bytes(const es_clip_vision* e);
+/* images: device uint8 HWC [n, image_size, image_size, 3], n <= max_n; out_pooled: device dtype [n, projection_dim] (image_embeds before
+ * the normalisation).  Asynchronous on `stream`, nothing is allocated or staged: capturable. */
+int es_clip_vision_encode(es_clip_vision* e, const uint8_t* images, int n, void* out_pooled, void* stream);
+/* The request call: imgs HOST array of `count` <= max_n garment photos (device memory, any size) -> es_image_resize_u8_ex(ES_FILTER_BICUBIC,
+ * ES_CROP_TRANSFORMERS) -> es_clip_vision_encode -> es_clip_score against the bank's rows; the outputs are es_clip_score's.  workspace:
+ * es_clip_pick_workspace_bytes(e, imgs, count) bytes of device memory (0 with es_last_error() set on bad arguments).  Asynchronous on
+ * `stream`; nothing is allocated inside. */
+size_t es_clip_pick_workspace_bytes(const es_clip_vision* e, const es_image_u8* imgs, int count);
+int es_clip_pick(es_clip_vision* e, const es_clip_bank* bank, const es_image_u8* imgs, int count, float logit_scale_exp,
+                 const int32_t* seg_ends, int nseg, int k, float* logits, float* probs, int32_t* topk, void* workspace,
+                 size_t workspace_bytes, void* stream);
+
 
 #ifdef __cplusplus
 }
