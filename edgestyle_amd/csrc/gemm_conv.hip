@@ -38,10 +38,10 @@
 #define ES_W_AUX 0
 #endif
 
-int es_conv_gemm8p_launch(const es_gemm_desc& d, hipStream_t st);   // gemm_conv8p.hip: the 256 x 320 | 256 x 256 phase-interleaved tile
-bool es_conv_gemm8p_takes(const es_gemm_desc& d);                    // ... and whether its epilogue has the form this launch needs
+#include "gemm_route.h"
 
 unsigned long long es_operand_limit_v = 0x7FFFFFFFull;   // bytes one activation operand of a launch may span (32-bit buffer offsets)
+int es_gemm_last_kernel_v = 0;                           // es_conv_gemm_last_kernel: written by the launchers of both files
 
 namespace {
 
@@ -946,92 +946,12 @@ __global__ __launch_bounds__(64 * (CB / 8)) void splitk_reduce_gn_kernel(const e
   gn_emit_partials<T, NTH>(smem, EROW, 64, CB, (float*)(smem + 64 * EROW), p.gn_part, mb * 64, M, ct * CB, p.Cout, HW, p.gn_groups, tid);
 }
 
-template <typename T>
-int launch(const es_gemm_desc& d0, hipStream_t st) {
-  es_gemm_desc d = d0;
-  // the 256 x 320 tile keeps the common epilogue forms only (gemm_conv8p.hip); an activation, time-embedding rows that differ inside a
-  // 128-pixel half or meet a residual, or a Cout that is no multiple of 8 run on the 128 x 160 tile: the same results
-  if (d.bn == 320 && !es_conv_gemm8p_takes(d)) { d.bn = 160; d.stages = 2; }
-  if (d.bn == 256 && !es_conv_gemm8p_takes(d)) { d.bn = 128; d.stages = 2; }      // (rows_padded % 256 == 0: the 128-wide tile fits too)
-  const int M = d.N * d.Hout * d.Wout;
-  const int nk = d.Kpad / BK;
-  const int Ctot = d.C1 + d.C2;
-  const bool aligned = (Ctot % BK == 0) && (d.C1 % BK == 0);
-  // Pixel tile: 128 rows (4 or 8 waves) by default, 64 rows with bn = 64; bn = 320 is the 256-pixel tile of gemm_conv8p.hip
-  const int tn = d.rows_padded / d.bn;
-  const int bm = d.bn == 64 ? 64 : 128;
-  dim3 grid(((M + bm - 1) / bm) * tn * d.splitk);
-  int stages = d.stages;
-  if (stages == 0) stages = 2;   // measured (tools/gemm_bench.py): 2 stages x 2 workgroups/CU beats a 3-4 deep ring at 1/CU
-#define ES_LAUNCH_F(BMV, BNV, AL, ST, FMV)                                                                  \
-  do {                                                                                                      \
-    if (AL && d.korder) ES_LAUNCH_K(BMV, BNV, AL, ST, FMV, AL);                                             \
-    else ES_LAUNCH_K(BMV, BNV, AL, ST, FMV, false);                                                         \
-  } while (0)
-#define ES_LAUNCH_K(BMV, BNV, AL, ST, FMV, KOV)                                                             \
-  do {                                                                                                      \
-    auto kfn = conv_gemm_kernel<T, BMV, BNV, AL, ST, FMV, false, KOV>;                                      \
-    const size_t lds = (size_t)ST * (BMV + BNV) * BK * 2;                                                   \
-    static bool attr_set = false;                                                                           \
-    if (!attr_set) {                                                                                        \
-      (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);    \
-      attr_set = true;                                                                                      \
-    }                                                                                                       \
-    hipLaunchKernelGGL(kfn, grid, dim3(BMV * 8 / FMV), lds, st, d, M, nk, d.t1, d.t2, d.Ct1, d.Ct2);                                  \
-  } while (0)
-#define ES_LAUNCH_LN(BMV, BNV, ST, FMV)                                                                      \
-  do {                                                                                                      \
-    auto kfn = conv_gemm_kernel<T, BMV, BNV, true, ST, FMV, true>;                                          \
-    const size_t lds = (size_t)ST * (BMV + BNV) * BK * 2;                                                   \
-    static bool attr_set = false;                                                                           \
-    if (!attr_set) {                                                                                        \
-      (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);    \
-      attr_set = true;                                                                                      \
-    }                                                                                                       \
-    hipLaunchKernelGGL(kfn, grid, dim3(BMV * 8 / FMV), lds, st, d, M, nk, d.t1, d.t2, d.Ct1, d.Ct2);                                  \
-  } while (0)
-#define ES_LAUNCH(BMV, BNV, AL, ST) ES_LAUNCH_F(BMV, BNV, AL, ST, 4)
-#define ES_LAUNCH_ST(BNV)                                                                                   \
-  do {                                                                                                      \
-    if (d.waves == 8 && stages == 4 && BNV == 128) ES_LAUNCH_F(128, 128, true, 4, 2);                       \
-    else if (d.waves == 8) ES_LAUNCH_F(128, BNV, true, 2, 2);                                               \
-    else if (stages == 2) ES_LAUNCH(128, BNV, true, 2);                                                     \
-    else if (stages == 3) ES_LAUNCH(128, BNV, true, 3);                                                     \
-    else ES_LAUNCH(128, BNV, true, 4);                                                                      \
-  } while (0)
-  if (d.bn == 256) { if (es_conv_gemm8p_launch(d, st)) return -2; }
-  else if (d.ln_colsum) {
-    // LayerNorm-folded linear layers: the instantiations the planner can pick for a 1x1 launch
-    const bool w8 = d.waves == 8;
-    if (d.bn == 64)            { if (stages == 4) ES_LAUNCH_LN(64, 64, 4, 2); else ES_LAUNCH_LN(64, 64, 2, 2); }
-    else if (d.bn == 128 && w8) { if (stages == 4) ES_LAUNCH_LN(128, 128, 4, 2); else ES_LAUNCH_LN(128, 128, 2, 2); }
-    else if (d.bn == 128)       { if (stages == 4) ES_LAUNCH_LN(128, 128, 4, 4); else ES_LAUNCH_LN(128, 128, 2, 4); }
-    else if (w8)                { ES_LAUNCH_LN(128, 160, 2, 2); }
-    else                        { if (stages == 4) ES_LAUNCH_LN(128, 160, 4, 4); else ES_LAUNCH_LN(128, 160, 2, 4); }
-  }
-  else if (d.bn == 64)  { if (stages == 4) ES_LAUNCH_F(64, 64, true, 4, 2); else ES_LAUNCH_F(64, 64, true, 2, 2); }
-  else if (d.bn == 320) { if (es_conv_gemm8p_launch(d, st)) return -2; }
-  else if (d.bn == 128) { if (aligned) ES_LAUNCH_ST(128); else ES_LAUNCH(128, 128, false, 2); }
-  else                  { if (aligned) ES_LAUNCH_ST(160); else ES_LAUNCH(128, 160, false, 2); }
-#undef ES_LAUNCH_ST
-#undef ES_LAUNCH
-#undef ES_LAUNCH_F
-#undef ES_LAUNCH_K
-#undef ES_LAUNCH_LN
-  if (d.splitk > 1 && d.gn_part) {
-    // statistics hand-over: 64 pixels x CB channels per workgroup, CB like the N tile the statistics' two-entry scheme assumes
-    // (CB channels per workgroup: 64 x CB / 8 <= 1024 threads, and CB must hold a GroupNorm group: es_conv_gemm checks cpg <= 64 here)
-    const int cb = (d.bn == 320 || d.bn == 160) ? 80 : (d.bn == 128 ? 128 : 64);
-    dim3 grid((unsigned)((M / 64) * (d.rows_padded / cb)));
-    if (cb == 80) hipLaunchKernelGGL((splitk_reduce_gn_kernel<T, 80>), grid, dim3(64 * 10), 0, st, d, M);
-    else if (cb == 128) hipLaunchKernelGGL((splitk_reduce_gn_kernel<T, 128>), grid, dim3(64 * 16), 0, st, d, M);
-    else hipLaunchKernelGGL((splitk_reduce_gn_kernel<T, 64>), grid, dim3(64 * 8), 0, st, d, M);
-  } else if (d.splitk > 1) {
-    const long long total = (long long)M * (d.rows_padded / 8);
-    hipLaunchKernelGGL(splitk_reduce_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, d, M);
-  }
-  return hipGetLastError() == hipSuccess ? 0 : -2;
-}
+// ---------------------------------------------------------------------------------------------------------------
+// Host side.  A call is CHECKED (gemm_check: every refusal, as its text), DECIDED (gemm_route: a pure function of the descriptor - table
+// row, grid, LDS bytes, split-K reduce, runs; pointer fields count as present or absent) and only then MADE (launch: a switch on the
+// route's row over ES_GEMM_TABLE; the launchers take every number from the route).  es_conv_gemm_route reports the same GemmRoute
+// without a GPU.
+// ---------------------------------------------------------------------------------------------------------------
 
 // ---- launches whose operands outgrow the kernels' 32-bit buffer offsets -------------------------------------------------------
 // The kernels address activations, tail sources and outputs through buffer resources with 32-bit byte offsets (2 GiB each).  At 512 x 512
@@ -1056,27 +976,222 @@ bool oversize(const es_gemm_desc& d) {
   return d.splitk > 1 && (long long)d.N * d.Hout * d.Wout * (d.rows_padded / 8) >= (1ll << 31);
 }
 
-int launch_in_chunks(const es_gemm_desc& d0, hipStream_t st, const char** why, bool dry) {      // dry: the checks alone
-  const long long hw = (long long)d0.Hout * d0.Wout;
-  const unsigned long long per = sample_bytes(d0);
-  if (d0.gn_part) { *why = "es_conv_gemm: a launch larger than 2 GiB per operand cannot hand GroupNorm statistics over (gn_part)"; return -1; }
-  if (d0.x_nmod && (unsigned long long)d0.x_nmod * d0.Hsrc * d0.Wsrc * d0.C1 * 2 >= ES_OPERAND_LIMIT) { *why = "es_conv_gemm: source larger than 2 GiB (32-bit buffer offsets)"; return -1; }
+// samples per run of an oversize launch (below 1: one sample's operands alone are too large)
+long long run_samples(const es_gemm_desc& d) {
+  const long long hw = (long long)d.Hout * d.Wout;
+  const unsigned long long per = sample_bytes(d);
   long long ns = (long long)((ES_OPERAND_LIMIT - 1) / (per ? per : 1));
-  if (d0.splitk > 1) { const long long cap = ((1ll << 31) - 1) / (hw * (d0.rows_padded / 8)); ns = ns < cap ? ns : cap; }
+  if (d.splitk > 1) { const long long cap = ((1ll << 31) - 1) / (hw * (d.rows_padded / 8)); ns = ns < cap ? ns : cap; }
   if (hw == 1 && ns >= 256) ns -= ns % 256;                          // linear layers: rows are the samples; cut between 256-row tiles
-  if (d0.x_nmod) ns -= ns % d0.x_nmod;
-  if (ns < 1) { *why = "es_conv_gemm: one sample's operands exceed 2 GiB (32-bit buffer offsets)"; return -1; }
-  const int ng = d0.ngroups > 1 ? d0.ngroups : 1;
+  if (d.x_nmod) ns -= ns % d.x_nmod;
+  return ns;
+}
+
+// the first sample past weight group g (an oversize grouped launch has groups of whole samples: check_oversize)
+long long group_end(const es_gemm_desc& d, int g) { return d.ngroups > 1 ? (long long)d.mt_end[g] * 128 / ((long long)d.Hout * d.Wout) : d.N; }
+
+const char* check_oversize(const es_gemm_desc& d) {
+  if (d.gn_part) return "es_conv_gemm: a launch larger than 2 GiB per operand cannot hand GroupNorm statistics over (gn_part)";
+  if (d.x_nmod && (unsigned long long)d.x_nmod * d.Hsrc * d.Wsrc * d.C1 * 2 >= ES_OPERAND_LIMIT) return "es_conv_gemm: source larger than 2 GiB (32-bit buffer offsets)";
+  if (run_samples(d) < 1) return "es_conv_gemm: one sample's operands exceed 2 GiB (32-bit buffer offsets)";
+  long long g0 = 0;
+  for (int g = 0; g < (d.ngroups > 1 ? d.ngroups : 1); ++g) {
+    if (d.ngroups > 1 && ((long long)d.mt_end[g] * 128) % ((long long)d.Hout * d.Wout)) return "es_conv_gemm: a grouped launch larger than 2 GiB per operand needs groups of whole samples";
+    if (d.x_nmod && g0 % d.x_nmod) return "es_conv_gemm: a launch larger than 2 GiB per operand needs groups that start on a multiple of x_nmod";
+    g0 = group_end(d, g);
+  }
+  return nullptr;
+}
+
+// every check of es_conv_gemm that needs no pointer's target: null = the descriptor can be launched, else the refusal's text
+const char* gemm_check(const es_gemm_desc* d) {
+  const int Ctot = d->C1 + d->C2;
+  const int Ktrue = d->ksize * d->ksize * Ctot + (d->t1 ? d->Ct1 + d->Ct2 : 0);
+  if (d->ngroups > 4) return "es_conv_gemm: at most 4 groups";
+  if (d->ngroups > 1) {
+    const int tm = (d->N * d->Hout * d->Wout + 127) / 128;
+    for (int g = 0; g < d->ngroups; ++g)
+      if (!d->w_g[g] || d->mt_end[g] <= (g ? d->mt_end[g - 1] : 0)) return "es_conv_gemm: bad group table";
+    if (d->mt_end[d->ngroups - 1] != tm || (d->N * d->Hout * d->Wout) % 128) return "es_conv_gemm: groups must tile M in whole 128-pixel tiles";
+    if (d->bn == 320 || d->bn == 256)
+      for (int g = 0; g < d->ngroups; ++g)
+        if (d->mt_end[g] & 1) return "es_conv_gemm: 256-pixel tiles need groups of whole 256-pixel tiles";
+  }
+  if (d->bn != 64 && d->bn != 128 && d->bn != 160 && d->bn != 320 && d->bn != 256) return "es_conv_gemm: bn must be 64, 128, 160, 256 or 320";
+  if (d->bn == 256 && (d->C1 % BK || d->C2 % BK || (d->stages != 0 && d->stages != 2) || d->waves == 8 || d->korder || d->temb))
+    return "es_conv_gemm: bn=256 is the 256-pixel phase-interleaved tile of the LayerNorm-folded / GEGLU linear layers: 64-aligned channels, 2 stages, tap-major K, no time embedding";
+  if (d->bn == 64 && (d->C1 % BK || d->C2 % BK || d->stages == 3 || d->waves == 8 || d->act == ES_ACT_GEGLU))
+    return "es_conv_gemm: bn=64 is the 64x64 tile: 64-aligned channels, 2 or 4 stages, no GEGLU";
+  if (d->bn == 320 && (d->C1 % BK || d->C2 % BK || (d->stages != 0 && d->stages != 2) || d->act == ES_ACT_GEGLU || d->waves == 8))
+    return "es_conv_gemm: bn=320 is the 256-pixel phase-interleaved tile: 64-aligned channels, 2 stages, no GEGLU";
+  if (d->rows_padded % d->bn || d->rows_padded < d->Cout) return "es_conv_gemm: bad rows_padded";
+  if (d->Kpad % BK || d->Kpad < Ktrue) return "es_conv_gemm: bad Kpad";
+  if (d->C1 % 8 || d->C2 % 8 || (d->C2 && !d->x2)) return "es_conv_gemm: channels must be multiples of 8";
+  if (d->C2 && (d->C1 % BK || d->C2 % BK)) return "es_conv_gemm: concatenated sources need C1, C2 multiples of 64";
+  if ((size_t)d->rows_padded * d->Kpad * 2 >= 0x7FFFFFFFull) return "es_conv_gemm: weights larger than 2 GiB (32-bit buffer offsets)";
+  // before oversize() / run_samples(): both divide by the sample size and by Hout * Wout * (rows_padded / 8)
+  if (d->N < 1 || d->Hout < 1 || d->Wout < 1 || d->Cout < 1) return "es_conv_gemm: empty problem";
+  if (oversize(*d))        // activations beyond the 32-bit buffer offsets: runs of whole samples, one launch each (launch_in_chunks)
+    if (const char* why = check_oversize(*d)) return why;
+  if (d->ksize != 1 && d->ksize != 3) return "es_conv_gemm: ksize must be 1 or 3";
+  if (d->t1 && (d->stride != 1 || d->upsample || d->C1 % BK || d->C2 % BK || d->Ct1 % BK || d->Ct2 % BK || d->Ct1 < BK ||
+                (d->Ct2 && !d->t2) || d->ln_colsum || d->Hout != d->Hsrc || d->Wout != d->Wsrc))
+    return "es_conv_gemm: 1x1 tail sources need stride 1, no upsample, same-size output, 64-aligned channels";
+  if (!d->t1 && (d->t2 || d->Ct1 || d->Ct2)) return "es_conv_gemm: tail fields set without t1";
+  if (d->x_nmod < 0 || (d->x_nmod && (d->x2 || d->t1 || d->x_nmod > d->N))) return "es_conv_gemm: x_nmod needs a single source and 0 < x_nmod <= N";
+  if (d->out_lo && (!d->residual || (d->Cout & 7) || d->act == ES_ACT_GEGLU))
+    return "es_conv_gemm: out_lo (wide residual stream) needs a residual and an output width that is a multiple of 8";
+  if (d->residual_lo && !d->out_lo) return "es_conv_gemm: residual_lo without out_lo";
+  if (d->gn_part) {
+    const int hw = d->Hout * d->Wout;
+    if (d->gn_groups < 1 || d->Cout % d->gn_groups || (d->Cout & 7) || hw % 64 || d->act == ES_ACT_GEGLU || d->ln_colsum ||
+        d->Cout / d->gn_groups > (d->bn == 320 ? 160 : d->bn) || (d->splitk > 1 && d->Cout / d->gn_groups > 64))
+      return "es_conv_gemm: gn_part needs H*W % 64 == 0, Cout % 8 == 0 and whole GroupNorm groups no wider than the N tile";
+  }
+  if (d->korder != 0 && (d->korder != 1 || d->ksize != 3 || d->C1 % BK || d->C2 % BK || d->ln_colsum))
+    return "es_conv_gemm: korder 1 (chunk-major K) needs ksize 3 and 64-aligned C1, C2";
+  if (d->splitk < 1 || d->splitk > d->Kpad / BK) return "es_conv_gemm: bad splitk";
+  if (d->splitk > 1 && (!d->workspace || d->act == ES_ACT_GEGLU)) return "es_conv_gemm: splitk needs workspace and no GEGLU";
+  if (d->act == ES_ACT_GEGLU && ((d->bn != 128 && d->bn != 256) || d->Cout % 32)) return "es_conv_gemm: GEGLU needs bn=128 | 256, Cout%32==0";
+  if (d->stages != 0 && (d->stages < 2 || d->stages > 4)) return "es_conv_gemm: stages must be 0 (auto), 2, 3 or 4";
+  if (d->waves != 0 && d->waves != 4 && d->waves != 8) return "es_conv_gemm: waves must be 0 (auto), 4 or 8";
+  if (d->ln_colsum && (d->ksize != 1 || d->stride != 1 || d->C2 || d->C1 % BK || d->Kpad != d->C1 || d->splitk != 1 ||
+                       d->bn == 320 || d->upsample || d->temb || d->stages == 3))
+    return "es_conv_gemm: LayerNorm fold needs a plain linear layer: ksize 1, one source, K = C1 (multiple of 64), splitk 1, bn 64|128|160";
+  if (d->ln_colsum && d->ngroups > 1)
+    for (int g = 0; g < d->ngroups; ++g)
+      if (!d->ln_colsum_g[g]) return "es_conv_gemm: grouped LayerNorm fold needs ln_colsum_g for every group";
+  if (d->waves == 8 && (d->bn == 320 || d->C1 % BK || d->C2 % BK || d->stages == 3 || (d->stages == 4 && d->bn != 128)))
+    return "es_conv_gemm: waves=8 is the 128-pixel tile on 8 waves: 64-aligned channels, 2 stages (4 with bn=128)";
+  return nullptr;
+}
+
+// whether the phase-interleaved tile's epilogue has the form a launch recorded with bn = 320 | 256 needs
+bool big_tile_takes(const es_gemm_desc& d) {
+  if (d.bn == 256) {
+    // the 256-wide form: plain, LayerNorm-folded and GEGLU epilogues (no time embedding; a residual only without GEGLU); split-K: plain only
+    if (d.temb || (d.Cout & 7) || (d.act != ES_ACT_NONE && d.act != ES_ACT_GEGLU)) return false;
+    if (d.act == ES_ACT_GEGLU && (d.residual || d.out_lo || d.gn_part || d.splitk > 1)) return false;
+    if (d.ln_colsum && (d.splitk > 1 || d.gn_part)) return false;
+    return true;
+  }
+  if (d.splitk > 1) return true;          // split-K launches write raw partials: every form
+  return es_conv_gemm8p_form_ok(d.act, d.Cout, d.temb != nullptr, (long long)d.Hout * d.Wout, d.residual != nullptr) != 0;
+}
+
+// of a descriptor gemm_check has passed
+GemmRoute gemm_route(const es_gemm_desc& d) {
+  GemmRoute r{};
+  const bool aligned = ((d.C1 + d.C2) % BK == 0) && (d.C1 % BK == 0), ln = d.ln_colsum != nullptr;
+  r.aligned = aligned;
+  r.bn = d.bn;
+  r.stages = d.stages ? d.stages : 2;   // measured (tools/gemm_bench.py): 2 stages x 2 workgroups/CU beats a 3-4 deep ring at 1/CU
+  // 1. the tile.  The 256 x 320 | 256 x 256 tile keeps the common epilogue forms only (gemm_conv8p.hip); an activation, time-embedding
+  // rows that differ inside a 128-pixel half or meet a residual, or a Cout that is no multiple of 8 run on the 128 x 160 | 128 x 128
+  // tile (rows_padded % 256 == 0: the 128-wide tile fits too): the same results
+  if (d.bn == 320 || d.bn == 256) {
+    if (big_tile_takes(d)) r.family = 1;
+    else { r.bn = d.bn / 2; r.stages = 2; }
+  }
+  // 2. the instantiation: its template arguments, then its row (the switch is over the packed arguments of every row of the tables)
+  int bm, key;
+  if (r.family) {
+    bm = 256; r.waves = 8;
+    key = gemm_kernel_id(256, r.bn, 2, 8, true, ln, r.bn == 320 && d.korder, d.act == ES_ACT_GEGLU, false);
+  } else {
+    // Pixel tile: 128 rows (4 or 8 waves) by default, 64 rows with bn = 64.  The ring depth and wave count asked for exist where it says
+    // so in ES_GEMM_TABLE: the 64-wide tile and the LayerNorm-folded forms have 2 | 4 stages, unaligned channels one form per tile
+    bm = r.bn == 64 ? 64 : 128;
+    int fm = 4;
+    if (r.bn == 64) { fm = 2; if (r.stages != 4) r.stages = 2; }
+    else if (!aligned) r.stages = 2;
+    else if (d.waves == 8) { fm = 2; if (!(r.stages == 4 && r.bn == 128)) r.stages = 2; }
+    else if (ln && r.stages != 4) r.stages = 2;
+    r.waves = bm * 8 / fm / 64;
+    key = gemm_kernel_id(bm, r.bn, r.stages, r.waves, aligned, ln, aligned && !ln && d.korder, false, false);
+  }
+  r.row = -1;
+  switch (key) {
+#define X(BM, BN, AL, ST, FM, LN, KO) \
+  case gemm_kernel_id(BM, BN, ST, BM * 8 / FM / 64, AL, LN, KO, false, false): r.row = ES_GEMM_ROW(BM, BN, AL, ST, FM, LN, KO); r.lds = gemm_lds(BM, BN, ST); break;
+    ES_GEMM_TABLE(X)
+#undef X
+#define X(KO, FN, LN, GG) \
+  case gemm_kernel_id(256, 64 * FN, 2, 8, true, LN, KO, GG, false): r.row = ES_GEMM8P_ROW(KO, FN, LN, GG); r.lds = gemm8p_lds(FN); break;
+    ES_GEMM8P_TABLE(X)
+#undef X
+  }
+  r.kernel = key | (d.dtype == ES_BF16 ? ES_GEMM_KERNEL_BF16 : 0);
+  r.threads = r.waves * 64;
+  // 3. the runs of a launch whose operands outgrow the 32-bit buffer offsets; the grids below are the first run's
+  long long N = d.N;
+  r.runs = 1;
+  r.samples_per_run = d.N;
+  if (oversize(d)) {
+    const long long ns = run_samples(d);
+    long long g0 = 0;
+    r.runs = 0;
+    for (int g = 0; g < (d.ngroups > 1 ? d.ngroups : 1); ++g) { const long long g1 = group_end(d, g); r.runs += (int)((g1 - g0 + ns - 1) / ns); g0 = g1; }
+    r.samples_per_run = (int)ns;
+    N = ns < group_end(d, 0) ? ns : group_end(d, 0);
+  }
+  const long long M = N * d.Hout * d.Wout;
+  r.grid = (int)((M + bm - 1) / bm) * (d.rows_padded / r.bn) * d.splitk;
+  // 4. split-K: the reduce launch
+  if (d.splitk > 1 && d.gn_part) {
+    // statistics hand-over: 64 pixels x CB channels per workgroup, CB like the N tile the statistics' two-entry scheme assumes
+    // (CB channels per workgroup: 64 x CB / 8 <= 1024 threads, and CB must hold a GroupNorm group: gemm_check has cpg <= 64 here)
+    r.reduce = GEMM_REDUCE_GN;
+    r.reduce_cb = (r.bn == 320 || r.bn == 160) ? 80 : (r.bn == 128 ? 128 : 64);
+    r.reduce_grid = (int)((M / 64) * (d.rows_padded / r.reduce_cb));
+    r.reduce_threads = 64 * (r.reduce_cb / 8);
+  } else if (d.splitk > 1) {
+    r.reduce = GEMM_REDUCE_PLAIN;
+    r.reduce_grid = (int)((M * (d.rows_padded / 8) + 255) / 256);
+    r.reduce_threads = 256;
+  }
+  return r;
+}
+
+template <typename T, int BM, int BN, bool ALIGNED, int STAGES, int FM, bool LN, bool KO>
+void launch_tile(const es_gemm_desc& d, const GemmRoute& r, hipStream_t st) {
+  es_gemm_last_kernel_v = gemm_kernel_id(BM, BN, STAGES, BM * 8 / FM / 64, ALIGNED, LN, KO, false, std::is_same<T, bf16>::value);
+  auto kfn = conv_gemm_kernel<T, BM, BN, ALIGNED, STAGES, FM, LN, KO>;
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, gemm_lds(BM, BN, STAGES));
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(kfn, dim3(r.grid), dim3(r.threads), r.lds, st, d, d.N * d.Hout * d.Wout, d.Kpad / BK, d.t1, d.t2, d.Ct1, d.Ct2);
+}
+
+template <typename T>
+int launch(const es_gemm_desc& d, const GemmRoute& r, hipStream_t st) {
+  const int M = d.N * d.Hout * d.Wout;
+  if (r.family) { if (es_conv_gemm8p_launch(d, r, st)) return -2; }
+  else switch (r.row) {
+#define X(BM, BN, AL, ST, FM, LN, KO) case ES_GEMM_ROW(BM, BN, AL, ST, FM, LN, KO): launch_tile<T, BM, BN, AL, ST, FM, LN, KO>(d, r, st); break;
+    ES_GEMM_TABLE(X)
+#undef X
+    default: return -2;
+  }
+  if (r.reduce == GEMM_REDUCE_GN) {
+    if (r.reduce_cb == 80) hipLaunchKernelGGL((splitk_reduce_gn_kernel<T, 80>), dim3(r.reduce_grid), dim3(r.reduce_threads), 0, st, d, M);
+    else if (r.reduce_cb == 128) hipLaunchKernelGGL((splitk_reduce_gn_kernel<T, 128>), dim3(r.reduce_grid), dim3(r.reduce_threads), 0, st, d, M);
+    else hipLaunchKernelGGL((splitk_reduce_gn_kernel<T, 64>), dim3(r.reduce_grid), dim3(r.reduce_threads), 0, st, d, M);
+  } else if (r.reduce == GEMM_REDUCE_PLAIN) {
+    hipLaunchKernelGGL(splitk_reduce_kernel<T>, dim3(r.reduce_grid), dim3(r.reduce_threads), 0, st, d, M);
+  }
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+// an oversize launch (check_oversize passed), cut into runs of ns samples per weight group
+int launch_in_chunks(const es_gemm_desc& d0, long long ns, hipStream_t st) {
+  const long long hw = (long long)d0.Hout * d0.Wout;
   const long long cs = d0.act == ES_ACT_GEGLU ? d0.Cout / 2 : d0.Cout;
   long long g0 = 0;
-  for (int g = 0; g < ng; ++g) {
-    long long g1 = d0.N;
-    if (d0.ngroups > 1) {
-      const long long px = (long long)d0.mt_end[g] * 128;
-      if (px % hw) { *why = "es_conv_gemm: a grouped launch larger than 2 GiB per operand needs groups of whole samples"; return -1; }
-      g1 = px / hw;
-    }
-    if (d0.x_nmod && g0 % d0.x_nmod) { *why = "es_conv_gemm: a launch larger than 2 GiB per operand needs groups that start on a multiple of x_nmod"; return -1; }
+  for (int g = 0; g < (d0.ngroups > 1 ? d0.ngroups : 1); ++g) {
+    const long long g1 = group_end(d0, g);
     for (long long n0 = g0; n0 < g1; n0 += ns) {
       es_gemm_desc s = d0;
       s.N = (int)((g1 - n0) < ns ? (g1 - n0) : ns);
@@ -1097,9 +1212,9 @@ int launch_in_chunks(const es_gemm_desc& d0, hipStream_t st, const char** why, b
       s.residual_lo = adv(d0.residual_lo, out_px * cs * 2);
       s.out = (void*)adv(d0.out, out_px * cs * 2);
       s.out_lo = (void*)adv(d0.out_lo, out_px * cs * 2);
-      if (dry) continue;
-      const int rc = s.dtype == ES_F16 ? launch<f16>(s, st) : launch<bf16>(s, st);
-      if (rc) { *why = "es_conv_gemm: launch failed"; return rc; }
+      const GemmRoute r = gemm_route(s);
+      const int rc = s.dtype == ES_F16 ? launch<f16>(s, r, st) : launch<bf16>(s, r, st);
+      if (rc) return rc;
     }
     g0 = g1;
   }
@@ -1121,84 +1236,33 @@ extern "C" size_t es_conv_gemm_workspace_bytes(const es_gemm_desc* d) {
   return (size_t)d->splitk * d->N * d->Hout * d->Wout * d->rows_padded * sizeof(float);
 }
 
+extern "C" int es_conv_gemm_last_kernel(void) { return es_gemm_last_kernel_v; }
+
+extern "C" int es_conv_gemm_route(const es_gemm_desc* d, int32_t out[ES_GEMM_ROUTE_FIELDS]) {
+  if (const char* why = gemm_check(d)) { es_set_error(why); return -1; }
+  const GemmRoute r = gemm_route(*d);
+  const int32_t v[ES_GEMM_ROUTE_FIELDS] = {r.kernel, r.row, r.family, r.bn, r.stages, r.waves, r.aligned, r.grid, r.threads, r.lds,
+                                           r.reduce, r.reduce_cb, r.reduce_grid, r.reduce_threads, r.runs, r.samples_per_run};
+  for (int i = 0; i < ES_GEMM_ROUTE_FIELDS; ++i) out[i] = v[i];
+  return 0;
+}
+
 extern "C" int es_conv_gemm(const es_gemm_desc* d, void* stream) {
-  const int Ctot = d->C1 + d->C2;
-  const int Ktrue = d->ksize * d->ksize * Ctot + (d->t1 ? d->Ct1 + d->Ct2 : 0);
   if (!d->x || !d->out || (d->ngroups <= 1 && !d->w)) { es_set_error("es_conv_gemm: null pointer"); return -1; }
-  if (d->ngroups > 4) { es_set_error("es_conv_gemm: at most 4 groups"); return -1; }
-  if (d->ngroups > 1) {
-    const int tm = (d->N * d->Hout * d->Wout + 127) / 128;
-    for (int g = 0; g < d->ngroups; ++g)
-      if (!d->w_g[g] || d->mt_end[g] <= (g ? d->mt_end[g - 1] : 0)) { es_set_error("es_conv_gemm: bad group table"); return -1; }
-    if (d->mt_end[d->ngroups - 1] != tm || (d->N * d->Hout * d->Wout) % 128) { es_set_error("es_conv_gemm: groups must tile M in whole 128-pixel tiles"); return -1; }
-    if (d->bn == 320 || d->bn == 256)
-      for (int g = 0; g < d->ngroups; ++g)
-        if (d->mt_end[g] & 1) { es_set_error("es_conv_gemm: 256-pixel tiles need groups of whole 256-pixel tiles"); return -1; }
-  }
-  if (d->bn != 64 && d->bn != 128 && d->bn != 160 && d->bn != 320 && d->bn != 256) { es_set_error("es_conv_gemm: bn must be 64, 128, 160, 256 or 320"); return -1; }
-  if (d->bn == 256 && (d->C1 % BK || d->C2 % BK || (d->stages != 0 && d->stages != 2) || d->waves == 8 || d->korder || d->temb)) {
-    es_set_error("es_conv_gemm: bn=256 is the 256-pixel phase-interleaved tile of the LayerNorm-folded / GEGLU linear layers: 64-aligned channels, 2 stages, tap-major K, no time embedding"); return -1; }
-  if (d->bn == 64 && (d->C1 % BK || d->C2 % BK || d->stages == 3 || d->waves == 8 || d->act == ES_ACT_GEGLU)) {
-    es_set_error("es_conv_gemm: bn=64 is the 64x64 tile: 64-aligned channels, 2 or 4 stages, no GEGLU"); return -1; }
-  if (d->bn == 320 && (d->C1 % BK || d->C2 % BK || (d->stages != 0 && d->stages != 2) || d->act == ES_ACT_GEGLU || d->waves == 8)) {
-    es_set_error("es_conv_gemm: bn=320 is the 256-pixel phase-interleaved tile: 64-aligned channels, 2 stages, no GEGLU"); return -1; }
-  if (d->rows_padded % d->bn || d->rows_padded < d->Cout) { es_set_error("es_conv_gemm: bad rows_padded"); return -1; }
-  if (d->Kpad % BK || d->Kpad < Ktrue) { es_set_error("es_conv_gemm: bad Kpad"); return -1; }
-  if (d->C1 % 8 || d->C2 % 8 || (d->C2 && !d->x2)) { es_set_error("es_conv_gemm: channels must be multiples of 8"); return -1; }
-  if (d->C2 && (d->C1 % BK || d->C2 % BK)) { es_set_error("es_conv_gemm: concatenated sources need C1, C2 multiples of 64"); return -1; }
-  if ((size_t)d->rows_padded * d->Kpad * 2 >= 0x7FFFFFFFull) { es_set_error("es_conv_gemm: weights larger than 2 GiB (32-bit buffer offsets)"); return -1; }
-  // before oversize() / the dry launch_in_chunks(): both divide by the sample size and by Hout * Wout * (rows_padded / 8)
-  if (d->N < 1 || d->Hout < 1 || d->Wout < 1 || d->Cout < 1) { es_set_error("es_conv_gemm: empty problem"); return -1; }
-  const bool chunked = oversize(*d);       // activations beyond the 32-bit buffer offsets: runs of whole samples, one launch each (launch_in_chunks)
-  if (chunked) {
-    const char* why = nullptr;
-    if (launch_in_chunks(*d, nullptr, &why, true)) { es_set_error(why); return -1; }
-  }
-  if (d->ksize != 1 && d->ksize != 3) { es_set_error("es_conv_gemm: ksize must be 1 or 3"); return -1; }
-  if (d->t1 && (d->stride != 1 || d->upsample || d->C1 % BK || d->C2 % BK || d->Ct1 % BK || d->Ct2 % BK || d->Ct1 < BK ||
-                (d->Ct2 && !d->t2) || d->ln_colsum || d->Hout != d->Hsrc || d->Wout != d->Wsrc ||
-                false)) {
-    es_set_error("es_conv_gemm: 1x1 tail sources need stride 1, no upsample, same-size output, 64-aligned channels"); return -1; }
-  if (!d->t1 && (d->t2 || d->Ct1 || d->Ct2)) { es_set_error("es_conv_gemm: tail fields set without t1"); return -1; }
-  if (d->x_nmod < 0 || (d->x_nmod && (d->x2 || d->t1 || d->x_nmod > d->N))) { es_set_error("es_conv_gemm: x_nmod needs a single source and 0 < x_nmod <= N"); return -1; }
-  if (d->out_lo && (!d->residual || (d->Cout & 7) || d->act == ES_ACT_GEGLU)) {
-    es_set_error("es_conv_gemm: out_lo (wide residual stream) needs a residual and an output width that is a multiple of 8"); return -1; }
-  if (d->residual_lo && !d->out_lo) { es_set_error("es_conv_gemm: residual_lo without out_lo"); return -1; }
-  if (d->gn_part) {
-    const int hw = d->Hout * d->Wout;
-    if (d->gn_groups < 1 || d->Cout % d->gn_groups || (d->Cout & 7) || hw % 64 || d->act == ES_ACT_GEGLU || d->ln_colsum ||
-        d->Cout / d->gn_groups > (d->bn == 320 ? 160 : d->bn) || (d->splitk > 1 && d->Cout / d->gn_groups > 64)) {
-      es_set_error("es_conv_gemm: gn_part needs H*W % 64 == 0, Cout % 8 == 0 and whole GroupNorm groups no wider than the N tile"); return -1; }
-  }
-  if (d->korder != 0 && (d->korder != 1 || d->ksize != 3 || d->C1 % BK || d->C2 % BK || d->ln_colsum)) {
-    es_set_error("es_conv_gemm: korder 1 (chunk-major K) needs ksize 3 and 64-aligned C1, C2"); return -1; }
-  if (d->splitk < 1 || d->splitk > d->Kpad / BK) { es_set_error("es_conv_gemm: bad splitk"); return -1; }
-  if (d->splitk > 1 && (!d->workspace || d->act == ES_ACT_GEGLU)) { es_set_error("es_conv_gemm: splitk needs workspace and no GEGLU"); return -1; }
-  if (d->act == ES_ACT_GEGLU && ((d->bn != 128 && d->bn != 256) || d->Cout % 32)) { es_set_error("es_conv_gemm: GEGLU needs bn=128 | 256, Cout%32==0"); return -1; }
-  if (d->stages != 0 && (d->stages < 2 || d->stages > 4)) { es_set_error("es_conv_gemm: stages must be 0 (auto), 2, 3 or 4"); return -1; }
-  if (d->waves != 0 && d->waves != 4 && d->waves != 8) { es_set_error("es_conv_gemm: waves must be 0 (auto), 4 or 8"); return -1; }
-  if (d->ln_colsum && (d->ksize != 1 || d->stride != 1 || d->C2 || d->C1 % BK || d->Kpad != d->C1 || d->splitk != 1 ||
-                       d->bn == 320 || d->upsample || d->temb || d->stages == 3)) {
-    es_set_error("es_conv_gemm: LayerNorm fold needs a plain linear layer: ksize 1, one source, K = C1 (multiple of 64), splitk 1, bn 64|128|160"); return -1; }
-  if (d->ln_colsum && d->ngroups > 1)
-    for (int g = 0; g < d->ngroups; ++g)
-      if (!d->ln_colsum_g[g]) { es_set_error("es_conv_gemm: grouped LayerNorm fold needs ln_colsum_g for every group"); return -1; }
-  if (d->waves == 8 && (d->bn == 320 || d->C1 % BK || d->C2 % BK || d->stages == 3 ||
-                        (d->stages == 4 && d->bn != 128))) {
-    es_set_error("es_conv_gemm: waves=8 is the 128-pixel tile on 8 waves: 64-aligned channels, 2 stages (4 with bn=128)"); return -1; }
+  if (const char* why = gemm_check(d)) { es_set_error(why); return -1; }
   ES_PLAN_RECORD(ES_OP_CONV_GEMM, d, sizeof(*d));       // after validation: a rejected call never enters a recording plan
   hipStream_t st = (hipStream_t)stream;
-  // the kernels find a tile's group as (t >= end[0]) + (t >= end[1]) + (t >= end[2]): unused entries must compare false
-  // (a caller's zero-initialised table sent every tile of a TWO-group launch to groups 1..3: null weights, GPU fault)
-  es_gemm_desc dd = *d;
-  for (int g = dd.ngroups > 1 ? dd.ngroups : 0; g < 4; ++g) dd.mt_end[g] = 0x7FFFFFFF;
-  if (chunked) {
-    const char* why = "es_conv_gemm: launch failed";
-    const int rc = launch_in_chunks(*d, st, &why, false);
-    if (rc) es_set_error(why);
-    return rc;
+  const GemmRoute r = gemm_route(*d);
+  int rc;
+  if (r.runs > 1) rc = launch_in_chunks(*d, r.samples_per_run, st);
+  else {
+    // the kernels find a tile's group as (t >= end[0]) + (t >= end[1]) + (t >= end[2]): unused entries must compare false
+    // (a caller's zero-initialised table sent every tile of a TWO-group launch to groups 1..3: null weights, GPU fault)
+    es_gemm_desc dd = *d;
+    for (int g = dd.ngroups > 1 ? dd.ngroups : 0; g < 4; ++g) dd.mt_end[g] = 0x7FFFFFFF;
+    rc = dd.dtype == ES_F16 ? launch<f16>(dd, r, st) : launch<bf16>(dd, r, st);
   }
-  int rc = dd.dtype == ES_F16 ? launch<f16>(dd, st) : launch<bf16>(dd, st);
   if (rc) es_set_error("es_conv_gemm: launch failed");
   return rc;
 }
+

@@ -38,6 +38,7 @@
 #endif
 #include "common.h"
 #include "../../include/edgestyle_hip.h"
+#include "gemm_route.h"
 
 // Tool-only builds (tools/ab8p.sh): ES8P_ABL removes one ingredient (results are wrong by construction).  ABL bits: 1 = every DMA out of range (issued, zero-filled, no memory traffic),
 // 2 = no MFMAs, 4 = no barrier stagger, 8 = activation DMAs out of range only, 16 = weight DMAs out of range only, 32 = chunk-major order with the
@@ -496,9 +497,9 @@ __global__ __launch_bounds__(512, 2) void conv_gemm8p_kernel(const es_gemm_desc 
   constexpr int CH = (GEGLU ? BN / 2 : BN) / 8;            // 16-byte chunks per tile row (40 | 32; GEGLU stores half the columns: 16)
   constexpr int RPF = GP * CH / 512;                       // chunks per thread and pass
   const int cbase = tile_n * (GEGLU ? BN / 2 : BN);        // first STORED channel of the tile
-  const bool tuni = p.temb != nullptr;                     // (es_conv_gemm8p_takes: then H*W % GP == 0 - one sample per pixel half - and no residual)
+  const bool tuni = p.temb != nullptr;                     // (gemm_route: then H*W % GP == 0 - one sample per pixel half - and no residual)
   // WMODE: 0 = bias only, 1 = bias + one time-embedding row per wave        SMODE: 0 = no residual, 1 = residual, 2 = value pair out, 3 = value pair in and out
-  // (an activation, per-pixel time-embedding rows, Cout % 8 != 0: es_conv_gemm runs those on the 128 x 160 tile, es_conv_gemm8p_takes)
+  // (an activation, per-pixel time-embedding rows, Cout % 8 != 0: es_conv_gemm runs those on the 128 x 160 tile, gemm_route)
   auto passes = [&](auto wmode_c, auto smode_c) __attribute__((always_inline)) {
     constexpr int WMODE = decltype(wmode_c)::value, SMODE = decltype(smode_c)::value;
     constexpr bool RES = SMODE != 0;
@@ -653,6 +654,30 @@ __global__ __launch_bounds__(512, 2) void conv_gemm8p_kernel(const es_gemm_desc 
 #endif
 }
 
+// Host side: the launch is decided by gemm_route (gemm_conv.hip), which names one row of ES_GEMM8P_TABLE; every number comes from the route
+template <typename T, bool KO, int FN, bool LN, bool GEGLU>
+void launch_tile8p(const es_gemm_desc& d, const GemmRoute& r, hipStream_t st) {
+  es_gemm_last_kernel_v = gemm_kernel_id(256, 64 * FN, 2, 8, true, LN, KO, GEGLU, std::is_same<T, bf16>::value);
+  auto kfn = conv_gemm8p_kernel<T, KO, 256, FN, LN, GEGLU>;
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, gemm8p_lds(FN));
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(kfn, dim3(r.grid), dim3(r.threads), r.lds, st, d, d.N * d.Hout * d.Wout, d.Kpad / 64, d.t1, d.t2, d.Ct1, d.Ct2);
+}
+
+template <typename T>
+int launch8p(const es_gemm_desc& d, const GemmRoute& r, hipStream_t st) {
+  switch (r.row) {
+#define X(KO, FN, LN, GG) case ES_GEMM8P_ROW(KO, FN, LN, GG): launch_tile8p<T, KO, FN, LN, GG>(d, r, st); break;
+    ES_GEMM8P_TABLE(X)
+#undef X
+    default: return -2;
+  }
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
 }  // namespace
 
 // the epilogue forms this tile implements (split-K launches write raw partials: every form)
@@ -661,50 +686,9 @@ extern "C" int es_conv_gemm8p_form_ok(int act, int cout, int has_temb, long long
   if (has_temb && ((out_hw & 127) || has_residual)) return 0;
   return 1;
 }
-bool es_conv_gemm8p_takes(const es_gemm_desc& d) {
-  if (d.bn == 256) {
-    // the 256-wide form: plain, LayerNorm-folded and GEGLU epilogues (no time embedding; a residual only without GEGLU); split-K: plain only
-    if (d.temb || (d.Cout & 7) || (d.act != ES_ACT_NONE && d.act != ES_ACT_GEGLU)) return false;
-    if (d.act == ES_ACT_GEGLU && (d.residual || d.out_lo || d.gn_part || d.splitk > 1)) return false;
-    if (d.ln_colsum && (d.splitk > 1 || d.gn_part)) return false;
-    return true;
-  }
-  if (d.splitk > 1) return true;
-  return es_conv_gemm8p_form_ok(d.act, d.Cout, d.temb != nullptr, (long long)d.Hout * d.Wout, d.residual != nullptr) != 0;
+
+// called by es_conv_gemm (gemm_conv.hip) for a route of this kernel family
+int es_conv_gemm8p_launch(const es_gemm_desc& d, const GemmRoute& r, hipStream_t st) {
+  return d.dtype == ES_F16 ? launch8p<f16>(d, r, st) : launch8p<bf16>(d, r, st);
 }
 
-// called by es_conv_gemm (gemm_conv.hip) after validation, for d.bn == 320 | 256
-int es_conv_gemm8p_launch(const es_gemm_desc& d, hipStream_t st) {
-  if (!es_conv_gemm8p_takes(d)) return -2;
-  const int M = d.N * d.Hout * d.Wout;
-  const int nk = d.Kpad / 64;
-  const int tn = d.rows_padded / d.bn;
-  constexpr int bm = 256;
-  dim3 grid(((M + bm - 1) / bm) * tn * d.splitk);
-#define ES8P_LAUNCH(TT, KOV, FNV, LNV, GGV)                                                                              \
-  do {                                                                                                                    \
-    auto kfn = conv_gemm8p_kernel<TT, KOV, 256, FNV, LNV, GGV>;                                                           \
-    constexpr size_t lds = 2 * ((size_t)256 * RB + (size_t)64 * FNV * RB);                                                \
-    static bool attr_set = false;                                                                                         \
-    if (!attr_set) {                                                                                                      \
-      (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                  \
-      attr_set = true;                                                                                                    \
-    }                                                                                                                     \
-    hipLaunchKernelGGL(kfn, grid, dim3(512), lds, st, d, M, nk, d.t1, d.t2, d.Ct1, d.Ct2);                                \
-  } while (0)
-#define ES8P_LAUNCH_T(TT)                                                                                                \
-  do {                                                                                                                    \
-    if (d.bn == 256) {                                                                                                    \
-      const bool ln = d.ln_colsum != nullptr, gg = d.act == ES_ACT_GEGLU;                                                 \
-      if (ln && gg) ES8P_LAUNCH(TT, false, 4, true, true);                                                                \
-      else if (ln) ES8P_LAUNCH(TT, false, 4, true, false);                                                                \
-      else if (gg) ES8P_LAUNCH(TT, false, 4, false, true);                                                                \
-      else ES8P_LAUNCH(TT, false, 4, false, false);                                                                       \
-    } else if (d.korder) ES8P_LAUNCH(TT, true, 5, false, false);                                                          \
-    else ES8P_LAUNCH(TT, false, 5, false, false);                                                                         \
-  } while (0)
-  if (d.dtype == ES_F16) ES8P_LAUNCH_T(f16); else ES8P_LAUNCH_T(bf16);
-#undef ES8P_LAUNCH_T
-#undef ES8P_LAUNCH
-  return hipGetLastError() == hipSuccess ? 0 : -2;
-}

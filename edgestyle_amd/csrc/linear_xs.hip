@@ -40,6 +40,8 @@
 #define XS_STAMPS 0
 #endif
 
+extern unsigned long long es_operand_limit_v;          // gemm_conv.hip: 0x7FFFFFFF unless a test lowered it
+
 namespace {
 
 typedef __attribute__((address_space(3))) void* lptr_t;
@@ -515,134 +517,217 @@ __global__ __launch_bounds__(512, 2) void linear_xs_kernel(const es_xs_desc p) {
 #endif
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Host side.  A call is CHECKED (xs_check: every refusal, as its text), DECIDED (xs_route: a pure function of the descriptor and the
+// knobs - form, grid, runs; pointer fields count as present or absent) and only then MADE (launch: a switch on the route's form over
+// XS_TABLE).  es_linear_xs_route reports the same XsRoute without a GPU.
+// ---------------------------------------------------------------------------------------------------------------
+
+// The tuning switch, read from the environment ONCE per process, on first use (the first launch, route query or es_linear_xs_set_pp;
+// earlier versions read it when the library was loaded):
+//   ES_XS_PP  1   form of the plain (no GEGLU) launches: 1 = two-barrier ping-pong, 0 = the one-barrier form (es_linear_xs_set_pp for A/B
+//                 runs inside one process).  Same arithmetic in the same order either way: bit-identical outputs.
+typedef es_xs_knobs XsKnobs;
+
+XsKnobs& xs_knobs() {
+  static XsKnobs knobs = [] {
+    XsKnobs k{};
+    const char* e = getenv("ES_XS_PP");
+    k.pp = e ? atoi(e) : 1;
+    return k;
+  }();
+  return knobs;
+}
+
+// Every instantiation of linear_xs_kernel that exists, per dtype: X(KC, GEGLU, LN, RES, PP, GN).  The one table the dispatch is written from.
+#define XS_TABLE(X)                                                                                      \
+  /* GroupNorm in front: the plain projection, the ping-pong form whatever the knob says */               \
+  X(10, 0, 0, 0, 1, 1)  X(20, 0, 0, 0, 1, 1)                                                              \
+  /* the ping-pong forms: no GEGLU; a residual at K = 320 without LayerNorm only */                        \
+  X(10, 0, 0, 1, 1, 0)  X(10, 0, 1, 0, 1, 0)  X(10, 0, 0, 0, 1, 0)  X(20, 0, 1, 0, 1, 0)  X(20, 0, 0, 0, 1, 0)   \
+  /* the one-barrier forms */                                                                             \
+  X(10, 0, 0, 1, 0, 0)  X(10, 1, 1, 0, 0, 0)  X(10, 1, 0, 0, 0, 0)  X(10, 0, 1, 0, 0, 0)  X(10, 0, 0, 0, 0, 0)   \
+  X(20, 1, 1, 0, 0, 0)  X(20, 1, 0, 0, 0, 0)  X(20, 0, 1, 0, 0, 0)  X(20, 0, 0, 0, 0, 0)
+
+// es_linear_xs_last_form / XsRoute::form: an instantiation's template arguments, packed (ES_XS_FORM_*)
+constexpr int xs_form_id(int kc, bool geglu, bool ln, bool res, bool pp, bool gn) {
+  return kc | (geglu ? ES_XS_FORM_GEGLU : 0) | (ln ? ES_XS_FORM_LN : 0) | (res ? ES_XS_FORM_RES : 0) | (pp ? ES_XS_FORM_PP : 0) | (gn ? ES_XS_FORM_GN : 0);
+}
+
+// Everything es_linear_xs decides, as numbers
+struct XsRoute {
+  int form;                        // xs_form_id of the instantiation
+  int grid, threads, lds;
+  int runs;                        // launches the call is cut into (1 unless an operand outgrows the 32-bit buffer offsets) ...
+  int rows_per_run;                // ... and rows per full run; the grid is then the first run's
+};
+
+// activations / outputs beyond the kernel's 32-bit buffer offsets: runs of whole 256-row blocks (whole samples with GroupNorm in front,
+// whose statistics are per sample), one launch each - like es_conv_gemm's launch_in_chunks: the row blocks of a launch never interact,
+// so the cuts change nothing in the results
+bool xs_oversize(const es_xs_desc& d) {
+  return (size_t)d.M * d.K * 2 >= es_operand_limit_v || ((size_t)d.M + 256) * d.ldo * 2 >= es_operand_limit_v;
+}
+
+long long xs_run_rows(const es_xs_desc& d) {         // below gn_hw: one sample alone is too large
+  const size_t wide = (size_t)(d.K > d.ldo ? d.K : d.ldo) * 2;
+  long long rows = es_operand_limit_v > 512 * wide ? (long long)((es_operand_limit_v - 256 * wide - 1) / wide) : 256;
+  rows -= rows % 256;
+  if (rows < 256) rows = 256;
+  if (d.gn_part && rows >= d.gn_hw) rows -= rows % d.gn_hw;
+  return rows;
+}
+
+// the first row past weight group g
+long long xs_group_end(const es_xs_desc& d, int g) { return d.ngroups > 1 && g + 1 < d.ngroups ? (long long)d.mt_end[g] * 128 : d.M; }
+
+// every check of es_linear_xs that needs no pointer's target: null = the descriptor can be launched, else the refusal's text
+const char* xs_check(const es_xs_desc* d) {
+  if (d->K != 320 && d->K != 640) return "es_linear_xs: K must be 320 or 640";
+  const int CH = d->K == 320 ? 64 : 32;
+  const int P = 128 / (d->geglu ? CH : CH * 2);
+  if (d->M < 1 || d->Cout < CH || d->Cout % (CH * P) || d->rows_padded < d->Cout)
+    return "es_linear_xs: Cout must be a multiple of the 128-byte output line (64 stored channels)";
+  const int total = d->Cout / CH;
+  if (d->nslices < 1 || d->chunks_per_slice < P || d->chunks_per_slice % P ||
+      (long long)d->nslices * d->chunks_per_slice < total || (long long)(d->nslices - 1) * d->chunks_per_slice >= total)
+    return "es_linear_xs: slices must cover Cout in whole output lines, none empty";
+  const int cstore = d->geglu ? d->Cout / 2 : d->Cout;
+  if (d->ldo < cstore || d->ldo % 8) return "es_linear_xs: bad output pitch";
+  if ((size_t)d->rows_padded * d->K * 2 >= 0x7FFFFFFFull) return "es_linear_xs: weights larger than 2 GiB (32-bit buffer offsets)";
+  if (d->ngroups > 4) return "es_linear_xs: at most 4 groups";
+  if (d->gn_part) {
+    if (d->geglu || d->ln || d->residual) return "es_linear_xs: GroupNorm in front (gn_part) needs the plain projection: no GEGLU, no LayerNorm fold, no residual";
+    if (d->gn_groups < 1 || d->gn_groups > 32 || d->K % d->gn_groups || d->gn_hw < 256 || d->gn_hw % 256 || d->M % d->gn_hw || d->gn_nchunk < 1 || d->gn_nchunk > 64)
+      return "es_linear_xs: gn_part needs 1..32 groups dividing K, samples of a whole number of 256-row blocks covering M, 1..64 chunks";
+    if (d->ngroups <= 1 && (!d->gn_gamma || !d->gn_beta)) return "es_linear_xs: gn_part without gn_gamma / gn_beta";
+    for (int g = 0; g < d->ngroups && d->ngroups > 1; ++g)
+      if (!d->gn_gamma_g[g] || !d->gn_beta_g[g]) return "es_linear_xs: gn_part without gn_gamma_g / gn_beta_g for every group";
+    // the statistics are per SAMPLE and gamma / beta / weights per GROUP: a sample split between two groups is no GroupNorm of either,
+    // and an oversize launch is cut into runs of whole samples
+    for (int g = 0; g < d->ngroups && d->ngroups > 1; ++g)
+      if (((long long)d->mt_end[g] * 128) % d->gn_hw) return "es_linear_xs: gn_part needs weight groups of whole samples (mt_end * 128 a multiple of gn_hw)";
+  }
+  if (d->residual && (d->K != 320 || d->geglu || d->ln)) return "es_linear_xs: a residual needs K = 320, no GEGLU, no LayerNorm fold (rows of ldo elements, like out)";
+  if (d->ngroups > 1) {
+    const int tm = (d->M + 127) / 128;
+    for (int g = 0; g < d->ngroups; ++g)
+      // (the LAST run may end anywhere: it ends the launch, and a row block's group is found from its first 128-row tile alone)
+      if (!d->w_g[g] || !d->bias_g[g] || d->mt_end[g] <= (g ? d->mt_end[g - 1] : 0) || (g + 1 < d->ngroups && (d->mt_end[g] & 1)))
+        return "es_linear_xs: groups must be non-empty runs of whole 256-row blocks (the last may be ragged)";
+    if (d->mt_end[d->ngroups - 1] != tm) return "es_linear_xs: groups must cover M";
+  }
+  if (d->gn_part && xs_oversize(*d) && xs_run_rows(*d) < d->gn_hw) return "es_linear_xs: one sample exceeds 2 GiB (32-bit buffer offsets)";
+  return nullptr;
+}
+
+// of a descriptor xs_check has passed
+XsRoute xs_route(const es_xs_desc& d, const XsKnobs& k) {
+  XsRoute r{};
+  const bool geglu = d.geglu != 0, gn = d.gn_part != nullptr;
+  r.form = xs_form_id(d.K / 32, geglu, d.ln != 0, d.residual != nullptr, gn || (k.pp && !geglu), gn);
+  r.threads = 512;
+  r.lds = XS_LDS;
+  long long M = d.M;
+  r.runs = 1;
+  r.rows_per_run = d.M;
+  if (xs_oversize(d)) {
+    const long long rows = xs_run_rows(d);
+    long long r0 = 0;
+    r.runs = 0;
+    for (int g = 0; g < (d.ngroups > 1 ? d.ngroups : 1); ++g) { const long long r1 = xs_group_end(d, g); r.runs += (int)((r1 - r0 + rows - 1) / rows); r0 = r1; }
+    r.rows_per_run = (int)rows;
+    M = rows < xs_group_end(d, 0) ? rows : xs_group_end(d, 0);
+  }
+  r.grid = (int)((M + XS_ROWS - 1) / XS_ROWS) * d.nslices;
+  return r;
+}
+
 // which instantiation the last launch of this process went to (es_linear_xs_last_form: tests assert the form they mean to run); written by
-// launch_one from its OWN template arguments, never recomputed from the descriptor
+// launch_one from its OWN template arguments, never copied from the route
 int xs_last_form = 0;
 
-template <typename T, int KC, bool GEGLU, bool LN, bool RES = false, bool PP = false, bool GN = false>
-int launch_one(const es_xs_desc& d, hipStream_t st) {
-  xs_last_form = KC | (GEGLU ? ES_XS_FORM_GEGLU : 0) | (LN ? ES_XS_FORM_LN : 0) | (RES ? ES_XS_FORM_RES : 0) | (PP ? ES_XS_FORM_PP : 0) |
-                 (GN ? ES_XS_FORM_GN : 0);
-  const int rbs = (d.M + XS_ROWS - 1) / XS_ROWS;
+template <typename T, int KC, bool GEGLU, bool LN, bool RES, bool PP, bool GN>
+int launch_one(const es_xs_desc& d, const XsRoute& r, hipStream_t st) {
+  xs_last_form = xs_form_id(KC, GEGLU, LN, RES, PP, GN);
   auto kfn = linear_xs_kernel<T, KC, GEGLU, LN, RES, PP, GN>;
   static bool attr_set = false;
   if (!attr_set) {
     (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, XS_LDS);
     attr_set = true;
   }
-  hipLaunchKernelGGL(kfn, dim3(rbs * d.nslices), dim3(512), XS_LDS, st, d);
+  hipLaunchKernelGGL(kfn, dim3(r.grid), dim3(r.threads), r.lds, st, d);
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
-// form of the plain (no GEGLU) launches: 1 = two-barrier ping-pong (default), 0 = the one-barrier form (ES_XS_PP=0; es_linear_xs_set_pp for
-// A/B runs inside one process).  Same arithmetic in the same order either way: bit-identical outputs.
-int xs_pp = [] { const char* e = getenv("ES_XS_PP"); return e ? atoi(e) : 1; }();
-
 template <typename T>
-int launch(const es_xs_desc& d, hipStream_t st) {
-  const bool g = d.geglu != 0, ln = d.ln != 0;
-  if (d.gn_part)       // GroupNorm in front (checked by es_linear_xs: plain projection); the ping-pong form whatever es_linear_xs_set_pp says
-    return d.K == 320 ? launch_one<T, 10, false, false, false, true, true>(d, st) : launch_one<T, 20, false, false, false, true, true>(d, st);
-  if (xs_pp && !g) {
-    if (d.residual) return launch_one<T, 10, false, false, true, true>(d, st);
-    if (d.K == 320) return ln ? launch_one<T, 10, false, true, false, true>(d, st) : launch_one<T, 10, false, false, false, true>(d, st);
-    return ln ? launch_one<T, 20, false, true, false, true>(d, st) : launch_one<T, 20, false, false, false, true>(d, st);
+int launch(const es_xs_desc& d, const XsRoute& r, hipStream_t st) {
+  switch (r.form) {
+#define X(KC, GEGLU, LN, RES, PP, GN) case xs_form_id(KC, GEGLU, LN, RES, PP, GN): return launch_one<T, KC, GEGLU, LN, RES, PP, GN>(d, r, st);
+    XS_TABLE(X)
+#undef X
   }
-  if (d.residual) return launch_one<T, 10, false, false, true>(d, st);     // (K = 320, no GEGLU, no LayerNorm: checked by es_linear_xs)
-  if (d.K == 320) {
-    if (g) return ln ? launch_one<T, 10, true, true>(d, st) : launch_one<T, 10, true, false>(d, st);
-    return ln ? launch_one<T, 10, false, true>(d, st) : launch_one<T, 10, false, false>(d, st);
+  return -2;
+}
+
+// an oversize launch, cut into runs of `rows` rows per weight group
+int launch_in_runs(const es_xs_desc& d, long long rows, hipStream_t st) {
+  long long r0 = 0;
+  for (int g = 0; g < (d.ngroups > 1 ? d.ngroups : 1); ++g) {
+    const long long r1 = xs_group_end(d, g);
+    for (long long a = r0; a < r1; a += rows) {
+      es_xs_desc s = d;
+      s.M = (int)(r1 - a < rows ? r1 - a : rows);
+      if (d.ngroups > 1) { s.w = d.w_g[g]; s.bias = d.bias_g[g]; }
+      s.ngroups = 0;
+      for (int k = 0; k < 4; ++k) s.mt_end[k] = 0x7FFFFFFF;
+      s.x = (const char*)d.x + (size_t)a * d.K * 2;
+      s.out = (char*)d.out + (size_t)a * d.ldo * 2;
+      if (d.residual) s.residual = (const char*)d.residual + (size_t)a * d.ldo * 2;
+      if (d.gn_part) {
+        s.gn_part = d.gn_part + (size_t)(a / d.gn_hw) * d.gn_nchunk * d.gn_groups * 2;
+        if (d.ngroups > 1) { s.gn_gamma = d.gn_gamma_g[g]; s.gn_beta = d.gn_beta_g[g]; }
+      }
+      const XsRoute r = xs_route(s, xs_knobs());
+      if (const int rc = s.dtype == ES_F16 ? launch<f16>(s, r, st) : launch<bf16>(s, r, st)) return rc;
+    }
+    r0 = r1;
   }
-  if (g) return ln ? launch_one<T, 20, true, true>(d, st) : launch_one<T, 20, true, false>(d, st);
-  return ln ? launch_one<T, 20, false, true>(d, st) : launch_one<T, 20, false, false>(d, st);
+  return 0;
 }
 
 }  // namespace
 
 extern "C" void es_set_error(const char* msg);
 
-extern unsigned long long es_operand_limit_v;          // gemm_conv.hip: 0x7FFFFFFF unless a test lowered it
+extern "C" int es_linear_xs_set_pp(int on) { const int prev = xs_knobs().pp; xs_knobs().pp = on; return prev; }
 
-extern "C" int es_linear_xs_set_pp(int on) { const int prev = xs_pp; xs_pp = on; return prev; }
+extern "C" void es_linear_xs_knobs(es_xs_knobs* out) { *out = xs_knobs(); }
 
 extern "C" int es_linear_xs_last_form(void) { return xs_last_form; }
 
+extern "C" int es_linear_xs_route(const es_xs_desc* d, const es_xs_knobs* knobs, int32_t out[ES_XS_ROUTE_FIELDS]) {
+  if (const char* why = xs_check(d)) { es_set_error(why); return -1; }
+  const XsRoute r = xs_route(*d, knobs ? *knobs : xs_knobs());
+  const int32_t v[ES_XS_ROUTE_FIELDS] = {r.form, r.grid, r.threads, r.lds, r.runs, r.rows_per_run};
+  for (int i = 0; i < ES_XS_ROUTE_FIELDS; ++i) out[i] = v[i];
+  return 0;
+}
+
 extern "C" int es_linear_xs(const es_xs_desc* d, void* stream) {
   if (!d->x || !d->out || (d->ngroups <= 1 && (!d->w || !d->bias))) { es_set_error("es_linear_xs: null pointer (bias is required: pass zeros)"); return -1; }
-  if (d->K != 320 && d->K != 640) { es_set_error("es_linear_xs: K must be 320 or 640"); return -1; }
-  const int CH = d->K == 320 ? 64 : 32;
-  const int P = 128 / (d->geglu ? CH : CH * 2);
-  if (d->M < 1 || d->Cout < CH || d->Cout % (CH * P) || d->rows_padded < d->Cout) {
-    es_set_error("es_linear_xs: Cout must be a multiple of the 128-byte output line (64 stored channels)"); return -1; }
-  const int total = d->Cout / CH;
-  if (d->nslices < 1 || d->chunks_per_slice < P || d->chunks_per_slice % P ||
-      (long long)d->nslices * d->chunks_per_slice < total || (long long)(d->nslices - 1) * d->chunks_per_slice >= total) {
-    es_set_error("es_linear_xs: slices must cover Cout in whole output lines, none empty"); return -1; }
-  const int cstore = d->geglu ? d->Cout / 2 : d->Cout;
-  if (d->ldo < cstore || d->ldo % 8) { es_set_error("es_linear_xs: bad output pitch"); return -1; }
-  if ((size_t)d->rows_padded * d->K * 2 >= 0x7FFFFFFFull) { es_set_error("es_linear_xs: weights larger than 2 GiB (32-bit buffer offsets)"); return -1; }
-  // activations / outputs beyond the kernel's 32-bit buffer offsets: runs of whole 256-row blocks, one launch each (below)
-  const bool chunked = (size_t)d->M * d->K * 2 >= es_operand_limit_v || ((size_t)d->M + 256) * d->ldo * 2 >= es_operand_limit_v;
-  if (d->ngroups > 4) { es_set_error("es_linear_xs: at most 4 groups"); return -1; }
-  if (d->gn_part) {
-    if (d->geglu || d->ln || d->residual) { es_set_error("es_linear_xs: GroupNorm in front (gn_part) needs the plain projection: no GEGLU, no LayerNorm fold, no residual"); return -1; }
-    if (d->gn_groups < 1 || d->gn_groups > 32 || d->K % d->gn_groups || d->gn_hw < 256 || d->gn_hw % 256 || d->M % d->gn_hw || d->gn_nchunk < 1 || d->gn_nchunk > 64) {
-      es_set_error("es_linear_xs: gn_part needs 1..32 groups dividing K, samples of a whole number of 256-row blocks covering M, 1..64 chunks"); return -1; }
-    if (d->ngroups <= 1 && (!d->gn_gamma || !d->gn_beta)) { es_set_error("es_linear_xs: gn_part without gn_gamma / gn_beta"); return -1; }
-    for (int g = 0; g < d->ngroups && d->ngroups > 1; ++g)
-      if (!d->gn_gamma_g[g] || !d->gn_beta_g[g]) { es_set_error("es_linear_xs: gn_part without gn_gamma_g / gn_beta_g for every group"); return -1; }
-    // the statistics are per SAMPLE and gamma / beta / weights per GROUP: a sample split between two groups is no GroupNorm of either,
-    // and the chunked path below cuts groups into runs of whole samples
-    for (int g = 0; g < d->ngroups && d->ngroups > 1; ++g)
-      if (((long long)d->mt_end[g] * 128) % d->gn_hw) { es_set_error("es_linear_xs: gn_part needs weight groups of whole samples (mt_end * 128 a multiple of gn_hw)"); return -1; }
-  }
-  if (d->residual && (d->K != 320 || d->geglu || d->ln)) { es_set_error("es_linear_xs: a residual needs K = 320, no GEGLU, no LayerNorm fold (rows of ldo elements, like out)"); return -1; }
-  es_xs_desc dd = *d;
-  if (d->ngroups > 1) {
-    const int tm = (d->M + 127) / 128;
-    for (int g = 0; g < d->ngroups; ++g)
-      // (the LAST run may end anywhere: it ends the launch, and a row block's group is found from its first 128-row tile alone)
-      if (!d->w_g[g] || !d->bias_g[g] || d->mt_end[g] <= (g ? d->mt_end[g - 1] : 0) || (g + 1 < d->ngroups && (d->mt_end[g] & 1))) {
-        es_set_error("es_linear_xs: groups must be non-empty runs of whole 256-row blocks (the last may be ragged)"); return -1; }
-    if (d->mt_end[d->ngroups - 1] != tm) { es_set_error("es_linear_xs: groups must cover M"); return -1; }
-  }
-  for (int g = dd.ngroups > 1 ? dd.ngroups : 0; g < 4; ++g) dd.mt_end[g] = 0x7FFFFFFF;
-  ES_PLAN_RECORD(ES_OP_LINEAR_XS, d, sizeof(*d));
-  int rc = 0;
-  if (chunked) {
-    // (like es_conv_gemm's launch_in_chunks: the row blocks of a launch never interact, so the cuts change nothing in the results)
-    const size_t wide = (size_t)(d->K > d->ldo ? d->K : d->ldo) * 2;
-    long long rows = es_operand_limit_v > 512 * wide ? (long long)((es_operand_limit_v - 256 * wide - 1) / wide) : 256;
-    rows -= rows % 256;
-    if (rows < 256) rows = 256;
-    if (d->gn_part) {                      // whole samples per cut: the statistics are per sample
-      if (rows < d->gn_hw) { es_set_error("es_linear_xs: one sample exceeds 2 GiB (32-bit buffer offsets)"); return -1; }
-      rows -= rows % d->gn_hw;
-    }
-    const int ng = d->ngroups > 1 ? d->ngroups : 1;
-    long long r0 = 0;
-    for (int g = 0; g < ng && !rc; ++g) {
-      const long long r1 = d->ngroups > 1 && g + 1 < ng ? (long long)d->mt_end[g] * 128 : d->M;
-      for (long long a = r0; a < r1 && !rc; a += rows) {
-        es_xs_desc s = *d;
-        s.M = (int)(r1 - a < rows ? r1 - a : rows);
-        if (d->ngroups > 1) { s.w = d->w_g[g]; s.bias = d->bias_g[g]; }
-        s.ngroups = 0;
-        for (int k = 0; k < 4; ++k) s.mt_end[k] = 0x7FFFFFFF;
-        s.x = (const char*)d->x + (size_t)a * d->K * 2;
-        s.out = (char*)d->out + (size_t)a * d->ldo * 2;
-        if (d->residual) s.residual = (const char*)d->residual + (size_t)a * d->ldo * 2;
-        if (d->gn_part) {
-          s.gn_part = d->gn_part + (size_t)(a / d->gn_hw) * d->gn_nchunk * d->gn_groups * 2;
-          if (d->ngroups > 1) { s.gn_gamma = d->gn_gamma_g[g]; s.gn_beta = d->gn_beta_g[g]; }
-        }
-        rc = s.dtype == ES_F16 ? launch<f16>(s, (hipStream_t)stream) : launch<bf16>(s, (hipStream_t)stream);
-      }
-      r0 = r1;
-    }
-  } else {
-    rc = dd.dtype == ES_F16 ? launch<f16>(dd, (hipStream_t)stream) : launch<bf16>(dd, (hipStream_t)stream);
+  if (const char* why = xs_check(d)) { es_set_error(why); return -1; }
+  ES_PLAN_RECORD(ES_OP_LINEAR_XS, d, sizeof(*d));       // after validation: a rejected call never enters a recording plan
+  hipStream_t st = (hipStream_t)stream;
+  const XsRoute r = xs_route(*d, xs_knobs());
+  int rc;
+  if (r.runs > 1) rc = launch_in_runs(*d, r.rows_per_run, st);
+  else {
+    es_xs_desc dd = *d;                // unused group ends must compare false, as in es_conv_gemm
+    for (int g = dd.ngroups > 1 ? dd.ngroups : 0; g < 4; ++g) dd.mt_end[g] = 0x7FFFFFFF;
+    rc = dd.dtype == ES_F16 ? launch<f16>(dd, r, st) : launch<bf16>(dd, r, st);
   }
   if (rc) es_set_error("es_linear_xs: launch failed");
   return rc;
 }
+

@@ -80,6 +80,10 @@ class AttnKnobs(C.Structure):       # es_attn_knobs
     _fields_ = [("big_thr", C.c_int64), ("kvres", C.c_int32), ("attn32", C.c_int32), ("qb", C.c_int32), ("pp", C.c_int32)]
 
 
+class XsKnobs(C.Structure):         # es_xs_knobs
+    _fields_ = [("pp", C.c_int32)]
+
+
 class GnDesc(C.Structure):
     _fields_ = [
         ("x", C.c_void_p), ("x2", C.c_void_p), ("out", C.c_void_p),
@@ -193,6 +197,17 @@ XS_FORM_KC_MASK, XS_FORM_GEGLU, XS_FORM_LN, XS_FORM_RES, XS_FORM_PP, XS_FORM_GN 
 GN_FORM_SLAB, GN_FORM_TWO_LAUNCHES = 1, 2        # ES_GN_FORM_*
 GN_ROUTE_FIELDS = ("form", "gpb", "slots", "cpt", "ppb", "nchunk", "ps", "lanes", "blocks", "ipt", "general", "lds")     # ES_GN_ROUTE_*
 ATTN_ROUTE_FIELDS = ("kernel", "q_per_wg", "q_per_wave", "grid_x", "grid_y", "grid_z", "threads", "lds", "qper")               # ES_ATTN_ROUTE_*
+GEMM_ROUTE_FIELDS = ("kernel", "row", "family", "bn", "stages", "waves", "aligned", "grid", "threads", "lds", "reduce", "reduce_cb",
+                     "reduce_grid", "reduce_threads", "runs", "samples_per_run")                                                # ES_GEMM_ROUTE_*
+XS_ROUTE_FIELDS = ("form", "grid", "threads", "lds", "runs", "rows_per_run")                                                     # ES_XS_ROUTE_*
+GEMM_REDUCE_NONE, GEMM_REDUCE_PLAIN, GEMM_REDUCE_GN = 0, 1, 2                                                                   # ES_GEMM_REDUCE_*
+GEMM_ROWS_128, GEMM_ROWS_256 = 33, 6             # rows of the instantiation table: the 128-pixel kernel's, then the 256-pixel kernel's
+
+
+def gemm_kernel_fields(kid: int) -> dict:
+    """es_conv_gemm_last_kernel / the route's kernel id, unpacked (ES_GEMM_KERNEL_*)"""
+    return dict(bn=kid & 0x1FF, bm=64 * (kid >> 9 & 7), stages=kid >> 12 & 7, waves=8 if kid & 0x8000 else 4, aligned=bool(kid & 0x10000),
+                ln=bool(kid & 0x20000), ko=bool(kid & 0x40000), geglu=bool(kid & 0x80000), bf16=bool(kid & 0x100000))
 
 # every symbol include/edgestyle_hip.h declares: (name, restype, argtypes)
 _P, _I, _F, _L = C.c_void_p, C.c_int, C.c_float, C.c_int64
@@ -206,6 +221,10 @@ SYMBOLS = {
     "es_linear_xs": (C.c_int, [C.POINTER(XsDesc), _P]),
     "es_linear_xs_set_pp": (C.c_int, [_I]),
     "es_linear_xs_last_form": (C.c_int, []),
+    "es_linear_xs_knobs": (None, [C.POINTER(XsKnobs)]),
+    "es_linear_xs_route": (C.c_int, [C.POINTER(XsDesc), C.POINTER(XsKnobs), C.POINTER(C.c_int32)]),
+    "es_conv_gemm_last_kernel": (C.c_int, []),
+    "es_conv_gemm_route": (C.c_int, [C.POINTER(GemmDesc), C.POINTER(C.c_int32)]),
     "es_attention": (C.c_int, [C.POINTER(AttnDesc), _P]),
     "es_attention_set_kvres": (C.c_int, [_I]),
     "es_attention_last_kernel": (C.c_int, []),
@@ -370,6 +389,22 @@ def group_norm_route(N: int, HW: int, C1: int, C2: int, groups: int, stats_only:
     out = (C.c_int32 * len(GN_ROUTE_FIELDS))()
     check(load().es_group_norm_route(C.byref(d), out), "es_group_norm_route")
     return dict(zip(GN_ROUTE_FIELDS, out))
+
+
+def gemm_route(desc: GemmDesc) -> dict:
+    """es_conv_gemm_route as a dict keyed by GEMM_ROUTE_FIELDS (raises where es_conv_gemm would refuse the descriptor; its pointers
+    count as present or absent only)"""
+    out = (C.c_int32 * len(GEMM_ROUTE_FIELDS))()
+    check(load().es_conv_gemm_route(C.byref(desc), out), "es_conv_gemm_route")
+    return dict(zip(GEMM_ROUTE_FIELDS, out))
+
+
+def xs_route(desc: XsDesc, knobs: "XsKnobs | None" = None) -> dict:
+    """es_linear_xs_route as a dict keyed by XS_ROUTE_FIELDS (raises where es_linear_xs would refuse the descriptor).  knobs None: the
+    process's own (ES_XS_PP and es_linear_xs_set_pp)."""
+    out = (C.c_int32 * len(XS_ROUTE_FIELDS))()
+    check(load().es_linear_xs_route(C.byref(desc), None if knobs is None else C.byref(knobs), out), "es_linear_xs_route")
+    return dict(zip(XS_ROUTE_FIELDS, out))
 
 
 def attention_route(N: int, heads: int, Sq: int, Skv: int, d: int, *, dtype: int = ES_F16, knobs: "AttnKnobs | None" = None, ld=None) -> dict:

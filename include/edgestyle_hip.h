@@ -27,8 +27,8 @@ enum { ES_ACT_NONE = 0, ES_ACT_SILU = 1, ES_ACT_GEGLU = 2 };
  * projection); es_conv_gemm8p_form_ok, es_ctx_graph_hazard, es_linear_xs_set_pp, es_attention_set_kvres, es_set_operand_limit,
  * es_group_norm_chunks, es_clock_probe.  Context images carry the version and are rebuilt across it.
  * (Host-only helpers that no plan or image records - es_plan_gemm_choice, es_linear_xs_eligible, es_linear_xs_last_form, es_launch_choose and its siblings
- * es_launch_route / es_launch_gn_fold / es_launch_gn_handover / es_launch_wide_stream, es_attention_route, es_attention_knobs - come and go
- * without a new version.) */
+ * es_launch_route / es_launch_gn_fold / es_launch_gn_handover / es_launch_wide_stream, es_attention_route, es_attention_knobs,
+ * es_conv_gemm_route, es_conv_gemm_last_kernel, es_linear_xs_route, es_linear_xs_knobs - come and go without a new version.) */
 #define ES_ABI_VERSION 7
 int es_abi_version(void);
 /* sizeof the descriptor structs as compiled (0 gemm, 1 attn, 2 gn, 3 fusion, 4 ln, 5 xs): lets a binding verify its mirror */
@@ -136,6 +136,42 @@ int es_conv_gemm(const es_gemm_desc* d, void* stream);
  * do not depend on the cuts.  Test knob: lower the limit so that small launches are cut (0 restores 2 GiB); returns the previous value. */
 unsigned long long es_set_operand_limit(unsigned long long bytes);
 size_t es_conv_gemm_workspace_bytes(const es_gemm_desc* d);
+/* test query: the kernel instantiation the last es_conv_gemm launch of this process went to (of a launch cut into runs: the last run's),
+ * packed from the template arguments the launcher instantiates, never from the route or the descriptor; 0 before the first launch, and a
+ * dry recording call leaves it alone.  Bits 0-8: couts per workgroup (64 | 128 | 160 | 256 | 320), the rest as below. */
+enum { ES_GEMM_KERNEL_BN_MASK = 0x1FF,
+       ES_GEMM_KERNEL_BM64_SHIFT = 9, ES_GEMM_KERNEL_BM64_MASK = 0x7,        /* pixels per workgroup / 64: 1 | 2, 4 = the phase-interleaved kernel */
+       ES_GEMM_KERNEL_STAGES_SHIFT = 12, ES_GEMM_KERNEL_STAGES_MASK = 0x7,   /* LDS ring depth 2 | 3 | 4 */
+       ES_GEMM_KERNEL_WAVES8 = 0x8000,     /* 8 waves per workgroup (else 4) */
+       ES_GEMM_KERNEL_ALIGNED = 0x10000,   /* channels in whole 64-deep K-steps */
+       ES_GEMM_KERNEL_LN = 0x20000,        /* LayerNorm folded in */
+       ES_GEMM_KERNEL_KO = 0x40000,        /* chunk-major K order */
+       ES_GEMM_KERNEL_GEGLU = 0x80000,     /* phase-interleaved kernel: the GEGLU epilogue's own instantiation */
+       ES_GEMM_KERNEL_BF16 = 0x100000 };
+int es_conv_gemm_last_kernel(void);
+/* host-only query (tests, tools): the launch es_conv_gemm would make for this descriptor.  Pointer fields are read as present or absent
+ * only, so NULL x / w / out are fine and no GPU is needed; -1 with the text es_conv_gemm would refuse the descriptor with. */
+enum { ES_GEMM_REDUCE_NONE = 0, ES_GEMM_REDUCE_PLAIN = 1, ES_GEMM_REDUCE_GN = 2 };
+enum {
+  ES_GEMM_ROUTE_KERNEL = 0,          /* the id es_conv_gemm_last_kernel reports after the launch */
+  ES_GEMM_ROUTE_ROW = 1,             /* row of the library's instantiation table (the 33 of the 128-pixel kernel, then the 6 of the 256-pixel one) */
+  ES_GEMM_ROUTE_FAMILY = 2,          /* 0: the 128- (64-) pixel kernel, 1: the phase-interleaved 256-pixel kernel */
+  ES_GEMM_ROUTE_BN = 3,              /* couts per workgroup as they run: a recorded 320 | 256 whose epilogue form the big tile lacks runs on 160 | 128 */
+  ES_GEMM_ROUTE_STAGES = 4,          /* ... LDS ring depth (0 = auto is 2) */
+  ES_GEMM_ROUTE_WAVES = 5,
+  ES_GEMM_ROUTE_ALIGNED = 6,         /* C1 and C1 + C2 multiples of 64 */
+  ES_GEMM_ROUTE_GRID = 7,
+  ES_GEMM_ROUTE_THREADS = 8,
+  ES_GEMM_ROUTE_LDS = 9,             /* dynamic LDS bytes */
+  ES_GEMM_ROUTE_REDUCE = 10,         /* split-K: ES_GEMM_REDUCE_* */
+  ES_GEMM_ROUTE_REDUCE_CB = 11,      /* ... GroupNorm hand-over: channels per workgroup (64 | 80 | 128), else 0 */
+  ES_GEMM_ROUTE_REDUCE_GRID = 12,
+  ES_GEMM_ROUTE_REDUCE_THREADS = 13,
+  ES_GEMM_ROUTE_RUNS = 14,           /* launches the call is cut into (operands beyond the 32-bit buffer offsets), else 1 */
+  ES_GEMM_ROUTE_SAMPLES_PER_RUN = 15,/* ... samples per full run; grid and reduce grid are then the first run's */
+  ES_GEMM_ROUTE_FIELDS = 16
+};
+int es_conv_gemm_route(const es_gemm_desc* d, int32_t out[ES_GEMM_ROUTE_FIELDS]);
 
 /* ---------------------------------------------------------------------------------------------------------
  * es_linear_xs — row-stationary short-K linear layer (K = 320 | 640): out = epilogue(LayerNorm?(x) W^T + bias).
@@ -180,8 +216,22 @@ typedef struct {
 } es_xs_desc;
 int es_linear_xs(const es_xs_desc* d, void* stream);
 /* tool / test knob: the form of the plain (no GEGLU) launches - 1 = two-barrier ping-pong between the wave groups (default; ES_XS_PP=0
- * in the environment turns it off), 0 = the one-barrier form.  Bit-identical outputs.  Returns the previous setting. */
+ * in the environment, read on first use, turns it off), 0 = the one-barrier form.  Bit-identical outputs.  Returns the previous setting. */
 int es_linear_xs_set_pp(int on);
+typedef struct { int32_t pp; } es_xs_knobs;
+void es_linear_xs_knobs(es_xs_knobs* out);        /* host-only: a copy of the process's knobs */
+/* host-only query (tests, tools): the launch es_linear_xs would make for this descriptor under these knobs (NULL: the process's).  Pointer
+ * fields are read as present or absent only, and no GPU is needed; -1 with the text es_linear_xs would refuse the descriptor with. */
+enum {
+  ES_XS_ROUTE_FORM = 0,              /* the id es_linear_xs_last_form reports after the launch (ES_XS_FORM_*) */
+  ES_XS_ROUTE_GRID = 1,
+  ES_XS_ROUTE_THREADS = 2,
+  ES_XS_ROUTE_LDS = 3,               /* dynamic LDS bytes */
+  ES_XS_ROUTE_RUNS = 4,              /* launches the call is cut into (operands beyond the 32-bit buffer offsets), else 1 */
+  ES_XS_ROUTE_ROWS_PER_RUN = 5,      /* ... rows per full run; the grid is then the first run's */
+  ES_XS_ROUTE_FIELDS = 6
+};
+int es_linear_xs_route(const es_xs_desc* d, const es_xs_knobs* knobs, int32_t out[ES_XS_ROUTE_FIELDS]);
 /* test query: the kernel instantiation the last es_linear_xs launch of this process went to (of a launch cut into runs: the last run's) -
  * K / 32 (10 | 20) in the low byte, or'ed with the flags below; 0 before the first launch.  Set by the launcher from the template arguments
  * it instantiates, not recomputed from the descriptor.  (Host-only, recorded by no plan or image: no new ES_ABI_VERSION.) */

@@ -1431,6 +1431,87 @@ def attn_route(N, heads, Sq, Skv, d, knobs=None):
     return tiled(2 if (big and two_forms) else 1, 4 * w, w, 256, lds)
 
 
+GEMM_ROUTE_KEYS = ("kernel", "row", "family", "bn", "stages", "waves", "aligned", "grid", "threads", "lds", "reduce", "reduce_cb", "reduce_grid",
+                   "reduce_threads", "runs", "samples_per_run")
+
+
+def gemm_kernel_id(bm, bn, stages, waves, aligned, ln, ko, geglu, bf16) -> int:
+    """es_conv_gemm_last_kernel of an instantiation (include/edgestyle_hip.h ES_GEMM_KERNEL_*): couts per workgroup in bits 0-8, pixels / 64
+    in 9-11, ring depth in 12-14, then one bit each for 8 waves, aligned channels, LayerNorm fold, chunk-major K, GEGLU (big tile), bf16"""
+    return bn | (bm // 64) << 9 | stages << 12 | (waves == 8) << 15 | bool(aligned) << 16 | bool(ln) << 17 | bool(ko) << 18 | bool(geglu) << 19 | \
+        bool(bf16) << 20
+
+
+def gemm_big_tile_takes(d) -> bool:
+    """whether the phase-interleaved 256-pixel kernel has the epilogue a launch recorded with bn = 320 | 256 needs (csrc/gemm_conv8p.hip,
+    DESIGN section 4): split-K partials of the 320 tile always; else no SiLU, whole 8-channel stores, and a time embedding only as one row
+    per 128-pixel half without a residual.  The 256-wide form: no time embedding at all, GEGLU only as the bare projection, and neither
+    GEGLU nor the LayerNorm fold with split-K or a GroupNorm hand-over."""
+    geglu, hw = d.act == 2, d.Hout * d.Wout
+    if d.Cout % 8:
+        return d.bn == 320 and d.splitk > 1
+    if d.bn == 320:
+        return d.splitk > 1 or (d.act == 0 and not (d.temb and (hw % 128 or d.residual)))
+    if d.temb or d.act == 1:
+        return False
+    bare = not (d.splitk > 1 or d.gn_part)
+    return (not geglu or (bare and not d.residual and not d.out_lo)) and (not d.ln_colsum or bare)
+
+
+def gemm_route(d, limit=0x7FFFFFFF):
+    """Python mirror of gemm_route() in csrc/gemm_conv.hip for a descriptor es_conv_gemm accepts (any object with es_gemm_desc's fields;
+    pointers count as present or absent), keyed like lib.GEMM_ROUTE_FIELDS with row = None: the mirror names the instantiation by its
+    template arguments, not by its place in the library's table.  Written from the rules (header of csrc/gemm_conv.hip):
+    which ring depths and wave counts exist for which tile, not the order in which the library looks them up."""
+    cdiv = lambda a, b: (a + b - 1) // b
+    hw, ln, geglu = d.Hout * d.Wout, bool(d.ln_colsum), d.act == 2
+    aligned = d.C1 % 64 == 0 and d.C2 % 64 == 0
+    bn, stages = d.bn, d.stages or 2
+    big = bn in (320, 256) and gemm_big_tile_takes(d)
+    if bn in (320, 256) and not big:
+        bn, stages = bn // 2, 2             # the tile of half the width, as the planner would have launched it
+    if big:
+        bm, waves, stages, ko = 256, 8, 2, bn == 320 and d.korder == 1
+    else:
+        bm = 64 if bn == 64 else 128
+        waves = 8 if (d.waves == 8 and bm == 128 and aligned) else 4
+        # ring depths that exist: 2 everywhere; 4 on aligned channels except 8 waves x 160; 3 only for the plain 4-wave 128-pixel tile
+        have = {2}
+        if aligned and not (waves == 8 and bn == 160):
+            have.add(4)
+        if aligned and bm == 128 and waves == 4 and not ln:
+            have.add(3)
+        stages = stages if stages in have else 2
+        ko = d.korder == 1 and aligned and not ln
+    kid = gemm_kernel_id(bm, bn, stages, waves, aligned or big, ln, ko, big and geglu, d.dtype == 1)
+    # operands beyond `limit` bytes: runs of whole samples per weight group
+    cs = d.Cout // 2 if geglu else d.Cout
+    per = max(0 if d.x_nmod else d.Hsrc * d.Wsrc * max(d.C1, d.C2) * 2, hw * cs * 2, hw * max(d.Ct1, d.Ct2) * 2 if d.t1 else 0)
+    slab_rows = hw * (d.rows_padded // 8)
+    over = per * d.N >= limit or (d.x_nmod and d.x_nmod * d.Hsrc * d.Wsrc * d.C1 * 2 >= limit) or (d.splitk > 1 and d.N * slab_rows >= 2 ** 31)
+    N, runs, ns = d.N, 1, d.N
+    if over:
+        ns = (limit - 1) // per
+        if d.splitk > 1:
+            ns = min(ns, (2 ** 31 - 1) // slab_rows)
+        if hw == 1 and ns >= 256:
+            ns -= ns % 256
+        if d.x_nmod:
+            ns -= ns % d.x_nmod
+        ends = [d.mt_end[g] * 128 // hw for g in range(d.ngroups)] if d.ngroups > 1 else [d.N]
+        runs = sum(cdiv(e - s, ns) for s, e in zip([0] + ends, ends))
+        N = min(ns, ends[0])
+    M = N * hw
+    r = dict(kernel=kid, row=None, family=int(big), bn=bn, stages=stages, waves=waves, aligned=int(aligned), grid=cdiv(M, bm) * (d.rows_padded // bn) * d.splitk,
+             threads=64 * waves, lds=stages * (bm + bn) * 64 * 2, reduce=0, reduce_cb=0, reduce_grid=0, reduce_threads=0, runs=runs, samples_per_run=ns)
+    if d.splitk > 1 and d.gn_part:
+        cb = {320: 80, 160: 80, 128: 128}.get(bn, 64)          # the statistics' two-entry scheme assumes the N tile of the 4-wave kernels
+        r.update(reduce=2, reduce_cb=cb, reduce_grid=(M // 64) * (d.rows_padded // cb), reduce_threads=64 * cb // 8)
+    elif d.splitk > 1:
+        r.update(reduce=1, reduce_grid=cdiv(M * (d.rows_padded // 8), 256), reduce_threads=256)
+    return r
+
+
 ATTN_INPUT_KINDS = ("randn", "shift-300", "shift+300", "last_key_decides", "one_loud_query", "loud_values_2e4")
 
 
@@ -1961,6 +2042,30 @@ def xs_form_id(K, kind, pp) -> int:
     """es_linear_xs_last_form of the instantiation (K, kind, pp)"""
     return K // 32 | (XS_FORM_GEGLU if kind.startswith("geglu") else 0) | (XS_FORM_LN if kind in ("ln", "geglu_ln") else 0) | \
         (XS_FORM_RES if kind == "res" else 0) | (XS_FORM_PP if pp else 0) | (XS_FORM_GN if kind == "gn" else 0)
+
+
+XS_ROUTE_KEYS = ("form", "grid", "threads", "lds", "runs", "rows_per_run")
+XS_LDS = 3 * (40960 + 256) + 8 * 32 * 144        # csrc/linear_xs.hip: three 40 KB weight stages (+ 64 fp32 bias values each), eight 32-row output tiles
+
+
+def xs_route(d, pp=1, limit=0x7FFFFFFF):
+    """Python mirror of xs_route() in csrc/linear_xs.hip for a descriptor es_linear_xs accepts (any object with es_xs_desc's fields), keyed
+    like lib.XS_ROUTE_FIELDS.  The form is what the descriptor's epilogue is called in XS_KINDS; the ping-pong form runs everything without
+    GEGLU when the knob is on and GroupNorm-in-front always."""
+    cdiv = lambda a, b: (a + b - 1) // b
+    kind = "gn" if d.gn_part else "res" if d.residual else ("geglu" if d.geglu else "") + ("_ln" if d.geglu and d.ln else "ln" if d.ln else "") or "plain"
+    form = xs_form_id(d.K, kind, kind == "gn" or (pp != 0 and not d.geglu))
+    M, runs, rows = d.M, 1, d.M
+    if d.M * d.K * 2 >= limit or (d.M + 256) * d.ldo * 2 >= limit:
+        # whole 256-row blocks (whole samples with GroupNorm in front) that leave one block of slack below the limit; never less than one block
+        row_bytes = max(d.K, d.ldo) * 2
+        rows = max(256, ((limit - 1) // row_bytes - 256) // 256 * 256 if limit > 512 * row_bytes else 256)
+        if d.gn_part:
+            rows -= rows % d.gn_hw
+        ends = [d.mt_end[g] * 128 for g in range(d.ngroups - 1)] + [d.M] if d.ngroups > 1 else [d.M]
+        runs = sum(cdiv(e - s, rows) for s, e in zip([0] + ends, ends))
+        M = min(rows, ends[0])
+    return dict(form=form, grid=cdiv(M, XS_ROWS) * d.nslices, threads=512, lds=XS_LDS, runs=runs, rows_per_run=rows)
 
 
 def xs_geometry(K, kind):

@@ -1,6 +1,7 @@
 """es_conv_gemm (csrc/gemm_conv.hip, the 256 x 320 tile of csrc/gemm_conv8p.hip) on odd geometries, judged by the misrounded share
 (tests/numerics.py): every launch writes into a slice cut from the middle of a NaN-filled buffer, the guard rows around the slice must
-stay NaN and the slice must hold none; the kernel that ran is read from the launch descriptor; the share of elements that differ from
+stay NaN and the slice must hold none; the kernel that ran is read from es_conv_gemm_last_kernel (the launcher's own template arguments)
+and must be the tile the row names, with its ring depth, waves and K order; the share of elements that differ from
 the correctly rounded fp64 result (with a residual: from base_alg, the design rounds twice there) must stay within MARGIN x the largest
 share among independent fp32 implementations of the same launch - base_alg with chains of 8 and of 32, torch's fp32 convolution, and
 F.unfold + torch.mm on the device's own matrix cores - all computed when the test runs; and the row_err bars of test_numerics_gpu.py.
@@ -14,6 +15,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from edgestyle_amd import lib
 from tests import numerics as nm
 from tests import test_numerics_gpu as T
 from tests.test_numerics_gpu import knobs, launches, judge, done
@@ -200,6 +202,38 @@ def row_id(row):
                      f"xcd{row['xcd']}", row["epi"]] + ([row["inputs"]] if row["inputs"] != "randn" else []) + ([row["weights"]] if row["weights"] != "randn" else []))
 
 
+def route_desc(row):
+    """the row's launch of one sample as a descriptor for lib.gemm_route: geometry and flags as launch() will record them, pointers as
+    present or absent (the route reads no more of them)"""
+    g, (C1, C2, Cout), epi, tails = _geometry(row), CHANNELS[row["chan"]], row["epi"], _tails(row)
+    pw_bn = 160 if (Cout % 160 == 0 and Cout % 128 != 0) else 128          # ops.choose_bn
+    d = lib.GemmDesc()
+    d.x = d.w = d.out = 1
+    d.N, d.Hsrc, d.Wsrc, d.C1, d.C2, d.x2 = 1, g["H"], g["W"], C1, C2, 1 if C2 else None
+    (d.Hout, d.Wout), d.Cout = g["out_hw"], Cout
+    d.rows_padded, d.Kpad = -(-Cout // pw_bn) * pw_bn, _nk(row) * 64
+    d.ksize, d.stride, d.pad, d.upsample = g["k"], g["stride"], g["pad"], int(g["upsample"])
+    d.splitk, d.workspace = row["splitk"], 1 if row["splitk"] > 1 else None
+    d.bn, d.waves = {"t64": 64, "t320": 320}.get(row["tile"], pw_bn), {"t4w": 4, "t8w": 8}.get(row["tile"], 0)
+    d.stages, d.korder, d.xcd_m_fastest, d.dtype = row["stages"], row["korder"], row["xcd"], lib.ES_F16 if row["dtype"] == torch.float16 else lib.ES_BF16
+    for i, ct in enumerate(tails):
+        setattr(d, f"t{i + 1}", 1)
+        setattr(d, f"Ct{i + 1}", ct)
+    d.temb = 1 if epi.startswith("temb") else None
+    d.act = lib.ACT_SILU if epi == "temb_silu_res" else lib.ACT_NONE
+    d.residual = 1 if epi in ("temb_silu_res", "wide1", "wide2") else None
+    d.out_lo, d.residual_lo = 1 if epi in ("wide1", "wide2") else None, 1 if epi == "wide2" else None
+    d.gn_part, d.gn_groups = 1 if epi == "gn_part" else None, 32
+    return d
+
+
+def expected_kernel(row, bn):
+    """es_conv_gemm_last_kernel, unpacked (lib.gemm_kernel_fields), of the tile the row names: its pixels, waves, ring depth and K order"""
+    C1, C2, _ = CHANNELS[row["chan"]]
+    return dict(bn=bn, bm=_tile_rows(row), stages=row["stages"], waves={"t8w": 8, "t320": 8}.get(row["tile"], 4),
+                aligned=C1 % 64 == 0 and C2 % 64 == 0, ln=False, ko=bool(row["korder"]), geglu=False, bf16=row["dtype"] == torch.bfloat16)
+
+
 def validate(row):
     """the preconditions of the row's form, so that a table entry that cannot run is found at import and not on the GPU"""
     g, (C1, C2, Cout) = _geometry(row), CHANNELS[row["chan"]]
@@ -221,8 +255,11 @@ def validate(row):
         assert hw % _tile_rows(row) != 0, name
     if row["epi"] in ("wide1", "wide2"):
         assert row["dtype"] == torch.bfloat16 and Cout % 8 == 0, name
-    if row["tile"] == "t320" and row["splitk"] == 1:        # es_conv_gemm8p_form_ok, restated; the test also asks the library
-        assert row["epi"] != "temb_silu_res" and row["epi"] != "temb_pix" and Cout % 8 == 0, name
+    # the tile the row names is the tile its descriptor reaches: the library's route (no GPU needed) and its Python mirror both say so.
+    # A t320 row whose epilogue the 256-pixel kernel lacks would run - and pass - on the 128 x 160 tile
+    d = route_desc(row)
+    got, mirror = lib.gemm_route(d), nm.gemm_route(d)
+    assert lib.gemm_kernel_fields(got["kernel"]) == lib.gemm_kernel_fields(mirror["kernel"]) == expected_kernel(row, d.bn), (name, got, mirror)
     if row["inputs"] == "peak":
         assert row["dtype"] == torch.float16, name
     if row["weights"] == "zero":
@@ -332,6 +369,9 @@ def launch(row, cases):
     got = {k: int(getattr(d, k)) for k in want}
     if got != want:
         problems.append(f"descriptor {got} != {want}")
+    ran = lib.gemm_kernel_fields(lib.load().es_conv_gemm_last_kernel())          # the launcher's own template arguments
+    if ran != expected_kernel(row, want["bn"]):
+        problems.append(f"kernel {ran} ran, the row's tile is {expected_kernel(row, want['bn'])}")
     if len(cases) > 1 and int(d.ngroups) != len(cases):
         problems.append(f"ngroups {int(d.ngroups)}")
     if wide and not (int(d.out_lo or 0) and (int(d.residual_lo or 0) != 0) == (c0["res_lo"] is not None)):
@@ -490,12 +530,6 @@ def run_row(row):
 def test_conv_gemm_on_odd_geometries(row):
     """one table row: N = 1 and N = 3 (and a larger N where those are small), guards, kernel identity, misrounded share, row_err bars,
     bit identity with the 4-wave tile on the non-square rows"""
-    from edgestyle_amd import lib
-    g, Cout = _geometry(row), CHANNELS[row["chan"]][2]
-    if row["tile"] == "t320" and row["splitk"] == 1:       # the recorded tile is the tile that runs only for the forms the 256 x 320 tile takes
-        epi = row["epi"]
-        assert lib.load().es_conv_gemm8p_form_ok(int(lib.ACT_SILU if epi == "temb_silu_res" else lib.ACT_NONE), Cout, int(epi.startswith("temb")),
-                                                 g["out_hw"][0] * g["out_hw"][1], int(epi in ("temb_silu_res", "wide1", "wide2")))
     done(run_row(row))
 
 

@@ -630,8 +630,8 @@ def test_linear_xs_refuses_a_weight_group_boundary_inside_a_group_norm_sample():
 
 
 def test_conv_gemm_refuses_an_empty_problem_before_it_sizes_the_launch():
-    """es_conv_gemm: N, Hout, Wout, Cout >= 1 are checked BEFORE the launch is sized for the 32-bit buffer offsets (oversize() and the
-    dry launch_in_chunks() divide by the sample size and by Hout * Wout * (rows_padded / 8)): a malformed descriptor returns -1 with
+    """es_conv_gemm: N, Hout, Wout, Cout >= 1 are checked BEFORE the launch is sized for the 32-bit buffer offsets (oversize() and
+    run_samples() divide by the sample size and by Hout * Wout * (rows_padded / 8)): a malformed descriptor returns -1 with
     a message.  The descriptors below are oversize ones (operand limit lowered) with split-K, the form that reached the divisions."""
     buf = (ctypes.c_char * 4096)()
     p = ctypes.addressof(buf)
@@ -1298,3 +1298,314 @@ def test_linear_xs_last_form_is_set_by_launches_only(monkeypatch):
     for name in ("GEGLU", "LN", "RES", "PP", "GN"):
         m = re.search(rf"ES_XS_FORM_{name} = (0x[0-9A-Fa-f]+)", hdr)
         assert m and int(m.group(1), 16) == getattr(lib, f"XS_FORM_{name}")
+
+
+# ---- es_conv_gemm_route / es_linear_xs_route: the launch as numbers, asked on the CPU ------------------------------------------------
+_HOSTBUF = (ctypes.c_char * 4096)()
+_PTR = ctypes.addressof(_HOSTBUF)
+_GEMM_PTRS = ("x2", "temb", "residual", "workspace", "ln_colsum", "t1", "t2", "residual_lo", "out_lo", "gn_part")
+
+
+def _gemm_desc(M=128, hw=None, C1=64, C2=0, ksize=1, Cout=1280, bn=128, groups=None, **kw):
+    """a descriptor es_conv_gemm accepts - M pixels as M // hw samples of hw x 1 (hw None: one sample), C1 (+ C2) -> Cout channels, host
+    buffers - with `kw` laid over it: pointer fields by truth value, `groups` = the mt_end table of a grouped launch, the rest as given"""
+    d = lib.GemmDesc()
+    d.x = d.w = d.out = _PTR
+    hw = hw or M
+    d.N, d.Hout, d.Wout, d.Hsrc, d.Wsrc = M // hw, hw, 1, hw, 1
+    d.C1, d.C2, d.x2 = C1, C2, _PTR if C2 else None
+    d.ksize, d.stride, d.pad = ksize, 1, ksize // 2
+    d.Cout, d.rows_padded = Cout, -(-Cout // bn) * bn if bn > 0 else Cout
+    d.Kpad = -(-ksize * ksize * (C1 + C2) // 64) * 64
+    d.splitk, d.bn, d.dtype, d.gn_groups = 1, bn, lib.ES_F16, 32
+    for g, end in enumerate(groups or ()):
+        d.ngroups, d.mt_end[g], d.w_g[g], d.bias_g[g] = len(groups), end, _PTR, _PTR
+    for name, v in kw.items():
+        setattr(d, name, (_PTR if v else None) if name in _GEMM_PTRS else v)
+    return d
+
+
+def _xs_desc(M=512, K=320, Cout=640, nslices=1, geglu=0, groups=None, **kw):
+    d = lib.XsDesc()
+    d.x = d.out = d.w = d.bias = _PTR
+    ch = 64 if K == 320 else 32
+    P = 128 // (ch if geglu else 2 * ch)
+    d.M, d.K, d.Cout, d.rows_padded, d.geglu, d.dtype = M, K, Cout, Cout, geglu, lib.ES_F16
+    d.ldo = Cout // 2 if geglu else Cout
+    d.nslices, d.chunks_per_slice = nslices, -(-(-(-(Cout // ch) // nslices)) // P) * P
+    d.gn_groups, d.gn_nchunk, d.gn_hw, d.gn_eps = 32, 4, 256, 1e-6
+    for g, end in enumerate(groups or ()):
+        d.ngroups, d.mt_end[g] = len(groups), end
+        d.w_g[g] = d.bias_g[g] = d.gn_gamma_g[g] = d.gn_beta_g[g] = _PTR
+    for name, v in kw.items():
+        setattr(d, name, (_PTR if v else None) if name in ("residual", "gn_part", "gn_gamma", "gn_beta") else v)
+    return d
+
+
+def _source_texts(path, who):
+    """every refusal text of `who` in a .hip file, but the two that need a pointer's target or a GPU"""
+    src = open(os.path.join(ROOT, "edgestyle_amd", "csrc", path)).read()
+    return {t for t in re.findall(rf'"({who}: [^"]+)"', src) if "null pointer" not in t and "launch failed" not in t}
+
+
+class _RouteSweep:
+    """Asks the route and a dry recording call of the entry point about each descriptor: both accept, or both refuse with one text.
+    Collects the refusal texts and the routes."""
+
+    def __init__(self, dry, route_fn, entry, fields, knobs=False):
+        self.L, self.dry, self.route_fn, self.entry, self.knobs = dry.L, dry, route_fn, entry, knobs
+        self.out, self.texts, self.fields = (ctypes.c_int32 * len(fields))(), set(), fields
+
+    def ask(self, d, knobs=None):
+        args = (ctypes.byref(d), knobs, self.out) if self.knobs else (ctypes.byref(d), self.out)
+        rc, size = self.route_fn(*args), self.dry.size()
+        if rc != 0:
+            text = self.L.es_last_error()
+            assert rc == -1 and self.entry(ctypes.byref(d), None) == -1 and self.L.es_last_error() == text, (text, self.L.es_last_error())
+            assert self.dry.size() == size
+            self.texts.add(text.decode())
+            return None
+        assert self.entry(ctypes.byref(d), None) == 0 and self.dry.size() == size + 1, self.L.es_last_error()
+        return dict(zip(self.fields, self.out))
+
+
+# one descriptor per refusal of gemm_check that the sweep below does not meet: (operand limit or 0, what to lay over _gemm_desc())
+_GEMM_REFUSED = [
+    (0, dict(ngroups=5)), (0, dict(ngroups=2)), (0, dict(M=256, groups=[1, 3])), (0, dict(M=256, bn=320, C1=128, ksize=3, groups=[1, 2])),
+    (0, dict(bn=96)), (0, dict(bn=256, waves=8)), (0, dict(rows_padded=1284)), (0, dict(Kpad=0)), (0, dict(C1=60, Kpad=64)),
+    (0, dict(C1=72, C2=64)), (0, dict(Cout=32768, Kpad=32768)), (0, dict(N=0)), (0, dict(ksize=2)),
+    (1 << 20, dict(M=1024, hw=128, gn_part=1)), (1 << 15, dict(M=1024, hw=128, x_nmod=2)), (1 << 16, dict(M=1024, hw=128)),
+    (1 << 20, dict(M=1024, hw=256, groups=[3, 8])), (1 << 21, dict(M=1024, hw=256, groups=[2, 8], x_nmod=2)),
+    (0, dict(t1=1, Ct1=32, Kpad=128)), (0, dict(Ct1=64, Kpad=128)), (0, dict(x_nmod=2)), (0, dict(out_lo=1)), (0, dict(residual_lo=1)),
+    (0, dict(gn_part=1, gn_groups=0)), (0, dict(korder=1)), (0, dict(splitk=0)), (0, dict(splitk=2, C1=128)), (0, dict(act=2, bn=160)),
+    (0, dict(stages=5)), (0, dict(waves=2)), (0, dict(ln_colsum=1, ksize=3)), (0, dict(M=256, ln_colsum=1, groups=[1, 2])),
+    (0, dict(waves=8, stages=3)),
+]
+
+
+def test_conv_gemm_route_is_the_mirrors_answer_and_refuses_what_the_launch_refuses():
+    """es_conv_gemm_route (gemm_route of csrc/gemm_conv.hip, which es_conv_gemm launches from) against the Python restatement of the rules
+    (tests/numerics.py gemm_route) in every field but the table row, over two hand-pruned grids: every tile request (bn x stages x waves x
+    channels x ksize x korder x LayerNorm fold) at M = 1 .. 257 pixels with the plain epilogue, and every epilogue (activation, time
+    embedding, residual, wide stream, split-K, GroupNorm hand-over, fold) on every tile at three sample sizes and two output widths.
+    Every descriptor is also given to es_conv_gemm on the dry recorder: both accept it, or both refuse it with the same text.  Between
+    them the grids and _GEMM_REFUSED reach every row of the instantiation table (33 + 6 per dtype, each under one kernel id) and
+    produce every refusal text gemm_check has."""
+    from tests import numerics as nm
+    assert lib.GEMM_ROUTE_FIELDS == nm.GEMM_ROUTE_KEYS
+    rows, n = {}, 0
+    with _DryPlan() as dry:
+        sweep = _RouteSweep(dry, dry.L.es_conv_gemm_route, dry.L.es_conv_gemm, lib.GEMM_ROUTE_FIELDS)
+
+        def point(d):
+            got = sweep.ask(d)
+            if got is not None:
+                want = nm.gemm_route(d)
+                assert {k: v for k, v in got.items() if k != "row"} == {k: v for k, v in want.items() if k != "row"}, (got, want)
+                assert rows.setdefault(got["row"], got["kernel"] & ~0x100000) == got["kernel"] & ~0x100000
+                f = lib.gemm_kernel_fields(got["kernel"])
+                assert (f["bn"], f["stages"], f["waves"], f["bm"] == 256) == (got["bn"], got["stages"], got["waves"], got["family"] == 1)
+            return got
+        for bn in (64, 128, 160, 256, 320):
+            for stages in (0, 2, 3, 4):
+                for waves in (0, 4, 8):
+                    for C1, C2 in ((64, 0), (128, 64), (72, 0)):
+                        for ksize, korder, ln in ((1, 0, 0), (1, 0, 1), (1, 1, 0), (3, 0, 0), (3, 1, 0), (3, 1, 1)):
+                            for M in (1, 64, 128, 129, 256, 257):
+                                n += 1
+                                point(_gemm_desc(M, C1=C1, C2=C2, ksize=ksize, bn=bn, stages=stages, waves=waves, korder=korder, ln_colsum=ln,
+                                                 dtype=n & 1))
+            for act in (lib.ACT_NONE, lib.ACT_SILU, lib.ACT_GEGLU):
+                for temb, residual, out_lo in ((0, 0, 0), (1, 0, 0), (0, 1, 0), (1, 1, 0), (0, 1, 1), (1, 1, 1), (0, 0, 1)):
+                    for splitk in (1, 2):
+                        for gn_part in (0, 1):
+                            for ln in (0, 1):
+                                for M, hw in ((128, 128), (256, 64), (257, 257)):
+                                    for Cout in (1280, 1276):
+                                        n += 1
+                                        point(_gemm_desc(M, hw, C1=128, Cout=Cout, bn=bn, act=act, temb=temb, residual=residual, out_lo=out_lo,
+                                                         residual_lo=out_lo and temb, splitk=splitk, workspace=1, gn_part=gn_part, ln_colsum=ln,
+                                                         dtype=n & 1))
+        for limit, kw in _GEMM_REFUSED:
+            prev = dry.L.es_set_operand_limit(limit)
+            try:
+                assert point(_gemm_desc(**kw)) is None, kw
+            finally:
+                dry.L.es_set_operand_limit(prev)
+    assert sorted(rows) == list(range(lib.GEMM_ROWS_128 + lib.GEMM_ROWS_256)) and len(set(rows.values())) == len(rows), sorted(rows)
+    assert all((lib.gemm_kernel_fields(k)["bm"] == 256) == (r >= lib.GEMM_ROWS_128) for r, k in rows.items())
+    missing = _source_texts("gemm_conv.hip", "es_conv_gemm") - sweep.texts
+    assert not missing and len(sweep.texts) >= 35, missing
+
+
+def test_conv_gemm_tile_downgrades():
+    """What a descriptor recorded with the big tile runs on when the phase-interleaved kernel lacks its epilogue, as literals: bn = 320
+    with SiLU, with a time embedding over samples that are no multiple of 128 pixels, with a time embedding and a residual, or with
+    Cout % 8 != 0 runs the 128 x 160 tile on a ring of 2; the same four with split-K stay on the 256-pixel kernel (it writes raw partials).
+    bn = 256 with SiLU, Cout % 8 != 0 or GEGLU + residual runs 128 x 128; the plain, folded and GEGLU forms stay."""
+    fam = lambda **kw: tuple(lib.gemm_route(_gemm_desc(256, C1=128, **kw))[k] for k in ("family", "bn", "stages", "waves", "threads"))
+    big320, big256, t160, t128 = (1, 320, 2, 8, 512), (1, 256, 2, 8, 512), (0, 160, 2, 4, 256), (0, 128, 2, 4, 256)
+    for kw in (dict(act=lib.ACT_SILU), dict(temb=1, hw=64), dict(temb=1, residual=1, hw=128), dict(Cout=1276)):
+        assert fam(bn=320, **kw) == t160, kw
+        assert fam(bn=320, splitk=2, workspace=1, **kw) == big320, kw
+    assert fam(bn=320) == fam(bn=320, temb=1, hw=128) == fam(bn=320, residual=1) == fam(bn=320, residual=1, out_lo=1) == big320
+    for kw in (dict(act=lib.ACT_SILU), dict(Cout=1276), dict(act=lib.ACT_GEGLU, residual=1)):
+        assert fam(bn=256, **kw) == t128, kw
+    for kw in (dict(), dict(ln_colsum=1), dict(act=lib.ACT_GEGLU), dict(act=lib.ACT_GEGLU, ln_colsum=1), dict(residual=1), dict(splitk=2, workspace=1)):
+        assert fam(bn=256, **kw) == big256, kw
+    r = lib.gemm_route(_gemm_desc(256, C1=128, bn=320, act=lib.ACT_SILU, korder=1, ksize=3))
+    assert lib.gemm_kernel_fields(r["kernel"]) == dict(bn=160, bm=128, stages=2, waves=4, aligned=True, ln=False, ko=True, geglu=False, bf16=False)
+    with pytest.raises(lib.EdgeStyleHipError, match="es_conv_gemm: bn=320 is the 256-pixel phase-interleaved tile"):
+        lib.gemm_route(_gemm_desc(256, C1=128, bn=320, stages=4))
+
+
+def test_conv_gemm_route_counts_the_runs_of_an_oversize_launch():
+    """With the operand limit lowered (es_set_operand_limit), the route's run count, samples per run and first-run grid against the
+    mirror: a plain launch, a grouped one (runs never span a weight group), one whose source repeats every x_nmod samples (runs of whole
+    periods), a split-K one (the reduce grid is the first run's), and a linear layer (hw = 1: cuts between 256-row tiles)."""
+    from tests import numerics as nm
+    L = lib.load()
+    cases = [(1 << 20, dict(M=1024, hw=128), (3, 3)), (1 << 20, dict(M=2048, hw=256, groups=[6, 16]), (8, 1)),
+             (1 << 22, dict(M=2560, hw=256, groups=[6, 20]), (3, 6)), (1 << 22, dict(M=2560, hw=256, x_nmod=2), (2, 6)),
+             (1 << 20, dict(M=1024, hw=128, splitk=2, C1=128, workspace=1), (3, 3)), (1 << 22, dict(M=4096, hw=1), (3, 1536))]           # 2560 B per row: 1638 rows fit, 1536 in whole 256-row tiles
+    for limit, kw, (runs, per) in cases:
+        prev = L.es_set_operand_limit(limit)
+        try:
+            d = _gemm_desc(**kw)
+            got, want = lib.gemm_route(d), nm.gemm_route(d, limit)
+        finally:
+            L.es_set_operand_limit(prev)
+        assert {k: v for k, v in got.items() if k != "row"} == {k: v for k, v in want.items() if k != "row"}, (kw, got, want)
+        assert (got["runs"], got["samples_per_run"]) == (runs, per), (kw, got)
+        assert lib.gemm_route(d)["runs"] == 1
+
+
+def test_conv_gemm_production_routes():
+    """Which kernel the launches of a 512 x 512 batch-1 step go to: what es_launch_choose picks at default knobs for the layers
+    test_every_knob_bends_the_launch_choice_as_before enumerates (those it sends to es_conv_gemm), laid into a descriptor and routed.
+    DESIGN section 4: the 3x3 convolutions of the grouped encoder's 64 x 64 level and the GEGLU of that level run the 256-pixel
+    phase-interleaved kernel, short-K 1x1 layers the 128-pixel tile on 8 waves, tiny launches the 64 x 64 tile (a ring of 4 where K is
+    long), split-K launches the 4-wave tile with the plain reduce.  The literals are a first run's; none contradicts DESIGN."""
+    L = lib.load()
+
+    def route(cin, cout, k, M, hw, geglu=False, **facts):
+        bn = 128 if geglu else ops.choose_bn(cout)
+        pw = ops.PackedWeight(torch.empty(-(-cout // bn) * bn, k * k * cin, device="meta"), None, cout, cin, k, bn, geglu,
+                              ln_colsum=torch.empty(0) if geglu else None)
+        ch, q = lib.LaunchChoice(), ops.launch_query(M, hw, pw, C1=cin, src_numel=M * cin, **facts)
+        assert L.es_launch_choose(ctypes.byref(q), ctypes.byref(ops.launch_knobs()), ctypes.byref(ch)) == 0 and ch.route == lib.ROUTE_CONV_GEMM
+        r = lib.gemm_route(_gemm_desc(M, hw, C1=cin, ksize=k, Cout=cout, bn=ch.bn, splitk=ch.splitk, stages=ch.stages, waves=ch.waves,
+                                      workspace=1, act=lib.ACT_GEGLU if geglu else 0, ln_colsum=geglu))
+        return r["family"], r["bn"], r["stages"], r["waves"], r["reduce"]
+    assert route(320, 960, 1, 1024, 1024) == (0, 64, 2, 4, 0)
+    assert route(320, 320, 1, 256, 256) == (0, 64, 2, 4, 0)
+    assert route(1280, 1280, 1, 4096, 4096) == (0, 128, 2, 8, 0)
+    assert route(320, 320, 3, 57344, 4096) == (1, 320, 2, 8, 0)
+    assert route(320, 640, 3, 57344, 4096) == (1, 320, 2, 8, 0)
+    assert route(1280, 1280, 1, 1024, 1024) == (0, 64, 4, 4, 0)
+    assert route(320, 320, 3, 8192, 4096, gn_groups=32) == (0, 160, 2, 4, lib.GEMM_REDUCE_PLAIN)
+    assert route(1280, 1280, 3, 512, 256, gn_groups=32) == (0, 128, 2, 4, lib.GEMM_REDUCE_PLAIN)
+    assert route(1280, 10240, 1, 28672, 4096, geglu=True) == (1, 256, 2, 8, 0)
+
+
+def test_conv_gemm_last_kernel_is_set_by_launches_only():
+    """es_conv_gemm_last_kernel: written by the launchers alone - 0 in a process that has launched nothing (no GPU: this one), and a dry
+    recording call or a route query leaves it as it was; the bit layout is the header's"""
+    L = lib.load()
+    before = L.es_conv_gemm_last_kernel()
+    if not torch.cuda.is_available():
+        assert before == 0
+    with _DryPlan() as dry:
+        assert L.es_conv_gemm(ctypes.byref(_gemm_desc()), None) == 0 and dry.size() == 1
+        assert lib.gemm_route(_gemm_desc())["kernel"] != 0 and L.es_conv_gemm_last_kernel() == before
+    hdr = open(os.path.join(ROOT, "include", "edgestyle_hip.h")).read()
+    bits = {name: int(v, 0) for name, v in re.findall(r"ES_GEMM_KERNEL_(\w+) = (0x[0-9A-Fa-f]+|\d+)", hdr)}
+    all_on = bits["BN_MASK"] | bits["BM64_MASK"] << bits["BM64_SHIFT"] | bits["STAGES_MASK"] << bits["STAGES_SHIFT"] | bits["WAVES8"] | \
+        bits["ALIGNED"] | bits["LN"] | bits["KO"] | bits["GEGLU"] | bits["BF16"]
+    assert lib.gemm_kernel_fields(all_on) == dict(bn=0x1FF, bm=64 * 7, stages=7, waves=8, aligned=True, ln=True, ko=True, geglu=True, bf16=True)
+    assert all_on == (1 << 21) - 1
+
+
+# one descriptor per refusal of xs_check that the sweep below does not meet
+_XS_REFUSED = [
+    (0, dict(K=384)), (0, dict(Cout=96)), (0, dict(chunks_per_slice=4)), (0, dict(ldo=324)), (0, dict(rows_padded=1 << 22)), (0, dict(ngroups=5)),
+    (0, dict(gn_part=1, gn_gamma=1, gn_beta=1, residual=1)), (0, dict(gn_part=1, gn_gamma=1, gn_beta=1, gn_hw=300)), (0, dict(gn_part=1)),
+    (0, dict(gn_part=1, groups=[2, 4], gn_gamma_g=(ctypes.c_void_p * 4)())), (0, dict(M=1024, gn_part=1, gn_hw=512, groups=[2, 8])),
+    (0, dict(residual=1, K=640)), (0, dict(groups=[3, 4])), (0, dict(groups=[2, 5])),
+    (1 << 19, dict(M=2048, Cout=320, gn_part=1, gn_gamma=1, gn_beta=1, gn_hw=1024)),
+]
+
+
+def test_linear_xs_route_is_the_mirrors_answer_and_refuses_what_the_launch_refuses():
+    """es_linear_xs_route (xs_route of csrc/linear_xs.hip, which es_linear_xs launches from) against the Python restatement (tests/numerics.py
+    xs_route) over K x GEGLU x LayerNorm x residual x GroupNorm-in-front x ping-pong knob x M x slices, and - operand limit lowered - over
+    launches cut into runs, grouped and with GroupNorm in front.  Every descriptor also goes to es_linear_xs on the dry recorder: both
+    accept, or both refuse with the same text.  The grid reaches all 16 instantiations, the grid and _XS_REFUSED every text of xs_check."""
+    from tests import numerics as nm
+    assert lib.XS_ROUTE_FIELDS == nm.XS_ROUTE_KEYS
+    forms = set()
+    with _DryPlan() as dry:
+        sweep = _RouteSweep(dry, dry.L.es_linear_xs_route, dry.L.es_linear_xs, lib.XS_ROUTE_FIELDS, knobs=True)
+        for K in (320, 640):
+            for geglu, ln, residual, gn in ((0, 0, 0, 0), (0, 1, 0, 0), (1, 0, 0, 0), (1, 1, 0, 0), (0, 0, 1, 0), (0, 0, 0, 1), (1, 0, 1, 0), (0, 1, 1, 0),
+                                            (1, 0, 0, 1), (0, 1, 0, 1)):
+                for pp in (0, 1):
+                    for M in (1, 255, 256, 257, 513):
+                        for nslices in (1, 2, 3):
+                            d = _xs_desc(M, K, nslices=nslices, geglu=geglu, ln=ln, residual=residual, gn_part=gn, gn_gamma=gn, gn_beta=gn, dtype=M & 1)
+                            got = sweep.ask(d, ctypes.byref(lib.XsKnobs(pp)))
+                            if got is not None:
+                                assert got == nm.xs_route(d, pp), (got, nm.xs_route(d, pp))
+                                forms.add(got["form"])
+        assert forms == {nm.xs_form_id(*f) for f in nm.XS_FORMS} and len(forms) == 16
+        # (1 MiB over rows of 1280 B: 819 rows less one block of slack, 512 in whole blocks; 3 + 6 runs of the groups of 1536 and 2561 rows;
+        #  a limit below two blocks, or rows of 2560 B: single blocks)
+        for limit, kw, (runs, rows) in [(1 << 20, dict(M=4096), (8, 512)), (1 << 20, dict(M=4097, groups=[12, 33]), (9, 512)),
+                                        (1 << 20, dict(M=4096, gn_part=1, gn_gamma=1, gn_beta=1, gn_hw=512), (8, 512)),
+                                        (1 << 16, dict(M=700), (3, 256)), (1 << 20, dict(M=4096, K=640, geglu=1, Cout=2560), (16, 256))]:
+            prev = dry.L.es_set_operand_limit(limit)
+            try:
+                d = _xs_desc(**kw)
+                got = sweep.ask(d, None)
+                assert got == nm.xs_route(d, 1, limit) and (got["runs"], got["rows_per_run"]) == (runs, rows), (kw, got, nm.xs_route(d, 1, limit))
+            finally:
+                dry.L.es_set_operand_limit(prev)
+        for limit, kw in _XS_REFUSED:
+            prev = dry.L.es_set_operand_limit(limit)
+            try:
+                assert sweep.ask(_xs_desc(**kw), None) is None, kw
+            finally:
+                dry.L.es_set_operand_limit(prev)
+    missing = _source_texts("linear_xs.hip", "es_linear_xs") - sweep.texts
+    assert not missing and len(sweep.texts) >= 15, missing
+
+
+def test_linear_xs_knobs_are_read_on_first_use_and_follow_set_pp():
+    """ES_XS_PP is read on first use, not when the library is loaded: a child process that sets it to 0 AFTER loading the library gets
+    the one-barrier form from its first route query; unset, the default is the ping-pong form; es_linear_xs_set_pp edits the struct
+    es_linear_xs_knobs copies and the route follows it"""
+    import subprocess
+    import sys
+    from tests import numerics as nm
+    child = ("import os, sys; sys.path.insert(0, %r); from edgestyle_amd import lib; L = lib.load(); os.environ['ES_XS_PP'] = '0'; "
+             "d, k = lib.XsDesc(), lib.XsKnobs(); d.M, d.K, d.Cout, d.rows_padded, d.ldo, d.nslices, d.chunks_per_slice = 512, 320, 640, 640, 640, 1, 10; "
+             "r = lib.xs_route(d); L.es_linear_xs_knobs(k); print(r['form'], k.pp)" % ROOT)
+    env = {k: v for k, v in os.environ.items() if k != "ES_XS_PP"}
+    out = subprocess.run([sys.executable, "-c", child], env=env, capture_output=True, text=True, check=True).stdout.split()
+    assert [int(v) for v in out] == [nm.xs_form_id(320, "plain", 0), 0], out
+    if "ES_XS_PP" in os.environ:
+        return
+    L, k = lib.load(), lib.XsKnobs()
+    L.es_linear_xs_knobs(k)
+    first = k.pp
+    assert L.es_linear_xs_set_pp(0) == first
+    try:
+        L.es_linear_xs_knobs(k)
+        assert k.pp == 0 and lib.xs_route(_xs_desc())["form"] == nm.xs_form_id(320, "plain", 0)
+        assert lib.xs_route(_xs_desc(), lib.XsKnobs(1))["form"] == nm.xs_form_id(320, "plain", 1)
+        assert lib.xs_route(_xs_desc(gn_part=1, gn_gamma=1, gn_beta=1))["form"] == nm.xs_form_id(320, "gn", 1)
+        assert L.es_linear_xs_set_pp(1) == 0 and lib.xs_route(_xs_desc())["form"] == nm.xs_form_id(320, "plain", 1)
+    finally:
+        L.es_linear_xs_set_pp(first)
+    L.es_linear_xs_knobs(k)
+    assert k.pp == first == 1
