@@ -34,16 +34,19 @@
 
 #include "../../include/edgestyle_hip.h"
 #include "plan.h"
+#include "host_util.h"
+#include "launch_policy.h"
 
 extern "C" void es_set_error(const char* msg);
 extern "C" int es_plan_set_dry(int on);
+
+using namespace es_host;
+using namespace es_policy;
 
 namespace {
 
 [[noreturn]] void fail(const std::string& m) { throw std::runtime_error(m); }
 inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
-inline int round_up(int a, int b) { return (a + b - 1) / b * b; }
-constexpr int BK = 64, BM = 128;
 constexpr unsigned long long FAKE_HEAP = 1ull << 44, FAKE_WS = 1ull << 45;
 
 void parallel_for(long long n, const std::function<void(long long, long long)>& fn) {
@@ -55,16 +58,6 @@ void parallel_for(long long n, const std::function<void(long long, long long)>& 
   for (long long a = 0; a < n; a += step) th.emplace_back(fn, a, std::min(n, a + step));
   for (auto& t : th) t.join();
 }
-
-// ---- 16-bit storage types, round to nearest even like torch's .to(dtype) ------------------------------------------------
-inline uint16_t f32_to_f16(float f) { _Float16 h = (_Float16)f; uint16_t u; memcpy(&u, &h, 2); return u; }
-inline float f16_to_f32(uint16_t u) { _Float16 h; memcpy(&h, &u, 2); return (float)h; }
-inline uint16_t f32_to_bf16(float f) {
-  uint32_t u; memcpy(&u, &f, 4);
-  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (uint16_t)((u >> 16) | 0x40);      // NaN stays NaN
-  return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
-}
-inline float bf16_to_f32(uint16_t h) { uint32_t u = (uint32_t)h << 16; float f; memcpy(&f, &u, 4); return f; }
 
 // ---- state dicts ----------------------------------------------------------------------------------------------------------
 struct Dict {
@@ -85,26 +78,9 @@ struct Dict {
   const es_tensor* find(const std::string& k) const { auto it = m.find(k); return it == m.end() ? nullptr : it->second; }
 };
 long long numel(const es_tensor* t) { long long n = 1; for (int i = 0; i < t->ndim; ++i) n *= t->shape[i]; return n; }
-// the source tensors may live on a device as well (a host that already holds the checkpoint there): copied to the host first
-bool on_device(const void* p) {
-  hipPointerAttribute_t a;
-  const bool dev = hipPointerGetAttributes(&a, p) == hipSuccess && a.type == hipMemoryTypeDevice;
-  (void)hipGetLastError();
-  return dev;
-}
 std::vector<float> to_f32(const es_tensor* t) {
-  const long long n = numel(t);
-  std::vector<float> v((size_t)n);
-  const void* src = t->data;
-  std::vector<char> tmp;
-  if (on_device(src)) {
-    tmp.resize((size_t)n * (t->dtype == ES_F32 ? 4 : 2));
-    if (hipMemcpy(tmp.data(), src, tmp.size(), hipMemcpyDeviceToHost) != hipSuccess) fail(std::string("es_load_weights: cannot read '") + t->key + "' from the device");
-    src = tmp.data();
-  }
-  if (t->dtype == ES_F32) memcpy(v.data(), src, (size_t)n * 4);
-  else if (t->dtype == ES_F16) { const uint16_t* s = (const uint16_t*)src; for (long long i = 0; i < n; ++i) v[i] = f16_to_f32(s[i]); }
-  else { const uint16_t* s = (const uint16_t*)src; for (long long i = 0; i < n; ++i) v[i] = bf16_to_f32(s[i]); }
+  std::vector<float> v;
+  if (!tensor_to_f32(t, &v)) fail(std::string("es_load_weights: cannot read '") + t->key + "' from the device");
   return v;
 }
 
@@ -298,172 +274,8 @@ struct CA {                       // keyword arguments of ops.conv_gemm
   int gn_groups = 0;              // > 0: the output is read by a GroupNorm over that many groups - hand the statistics over
 };
 
-// ---- the launch planner (es_plan_gemm_choice; ops.plan_gemm_reference restates it and tests/test_load_weights_cpu.py sweeps both) ----
+// (no contraction from here on: pack_ln, the LayerNorm and proj_out folds and the fusion packing round like the Python host)
 #pragma clang fp contract(off)
-constexpr double PLAN_T160 = 1.25, PLAN_ALONE = 0.9, PLAN_TFIX = 2.0, PLAN_RED_FIX = 12.0, PLAN_SLAB_BYTES_PER_UNIT = 4.0e6;
-constexpr double PLAN_T320 = 2.3, PLAN_T320_FIX = 3.0;
-// the 256 x 256 tile of the LayerNorm-folded / GEGLU linear layers (tools/ln256_bench.py, round 5)
-constexpr double PLAN_T256 = 2.6, PLAN_T256_FIX = 6.0, PLAN_T256_GEGLU = 7.0, PLAN_LN_TK = 1.55, PLAN_T256_MARGIN = 0.93;
-constexpr int PLAN_BIG_MIN_M = 2048, PLAN_BIG_MIN_NK = 16;
-constexpr double PLAN_T64_ALONE = 0.5, PLAN_T64 = 0.16, PLAN_T64_LONG = 1.5;
-constexpr int PLAN_SMALL_MAX_M = 16384, PLAN_MIN_SLICE = 12, PLAN_NK_NOSPLIT = 10, PLAN_RESIDENT = 512;
-
-// Tool knobs (tools/ab_env_bench.sh: A/Bs of the planner's constants INSIDE the pipeline - the constants were fitted on launches timed
-// in isolation, and the step runs at the package power limit where the ranking can differ): ES_PLAN_T320 (cost of a K-step of the 256 x 320
-// tile, default 2.3), ES_PLAN_BIG_MIN_NK (fewest K-steps it is offered for, 16), ES_PLAN_T256_MARGIN (0.93).  Unset: the fitted values.
-double plan_env(const char* name, double dflt) { const char* e = getenv(name); return e && *e ? atof(e) : dflt; }
-bool plan_gemm(long long M, int rows_padded, int kpad, bool geglu, const int* bns, int nb, bool allow_split, int* o_bn, int* o_sk, int* o_st) {
-  static const double PLAN_T320 = plan_env("ES_PLAN_T320", ::PLAN_T320), PLAN_T256_MARGIN = plan_env("ES_PLAN_T256_MARGIN", ::PLAN_T256_MARGIN);
-  static const int PLAN_BIG_MIN_NK = (int)plan_env("ES_PLAN_BIG_MIN_NK", ::PLAN_BIG_MIN_NK);
-  // The 256 x 256 phase-interleaved tile (round 5) is offered by the callers for the LayerNorm-folded / GEGLU linear layers whose N is a
-  // multiple of 256.  The choice among the OTHER tiles is made first, exactly as before; the 256-wide tile then replaces it where a
-  // model fitted on those layers (tools/ln256_bench.py, profiles/r05_ln256_bench.txt: a round of 512 workgroups of the 128-wide tile
-  // takes nk x 1.55 + 6 units with the fold's statistics, a round of 256 workgroups of the 256 x 256 tile nk x 2.6 + 6, + 7 with the
-  // GEGLU epilogue; WHOLE rounds - its last part-filled round costs a full tile time) says it is at least 7 % faster.
-  int others[8], no = 0;
-  bool has256 = false;
-  for (int bi = 0; bi < nb; ++bi) { if (bns[bi] == 256) has256 = true; else if (no < 8) others[no++] = bns[bi]; }
-  if (has256) {
-    const int nk = kpad / BK;
-    int obn = 0, osk = 1, ost = 2;
-    const bool have_other = no > 0 && plan_gemm(M, rows_padded, kpad, geglu, others, no, allow_split, &obn, &osk, &ost);
-    if (rows_padded % 256) { if (!have_other) return false; *o_bn = obn; *o_sk = osk; *o_st = ost; return true; }
-    const long long t256 = ((M + 255) / 256) * (rows_padded / 256);
-    const double c256 = (double)((t256 + 255) / 256) * ((double)nk * PLAN_T256 + PLAN_T256_FIX + (geglu ? PLAN_T256_GEGLU : 0.0));
-    bool take = !have_other;
-    if (have_other && M >= PLAN_BIG_MIN_M && nk >= PLAN_BIG_MIN_NK && osk == 1 && obn != 64) {
-      const long long to = ((M + BM - 1) / BM) * (rows_padded / obn);
-      const double co = (double)((to + PLAN_RESIDENT - 1) / PLAN_RESIDENT) * ((double)nk * PLAN_LN_TK * (obn == 160 ? PLAN_T160 : 1.0) + PLAN_T256_FIX);
-      take = c256 < PLAN_T256_MARGIN * co;
-    }
-    if (take) { *o_bn = 256; *o_sk = 1; *o_st = 2; } else { *o_bn = obn; *o_sk = osk; *o_st = ost; }
-    return true;
-  }
-  if (geglu) { *o_bn = 128; *o_sk = 1; *o_st = 2; return true; }
-  const int nk = kpad / BK;
-  bool have = false;
-  double bt = 0; int bbn = 0, bsk = 0; long long bwgs = 0;
-  for (int bi = 0; bi < nb; ++bi) {
-    const int bn = bns[bi];
-    if (rows_padded % bn) continue;
-    if (bn == 320 && (M < PLAN_BIG_MIN_M || nk < PLAN_BIG_MIN_NK) && nb > 1) continue;
-    if (bn == 64 && M > PLAN_SMALL_MAX_M && nb > 1) continue;
-    const int bm = bn == 320 ? 256 : (bn == 64 ? 64 : BM);
-    const int resident = bn == 320 ? PLAN_RESIDENT / 2 : (bn == 64 ? 2 * PLAN_RESIDENT : PLAN_RESIDENT);
-    const long long tiles = ((M + bm - 1) / bm) * (rows_padded / bn);
-    int last = 1;
-    if (allow_split && tiles < resident / 2 && nk > PLAN_NK_NOSPLIT) last = std::max(1, std::min(nk / PLAN_MIN_SLICE, 32));
-    for (int sk = 1; sk <= last; ++sk) {
-      const long long wgs = tiles * sk;
-      double tk;
-      if (bn == 320) tk = PLAN_T320;
-      else if (bn == 64) {
-        if (sk > 1 && wgs > PLAN_RESIDENT) continue;
-        const double w = (double)wgs / (double)(PLAN_RESIDENT / 2);
-        const double ex = std::max(0.0, w - 1.0);
-        tk = (PLAN_T64_ALONE + PLAN_T64 * (ex * ex)) * (nk <= 40 ? 1.0 : PLAN_T64_LONG);
-      } else tk = (bn == 160 ? PLAN_T160 : 1.0) * (wgs <= PLAN_RESIDENT / 2 ? PLAN_ALONE : 1.0);
-      // (the 256 x 320 tile costs its fractional number of rounds, no less than 0.9: ops.plan_gemm_reference)
-      const double rounds = bn == 320 ? std::max((double)wgs / 256.0, 0.9) : (double)((wgs + resident - 1) / resident);
-      double t = rounds * (((double)nk / (double)sk) * tk + (bn == 320 ? PLAN_T320_FIX : PLAN_TFIX));
-      if (sk > 1) t += PLAN_RED_FIX + (double)sk * (double)M * (double)rows_padded * 8.0 / PLAN_SLAB_BYTES_PER_UNIT;
-      if (!have || t < bt) { have = true; bt = t; bbn = bn; bsk = sk; bwgs = wgs; }
-    }
-  }
-  if (!have) return false;
-  *o_bn = bbn; *o_sk = bsk;
-  if (bbn == 64) *o_st = (bwgs <= PLAN_RESIDENT && nk / bsk >= 6) ? 4 : 2;
-  else *o_st = (bbn != 320 && bwgs <= PLAN_RESIDENT / 2 && nk / bsk >= 6) ? 4 : 2;
-  return true;
-}
-
-constexpr int XS_TARGET_WGS = 256, XS_MIN_M = 8192;
-bool xs_shape_fits(int ksize, int kpad, int cin, int ctail, int cout, bool geglu) {      // what the kernel can run at all
-  if (ksize != 1 || (kpad != 320 && kpad != 640) || cin != kpad || ctail) return false;
-  const int ch = kpad == 320 ? 64 : 32;
-  const int line = ch * (128 / (geglu ? ch : 2 * ch));
-  return !(cout % line || cout < 4 * line);
-}
-bool xs_shape_ok(long long M, int ksize, int kpad, int cin, int ctail, int cout, bool geglu, long long min_m) {       // ... and where it wins (min_m 0: everywhere)
-  if (!xs_shape_fits(ksize, kpad, cin, ctail, cout, geglu)) return false;
-  if (min_m && (M < min_m || (M < 4 * min_m && cout < (kpad == 320 ? 960 : 1920)))) return false;
-  return true;
-}
-int choose_bn(int cout) { return (cout % 160 == 0 && cout % 128 != 0) ? 160 : 128; }
-
-// ---- the launch policy (include/edgestyle_hip.h es_launch_choose): what BOTH hosts ask between validating a call and filling its
-// descriptor - ops.conv_gemm / gn_proj_in / group_norm and the Builder below ---------------------------------------------------------
-bool wide_stream(int dtype, const es_launch_knobs& k) { return k.wide_stream == 1 || (k.wide_stream < 0 && dtype == ES_BF16); }
-// a rule of the SHAPE alone (grouped and per-net launches of a layer must agree): where the stand-alone GroupNorm is the two-launch form -
-// slabs too large for a workgroup's registers, the 64 x 64 level - the hand-over removes its statistics launch and second read
-bool gn_handover(long long hw, int c, int groups, const es_launch_knobs& k) {
-  if (!k.gn_handover || groups < 1 || c % 8 || hw % 64 || c % groups || c / groups > 64) return false;
-  return k.gn_handover == 2 || !es_group_norm_is_slab((int)hw, c, groups);
-}
-bool groups_tile_256(const es_launch_query& q) {
-  for (int g = 0; g < std::min(q.n_counts, 4); ++g) if ((q.group_n[g] * q.hw) % 256) return false;
-  return true;
-}
-// does this plain linear launch go to es_linear_xs?  (A residual rides along at K = 320 - Attention.to_out / proj_out of the 64 x 64
-// level - unless the launch carries the two-word residual stream, which only es_conv_gemm implements.)
-bool launch_takes_xs(const es_launch_query& q, const es_launch_knobs& k) {
-  const bool xs_res = !q.has_residual || (k.xs_residual && q.kpad == 320 && !q.geglu && !q.has_ln && q.residual_dense && !(q.wide && wide_stream(q.dtype, k)));
-  if (!(q.ksize == 1 && q.stride == 1 && !q.upsample && !q.C2 && !q.has_temb && xs_res && !q.n_tails && q.x_rep == 1 && q.act == ES_ACT_NONE &&
-        q.unit_scale && !q.force_splitk && !k.force_bn && k.xs_enabled)) return false;
-  if (q.ngroups > 1 && (q.ngroups > 4 || !groups_tile_256(q) || !q.groups_agree)) return false;
-  return xs_shape_ok(q.M, q.ksize, q.kpad, q.cin, q.ctail, q.cout, q.geglu != 0, k.xs_min_m);
-}
-bool launch_choose(const es_launch_query& q, const es_launch_knobs& k, es_launch_choice* o) {
-  memset(o, 0, sizeof(*o));
-  if (launch_takes_xs(q, k)) { o->route = ES_ROUTE_LINEAR_XS; return true; }
-  const bool aligned = q.C1 % BK == 0 && q.C2 % BK == 0;
-  const bool big_ok = k.big_tile && aligned && !q.geglu && !q.has_ln && groups_tile_256(q);
-  const bool small_ok = k.small_tile && aligned && !q.geglu && k.force_waves != 8;
-  // the 256 x 256 phase-interleaved tile: LayerNorm-folded and GEGLU linear layers whose N is a multiple of 256
-  const bool ln256_ok = k.big_tile_256 && (q.geglu || q.has_ln) && q.ksize == 1 && q.stride == 1 && !q.upsample && !q.C2 && !q.n_tails && !q.has_temb &&
-                        q.x_rep == 1 && q.C1 % BK == 0 && q.rows_padded % 256 == 0 && q.cout % 8 == 0 && !(q.geglu && q.has_residual) && !q.wide &&
-                        q.gn_groups == 0 && k.force_waves != 8 && groups_tile_256(q);
-  int cand[5], nc = 0;
-  if (ln256_ok) cand[nc++] = 256;
-  if (big_ok) cand[nc++] = 320;
-  cand[nc++] = 160; cand[nc++] = 128;
-  if (small_ok) cand[nc++] = 64;
-  if (k.force_bn) { cand[0] = k.force_bn; nc = 1; }
-  const bool geglu = q.geglu != 0, allow_split = !q.has_ln;
-  int bn, splitk, stages;
-  if (!plan_gemm(q.M, q.rows_padded, q.kpad, geglu, cand, nc, allow_split, &bn, &splitk, &stages)) return false;
-  if (bn == 320 && !k.force_bn && (q.force_splitk ? q.force_splitk : splitk) == 1 &&
-      !es_conv_gemm8p_form_ok(geglu ? ES_ACT_GEGLU : q.act, q.cout, q.has_temb, q.hw, q.has_residual)) {
-    // the 256 x 320 tile does not implement this epilogue form (an activation, time-embedding rows that differ inside a 128-pixel half
-    // or meet a residual): plan again without it, so that the tile planned, recorded and reported is the tile that runs
-    const int at = (int)(std::find(cand, cand + nc, 320) - cand);
-    std::copy(cand + at + 1, cand + nc, cand + at);
-    if (!plan_gemm(q.M, q.rows_padded, q.kpad, geglu, cand, nc - 1, allow_split, &bn, &splitk, &stages)) return false;
-  }
-  if (stages == 4 && !k.deep_ring) stages = 2;
-  if (q.force_splitk) { splitk = q.force_splitk; stages = q.stages; }       // (the planner's ring depth belongs to ITS split)
-  else if (q.stages) stages = q.stages;
-  if (!stages) stages = k.force_stages;
-  o->bn = bn; o->splitk = splitk; o->stages = stages;
-  // 1x1 convs / linears are short-K, latency-bound launches: two waves per SIMD on the same 128-pixel tile overlap DMA issue, fragment reads
-  // and MFMAs (tools/gemm_tune.py: 3-15 % on every 1x1 shape of a batch-1 step, none on 3x3 or on the memory-bound 1x1 launches of large batches)
-  if (k.force_waves) o->waves = k.force_waves;
-  else if (k.eight_waves && q.ksize == 1 && q.M <= 65536 && aligned && bn != 64 && bn != 320 && bn != 256 && !(stages == 4 && bn != 128) && stages != 3) o->waves = 8;
-  // XCD chunk order: keep the larger operand's tiles together on one XCD (gemm_conv.hip conv_gemm_kernel)
-  o->xcd_m_fastest = k.xcd_order < 0 ? (q.ngroups <= 1 && splitk == 1 && q.M <= 2048 && q.w_numel > q.src_numel) : k.xcd_order;
-  const int cstore = geglu ? q.cout / 2 : q.cout;
-  o->gn_partials = q.gn_groups > 0 && gn_handover(q.hw, cstore, q.gn_groups, k) && !geglu && !q.has_ln && q.cout / q.gn_groups <= (bn == 320 ? 160 : bn);
-  o->wide = q.wide && q.has_residual && wide_stream(q.dtype, k) && cstore % 8 == 0 && !geglu;
-  return true;
-}
-// Transformer2DModel.norm -> proj_in as a statistics pass and the projection on es_linear_xs, which applies the GroupNorm to the rows it
-// holds in registers: where the projection runs on that kernel anyway, and at K = 320 from 8192 rows on (profiles/r05_gn_proj_in.txt)
-bool launch_gn_fold(const es_launch_query& q, int groups, const es_launch_knobs& k) {
-  if (!(k.gn_fold && k.xs_enabled) || k.gn_handover || q.hw % 256 || groups < 1 || groups > 32) return false;
-  if (q.geglu || q.has_ln || q.kpad % groups || !xs_shape_fits(q.ksize, q.kpad, q.cin, q.ctail, q.cout, false)) return false;
-  if (q.M < (q.kpad == 320 ? 8192 : 32768)) return false;
-  return !(q.ngroups > 1 && (q.ngroups > 4 || !groups_tile_256(q) || !q.groups_agree));
-}
 // The switches es_load_weights honours (README.md), read once per build; every other knob is at its default.  ES_CHUNK_MAJOR belongs to
 // weight packing (ops.choose_korder), not to a launch.
 struct BuildEnv { es_launch_knobs knobs; bool chunk_major; };
@@ -473,8 +285,7 @@ BuildEnv read_build_env() {
   BuildEnv b;
   b.chunk_major = env("ES_CHUNK_MAJOR", "0") == "1";
   es_launch_knobs& k = b.knobs;
-  memset(&k, 0, sizeof(k));
-  k.xs_enabled = k.big_tile = k.small_tile = k.eight_waves = k.deep_ring = 1; k.xs_min_m = XS_MIN_M; k.xcd_order = -1;
+  launch_default_knobs(&k);
   k.xs_residual = env("ES_XS_RESIDUAL", "1") == "1"; k.big_tile_256 = env("ES_BIG_TILE_256", "1")[0] != '0'; k.gn_fold = env("ES_GN_FOLD", "1") == "1";
   k.gn_handover = ho == "all" ? 2 : ho == "1"; k.wide_stream = ws == "auto" ? -1 : ws == "1";
   return b;
@@ -675,14 +486,10 @@ struct Builder {
   T linear_xs(const T& x, const PWs& pl, long long M, const T& out, const std::vector<long long>& group_rows, const T& residual = T(),
               const GnFront* gn = nullptr) {
     const PW* pw = pl[0];
-    const int K = pw->kpad, ch = K == 320 ? 64 : 32;
-    const int pline = 128 / (pw->geglu ? ch : 2 * ch);
-    const int total = pw->cout / ch, lines = total / pline;
-    const long long rbs = (M + 255) / 256;
-    const int want = (int)std::max<long long>(1, std::min<long long>(lines, XS_TARGET_WGS / rbs));
-    const int lps = cdiv(lines, want), nslices = cdiv(lines, lps);
+    const int K = pw->kpad;
     es_xs_desc d;
     memset(&d, 0, sizeof(d));
+    if (!launch_xs_slices(M, K, pw->cout, pw->geglu, 0, &d.nslices, &d.chunks_per_slice)) fail("linear_xs: no shape es_linear_xs runs");
     auto bias_of = [&](const PW* q) -> unsigned long long {
       if (q->bias) return q->bias;
       auto it = zero_bias.find(q->rows_padded);
@@ -692,7 +499,7 @@ struct Builder {
     d.x = x.ptr(); d.out = out.ptr(); d.w = (const void*)pw->w; d.bias = (const float*)bias_of(pw);
     d.M = (int)M; d.K = K; d.Cout = pw->cout; d.rows_padded = pw->rows_padded; d.ldo = out.c;
     d.geglu = pw->geglu; d.ln = pw->ln_colsum != 0; d.ln_eps = pw->ln_eps;
-    d.nslices = nslices; d.chunks_per_slice = lps * pline; d.dtype = dt;
+    d.dtype = dt;
     if (residual) d.residual = residual.ptr();
     if (gn) {
       d.gn_part = (const float*)gn->part; d.gn_groups = gn->groups; d.gn_nchunk = gn->nchunk; d.gn_hw = gn->hw; d.gn_eps = gn->eps;
@@ -1629,24 +1436,6 @@ struct Recording {
 };
 
 }  // namespace
-
-extern "C" int es_plan_gemm_choice(long long M, int rows_padded, int kpad, int geglu, const int* bns, int n_bns, int allow_split, int* bn, int* splitk, int* stages) {
-  if (!bns || n_bns < 1 || !bn || !splitk || !stages) { es_set_error("es_plan_gemm_choice: null argument"); return -1; }
-  if (!plan_gemm(M, rows_padded, kpad, geglu != 0, bns, n_bns, allow_split != 0, bn, splitk, stages)) { es_set_error("es_plan_gemm_choice: rows_padded fits no N tile"); return -1; }
-  return 0;
-}
-extern "C" int es_linear_xs_eligible(long long M, int ksize, int kpad, int cin, int ctail, int cout, int geglu) {
-  return xs_shape_ok(M, ksize, kpad, cin, ctail, cout, geglu != 0, XS_MIN_M) ? 1 : 0;
-}
-extern "C" int es_launch_choose(const es_launch_query* q, const es_launch_knobs* k, es_launch_choice* out) {
-  if (!q || !k || !out) { es_set_error("es_launch_choose: null argument"); return -1; }
-  if (!launch_choose(*q, *k, out)) { es_set_error("es_launch_choose: rows_padded fits no N tile"); return -1; }
-  return 0;
-}
-extern "C" int es_launch_route(const es_launch_query* q, const es_launch_knobs* k) { return q && k && launch_takes_xs(*q, *k) ? ES_ROUTE_LINEAR_XS : ES_ROUTE_CONV_GEMM; }
-extern "C" int es_launch_gn_fold(const es_launch_query* q, int groups, const es_launch_knobs* k) { return q && k && launch_gn_fold(*q, groups, *k); }
-extern "C" int es_launch_gn_handover(long long hw, int c, int groups, const es_launch_knobs* k) { return k && gn_handover(hw, c, groups, *k); }
-extern "C" int es_launch_wide_stream(int dtype, const es_launch_knobs* k) { return k && wide_stream(dtype, *k); }
 
 extern "C" int es_load_weights(const es_weights* wts, const es_model_config* mc, const es_ctx_geometry* g, int device, es_ctx** out) {
   if (!wts || !mc || !g || !out) { es_set_error("es_load_weights: null argument"); return -1; }

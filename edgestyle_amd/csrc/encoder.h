@@ -1,5 +1,5 @@
 // What the two CLIP towers share on the host (text.hip: es_text_encoder, clip.hip: es_clip_vision and the text side of es_clip_bank):
-// the 16-bit storage conversions, one packed linear layer (Lin), the state-dict reader and packer (EncBuilder) and the launch of a
+// one packed linear layer (Lin), the state-dict reader and packer (EncBuilder) and the launch of a
 // linear layer through the shared launch policy.  Header-only, included by those two files; the launch helpers are templates over
 // the owning object, which must have the members dtype, cfg.ln_eps, knobs, arena, ws and ws_bytes.
 #pragma once
@@ -15,13 +15,16 @@
 
 #include "common.h"
 #include "../../include/edgestyle_hip.h"
+#include "host_util.h"
+#include "launch_policy.h"
 #include "plan.h"
 
 extern "C" void es_set_error(const char* msg);
 
 namespace es_enc {
 
-constexpr int BK = 64;
+using namespace es_host;
+using es_policy::BK;
 constexpr float QUICK_GELU = 1.702f;
 
 inline int fail(int rc, const char* who, const std::string& what) {
@@ -35,17 +38,6 @@ inline bool capturing(hipStream_t st) {
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
   return hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
 }
-
-// ---- 16-bit storage types, round to nearest even like torch's .to(dtype) ----
-inline uint16_t f32_to_f16(float f) { _Float16 h = (_Float16)f; uint16_t u; memcpy(&u, &h, 2); return u; }
-inline float f16_to_f32(uint16_t u) { _Float16 h; memcpy(&h, &u, 2); return (float)h; }
-inline uint16_t f32_to_bf16(float f) {
-  uint32_t u; memcpy(&u, &f, 4);
-  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (uint16_t)((u >> 16) | 0x40);
-  return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
-}
-inline float bf16_to_f32(uint16_t h) { uint32_t u = (uint32_t)h << 16; float f; memcpy(&f, &u, 4); return f; }
-inline int round_up(int a, int b) { return (a + b - 1) / b * b; }
 
 struct Lin {                      // one packed linear layer: [rows_padded][kpad] dtype, bias fp32 [rows_padded], optional LayerNorm fold
   size_t w = 0, bias = 0, colsum = 0;
@@ -103,22 +95,8 @@ struct EncBuilder {
       err = s + ")";
       return {};
     }
-    size_t n = 1;
-    for (int j = 0; j < nd; ++j) n *= (size_t)want[j];
-    std::vector<float> v(n);
-    const void* src = t->data;
-    std::vector<char> tmp;
-    hipPointerAttribute_t a;
-    const bool dev = hipPointerGetAttributes(&a, src) == hipSuccess && a.type == hipMemoryTypeDevice;
-    (void)hipGetLastError();
-    if (dev) {
-      tmp.resize(n * (t->dtype == ES_F32 ? 4 : 2));
-      if (hipMemcpy(tmp.data(), src, tmp.size(), hipMemcpyDeviceToHost) != hipSuccess) { err = "cannot read '" + key + "' from the device"; return {}; }
-      src = tmp.data();
-    }
-    if (t->dtype == ES_F32) memcpy(v.data(), src, n * 4);
-    else if (t->dtype == ES_F16) { const uint16_t* s = (const uint16_t*)src; for (size_t i = 0; i < n; ++i) v[i] = f16_to_f32(s[i]); }
-    else { const uint16_t* s = (const uint16_t*)src; for (size_t i = 0; i < n; ++i) v[i] = bf16_to_f32(s[i]); }
+    std::vector<float> v;
+    if (!tensor_to_f32(t, &v)) { err = "cannot read '" + key + "' from the device"; return {}; }
     return v;
   }
   size_t upload_f32(std::vector<float>&& v) {
@@ -131,7 +109,7 @@ struct EncBuilder {
   Lin pack(const std::vector<float>& w, const std::vector<float>& b, int cout, int cin, const std::vector<float>* gamma, const std::vector<float>* beta, double mul) {
     Lin L;
     L.cout = cout; L.cin = cin;
-    const int bn = (cout % 160 == 0 && cout % 128 != 0) ? 160 : 128;
+    const int bn = es_policy::choose_bn(cout);
     L.rows_padded = round_up(cout, bn); L.kpad = round_up(cin, BK);
     L.w = alloc((size_t)L.rows_padded * L.kpad * 2);
     uint16_t* dw = (uint16_t*)staged(L.w, (size_t)L.rows_padded * L.kpad * 2);
@@ -176,12 +154,11 @@ struct EncBuilder {
   }
 };
 
-// the policy's defaults (builder.hip read_build_env) with es_linear_xs off: that kernel serves K = 320 | 640 from 8192 rows on, and an
-// encoder batch is a few hundred rows of K = hidden
+// the policy's defaults with es_linear_xs off: that kernel serves K = 320 | 640 from 8192 rows on, and an encoder batch is a few hundred
+// rows of K = hidden
 inline void default_knobs(es_launch_knobs* k) {
-  memset(k, 0, sizeof(*k));
-  k->big_tile = k->big_tile_256 = k->small_tile = k->eight_waves = k->deep_ring = 1;
-  k->xcd_order = -1; k->wide_stream = 0;
+  es_policy::launch_default_knobs(k);
+  k->xs_enabled = 0;
 }
 
 template <typename E>

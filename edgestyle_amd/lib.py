@@ -296,6 +296,8 @@ SYMBOLS = {
     "es_launch_gn_fold": (C.c_int, [C.POINTER(LaunchQuery), _I, C.POINTER(LaunchKnobs)]),
     "es_launch_gn_handover": (C.c_int, [C.c_longlong, _I, _I, C.POINTER(LaunchKnobs)]),
     "es_launch_wide_stream": (C.c_int, [_I, C.POINTER(LaunchKnobs)]),
+    "es_launch_default_knobs": (None, [C.POINTER(LaunchKnobs)]),
+    "es_launch_xs_slices": (C.c_int, [C.c_longlong, _I, _I, _I, _I, C.POINTER(_I32), C.POINTER(_I32)]),
     "es_conv_gemm8p_form_ok": (C.c_int, [_I, _I, _I, C.c_longlong, _I]),
     "es_ctx_graph_hazard": (C.c_int, []),
     "es_plan_set_dry": (C.c_int, [_I]),

@@ -255,37 +255,16 @@ def _get_workspace(nbytes: int, device) -> torch.Tensor:
     return ws
 
 
-# Launch planner.  A launch is described by (bn, splitk, stages); its cost model below is in units of one K-step of a
-# 128-wide tile on a CU shared by two workgroups (~0.77 us) and was fitted on tools/gemm_tune.py sweeps over the
-# shapes of a batch-1 denoising step (total within 1.1 % of the per-shape best configuration, 6.4 % below the
-# previous tiles-vs-target rules):
-#   * 512 workgroups are resident at once (256 CUs x 2); a launch takes ceil(WGs / 512) rounds of one workgroup's time;
-#   * a 160-wide tile costs 1.25x a 128-wide one per K-step; a workgroup alone on its CU runs ~10 % faster;
-#   * split-K pays a reduce launch (~12 units) plus the fp32 slab round trip, needs >= 12 K-steps per slice and is
-#     never worth it for K <= 640.
-#   * the big tile (256 px x 320 couts, one workgroup per CU) does the work of two 160-wide workgroups in ~8 % less
-#     time (half the L2->LDS bytes) and is charged FRACTIONAL rounds; since round 4 (lean epilogue) it is offered from 2048 pixels up,
-#     where it wins as a split-K launch of ~256 workgroups (the 16 x 16 decoder level at batch 8: 1.3-1.5x, tools/plan_fit_bench.py).
-PLAN_T160, PLAN_ALONE, PLAN_TFIX, PLAN_RED_FIX, PLAN_SLAB_BYTES_PER_UNIT = 1.25, 0.9, 2.0, 12.0, 4.0e6
-PLAN_T320, PLAN_BIG_MIN_M, PLAN_T320_FIX, PLAN_BIG_MIN_NK = 2.3, 2048, 3.0, 16
-# the 256 x 256 tile of the LayerNorm-folded / GEGLU layers against the 128-wide tile on the same layers (csrc/builder.hip plan_gemm)
-PLAN_T256, PLAN_T256_FIX, PLAN_T256_GEGLU, PLAN_LN_TK, PLAN_T256_MARGIN = 2.6, 6.0, 7.0, 1.55, 0.93
-#   * the 64x64 tile (tiny launches): a K-step costs 0.5 units with the CU to itself and 0.5 + 0.16 (w - 1)^2 with w
-#     workgroups per CU (measured 0.87 at w = 2.5, 2.0 at w = 3.75); x1.5 for K > 2560, where MFMA throughput starts to
-#     matter and the small tile reads LDS twice as often per FLOP;
-#     1024 resident workgroups (32 KB of LDS each); offered up to 16k pixels.
-PLAN_T64_ALONE, PLAN_T64, PLAN_T64_LONG, PLAN_SMALL_MAX_M = 0.5, 0.16, 1.5, 16384
-# the 256 x 320 phase-interleaved tile (csrc/gemm_conv8p.hip): 1.03-1.15x the 128-pixel tile on launches of >= 1 round of
-# 256 workgroups with K >= 1024 (tools/gemm8p_bench.py: 1.07-1.30 PFLOP/s on the batch-8 3x3 launches)
+# Launch planner: the cost model, its constants and what they were fitted on live with the launch policy (csrc/launch_policy.hip).
+# the 256 x 320 phase-interleaved tile (csrc/gemm_conv8p.hip)
 BIG_TILE = _os.environ.get("ES_BIG_TILE", "1") == "1"
 BIG_TILE_256 = _os.environ.get("ES_BIG_TILE_256", "1") != "0"     # its 256-wide form for the LayerNorm-folded / GEGLU linear layers
-PLAN_MIN_SLICE, PLAN_NK_NOSPLIT, PLAN_RESIDENT = 12, 10, 512
 
 
 def plan_gemm(M: int, rows_padded: int, kpad: int, geglu: bool = False, bns=(160, 128, 64), allow_split: bool = True):
-    """(bn, splitk, stages) of an es_conv_gemm launch among the tiles `bns`: the library's planner (es_plan_gemm_choice, csrc/builder.hip),
-    the one inside the launch policy both hosts ask (es_launch_choose).  For tools and tests; `plan_gemm_reference` below is the independent
-    restatement tests/test_load_weights_cpu.py holds the library against."""
+    """(bn, splitk, stages) of an es_conv_gemm launch among the tiles `bns`: the library's planner (es_plan_gemm_choice,
+    csrc/launch_policy.hip), the one inside the launch policy both hosts ask (es_launch_choose).  For tools and tests; tests/numerics.py
+    holds its independent restatement (plan_gemm_reference), which tests/test_load_weights_cpu.py sweeps the library against."""
     arr = (C.c_int * len(bns))(*[int(b) for b in bns])
     bn, sk, st = C.c_int(), C.c_int(), C.c_int()
     if L.load().es_plan_gemm_choice(int(M), int(rows_padded), int(kpad), int(bool(geglu)), arr, len(bns), int(bool(allow_split)),
@@ -295,82 +274,6 @@ def plan_gemm(M: int, rows_padded: int, kpad: int, geglu: bool = False, bns=(160
     if stages == 4 and not (DEEP_RING and LANE == 0):       # tool knobs: no 4-deep ring
         stages = 2
     return bn.value, sk.value, stages
-
-
-def plan_gemm_reference(M: int, rows_padded: int, kpad: int, geglu: bool = False, bns=(160, 128, 64), allow_split: bool = True):
-    """An independent restatement of the library's planner, for tests only: (bn, splitk, stages) with the
-    lowest modelled time among the legal N tiles (ties go to the wider tile).  bn = 256 (the 256 x 256 phase-interleaved tile,
-    offered for the LayerNorm-folded / GEGLU linear layers whose N is a multiple of 256) is decided AFTER the choice among the
-    other tiles, on a model fitted on those layers (csrc/builder.hip plan_gemm, tools/ln256_bench.py)."""
-    if 256 in bns:
-        others = tuple(b for b in bns if b != 256)
-        nk = kpad // BK
-        other = None
-        if others:
-            try:
-                other = plan_gemm_reference(M, rows_padded, kpad, geglu, others, allow_split)
-            except L.EdgeStyleHipError:
-                other = None
-        if rows_padded % 256:
-            if other is None:
-                raise L.EdgeStyleHipError(f"plan_gemm: rows_padded {rows_padded} fits no N tile")
-            return other
-        t256 = ((M + 255) // 256) * (rows_padded // 256)
-        c256 = float(-(-t256 // 256)) * (nk * PLAN_T256 + PLAN_T256_FIX + (PLAN_T256_GEGLU if geglu else 0.0))
-        take = other is None
-        if other is not None and M >= PLAN_BIG_MIN_M and nk >= PLAN_BIG_MIN_NK and other[1] == 1 and other[0] != 64:
-            to = ((M + BM - 1) // BM) * (rows_padded // other[0])
-            co = float(-(-to // PLAN_RESIDENT)) * (nk * PLAN_LN_TK * (PLAN_T160 if other[0] == 160 else 1.0) + PLAN_T256_FIX)
-            take = c256 < PLAN_T256_MARGIN * co
-        return (256, 1, 2) if take else other
-    if geglu:
-        return 128, 1, 2
-    nk = kpad // BK
-    best = None
-    for bn in bns:
-        if rows_padded % bn:
-            continue
-        if bn == 320 and (M < PLAN_BIG_MIN_M or nk < PLAN_BIG_MIN_NK) and len(bns) > 1:
-            continue
-        if bn == 64 and M > PLAN_SMALL_MAX_M and len(bns) > 1:
-            continue
-        bm = {320: 256, 64: 64}.get(bn, BM)
-        resident = {320: PLAN_RESIDENT // 2, 64: 2 * PLAN_RESIDENT}.get(bn, PLAN_RESIDENT)
-        tiles = ((M + bm - 1) // bm) * (rows_padded // bn)
-        cands = [1]
-        if allow_split and tiles < resident // 2 and nk > PLAN_NK_NOSPLIT:
-            cands += list(range(2, min(nk // PLAN_MIN_SLICE, 32) + 1))
-        for sk in cands:
-            wgs = tiles * sk
-            if bn == 320:
-                tk = PLAN_T320
-            elif bn == 64:
-                if sk > 1 and wgs > PLAN_RESIDENT:
-                    continue
-                w = wgs / (PLAN_RESIDENT // 2)                 # workgroups per CU
-                tk = (PLAN_T64_ALONE + PLAN_T64 * max(0.0, w - 1.0) ** 2) * (1.0 if nk <= 40 else PLAN_T64_LONG)
-            else:
-                tk = (PLAN_T160 if bn == 160 else 1.0) * (PLAN_ALONE if wgs <= PLAN_RESIDENT // 2 else 1.0)
-            # rounds of workgroups: whole ones for the two-per-CU tiles; the 256 x 320 tile (one workgroup per CU, long tiles) is
-            # measured to cost its FRACTIONAL number of rounds - 896 tiles = 3.5 rounds run in 3.5 tile times, the CUs of a part-filled
-            # round run faster (tools/plan_fit_bench.py, round 4) - and no less than 0.9 of a round
-            rounds = max(wgs / 256.0, 0.9) if bn == 320 else float(-(-wgs // resident))
-            t = rounds * ((nk / sk) * tk + (PLAN_T320_FIX if bn == 320 else PLAN_TFIX))
-            if sk > 1:
-                t += PLAN_RED_FIX + sk * M * rows_padded * 8.0 / PLAN_SLAB_BYTES_PER_UNIT
-            if best is None or t < best[0]:
-                best = (t, bn, sk, wgs)
-    if best is None:
-        raise L.EdgeStyleHipError(f"plan_gemm: rows_padded {rows_padded} fits no N tile")
-    _, bn, sk, wgs = best
-    # at most one workgroup per CU: a 4-deep LDS ring (3 K-steps of DMA in flight) hides the HBM round trip that the
-    # 2-stage ring leaves exposed when no second workgroup shares the CU.  Not inside concurrent chains (LANE > 0,
-    # ES_CHAIN_MODE=streams): there 2 stages = 72 KB LDS let workgroups of different chains share a CU.
-    if bn == 64:
-        stages = 4 if (DEEP_RING and LANE == 0 and wgs <= PLAN_RESIDENT and nk // sk >= 6) else 2
-    else:
-        stages = 4 if (bn != 320 and DEEP_RING and LANE == 0 and wgs <= PLAN_RESIDENT // 2 and nk // sk >= 6) else 2
-    return bn, sk, stages
 
 
 def choose_launch_bn(M: int, pw: "PackedWeight") -> int:
@@ -389,28 +292,9 @@ def plan_launch(M: int, pw: "PackedWeight", bn: int):
 
 XS_ENABLED = _os.environ.get("ES_XS", "1") == "1"      # row-stationary short-K linear kernel (csrc/linear_xs.hip)
 XS_RESIDUAL = _os.environ.get("ES_XS_RESIDUAL", "1") == "1"   # ... also for the K = 320 output projections that add a residual
-XS_TARGET_WGS = 256
-XS_FORCE_SLICES = 0
+XS_FORCE_SLICES = 0                                    # tool knob (tools/xs_slices_bench.py): cut every launch into this many slices
 XS_MIN_M = int(_os.environ.get("ES_XS_MIN_M", "8192"))   # 0: no size policy (tests exercise every shape)
 _zero_bias = {}
-
-
-def xs_shape_reference(M: int, pw: "PackedWeight", min_m: int) -> bool:
-    """An independent restatement of the library's es_linear_xs_eligible (min_m = 8192) / "can the kernel run this" (min_m = 0), for
-    tests only.  K = 320 | 640 linear layers with an output width of whole 128-byte
-    lines: the to_q|k|v and GEGLU projections of the 64x64 and 32x32 levels."""
-    if pw.ksize != 1 or pw.kpad not in (320, 640) or pw.cin != pw.kpad or pw.ctail:
-        return False
-    ch = 64 if pw.kpad == 320 else 32
-    line = ch * (128 // (ch if pw.geglu else 2 * ch))        # GEMM columns per 128-byte output line
-    if pw.cout % line or pw.cout < 4 * line:
-        return False
-    # where it wins (tools/xs_bench.py, batch-1 shapes): 1.4-1.6x on the 14-sample launches of both levels and 1.05-1.1x on
-    # the decoder's wide K = 320 projections; it loses where a workgroup's share of N is a few chunks (the activation
-    # rows are re-read per slice and the 40 KB stages no longer amortise): small M with K = 640, narrow N at small M
-    if min_m and (M < min_m or (M < 4 * min_m and pw.cout < (960 if pw.kpad == 320 else 1920))):
-        return False
-    return True
 
 
 def launch_knobs(**over) -> "L.LaunchKnobs":
@@ -487,16 +371,8 @@ def linear_xs(x: torch.Tensor, pw, M: int, out: torch.Tensor, group_rows=None, r
         if any(n % 256 for n in list(group_rows)[:-1]):
             raise bad(f"group_rows {list(group_rows)}: every run but the last must be whole 256-row blocks")
     K = pw.kpad
-    ch = 64 if K == 320 else 32
-    pline = 128 // (ch if pw.geglu else 2 * ch)             # chunks per 128-byte output line
-    total = pw.cout // ch
-    lines = total // pline
-    rbs = (M + 255) // 256
-    want = max(1, min(lines, XS_TARGET_WGS // rbs))
-    if XS_FORCE_SLICES:                                      # tool knob (tools/xs_slices_bench.py)
-        want = max(1, min(lines, XS_FORCE_SLICES))
-    lps = -(-lines // want)                                  # lines per slice
-    nslices = -(-lines // lps)
+    nslices, cps = C.c_int32(), C.c_int32()
+    L.check(L.load().es_launch_xs_slices(M, K, pw.cout, int(pw.geglu), XS_FORCE_SLICES, C.byref(nslices), C.byref(cps)), "es_launch_xs_slices")
     d = L.XsDesc()
     d.x, d.out = x.data_ptr(), out.data_ptr()
 
@@ -512,7 +388,7 @@ def linear_xs(x: torch.Tensor, pw, M: int, out: torch.Tensor, group_rows=None, r
     d.M, d.K, d.Cout, d.rows_padded = M, K, pw.cout, pw.rows_padded
     d.ldo = ldo
     d.geglu, d.ln, d.ln_eps = int(pw.geglu), int(pw.ln_colsum is not None), pw.ln_eps
-    d.nslices, d.chunks_per_slice, d.dtype = nslices, lps * pline, _dt(x)
+    d.nslices, d.chunks_per_slice, d.dtype = nslices.value, cps.value, _dt(x)
     d.residual = residual.data_ptr() if residual is not None else None
     if gn is not None:
         d.gn_part, d.gn_groups, d.gn_nchunk, d.gn_hw, d.gn_eps = gn["part"].data_ptr(), gn["groups"], gn["nchunk"], gn["hw"], gn["eps"]

@@ -27,7 +27,8 @@ enum { ES_ACT_NONE = 0, ES_ACT_SILU = 1, ES_ACT_GEGLU = 2 };
  * projection); es_conv_gemm8p_form_ok, es_ctx_graph_hazard, es_linear_xs_set_pp, es_attention_set_kvres, es_set_operand_limit,
  * es_group_norm_chunks, es_clock_probe.  Context images carry the version and are rebuilt across it.
  * (Host-only helpers that no plan or image records - es_plan_gemm_choice, es_linear_xs_eligible, es_linear_xs_last_form, es_launch_choose and its siblings
- * es_launch_route / es_launch_gn_fold / es_launch_gn_handover / es_launch_wide_stream, es_attention_route, es_attention_knobs,
+ * es_launch_route / es_launch_gn_fold / es_launch_gn_handover / es_launch_wide_stream / es_launch_default_knobs / es_launch_xs_slices,
+ * es_attention_route, es_attention_knobs,
  * es_conv_gemm_route, es_conv_gemm_last_kernel, es_linear_xs_route, es_linear_xs_knobs - come and go without a new version.) */
 #define ES_ABI_VERSION 7
 int es_abi_version(void);
@@ -654,6 +655,13 @@ int es_launch_route(const es_launch_query* q, const es_launch_knobs* k);
 int es_launch_gn_fold(const es_launch_query* q, int groups, const es_launch_knobs* k);
 int es_launch_gn_handover(long long hw, int c, int groups, const es_launch_knobs* k);
 int es_launch_wide_stream(int dtype, const es_launch_knobs* k);
+/* the knobs as every host starts from them, before it reads its switches: every kernel and tile on (xs_enabled, xs_residual, big_tile,
+ * big_tile_256, small_tile, eight_waves, deep_ring, gn_fold = 1), xs_min_m = 8192, xcd_order = wide_stream = -1, the rest 0 */
+void es_launch_default_knobs(es_launch_knobs* k);
+/* how an es_linear_xs launch of M rows, K = kpad, `cout` GEMM columns is cut into slices of whole 128-byte output lines
+ * (es_xs_desc.nslices / chunks_per_slice): towards 256 workgroups, or towards `force_slices` slices where that is > 0 (a tool knob).
+ * -1 (es_last_error) for a shape es_linear_xs does not run: K other than 320 | 640, no row, Cout not in whole lines. */
+int es_launch_xs_slices(long long M, int kpad, int cout, int geglu, int force_slices, int32_t* nslices, int32_t* chunks_per_slice);
 /* Does the 256 x 320 tile (bn = 320) implement the epilogue of a splitk == 1 launch with this form?  (It keeps the common
  * forms only - bias [+ one time-embedding row per 128-pixel half] [+ residual]; split-K launches write raw partials: every
  * form.)  1 = yes.  Both hosts ask BEFORE they fix bn, so that the tile a launch is planned, recorded and reported with is the

@@ -39,6 +39,8 @@ import math
 import torch
 import torch.nn.functional as F
 
+from edgestyle_amd.lib import EdgeStyleHipError
+
 MARGIN = 2.0
 PROBE_MARGIN = 4.0
 LAZY = 8.0                      # csrc/attention.hip: the running softmax reference may sit up to 2^8 below the true maximum
@@ -1510,6 +1512,136 @@ def gemm_route(d, limit=0x7FFFFFFF):
     elif d.splitk > 1:
         r.update(reduce=1, reduce_grid=cdiv(M * (d.rows_padded // 8), 256), reduce_threads=256)
     return r
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# The launch policy (csrc/launch_policy.hip): independent restatements of its planner, of where es_linear_xs is taken and of how such a
+# launch is cut into slices (tests/test_load_weights_cpu.py and tests/test_host_cpu.py sweep the library against them)
+# ----------------------------------------------------------------------------------------------------------------
+PLAN_BK, PLAN_BM = 64, 128
+PLAN_T160, PLAN_ALONE, PLAN_TFIX, PLAN_RED_FIX, PLAN_SLAB_BYTES_PER_UNIT = 1.25, 0.9, 2.0, 12.0, 4.0e6
+PLAN_T320, PLAN_BIG_MIN_M, PLAN_T320_FIX, PLAN_BIG_MIN_NK = 2.3, 2048, 3.0, 16
+PLAN_T256, PLAN_T256_FIX, PLAN_T256_GEGLU, PLAN_LN_TK, PLAN_T256_MARGIN = 2.6, 6.0, 7.0, 1.55, 0.93
+PLAN_T64_ALONE, PLAN_T64, PLAN_T64_LONG, PLAN_SMALL_MAX_M = 0.5, 0.16, 1.5, 16384
+PLAN_MIN_SLICE, PLAN_NK_NOSPLIT, PLAN_RESIDENT = 12, 10, 512
+
+
+def plan_gemm_reference(M: int, rows_padded: int, kpad: int, geglu: bool = False, bns=(160, 128, 64), allow_split: bool = True, deep_ring: bool = True):
+    """An independent restatement of the library's planner (csrc/launch_policy.hip plan_gemm): (bn, splitk, stages) with the
+    lowest modelled time among the legal N tiles (ties go to the wider tile).  bn = 256 (the 256 x 256 phase-interleaved tile,
+    offered for the LayerNorm-folded / GEGLU linear layers whose N is a multiple of 256) is decided AFTER the choice among the
+    other tiles, on a model fitted on those layers (tools/ln256_bench.py).  deep_ring False (the knob, or a concurrent chain of the Python
+    host): no 4-deep ring."""
+    if 256 in bns:
+        others = tuple(b for b in bns if b != 256)
+        nk = kpad // PLAN_BK
+        other = None
+        if others:
+            try:
+                other = plan_gemm_reference(M, rows_padded, kpad, geglu, others, allow_split, deep_ring)
+            except EdgeStyleHipError:
+                other = None
+        if rows_padded % 256:
+            if other is None:
+                raise EdgeStyleHipError(f"plan_gemm: rows_padded {rows_padded} fits no N tile")
+            return other
+        t256 = ((M + 255) // 256) * (rows_padded // 256)
+        c256 = float(-(-t256 // 256)) * (nk * PLAN_T256 + PLAN_T256_FIX + (PLAN_T256_GEGLU if geglu else 0.0))
+        take = other is None
+        if other is not None and M >= PLAN_BIG_MIN_M and nk >= PLAN_BIG_MIN_NK and other[1] == 1 and other[0] != 64:
+            to = ((M + PLAN_BM - 1) // PLAN_BM) * (rows_padded // other[0])
+            co = float(-(-to // PLAN_RESIDENT)) * (nk * PLAN_LN_TK * (PLAN_T160 if other[0] == 160 else 1.0) + PLAN_T256_FIX)
+            take = c256 < PLAN_T256_MARGIN * co
+        return (256, 1, 2) if take else other
+    if geglu:
+        return 128, 1, 2
+    nk = kpad // PLAN_BK
+    best = None
+    for bn in bns:
+        if rows_padded % bn:
+            continue
+        if bn == 320 and (M < PLAN_BIG_MIN_M or nk < PLAN_BIG_MIN_NK) and len(bns) > 1:
+            continue
+        if bn == 64 and M > PLAN_SMALL_MAX_M and len(bns) > 1:
+            continue
+        bm = {320: 256, 64: 64}.get(bn, PLAN_BM)
+        resident = {320: PLAN_RESIDENT // 2, 64: 2 * PLAN_RESIDENT}.get(bn, PLAN_RESIDENT)
+        tiles = ((M + bm - 1) // bm) * (rows_padded // bn)
+        cands = [1]
+        if allow_split and tiles < resident // 2 and nk > PLAN_NK_NOSPLIT:
+            cands += list(range(2, min(nk // PLAN_MIN_SLICE, 32) + 1))
+        for sk in cands:
+            wgs = tiles * sk
+            if bn == 320:
+                tk = PLAN_T320
+            elif bn == 64:
+                if sk > 1 and wgs > PLAN_RESIDENT:
+                    continue
+                w = wgs / (PLAN_RESIDENT // 2)                 # workgroups per CU
+                tk = (PLAN_T64_ALONE + PLAN_T64 * max(0.0, w - 1.0) ** 2) * (1.0 if nk <= 40 else PLAN_T64_LONG)
+            else:
+                tk = (PLAN_T160 if bn == 160 else 1.0) * (PLAN_ALONE if wgs <= PLAN_RESIDENT // 2 else 1.0)
+            # rounds of workgroups: whole ones for the two-per-CU tiles; the 256 x 320 tile (one workgroup per CU, long tiles) is
+            # measured to cost its FRACTIONAL number of rounds - 896 tiles = 3.5 rounds run in 3.5 tile times, the CUs of a part-filled
+            # round run faster (tools/plan_fit_bench.py, round 4) - and no less than 0.9 of a round
+            rounds = max(wgs / 256.0, 0.9) if bn == 320 else float(-(-wgs // resident))
+            t = rounds * ((nk / sk) * tk + (PLAN_T320_FIX if bn == 320 else PLAN_TFIX))
+            if sk > 1:
+                t += PLAN_RED_FIX + sk * M * rows_padded * 8.0 / PLAN_SLAB_BYTES_PER_UNIT
+            if best is None or t < best[0]:
+                best = (t, bn, sk, wgs)
+    if best is None:
+        raise EdgeStyleHipError(f"plan_gemm: rows_padded {rows_padded} fits no N tile")
+    _, bn, sk, wgs = best
+    # at most one workgroup per CU: a 4-deep LDS ring (3 K-steps of DMA in flight) hides the HBM round trip that the
+    # 2-stage ring leaves exposed when no second workgroup shares the CU.  Not inside concurrent chains of the Python host (ops.LANE > 0,
+    # ES_CHAIN_MODE=streams): there 2 stages = 72 KB LDS let workgroups of different chains share a CU.
+    if bn == 64:
+        stages = 4 if (deep_ring and wgs <= PLAN_RESIDENT and nk // sk >= 6) else 2
+    else:
+        stages = 4 if (bn != 320 and deep_ring and wgs <= PLAN_RESIDENT // 2 and nk // sk >= 6) else 2
+    return bn, sk, stages
+
+
+def xs_shape_reference(M: int, pw, min_m: int) -> bool:
+    """An independent restatement of the library's es_linear_xs_eligible (min_m = 8192) / "can the kernel run this" (min_m = 0):
+    csrc/launch_policy.hip xs_shape_ok.  pw: an ops.PackedWeight.  K = 320 | 640 linear layers with an output width of whole 128-byte
+    lines: the to_q|k|v and GEGLU projections of the 64x64 and 32x32 levels."""
+    if pw.ksize != 1 or pw.kpad not in (320, 640) or pw.cin != pw.kpad or pw.ctail:
+        return False
+    ch = 64 if pw.kpad == 320 else 32
+    line = ch * (128 // (ch if pw.geglu else 2 * ch))        # GEMM columns per 128-byte output line
+    if pw.cout % line or pw.cout < 4 * line:
+        return False
+    # where it wins (tools/xs_bench.py, batch-1 shapes): 1.4-1.6x on the 14-sample launches of both levels and 1.05-1.1x on
+    # the decoder's wide K = 320 projections; it loses where a workgroup's share of N is a few chunks (the activation
+    # rows are re-read per slice and the 40 KB stages no longer amortise): small M with K = 640, narrow N at small M
+    if min_m and (M < min_m or (M < 4 * min_m and pw.cout < (960 if pw.kpad == 320 else 1920))):
+        return False
+    return True
+
+
+XS_WGS_WANTED = 256             # workgroups an es_linear_xs launch is cut towards
+
+
+def xs_slices_reference(M: int, kpad: int, cout: int, geglu: bool, force_slices: int = 0):
+    """An independent restatement of es_launch_xs_slices: (nslices, chunks_per_slice) of an es_linear_xs launch over M rows, or None where
+    the kernel does not run the shape (K, no row, Cout not in whole 128-byte lines).  The arithmetic ops.linear_xs used to write out."""
+    if M < 1 or kpad not in (320, 640):
+        return None
+    ch = 64 if kpad == 320 else 32
+    pline = 128 // (ch if geglu else 2 * ch)                # chunks per 128-byte output line
+    total = cout // ch
+    lines = total // pline
+    if cout % (ch * pline) or lines < 1:
+        return None
+    rbs = (M + 255) // 256
+    want = max(1, min(lines, XS_WGS_WANTED // rbs))
+    if force_slices > 0:
+        want = max(1, min(lines, force_slices))
+    lps = -(-lines // want)                                  # lines per slice
+    nslices = -(-lines // lps)
+    return nslices, lps * pline
 
 
 ATTN_INPUT_KINDS = ("randn", "shift-300", "shift+300", "last_key_decides", "one_loud_query", "loud_values_2e4")

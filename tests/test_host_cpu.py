@@ -165,6 +165,7 @@ def test_splitk_heuristic_bounds():
 def test_plan_gemm_returns_legal_launches():
     """Every (M, Cout, K) of the SD1.5 path gets a launch the C ABI accepts: bn divides rows_padded, split-K only where
     it is allowed, 4-stage rings only with at most one workgroup per CU, the 64x64 tile only for small launches."""
+    from tests import numerics as nm
     for M in (2, 128, 512, 896, 2048, 3584, 8192, 14336, 57344, 458752):
         for rows in (320, 640, 960, 1280, 1920, 2560, 3840):
             for kpad in (320, 640, 1280, 2880, 5760, 11520, 23040):
@@ -175,9 +176,9 @@ def test_plan_gemm_returns_legal_launches():
                     assert rows % bn == 0 and bn in bns
                     assert 1 <= sk <= max(1, kpad // 64) and st in (2, 4)
                     if bn == 64:
-                        assert M <= ops.PLAN_SMALL_MAX_M or len(bns) == 1
+                        assert M <= nm.PLAN_SMALL_MAX_M or len(bns) == 1
                     if bn == 320:
-                        assert st == 2 and M >= ops.PLAN_BIG_MIN_M
+                        assert st == 2 and M >= nm.PLAN_BIG_MIN_M
                     assert ops.plan_gemm(M, rows, kpad, bns=bns, allow_split=False)[1] == 1
 
 
@@ -217,6 +218,101 @@ def test_every_knob_bends_the_launch_choice_as_before():
     assert choose(1280, 10240, 1, 28672, 4096, {}, {}, geglu=True) == (256, 1, 2, 0, 0, 0, 0)
     assert choose(1280, 10240, 1, 28672, 4096, {}, dict(big_tile_256=0), geglu=True) == (128, 1, 2, 8, 0, 0, 0)
     assert b"fits no N tile" in choose(320, 320, 3, 57344, 4096, {}, dict(force_bn=128))          # (rows_padded 320)
+
+
+_KNOB_DEFAULTS = dict(xs_enabled=1, xs_residual=1, xs_min_m=8192, big_tile=1, big_tile_256=1, small_tile=1, eight_waves=1, deep_ring=1,
+                      gn_handover=0, wide_stream=-1, gn_fold=1, force_bn=0, force_waves=0, force_stages=0, xcd_order=-1)
+
+
+def test_default_knobs_are_the_python_hosts_in_a_process_without_switches():
+    """es_launch_default_knobs: the values include/edgestyle_hip.h states, and - in a fresh child whose environment holds no ES_* variable,
+    which imports the package and loads the library and nothing else - ops.launch_knobs() field by field."""
+    import json
+    import subprocess
+    import sys
+    k = lib.LaunchKnobs(*([77] * len(lib.LaunchKnobs._fields_)))
+    lib.load().es_launch_default_knobs(ctypes.byref(k))
+    assert {n: getattr(k, n) for n, _ in lib.LaunchKnobs._fields_} == _KNOB_DEFAULTS
+    lib.load().es_launch_default_knobs(None)                      # (a null pointer is ignored)
+    code = ("import ctypes, json\nfrom edgestyle_amd import lib, ops\nk = lib.LaunchKnobs()\nlib.load().es_launch_default_knobs(ctypes.byref(k))\n"
+            "f = [n for n, _ in lib.LaunchKnobs._fields_]\nh = ops.launch_knobs()\n"
+            "print(json.dumps([{n: getattr(k, n) for n in f}, {n: getattr(h, n) for n in f}]))")
+    env = {n: v for n, v in os.environ.items() if not n.startswith("ES_")}
+    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    native, host = json.loads(r.stdout.strip().splitlines()[-1])
+    assert set(native) == set(_KNOB_DEFAULTS)
+    for name in native:
+        assert native[name] == host[name] == _KNOB_DEFAULTS[name], (name, native[name], host[name])
+
+
+def test_encoder_towers_choose_the_same_launches_under_the_shared_defaults():
+    """The CLIP towers (csrc/encoder.h) used to fill their knobs by hand - the tiles, eight waves and the deep ring on, the rest 0 - and now
+    start from es_launch_default_knobs with es_linear_xs off, which also leaves xs_residual, gn_fold and xs_min_m set and wide_stream at
+    auto.  None of those is read without xs_enabled or a `wide` call: over the towers' layer shapes, queried as encoder.h's choose() does,
+    the two knob sets give the same return code and the same es_launch_choice, byte for byte."""
+    L = lib.load()
+    old = lib.LaunchKnobs(big_tile=1, big_tile_256=1, small_tile=1, eight_waves=1, deep_ring=1, xcd_order=-1)
+    new = lib.LaunchKnobs()
+    L.es_launch_default_knobs(ctypes.byref(new))
+    new.xs_enabled = 0
+    assert bytes(old) != bytes(new)
+    n = 0
+    for hidden in (128, 768, 1024):
+        inter = 4 * hidden
+        for cout, cin in ((3 * hidden, hidden), (hidden, hidden), (inter, hidden), (hidden, inter)):      # q|k|v, out_proj, fc1, fc2
+            bn = ops.choose_bn(cout)
+            rows_padded, kpad = -(-cout // bn) * bn, -(-cin // 64) * 64
+            for M in (77, 2 * 77, 16 * 77, 50, 257, 2 * 257, 16 * 257):
+                for ln in (0, 1):
+                    for res in (0, 1):
+                        for act in (lib.ACT_NONE, lib.ACT_SILU):
+                            for dtype in (lib.ES_F16, lib.ES_BF16):
+                                q = lib.LaunchQuery(M=M, hw=1, w_numel=rows_padded * kpad, src_numel=M * cin, ksize=1, stride=1, C1=cin,
+                                                    rows_padded=rows_padded, kpad=kpad, cin=cin, cout=cout, has_ln=ln, act=act, has_residual=res,
+                                                    residual_dense=1, unit_scale=1, x_rep=1, dtype=dtype)
+                                got = []
+                                for knobs in (old, new):
+                                    k = lib.LaunchKnobs.from_buffer_copy(knobs)
+                                    if act != lib.ACT_NONE:
+                                        k.big_tile_256 = 0
+                                    ch = lib.LaunchChoice(*([-1] * 8))
+                                    got.append((L.es_launch_choose(ctypes.byref(q), ctypes.byref(k), ctypes.byref(ch)), bytes(ch)))
+                                assert got[0] == got[1] and got[0][0] == 0, (hidden, cout, cin, M, ln, res, act, dtype, got)
+                                n += 1
+    assert n == 3 * 4 * 7 * 16
+
+
+def test_linear_xs_slice_rule_of_the_library_equals_its_mirror():
+    """es_launch_xs_slices (what ops.linear_xs and es_load_weights both ask) against tests/numerics.py xs_slices_reference, the arithmetic the
+    two hosts used to write out: every row count around a 256-row block and up to 2^20, both K, Cout from one line (the kernel runs fewer
+    than the four lines the policy routes to it, and its tests launch them) to 5120, GEGLU on and off, the slice count forced and not;
+    every answer is a cut es_linear_xs accepts; what that kernel does not run is refused with a text."""
+    from tests import numerics as nm
+    L = lib.load()
+    ns, cps = ctypes.c_int32(), ctypes.c_int32()
+    n = 0
+    for M in (1, 255, 256, 257, 4096, 8192, 57344, 458752, 1 << 20):
+        for K in (320, 640):
+            for geglu in (False, True):
+                ch = 64 if K == 320 else 32
+                pline = 128 // (ch if geglu else 2 * ch)
+                line = ch * pline
+                for cout in sorted({line * i for i in (1, 2, 3, 4, 5, 7, 8, 15, 16, 30)} | {c for c in (320, 640, 960, 1280, 1920, 2560, 5120) if c % line == 0}):
+                    for force in (0, 1, 3, 1000):
+                        want = nm.xs_slices_reference(M, K, cout, geglu, force)
+                        assert L.es_launch_xs_slices(M, K, cout, int(geglu), force, ctypes.byref(ns), ctypes.byref(cps)) == 0, (M, K, cout, geglu, force)
+                        assert (ns.value, cps.value) == want, (M, K, cout, geglu, force, ns.value, cps.value, want)
+                        total = cout // ch                   # (es_linear_xs: slices cover Cout in whole output lines, none empty)
+                        assert cps.value % pline == 0 and ns.value * cps.value >= total > (ns.value - 1) * cps.value
+                        if force:
+                            assert ns.value <= force
+                        n += 1
+    assert n > 1500
+    for M, K, cout, geglu in ((0, 320, 960, 0), (4096, 1280, 1280, 0), (4096, 320, 96, 0), (4096, 640, 32, 0), (4096, 320, 0, 0), (4096, 640, 2560 + 32, 1)):
+        assert nm.xs_slices_reference(M, K, cout, bool(geglu)) is None
+        assert L.es_launch_xs_slices(M, K, cout, geglu, 0, ctypes.byref(ns), ctypes.byref(cps)) == -1 and b"es_launch_xs_slices: " in L.es_last_error()
+    assert L.es_launch_xs_slices(4096, 320, 960, 0, 0, None, ctypes.byref(cps)) == -1 and b"null argument" in L.es_last_error()
 
 
 def test_layer_norm_fold_algebra():

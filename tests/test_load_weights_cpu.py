@@ -12,6 +12,7 @@ import torch
 
 from edgestyle_amd import config as Cfg, lib as L, ops
 from edgestyle_amd.native import NativeContext
+from tests import numerics as nm
 from tests.helpers import make_weights, quantize, python_dry_context, diff_plans, plan_constants
 
 
@@ -26,14 +27,14 @@ def test_launch_planner_of_the_library_equals_the_python_hosts():
     """es_plan_gemm_choice == ops.plan_gemm over the GEMM shapes of the model (all levels, batch 1..8, every candidate set)."""
     lib = L.load()
     bn, sk, st = C.c_int(), C.c_int(), C.c_int()
-    n = 0
+    n, deep = 0, bool(ops.DEEP_RING and ops.LANE == 0)          # (what ops.plan_gemm makes of the planner's 4-deep ring)
     Ms = [77 * 2, 154 * 3, 64, 256, 1024, 2048, 4096, 8192, 12288, 16384, 24576, 32768, 57344, 65536, 131072, 229376, 458752, 1 << 20]
     rows = [128, 256, 320, 384, 640, 1280, 1920, 2560, 3840, 5120, 10240]
     ks = [64, 320, 640, 1280, 2880, 3200, 5760, 6400, 8640, 11520, 17280, 23040]
     cands = [(160, 128), (320, 160, 128, 64), (160, 128, 64), (320, 160, 128)]
     for M, r, k, cand, split in itertools.product(Ms, rows, ks, cands, (True, False)):
         try:
-            want = ops.plan_gemm_reference(M, r, k, False, bns=cand, allow_split=split)
+            want = nm.plan_gemm_reference(M, r, k, False, bns=cand, allow_split=split, deep_ring=deep)
             assert ops.plan_gemm(M, r, k, False, bns=cand, allow_split=split) == want          # the Python host now asks the library
         except L.EdgeStyleHipError:
             want = None
@@ -46,14 +47,14 @@ def test_launch_planner_of_the_library_equals_the_python_hosts():
     # the 256 x 256 tile of the LayerNorm-folded / GEGLU linear layers (round 5): offered first, with and without GEGLU, never split
     for M, r, k, geglu in itertools.product(Ms, [1280, 3840, 10240, 2560, 5120], [320, 640, 1280], (False, True)):
         for cand in ((256, 160, 128), (256, 160, 128, 64), (256,)):
-            want = ops.plan_gemm_reference(M, r, k, geglu, bns=cand, allow_split=False)
+            want = nm.plan_gemm_reference(M, r, k, geglu, bns=cand, allow_split=False, deep_ring=deep)
             assert ops.plan_gemm(M, r, k, geglu, bns=cand, allow_split=False) == want, (M, r, k, geglu, cand)
             assert want[1] == 1 and (not geglu or want[0] in (128, 256))
             if want[0] == 256:
-                assert want[2] == 2 and (len(cand) == 1 or (M >= ops.PLAN_BIG_MIN_M and k // 64 >= ops.PLAN_BIG_MIN_NK))
+                assert want[2] == 2 and (len(cand) == 1 or (M >= nm.PLAN_BIG_MIN_M and k // 64 >= nm.PLAN_BIG_MIN_NK))
     arr = (C.c_int * 2)(160, 128)
     assert lib.es_plan_gemm_choice(4096, 2560, 320, 1, arr, 2, 1, C.byref(bn), C.byref(sk), C.byref(st)) == 0
-    assert (bn.value, sk.value, st.value) == ops.plan_gemm(4096, 2560, 320, True) == ops.plan_gemm_reference(4096, 2560, 320, True)
+    assert (bn.value, sk.value, st.value) == ops.plan_gemm(4096, 2560, 320, True) == nm.plan_gemm_reference(4096, 2560, 320, True, deep_ring=deep)
 
 
 def test_short_k_kernel_policy_of_the_library_equals_the_python_hosts():
@@ -61,7 +62,7 @@ def test_short_k_kernel_policy_of_the_library_equals_the_python_hosts():
     for M, K, cout, geglu in itertools.product([1024, 8192, 16384, 32768, 57344, 458752], [320, 640, 1280, 768], [320, 640, 960, 1920, 2560, 5120],
                                                [False, True]):
         pw = ops.PackedWeight(w=torch.empty(0, K), bias=None, cout=cout, cin=K, ksize=1, bn=128, geglu=geglu)
-        want = ops.xs_shape_reference(M, pw, 8192)
+        want = nm.xs_shape_reference(M, pw, 8192)
         assert bool(lib.es_linear_xs_eligible(M, 1, K, K, 0, cout, int(geglu))) == want == ops.xs_eligible(M, pw, None, None, 1), (M, K, cout, geglu)
 
 

@@ -110,7 +110,7 @@ def _ln_variants(ops, M, pw):
         out.append(("tile64", dict(XS_ENABLED=False, FORCE_BN=64), "fold", lambda d: d.bn == 64))
     if pw.kpad == 1280 and pw.rows_padded % 256 == 0:
         out.append(("tile256", dict(XS_ENABLED=False, FORCE_BN=256), "fold", lambda d: d.bn == 256))
-    if pw.kpad in (320, 640) and ops.xs_shape_reference(M, pw, 0):
+    if pw.kpad in (320, 640) and nm.xs_shape_reference(M, pw, 0):
         from edgestyle_amd import lib
         out.append(("linear_xs", dict(XS_ENABLED=True, XS_MIN_M=0), "xs", lambda d: isinstance(d, lib.XsDesc)))
     return out

@@ -13,6 +13,7 @@ import sys
 import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from edgestyle_amd import lib as L  # noqa: E402
 from edgestyle_amd.native import NativeContext  # noqa: E402
 from tests.helpers import full_weights, python_dry_context, diff_plans, plan_constants  # noqa: E402
 
