@@ -59,6 +59,9 @@ def parse_args(argv: Optional[List[str]] = None):
     p.add_argument("--native_text_encoder", action="store_true",
                    help="encode the prompts on the GPU with the library's own CLIP text encoder (edgestyle_amd/text.py) instead of "
                         "with transformers on the host; needs the tokenizer/ and text_encoder/ directories")
+    p.add_argument("--native_tokenizer", action="store_true",
+                   help="tokenise the prompts with the library's own CLIP BPE tokenizer (edgestyle_amd/tokenizer.py: vocab.json and "
+                        "merges.txt of the tokenizer/ directory) instead of with transformers; ASCII prompts only, anything else is refused")
     p.add_argument("--native_prompt_picker", action="store_true",
                    help="with --clip_model_name_or_path: pick the prompt on the GPU with the library's own CLIP image tower and scorer "
                         "(edgestyle_amd/clip.py) - the directory's weights are read, transformers' forward is not run")
@@ -137,8 +140,11 @@ def main(args):
         if args.native_text_encoder:
             from .text import NativeCLIPTextEncoder
             text_encoder = NativeCLIPTextEncoder.from_module(text_encoder, dtype=weight_dtype, device=device, max_n=2)
-    elif args.native_text_encoder:
-        raise SystemExit("--native_text_encoder needs tokenizer/ and text_encoder/ under --pretrained_model_name_or_path")
+        if args.native_tokenizer:
+            from .tokenizer import NativeCLIPTokenizer
+            tokenizer = NativeCLIPTokenizer.from_pretrained(tok_dir, model_max_length=tokenizer.model_max_length)
+    elif args.native_text_encoder or args.native_tokenizer:
+        raise SystemExit("--native_text_encoder / --native_tokenizer need tokenizer/ and text_encoder/ under --pretrained_model_name_or_path")
     vae = AutoencoderKL.from_pretrained(args.pretrained_vae_name_or_path or os.path.join(args.pretrained_model_name_or_path, "vae"))
     unet = UNet2DConditionModel.from_pretrained(args.pretrained_model_name_or_path, subfolder="unet", torch_dtype=weight_dtype)
     openpose = ControlNetModel.from_pretrained(args.pretrained_openpose_name_or_path, torch_dtype=weight_dtype)

@@ -4,8 +4,9 @@ csrc/clip.hip).
 `NativeBestEmbeddings` has the call surface of `prompts.BestEmbeddings` (model/utils.py:647-684): `picker(images)` gives one prompt
 "<prefix>, c1, c2, i1, i2" per garment image.  The words' text embeddings are computed once, at construction, by the library's text
 encoder into a bank on the device; a call then resizes the photos (Pillow's bicubic, transformers' crop), runs the image tower and
-scores against the bank, all on the GPU.  Tokenisation stays with the caller's CLIPTokenizer.  There is no fallback: a refused
-configuration raises."""
+scores against the bank, all on the GPU.  The tokenizer is the caller's: transformers' CLIPTokenizer, or the library's own
+(tokenizer.NativeCLIPTokenizer).  With the latter `encode_prompts` goes from the photos to the text states `ehs` without the host:
+es_clip_pick -> es_prompt_assemble -> es_text_encode_dev on one stream.  There is no fallback: a refused configuration raises."""
 import ctypes as C
 import json
 import os
@@ -18,6 +19,7 @@ from . import lib as L
 from .lib import EdgeStyleHipError
 from .prompts import DEFAULT_CLOTHING_ITEMS, DEFAULT_COLORS
 from .text import NativeCLIPTextEncoder, _ACTS, _DT, state_dict_descriptors
+from .tokenizer import NativeCLIPTokenizer
 
 OPENAI_CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)
 OPENAI_CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
@@ -65,6 +67,16 @@ def image_bytes(img) -> np.ndarray:
     return np.ascontiguousarray(img)
 
 
+def check_comma_join(tokenizer, prefix: str, words: Sequence[str]) -> None:
+    """Once per vocabulary, on the host, with the native tokenizer: es_prompt_assemble joins the pieces with spaces, the reference's
+    string (and NativeBestEmbeddings.__call__'s) with ", ".  The two tokenise alike unless a piece ends with punctuation, which
+    then runs into the comma ("t-shirt!, x" and "t-shirt! , x" differ): such a word is named here."""
+    for w in [prefix] + list(words):
+        if tokenizer.tokenize_ids(f"{prefix}, {w}, {w}") != tokenizer.tokenize_ids(f"{prefix} , {w} , {w}"):
+            raise EdgeStyleHipError(f"the word {w!r} tokenises differently inside the comma-joined prompt than on its own (it ends with "
+                                    "punctuation): encode_prompts could not give the ids of the prompt __call__ returns")
+
+
 class NativeBestEmbeddings:
     """clip_state_dict: CLIPModel's state dict; clip_config: its CLIPConfig (or a dict with text_config, vision_config, projection_dim);
     tokenizer: the CLIPTokenizer of the checkpoint.  max_images: the most images one call scores."""
@@ -104,6 +116,13 @@ class NativeBestEmbeddings:
                 self.close()
                 raise
         self._segments = [len(self.colors), len(self.colors) + len(self.clothing_items)]
+        self._tables = {}
+        if isinstance(tokenizer, NativeCLIPTokenizer):
+            try:
+                check_comma_join(tokenizer, self.prefix, self.colors + self.clothing_items)
+            except Exception:
+                self.close()
+                raise
 
     @classmethod
     def from_module(cls, model, tokenizer, **kw):
@@ -170,6 +189,13 @@ class NativeBestEmbeddings:
     # ---- the request side ----
     def score(self, images, bank, segments: Sequence[int], k: int):
         """(logits [n, W], probs [n, W], topk [n, nseg, k]) on the device for these images against `bank`"""
+        out = self._pick(images, bank, segments, k)
+        torch.cuda.synchronize(self.device)
+        return out
+
+    def _pick(self, images, bank, segments: Sequence[int], k: int):
+        """score without the synchronisation: everything is queued on the current stream, and the tensors that go out of scope here
+        return to torch's allocator, which hands them out again in that stream's order"""
         arrs = [image_bytes(im) for im in (images if isinstance(images, (list, tuple)) else [images])]
         n = len(arrs)
         if not 1 <= n <= self.max_images:
@@ -192,8 +218,25 @@ class NativeBestEmbeddings:
             L.check(self.lib.es_clip_pick(self._vision, bank, imgs, n, self.logit_scale_exp, seg, len(segments), k, C.c_void_p(logits.data_ptr()),
                                           C.c_void_p(probs.data_ptr()), C.c_void_p(topk.data_ptr()), C.c_void_p(ws.data_ptr()), need, stream),
                     "es_clip_pick")
-            torch.cuda.synchronize(self.device)      # dev / ws go out of scope here: the work that reads them has finished
         return logits, probs, topk
+
+    def prompt_table(self, suffix: str = ""):
+        """the es_prompt_table of this picker's words for one suffix, built on first use (a device allocation and an upload) and kept"""
+        if not isinstance(self.tokenizer, NativeCLIPTokenizer):
+            raise EdgeStyleHipError("encode_prompts needs tokenizer=NativeCLIPTokenizer: the prompt is assembled from its token table")
+        if suffix not in self._tables:
+            self._tables[suffix] = self.tokenizer.prompt_table(self.colors + self.clothing_items, self._segments, prefix=self.prefix,
+                                                               separator=",", suffix=suffix, device=self.device.index)
+        return self._tables[suffix]
+
+    def encode_prompts(self, images, text_encoder: NativeCLIPTextEncoder, suffix: str = "", out=None) -> torch.Tensor:
+        """photos -> the text states of `picker(images)[i] + " " + suffix`, dtype [n, max_positions, hidden] on the device:
+        es_clip_pick -> es_prompt_assemble -> es_text_encode_dev on the current stream, no synchronisation and no copy to the host."""
+        table = self.prompt_table(suffix)
+        with torch.cuda.device(self.device):
+            _, _, topk = self._pick(images, self._bank, self._segments, 2)
+            ids, _ = table.assemble(topk)
+            return text_encoder.encode_ids_device(ids, out=out)
 
     def __call__(self, images) -> List[str]:
         """One prompt per image: "<prefix>, c1, c2, i1, i2" (MU:652-664) - both lists in ONE pass over the cached bank."""
@@ -224,6 +267,9 @@ class NativeBestEmbeddings:
     def close(self):
         v, self._vision = getattr(self, "_vision", None), None
         b, self._bank = getattr(self, "_bank", None), None
+        for t in getattr(self, "_tables", {}).values():
+            t.close()
+        self._tables = {}
         if b:
             self.lib.es_clip_bank_destroy(b)
         if v:

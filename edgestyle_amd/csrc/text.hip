@@ -314,27 +314,12 @@ extern "C" int es_text_encoder_create(const es_state_dict* sd, const es_text_con
   return 0;
 }
 
-extern "C" int es_text_encode(es_text_encoder* e, const int32_t* ids_host, int n, void* out_ehs, void* stream) {
-  const char* who = "es_text_encode";
-  if (!e || !ids_host || !out_ehs) return fail(-1, who, "null pointer");
-  if (es_plan_recording()) return fail(-1, who, kRecording);
-  if (n < 1 || n > e->max_n) return fail(-1, who, "n = " + std::to_string(n) + " is outside 1..max_n = " + std::to_string(e->max_n));
-  if (!e->arena) return fail(-1, who, "this encoder is a dry build (es_text_encoder_create device -1): it holds no device memory and cannot run");
+// the forward from ids on the device: what es_text_encode and es_text_encode_dev share
+static int forward(const char* who, es_text_encoder* e, const int32_t* ids_dev, int n, void* out_ehs, void* stream) {
   const int C = e->cfg.hidden, S = e->cfg.max_positions, V = e->cfg.vocab_size, M = n * S;
-  for (int i = 0; i < M; ++i)
-    if (ids_host[i] < 0 || ids_host[i] >= V)
-      return fail(-1, who, "token id " + std::to_string(ids_host[i]) + " at row " + std::to_string(i / S) + ", position " + std::to_string(i % S) + " is outside [0, " + std::to_string(V) + ")");
   hipStream_t st = (hipStream_t)stream;
-  if (capturing(st)) return fail(-1, who, "the stream is capturing; this entry point stages the token ids through pinned memory and cannot be captured");
-  int dev = -1;
-  if (hipGetDevice(&dev) != hipSuccess || dev != e->device) return fail(-1, who, "the current device is not the one the encoder was built on");
-  if (hipEventSynchronize(e->staged) != hipSuccess) return fail(-2, who, "hipEventSynchronize failed");      // the previous call's copy has completed
-  memcpy(e->ids_pinned, ids_host, (size_t)M * 4);
   char* A = e->arena;
-  if (hipMemcpyAsync(A + e->ids, e->ids_pinned, (size_t)M * 4, hipMemcpyHostToDevice, st) != hipSuccess) return fail(-2, who, "copy of the token ids failed");
-  if (hipEventRecord(e->staged, st) != hipSuccess) return fail(-2, who, "hipEventRecord failed");
-
-  int rc = es_text_embed((const int32_t*)(A + e->ids), (const float*)(A + e->tok), (const float*)(A + e->pos), A + e->xa, M, S, C, V, e->dtype, stream);
+  int rc = es_text_embed(ids_dev, (const float*)(A + e->tok), (const float*)(A + e->pos), A + e->xa, M, S, C, V, e->dtype, stream);
   if (rc) return rc;
   const int dh = C / e->cfg.heads;
   es_attn_desc a;
@@ -352,4 +337,39 @@ extern "C" int es_text_encode(es_text_encoder* e, const int32_t* ids_host, int n
     if ((rc = linear(who, e, L.fc2, A + e->hid, A + e->xa, A + e->xb, M, ES_ACT_NONE, 1.f, st))) return rc;
   }
   return es_layer_norm(A + e->xa, out_ehs, (const float*)(A + e->fln_g), (const float*)(A + e->fln_b), M, C, e->cfg.ln_eps, e->dtype, stream);
+}
+
+extern "C" int es_text_encode(es_text_encoder* e, const int32_t* ids_host, int n, void* out_ehs, void* stream) {
+  const char* who = "es_text_encode";
+  if (!e || !ids_host || !out_ehs) return fail(-1, who, "null pointer");
+  if (es_plan_recording()) return fail(-1, who, kRecording);
+  if (n < 1 || n > e->max_n) return fail(-1, who, "n = " + std::to_string(n) + " is outside 1..max_n = " + std::to_string(e->max_n));
+  if (!e->arena) return fail(-1, who, "this encoder is a dry build (es_text_encoder_create device -1): it holds no device memory and cannot run");
+  const int S = e->cfg.max_positions, V = e->cfg.vocab_size, M = n * S;
+  for (int i = 0; i < M; ++i)
+    if (ids_host[i] < 0 || ids_host[i] >= V)
+      return fail(-1, who, "token id " + std::to_string(ids_host[i]) + " at row " + std::to_string(i / S) + ", position " + std::to_string(i % S) + " is outside [0, " + std::to_string(V) + ")");
+  hipStream_t st = (hipStream_t)stream;
+  if (capturing(st)) return fail(-1, who, "the stream is capturing; this entry point stages the token ids through pinned memory and cannot be captured");
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess || dev != e->device) return fail(-1, who, "the current device is not the one the encoder was built on");
+  if (hipEventSynchronize(e->staged) != hipSuccess) return fail(-2, who, "hipEventSynchronize failed");      // the previous call's copy has completed
+  memcpy(e->ids_pinned, ids_host, (size_t)M * 4);
+  char* A = e->arena;
+  if (hipMemcpyAsync(A + e->ids, e->ids_pinned, (size_t)M * 4, hipMemcpyHostToDevice, st) != hipSuccess) return fail(-2, who, "copy of the token ids failed");
+  if (hipEventRecord(e->staged, st) != hipSuccess) return fail(-2, who, "hipEventRecord failed");
+  return forward(who, e, (const int32_t*)(A + e->ids), n, out_ehs, stream);
+}
+
+// es_text_encode with the ids already on the device: no pinned staging, nothing allocated - capturable.  Everything after the id copy
+// is es_text_encode's own code (forward), so the two agree bit for bit; an id outside the vocabulary is clamped by the embed kernel.
+extern "C" int es_text_encode_dev(es_text_encoder* e, const int32_t* ids_dev, int n, void* out_ehs, void* stream) {
+  const char* who = "es_text_encode_dev";
+  if (!e || !ids_dev || !out_ehs) return fail(-1, who, "null pointer");
+  if (es_plan_recording()) return fail(-1, who, kRecording);
+  if (n < 1 || n > e->max_n) return fail(-1, who, "n = " + std::to_string(n) + " is outside 1..max_n = " + std::to_string(e->max_n));
+  if (!e->arena) return fail(-1, who, "this encoder is a dry build (es_text_encoder_create device -1): it holds no device memory and cannot run");
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess || dev != e->device) return fail(-1, who, "the current device is not the one the encoder was built on");
+  return forward(who, e, ids_dev, n, out_ehs, stream);
 }

@@ -342,6 +342,22 @@ SYMBOLS = {
     "es_clip_vision_encode": (C.c_int, [_P, _P, _I, _P, _P]),
     "es_clip_pick_workspace_bytes": (C.c_size_t, [_P, C.POINTER(ImageU8), _I]),
     "es_clip_pick": (C.c_int, [_P, _P, C.POINTER(ImageU8), _I, _F, C.POINTER(C.c_int32), _I, _I, _P, _P, _P, _P, C.c_size_t, _P]),
+    "es_text_encode_dev": (C.c_int, [_P, _P, _I, _P, _P]),
+    "es_tokenizer_create": (C.c_int, [C.c_char_p, C.c_char_p, _I, C.POINTER(_P)]),
+    "es_tokenizer_create_from_memory": (C.c_int, [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, _I, C.POINTER(_P)]),
+    "es_tokenizer_destroy": (None, [_P]),
+    "es_tokenizer_vocab_size": (C.c_int, [_P]),
+    "es_tokenizer_max_length": (C.c_int, [_P]),
+    "es_tokenizer_bos_id": (C.c_int, [_P]),
+    "es_tokenizer_eos_id": (C.c_int, [_P]),
+    "es_tokenizer_pad_id": (C.c_int, [_P]),
+    "es_tokenize": (C.c_int, [_P, C.c_char_p, C.c_size_t, C.POINTER(C.c_int32), _I]),
+    "es_tokenize_padded": (C.c_int, [_P, C.c_char_p, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "es_prompt_table_create": (C.c_int, [_P, C.POINTER(C.c_char_p), _I, C.POINTER(C.c_int32), _I, C.c_char_p, C.c_char_p, C.c_char_p, _I,
+                                         C.POINTER(_P)]),
+    "es_prompt_table_destroy": (None, [_P]),
+    "es_prompt_assemble": (C.c_int, [_P, _P, _I, _I, _P, _P, _P]),
+    "es_prompt_assemble_host": (C.c_int, [_P, C.POINTER(C.c_int32), _I, _I, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
 }
 
 _lib = None

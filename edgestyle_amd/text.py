@@ -2,7 +2,8 @@
 
 `NativeCLIPTextEncoder` is a drop-in for the pipeline's `text_encoder=`: `encoder(input_ids)[0]` is CLIPTextModel's
 last_hidden_state, computed by the library's kernels on the GPU instead of by transformers on the host's CPU threads.
-Tokenisation stays with the caller (CLIPTokenizer).  There is no fallback: a refused configuration raises."""
+The ids come from the caller's tokenizer - transformers' CLIPTokenizer, or the library's own (tokenizer.NativeCLIPTokenizer) - or,
+already on the device, from es_prompt_assemble (`encode_ids_device`).  There is no fallback: a refused configuration raises."""
 import ctypes as C
 
 import torch
@@ -97,6 +98,22 @@ class NativeCLIPTextEncoder:
                 out = torch.empty((n, self.cfg.max_positions, self.cfg.hidden), dtype=self.dtype, device=self.device)
             stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
             L.check(self.lib.es_text_encode(self._h, C.c_void_p(ids.data_ptr()), n, C.c_void_p(out.data_ptr()), stream), "es_text_encode")
+        return out
+
+    def encode_ids_device(self, ids_dev: torch.Tensor, out=None) -> torch.Tensor:
+        """ids_dev: int32 [n, max_positions] on the device (es_prompt_assemble's rows) -> dtype [n, max_positions, hidden] there, on the
+        current stream: no host copy, no synchronisation, capturable.  Bit-equal to encode_ids of the same ids."""
+        if self.device is None:
+            raise EdgeStyleHipError("this encoder is a dry build: it holds no device memory and cannot run")
+        if not ids_dev.is_cuda or ids_dev.device != self.device or ids_dev.dtype != torch.int32 or not ids_dev.is_contiguous() \
+                or ids_dev.dim() != 2 or ids_dev.shape[1] != self.cfg.max_positions:
+            raise EdgeStyleHipError(f"ids_dev must be a contiguous int32 [n, {self.cfg.max_positions}] tensor on {self.device}")
+        n = ids_dev.shape[0]
+        with torch.cuda.device(self.device):
+            if out is None:
+                out = torch.empty((n, self.cfg.max_positions, self.cfg.hidden), dtype=self.dtype, device=self.device)
+            stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            L.check(self.lib.es_text_encode_dev(self._h, C.c_void_p(ids_dev.data_ptr()), n, C.c_void_p(out.data_ptr()), stream), "es_text_encode_dev")
         return out
 
     def __call__(self, input_ids, *args, **kwargs):

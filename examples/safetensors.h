@@ -101,7 +101,7 @@ struct SafeTensors {
     for (const auto& kv : h.obj) {
       if (kv.first == "__metadata__") continue;
       const Json *dt = kv.second.get("dtype"), *sh = kv.second.get("shape"), *of = kv.second.get("data_offsets");
-      if (!dt || !sh || !of || of->arr.size() != 2 || sh->arr.size() > 4 || sh->arr.empty()) { fprintf(stderr, "%s: entry '%s' not understood\n", path.c_str(), kv.first.c_str()); return false; }
+      if (!dt || !sh || !of || of->arr.size() != 2 || sh->arr.size() > 4) { fprintf(stderr, "%s: entry '%s' not understood\n", path.c_str(), kv.first.c_str()); return false; }
       es_tensor t;
       memset(&t, 0, sizeof(t));
       t.dtype = dt->str == "F32" ? ES_F32 : dt->str == "F16" ? ES_F16 : dt->str == "BF16" ? ES_BF16 : -1;
@@ -110,6 +110,7 @@ struct SafeTensors {
       t.ndim = (int32_t)sh->arr.size();
       size_t n = t.dtype == ES_F32 ? 4 : 2;
       for (int i = 0; i < t.ndim; ++i) { t.shape[i] = (int64_t)sh->arr[i].num; n *= (size_t)t.shape[i]; }
+      if (t.ndim == 0) { t.ndim = 1; t.shape[0] = 1; }          // a scalar (CLIPModel's logit_scale) is described as [1]
       const size_t a = (size_t)of->arr[0].num, b = (size_t)of->arr[1].num;
       if (b - a != n || 8 + hl + b > bytes) { fprintf(stderr, "%s: '%s' lies outside the file\n", path.c_str(), kv.first.c_str()); return false; }
       t.data = data + a;

@@ -1,8 +1,9 @@
 // From a text_encoder/ directory and token ids to the text states of a try-on request in plain C++: no Python, no torch, no transformers.
 // The host memory-maps the safetensors file of a CLIPTextModel checkpoint (transformers save_pretrained: config.json + model.safetensors,
 // keys bare or with the `text_model.` prefix of the SD1.5 checkpoints), describes its tensors to es_text_encoder_create
-// (include/edgestyle_hip.h) and encodes the ids with es_text_encode.  Tokenisation stays with the caller: the ids come from whatever
-// CLIP BPE tokenizer it links, padded to max_position_embeddings like the reference pads them (padding="max_length").
+// (include/edgestyle_hip.h) and encodes the ids with es_text_encode.  The ids come from es_tokenize_padded
+// (examples/prompt_host.cpp goes from text and a photo to the same record) or from whatever CLIP BPE tokenizer the caller links, padded to
+// max_position_embeddings like the reference pads them (padding="max_length").
 //
 //   hipcc -O2 -Iinclude examples/text_host.cpp -Ledgestyle_amd/lib -ledgestyle_hip -Wl,-rpath,$PWD/edgestyle_amd/lib -o text_host
 //   ./text_host <text_encoder_dir> ids.bin ehs.bin [fp16|bf16]

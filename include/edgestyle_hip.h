@@ -822,7 +822,8 @@ int es_ctx_draw_cond_noise(es_ctx* c, es_philox* gen, int round_dtype, void* str
 /* =========================================================================================================
  * Text encoder (csrc/text.hip): token ids in, the text states `ehs` of es_denoise_step / es_denoise_loop out - CLIPTextModel's
  * last_hidden_state, which the reference computes per request with transformers (app.py:163-176: the prompt and the negative
- * prompt; model/edgestyle_pipeline.py encode_prompt).  Tokenisation (BPE, vocabulary files) stays with the caller.
+ * prompt; model/edgestyle_pipeline.py encode_prompt).  The ids come from es_tokenize_padded or es_prompt_assemble (below), or from
+ * any CLIP BPE tokenizer the caller links.
  * A self-contained object beside es_ctx: it owns one arena (fp32 embedding tables, packed weights, activations for max_n prompts)
  * and runs on the library's own kernels - es_conv_gemm through the launch policy (es_launch_choose; LayerNorm1 / LayerNorm2 folded
  * into q|k|v and fc1, residual adds in the epilogues of out_proj and fc2), the two kernels below and es_layer_norm.
@@ -861,6 +862,11 @@ size_t es_text_encoder_arena_bytes(const es_text_encoder* e);
  * the `ehs` operand - under CFG the negative prompts first, then the prompts.  out_ehs: device dtype [n, max_positions, hidden].
  * The ids are staged through pinned memory: a capturing stream is refused, as es_denoise_step refuses it.  Asynchronous on `stream`. */
 int es_text_encode(es_text_encoder* e, const int32_t* ids_host, int n, void* out_ehs, void* stream);
+/* es_text_encode with the ids already on the device (ids_dev: DEVICE int32 [n, max_positions], for instance es_prompt_assemble's
+ * output): no pinned staging, nothing allocated, so a capturing stream is accepted.  Everything after the id copy is es_text_encode's
+ * own code: the same ids give the same bits.  The ids cannot be checked on the host; the embedding kernel clamps them to
+ * [0, vocab_size). */
+int es_text_encode_dev(es_text_encoder* e, const int32_t* ids_dev, int n, void* out_ehs, void* stream);
 
 /* =========================================================================================================
  * CLIP prompt picker (csrc/clip.hip): garment bytes in, the best words of the caller's vocabularies out.  Replaces BestEmbeddings
@@ -869,7 +875,8 @@ int es_text_encode(es_text_encoder* e, const int32_t* ids_host, int n, void* out
  * two best words of each list.  The word side is computed ONCE per vocabulary into an es_clip_bank; a request is es_clip_pick.
  * The transformer layers are the text encoder's (csrc/encoder.h) without the causal mask: es_conv_gemm through the launch policy with
  * LayerNorm1 / LayerNorm2 folded into q|k|v and fc1, es_attention over Q, K, V as column slices of the [M, 3C] projection, residual adds
- * in the epilogues of out_proj and fc2, quick_gelu on the SiLU epilogue.  Tokenisation stays with the caller.
+ * in the epilogues of out_proj and fc2, quick_gelu on the SiLU epilogue.  The words reach es_clip_text_pool as token ids: the
+ * caller's tokenizer, or es_tokenize_padded (below), whose eos_pos_out is the position es_clip_text_pool asks for.
  * None of these calls is ever part of a plan: while a plan records on the calling thread they return -1.  No new
  * ES_ABI_VERSION: no plan or context image records them.
  * ========================================================================================================= */
@@ -942,6 +949,58 @@ size_t es_clip_pick_workspace_bytes(const es_clip_vision* e, const es_image_u8* 
 int es_clip_pick(es_clip_vision* e, const es_clip_bank* bank, const es_image_u8* imgs, int count, float logit_scale_exp,
                  const int32_t* seg_ends, int nseg, int k, float* logits, float* probs, int32_t* topk, void* workspace,
                  size_t workspace_bytes, void* stream);
+
+/* =========================================================================================================
+ * Tokenizer and prompt assembly (csrc/bpe.h, csrc/prompt.hip): the link between es_clip_pick and es_text_encode.  The reference joins
+ * the picked words into "edgestyle, c1, c2, i1, i2" + " " + suffix on the host (model/utils.py:661, app.py:165) and runs transformers'
+ * CLIPTokenizer over it; here the tokenizer is in the library, and the picker's topk becomes the id row on the device.
+ * The tokenizer is CLIP's byte-level BPE as transformers' CLIPTokenizer (the `tokenizers` backend) computes it: NFC, white space runs
+ * to one space, lowercase; split by 's|'t|'re|'ve|'m|'ll|'d|[\p{L}]+|[\p{N}]|[^\s\p{L}\p{N}]+; BPE with the end-of-word suffix </w>;
+ * unk = pad = eos = <|endoftext|> (a symbol missing from the vocabulary is one unk id); BOS ... EOS, truncation keeps the EOS in the
+ * last slot, padding is EOS.  Domain: exact or refused.  Accepted bytes are 0x09-0x0D and 0x20-0x7E; any other byte (non-ASCII
+ * needs Unicode tables the library does not ship; NUL: the text is pointer + length and is never cut) is refused with its offset in
+ * es_last_error(), and so is a text that holds the literal <|startoftext|> or <|endoftext|> in any letter case.
+ * An es_tokenizer caches the ids of the words it has seen and is NOT thread-safe: one per thread, or a lock around it.
+ * None of the es_prompt_* calls nor es_text_encode_dev is ever part of a plan: while a plan records on the calling thread they
+ * return -1.  No new ES_ABI_VERSION: no plan or context image records them.
+ * ========================================================================================================= */
+typedef struct es_tokenizer es_tokenizer;
+/* vocab.json (one flat JSON object token -> id; keys in raw UTF-8 or with \uXXXX escapes) and merges.txt ("left right" per line, lines
+ * starting with #version skipped) of a CLIPTokenizer directory.  max_length: the row length of es_tokenize_padded (77 for SD1.5).
+ * An error names the line or key: a merge whose parts or result are not in the vocabulary, a missing special token, max_length < 2. */
+int es_tokenizer_create(const char* vocab_json_path, const char* merges_txt_path, int max_length, es_tokenizer** out);
+int es_tokenizer_create_from_memory(const char* vocab_json, size_t vocab_bytes, const char* merges_txt, size_t merges_bytes,
+                                    int max_length, es_tokenizer** out);
+void es_tokenizer_destroy(es_tokenizer* t);
+int es_tokenizer_vocab_size(const es_tokenizer* t);
+int es_tokenizer_max_length(const es_tokenizer* t);
+int es_tokenizer_bos_id(const es_tokenizer* t);
+int es_tokenizer_eos_id(const es_tokenizer* t);
+int es_tokenizer_pad_id(const es_tokenizer* t);            /* == eos */
+/* text[0 .. len) -> its ids without BOS / EOS, untruncated.  Returns their count (the first min(count, capacity) are written to
+ * ids_out; ids_out may be NULL with capacity 0 to ask for the count), or -1 for a refused text. */
+int es_tokenize(es_tokenizer* t, const char* text, size_t len, int32_t* ids_out, int capacity);
+/* the row of tokenizer(text, padding="max_length", max_length=max_length, truncation=True): ids_out HOST int32 [max_length];
+ * eos_pos_out (may be NULL): the position of the row's first EOS - what es_clip_text_pool asks its caller for.  0, or -1. */
+int es_tokenize_padded(es_tokenizer* t, const char* text, size_t len, int32_t* ids_out, int32_t* eos_pos_out);
+/* Every word of the picker's vocabularies (words[n_words], NUL-terminated; seg_ends / nseg as es_clip_score takes them, the last ==
+ * n_words) and the three fixed pieces (NULL = empty), tokenised once and uploaded to `device`: tokens[W, Lw], len[W], the fixed ids,
+ * bos, eos and the tokenizer's max_length.  device -1: a table in host memory alone, for es_prompt_assemble_host. */
+typedef struct es_prompt_table es_prompt_table;
+int es_prompt_table_create(es_tokenizer* tok, const char* const* words, int n_words, const int32_t* seg_ends, int nseg,
+                           const char* prefix, const char* separator, const char* suffix, int device, es_prompt_table** out);
+void es_prompt_table_destroy(es_prompt_table* t);
+/* topk_dev: DEVICE int32 [n, nseg, k] (es_clip_pick's topk, k <= 8) -> ids_out_dev: DEVICE int32 [n, max_length]; eos_pos_dev: DEVICE
+ * int32 [n], may be NULL.  Row = BOS, prefix, then for every segment and every j < k in topk order: separator, word; then suffix; cut
+ * to max_length - 2 ids, then EOS, then EOS padding; eos_pos = 1 + min(total, max_length - 2).  A topk entry outside [0, segment
+ * size) - es_clip_score's -1 is one - is skipped and never used as an index.  The row equals the tokenizer's row of the pieces joined
+ * by single spaces (a piece boundary is always a split boundary); the reference's comma-joined string gives the same ids as long as
+ * no piece ends with punctuation, which would run into the comma ("t-shirt!, x" and "t-shirt! , x" differ).  One wave per row, plain stores, nothing
+ * allocated or staged: capturable. */
+int es_prompt_assemble(const es_prompt_table* t, const int32_t* topk_dev, int n, int k, int32_t* ids_out_dev, int32_t* eos_pos_dev,
+                       void* stream);
+/* the same rows from HOST topk into HOST memory, by the kernel's own index code */
+int es_prompt_assemble_host(const es_prompt_table* t, const int32_t* topk, int n, int k, int32_t* ids_out, int32_t* eos_pos);
 
 
 #ifdef __cplusplus

@@ -6,11 +6,15 @@ projection 768) with seeded random weights, one 768 x 1024 photo, 270 + 190 synt
 The native bank (the 460 text forwards) is built once, beforehand, and its build time is reported on its own; the host path runs the text
 tower inside every request, as the reference does.
 
-    python tools/clip_picker_bench.py [--reps 20] [--warmup 3] [--host_reps 3] [--dtype fp16] [--small]
+    python tools/clip_picker_bench.py [--reps 20] [--warmup 3] [--host_reps 3] [--dtype fp16] [--small] [--suffix TEXT]
 
 Native requests are timed twice: device events around es_clip_pick alone (the photo already on the device), and a host clock around the
 whole NativeBestEmbeddings call (upload, workspace allocation, the call, top-k read back, ending in a synchronise).  Prints every
-repetition's spread (min / median / max).  Needs a GPU: there is no fallback."""
+repetition's spread (min / median / max).
+The last native section times photo -> text states `ehs`: NativeBestEmbeddings.encode_prompts (es_clip_pick -> es_prompt_assemble ->
+es_text_encode_dev on one stream, tokenizer.NativeCLIPTokenizer) against the path it replaces - picker(images), the transformers
+tokenizer over the string, encode_ids - both from the photo on the host to a synchronise, host clock, and checks that the two give
+the same bits.  --host_reps 0 skips the transformers-on-the-host section.  Needs a GPU: there is no fallback."""
 import argparse
 import json
 import os
@@ -62,6 +66,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--host_reps", type=int, default=3)
     ap.add_argument("--dtype", default="fp16", choices=["fp16", "bf16"])
+    ap.add_argument("--suffix", default="a photo of a person wearing it, best quality", help="the caller's prompt suffix of the photo -> ehs section")
     ap.add_argument("--small", action="store_true", help="a 2-layer model of the tests' widths: a rehearsal of the script, not a measurement")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -141,6 +146,43 @@ def main():
         print(f"native: es_clip_pick alone (photo on the device), device events: {spread(ev)}")
     finally:
         be.close()
+
+    # ---- photo -> ehs: the device chain against picker -> string -> transformers tokenizer -> encode_ids ----
+    from edgestyle_amd.text import NativeCLIPTextEncoder
+    from edgestyle_amd.tokenizer import NativeCLIPTokenizer
+    ntok = NativeCLIPTokenizer.from_pretrained(tmp, model_max_length=77)
+    be2 = NativeBestEmbeddings.from_module(model, ntok, colors=colors, clothing_items=items, dtype=dtype, device="cuda", max_images=1, text_batch=64)
+    text_sd = {k[len("text_model."):]: v for k, v in model.state_dict().items() if k.startswith("text_model.")}       # the text tower stands in for SD1.5's
+    enc = NativeCLIPTextEncoder.from_state_dict(text_sd, cfg.text_config, dtype=dtype, device="cuda", max_n=1)
+    try:
+        def parent_path():
+            text = be2([pil])[0] + " " + args.suffix
+            return enc.encode_ids(tok([text], padding="max_length", max_length=77, truncation=True, return_tensors="pt").input_ids)
+
+        def device_path():
+            return be2.encode_prompts([pil], enc, suffix=args.suffix)
+        timings = {}
+        for name, fn in (("parent", parent_path), ("device", device_path)):
+            for _ in range(args.warmup):
+                fn()
+            ms = []
+            for _ in range(args.reps):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                ms.append((time.perf_counter() - t0) * 1e3)
+            timings[name] = ms
+        same = torch.equal(parent_path(), device_path())
+        print(f"photo -> ehs, parent path (picker call, transformers tokenizer, encode_ids), host clock: {spread(timings['parent'])}")
+        print(f"photo -> ehs, encode_prompts (es_clip_pick -> es_prompt_assemble -> es_text_encode_dev), host clock: {spread(timings['device'])}")
+        print(f"photo -> ehs: the two paths give the same bits: {same}; ratio of medians, parent / encode_prompts: "
+              f"{statistics.median(timings['parent']) / statistics.median(timings['device']):.2f}")
+    finally:
+        enc.close()
+        be2.close()
+    if args.host_reps < 1:
+        return
 
     # ---- the parent path: prompts.BestEmbeddings over transformers on the host ----
     proc = CLIPProcessor(image_processor=CLIPImageProcessor(size={"shortest_edge": rr}, crop_size={"height": rr, "width": rr}), tokenizer=tok)
