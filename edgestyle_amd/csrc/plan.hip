@@ -121,7 +121,7 @@ extern "C" int es_plan_launch(const es_plan* p, void* stream) {
 }
 
 // Pointer fields of a recorded call, by op kind: byte offset inside the argument record and how the op uses the memory
-// behind it (1 = reads, 2 = writes, 3 = both).  This is what a relocator needs (edgestyle_amd/native.py save()): exactly
+// behind it (1 = reads, 2 = writes, 3 = both).  This is what a relocator needs (write_image below): exactly
 // these 8-byte words are device addresses - nothing else in a record is ever treated as one - and a block of memory that
 // every plan only READS holds persistent data (packed weights, parameters, tables) and must travel with a context image,
 // while blocks that some call writes are produced at run time and only need their space.  `elem_bytes`: records of the
@@ -219,7 +219,7 @@ int es_plan_relocate(es_plan* p, unsigned long long (*map)(unsigned long long, i
   return 0;
 }
 // Flat image of a plan (es_ctx_save / es_ctx_load): u64 n_ops, u64 blob bytes, n_ops x {i64 kind, u64 off, u64 bytes}, blob.
-// The blob still holds the RECORDED device addresses: whoever moves it relocates them (edgestyle_amd/native.py save()).
+// The blob still holds the RECORDED device addresses: whoever moves it relocates them (write_image below).
 extern "C" size_t es_plan_export(const es_plan* p, void* out, size_t cap) {
   if (!p) return 0;
   const size_t need = 16 + p->ops.size() * 24 + p->blob.size();
@@ -624,11 +624,20 @@ extern "C" es_plan* es_ctx_plan(es_ctx* c, int which) {           // borrowed: t
   return (c && which >= 0 && which < ES_PLAN_COUNT) ? c->plan[which] : nullptr;
 }
 
-// A context image written by edgestyle_amd/native.py NativeEngine.save(): geometry, options, the five plans with a
-// relocation table each, the bound slots, and the contents of every device block a recorded pointer falls into (packed
-// weights, tables, static buffers, activation scratch).  Loading it needs no Python, no torch and no model code: one
+// A context image, written by write_image below (es_ctx_save, es_ctx_save_ranges) and by nobody else: geometry, options, the
+// plans with a relocation table each, the bound slots, and the contents of the memory that the plans read and never write
+// (packed weights, parameters, tables); everything else is space.  Loading it needs no Python, no torch and no model code: one
 // hipMalloc, one pass of copies, pointer relocation - the counterpart of SURVEY 8b's es_load_weights for a host that cannot
-// walk the model itself.  Layout (little endian, 8-byte aligned): see save().
+// walk the model itself.  Layout (little endian, 8-byte aligned):
+//   ImageHeader | es_ctx_geometry | ImageOptions | f32 schedule (padded to 8 bytes) | f64 schedule
+//   | n_blocks x {u64 arena offset, u64 bytes} | per plan: u64 size (0 = absent) | plan image, offsets in its blob | u64 n_rel | n_rel x {u64
+//   blob position, u64 arena offset} | per slot: {i64 arena offset or -1, u64 bytes} | u64 n_ext | n_ext x {u64 arena offset, u64 bytes} | the
+//   extents' bytes, in table order
+namespace {
+struct ImageHeader { char magic[8]; unsigned abi, n_blocks; unsigned long long arena_bytes; };
+struct ImageOptions { float cond_scales[6]; float start, end; int use_graphs; unsigned n_alphas; int scheduler; unsigned n_alphas_f64; };
+const char IMAGE_MAGIC[8] = {'E', 'S', 'C', 'T', 'X', 3, 0, 0};
+}  // namespace
 extern "C" int es_ctx_load(const char* path, int device, es_ctx** out) {
   if (!path || !out) { es_set_error("es_ctx_load: null argument"); return -1; }
   FILE* f = fopen(path, "rb");
@@ -637,14 +646,14 @@ extern "C" int es_ctx_load(const char* path, int device, es_ctx** out) {
   std::vector<char> buf;
   auto fail = [&](const char* msg) { es_set_error(msg); if (c) es_ctx_destroy(c); fclose(f); return -1; };
   auto rd = [&](void* dst, size_t n) { return fread(dst, 1, n, f) == n; };
-  struct { char magic[8]; unsigned abi, n_blocks; unsigned long long arena_bytes; } h;
-  if (!rd(&h, sizeof(h)) || memcmp(h.magic, "ESCTX\3\0\0", 8) != 0) return fail("es_ctx_load: not a context image (or one of an older format: rebuild it)");
+  ImageHeader h;
+  if (!rd(&h, sizeof(h)) || memcmp(h.magic, IMAGE_MAGIC, 8) != 0) return fail("es_ctx_load: not a context image (or one of an older format: rebuild it)");
   if (h.abi != ES_ABI_VERSION) return fail("es_ctx_load: the image was written for another ABI version");
   if (h.arena_bytes > (1ull << 40) || h.n_blocks > (1u << 24)) return fail("es_ctx_load: implausible header");
   if (hipSetDevice(device) != hipSuccess) return fail("es_ctx_load: hipSetDevice failed");
   c = new es_ctx();
   c->device = device;
-  struct { float cond_scales[6]; float start, end; int use_graphs; unsigned n_alphas; int scheduler; unsigned n_alphas_f64; } o;
+  ImageOptions o;
   if (!rd(&c->g, sizeof(c->g)) || !rd(&o, sizeof(o))) return fail("es_ctx_load: truncated header");
   if (o.n_alphas > (1u << 20) || o.n_alphas_f64 > (1u << 20)) return fail("es_ctx_load: implausible schedule length");
   if (o.scheduler != ES_SCHED_DDIM && o.scheduler != ES_SCHED_UNIPC) return fail("es_ctx_load: unknown scheduler in the image");
@@ -743,43 +752,53 @@ extern "C" int es_ctx_load(const char* path, int device, es_ctx** out) {
   return 0;
 }
 
-// Write a context that owns its arena (es_load_weights, es_ctx_load) as a context image es_ctx_load reads: the same format
-// NativeEngine.save (edgestyle_amd/native.py) writes for a Python-built context.  Every pointer field of every recorded call
-// (typed tables above) and every bound slot must lie inside the arena; only the persistent DATA extents travel as bytes, the rest
-// of the arena (activations, slabs, scratch, input slots) as zero-filled space.
-extern "C" int es_ctx_save(const es_ctx* c, const char* path) {
-  if (!c || !path) { es_set_error("es_ctx_save: null argument"); return -1; }
-  if (!c->arena || c->arena_on_host) { es_set_error("es_ctx_save: the context does not own a device arena (built by a Python host: use NativeEngine.save)"); return -1; }
-  const unsigned long long base = (unsigned long long)c->arena, size = c->arena_bytes;
-  auto inside = [&](unsigned long long a, unsigned long long n) { return a >= base && a - base <= size && n <= size - (a - base); };
-  // written under a temporary name and renamed on success: a failure (a pointer outside the arena, a failed device copy, a full
-  // disk) never leaves a truncated image under the final name
-  const std::string tmp = std::string(path) + ".tmp";
-  FILE* f = fopen(tmp.c_str(), "wb");
-  if (!f) { es_set_error("es_ctx_save: cannot open the file"); return -1; }
-  auto fail = [&](const char* msg) { es_set_error(msg); fclose(f); (void)remove(tmp.c_str()); return -1; };
-  auto wr = [&](const void* p, size_t n) { return fwrite(p, 1, n, f) == n; };
-  struct { char magic[8]; unsigned abi, n_blocks; unsigned long long arena_bytes; } h = {{'E', 'S', 'C', 'T', 'X', 3, 0, 0}, ES_ABI_VERSION, 1, size};
-  struct { float cond_scales[6]; float start, end; int use_graphs; unsigned n_alphas; int scheduler; unsigned n_alphas_f64; } o;
-  memcpy(o.cond_scales, c->cond_scales, sizeof(o.cond_scales));
-  o.start = c->control_start; o.end = c->control_end; o.use_graphs = c->use_graphs; o.n_alphas = (unsigned)c->alphas_cumprod.size();
-  o.scheduler = c->scheduler; o.n_alphas_f64 = (unsigned)c->alphas_cumprod_f64.size();
-  if (!wr(&h, sizeof(h)) || !wr(&c->g, sizeof(c->g)) || !wr(&o, sizeof(o))) return fail("es_ctx_save: write failed");
-  if (o.n_alphas && !wr(c->alphas_cumprod.data(), o.n_alphas * sizeof(float))) return fail("es_ctx_save: write failed");
-  const unsigned zero4 = 0;
-  if ((o.n_alphas & 1) && !wr(&zero4, 4)) return fail("es_ctx_save: write failed");
-  if (o.n_alphas_f64 && !wr(c->alphas_cumprod_f64.data(), o.n_alphas_f64 * sizeof(double))) return fail("es_ctx_save: write failed");
-  const unsigned long long blk[2] = {0, size};
-  if (!wr(blk, 16)) return fail("es_ctx_save: write failed");
+// The one writer of a context image.  `segs` is the memory the context's pointers may fall into: the context's own arena
+// (es_ctx_save), or the segments of a host's allocator (es_ctx_save_ranges).  Phase 1 scans and lays out - every pointer field
+// of every recorded call (typed tables above) and every bound slot is located in a segment, the used segments become the
+// arena's slots, the data extents are chosen - and touches neither the disk nor the device; phase 2 writes.
+namespace {
+typedef unsigned long long u64;
+struct Range { u64 addr, bytes, off; int use; };        // off: a segment's arena offset (~0 = unused); use: OR of the uses of a block's pointers
+const u64 UNUSED = ~0ull;
+// sorted by address; refuses empty, implausible (> 1 TiB, wrapping) and overlapping ranges
+bool sorted_ranges(const es_mem_range* r, int n, std::vector<Range>& out) {
+  for (int i = 0; i < n; ++i) {
+    if (!r[i].addr || !r[i].bytes || r[i].bytes > (1ull << 40) || r[i].addr + r[i].bytes < r[i].addr) return false;
+    out.push_back({r[i].addr, r[i].bytes, UNUSED, 0});
+  }
+  std::sort(out.begin(), out.end(), [](const Range& a, const Range& b) { return a.addr < b.addr; });
+  for (size_t i = 1; i < out.size(); ++i) if (out[i - 1].addr + out[i - 1].bytes > out[i].addr) return false;
+  return true;
+}
+Range* locate(std::vector<Range>& v, u64 a) {
+  auto it = std::upper_bound(v.begin(), v.end(), a, [](u64 x, const Range& r) { return x < r.addr; });
+  return (it != v.begin() && a - (it - 1)->addr < (it - 1)->bytes) ? &*(it - 1) : nullptr;
+}
+struct Reloc { u64 pos; const Range* seg; u64 delta; };   // blob position of a pointer field; where it points, relative to its segment
+struct Extent { u64 src; const Range* seg; u64 delta, bytes; };
+
+int write_image(const es_ctx* c, const char* path, const es_mem_range* seg_in, int n_seg, const es_mem_range* blk_in, int n_blk,
+                es_ctx_image_info* info) {
+  char msg[256];
+  auto refuse = [&](const char* m) { es_set_error(m); return -1; };
+  std::vector<Range> segs, blks;
+  if (!sorted_ranges(seg_in, n_seg, segs)) return refuse("es_ctx_save: empty, implausible or overlapping segments");
+  if (blk_in && !sorted_ranges(blk_in, n_blk, blks)) return refuse("es_ctx_save: empty, implausible or overlapping blocks");
+  // -- phase 1: scan and lay out ---------------------------------------------------------------------------------------
+  auto visit = [&](u64 a, int use) -> Range* {           // the segment of a pointer (now used); its block, if any, learns the use
+    Range* s = locate(segs, a);
+    if (!s) return nullptr;
+    s->off = 0;
+    if (Range* b = locate(blks, a)) b->use |= use;
+    return s;
+  };
+  std::vector<char> img[ES_PLAN_COUNT];
+  std::vector<Reloc> rel[ES_PLAN_COUNT];
   for (int which = 0; which < ES_PLAN_COUNT; ++which) {
     const es_plan* p = c->plan[which];
-    unsigned long long pb = p ? es_plan_export(p, nullptr, 0) : 0;
-    if (!wr(&pb, 8)) return fail("es_ctx_save: write failed");
     if (!p) continue;
-    std::vector<char> img((size_t)pb);
-    es_plan_export(p, img.data(), img.size());
-    const size_t blob0 = 16 + p->ops.size() * 24;
-    std::vector<unsigned long long> rel;
+    img[which].resize(es_plan_export(p, nullptr, 0));
+    es_plan_export(p, img[which].data(), img[which].size());
     for (const auto& op : p->ops) {
       int elem = 0;
       const auto& fl = ptr_fields(op.kind, elem);
@@ -787,42 +806,127 @@ extern "C" int es_ctx_save(const es_ctx* c, const char* path) {
       for (size_t r = 0; r < reps; ++r)
         for (const auto& pf : fl) {
           const size_t pos = op.off + r * (size_t)elem + (size_t)pf.off;
-          unsigned long long a;
+          if (pos + 8 > op.off + op.bytes) return refuse("es_ctx_save: a pointer field lies outside its record (ABI mismatch)");
+          u64 a;
           memcpy(&a, p->blob.data() + pos, 8);
           if (!a) continue;
-          if (!inside(a, 1)) return fail("es_ctx_save: a recorded pointer lies outside the context's arena");
-          rel.push_back(pos); rel.push_back(a - base);
-          const unsigned long long off = a - base;          // the image holds no absolute address: the same context saves to the same bytes
-          memcpy(img.data() + blob0 + pos, &off, 8);
+          const Range* s = visit(a, pf.use);
+          if (!s) {
+            snprintf(msg, sizeof(msg), "es_ctx_save: op kind %d holds a device pointer %#llx outside every segment - it cannot be relocated", op.kind, a);
+            return refuse(msg);
+          }
+          rel[which].push_back({pos, s, a - s->addr});
         }
     }
-    if (!wr(img.data(), img.size())) return fail("es_ctx_save: write failed");
-    const unsigned long long nrel = rel.size() / 2;
-    if (!wr(&nrel, 8) || (nrel && !wr(rel.data(), rel.size() * 8))) return fail("es_ctx_save: write failed");
   }
-  for (int slot = 0; slot < ES_BUF_COUNT; ++slot) {
-    long long r[2] = {-1, 0};
-    if (c->buf[slot]) {
-      if (!inside((unsigned long long)c->buf[slot], c->bytes[slot])) return fail("es_ctx_save: a bound slot lies outside the context's arena");
-      r[0] = (long long)((unsigned long long)c->buf[slot] - base); r[1] = (long long)c->bytes[slot];
+  Reloc slot[ES_BUF_COUNT] = {};
+  for (int i = 0; i < ES_BUF_COUNT; ++i) {
+    if (!c->buf[i]) continue;
+    const u64 a = (u64)c->buf[i];
+    const Range* s = visit(a, 2);                          // filled by the host entry points at run time
+    if (!s || c->bytes[i] > s->bytes - (a - s->addr)) {
+      snprintf(msg, sizeof(msg), "es_ctx_save: bound slot %d (%#llx, %zu bytes) lies outside every segment", i, a, c->bytes[i]);
+      return refuse(msg);
     }
-    if (!wr(r, 16)) return fail("es_ctx_save: write failed");
+    slot[i] = {0, s, a - s->addr};
   }
-  const unsigned long long n_ext = c->extents.size();
-  if (!wr(&n_ext, 8)) return fail("es_ctx_save: write failed");
-  for (const auto& e : c->extents) { const unsigned long long r[2] = {e.first, e.second}; if (!wr(r, 16)) return fail("es_ctx_save: write failed"); }
-  if (hipSetDevice(c->device) != hipSuccess) return fail("es_ctx_save: hipSetDevice failed");
-  std::vector<char> buf(64u << 20);
-  for (const auto& e : c->extents)
-    for (unsigned long long done = 0; done < e.second;) {
-      const size_t n = (size_t)std::min<unsigned long long>(e.second - done, buf.size());
-      if (hipMemcpy(buf.data(), (const char*)c->arena + e.first + done, n, hipMemcpyDeviceToHost) != hipSuccess) return fail("es_ctx_save: copy from the device failed");
-      if (!wr(buf.data(), n)) return fail("es_ctx_save: write failed");
-      done += n;
+  // what travels as bytes: blocks that are only ever read, and small ones in any case (tables / flags a few KB large); without
+  // a block table, what the context's builder recorded as persistent data of its arena
+  std::vector<Extent> ext;
+  if (blk_in) {
+    for (const auto& b : blks) {
+      if (!b.use || ((b.use & 2) && b.bytes > (64u << 10))) continue;
+      const Range* s = locate(segs, b.addr);
+      if (!s || b.bytes > s->bytes - (b.addr - s->addr)) return refuse("es_ctx_save: a referenced block does not lie inside one segment");
+      ext.push_back({b.addr, s, b.addr - s->addr, b.bytes});
     }
-  if (fclose(f) != 0) { es_set_error("es_ctx_save: write failed"); (void)remove(tmp.c_str()); return -1; }
-  if (rename(tmp.c_str(), path) != 0) { es_set_error("es_ctx_save: cannot rename the finished image to its final name"); (void)remove(tmp.c_str()); return -1; }
+  } else {
+    for (const auto& e : c->extents) {
+      const u64 a = (u64)c->arena + e.first;
+      const Range* s = visit(a, 0);
+      if (!s || e.second > s->bytes - (a - s->addr)) return refuse("es_ctx_save: a data extent of the context lies outside every segment");
+      ext.push_back({a, s, a - s->addr, e.second});
+    }
+  }
+  ImageHeader h = {};
+  memcpy(h.magic, IMAGE_MAGIC, 8);
+  h.abi = ES_ABI_VERSION;
+  for (auto& s : segs)
+    if (s.off != UNUSED) { s.off = h.arena_bytes; h.arena_bytes += (s.bytes + 255) & ~255ull; ++h.n_blocks; }
+  u64 data_bytes = 0;
+  for (const auto& e : ext) data_bytes += e.bytes;
+  if (info) {
+    *info = {};
+    info->arena_bytes = h.arena_bytes; info->data_bytes = data_bytes;
+    info->segments = (int32_t)h.n_blocks; info->extents = (int32_t)ext.size();
+    for (int which = 0; which < ES_PLAN_COUNT; ++which) info->relocations[which] = (int32_t)rel[which].size();
+  }
+  if (!path) return 0;
+  // -- phase 2: write, under a temporary name that is renamed on success: a failure (a failed device copy, a full disk) never
+  // leaves a truncated image under the final name
+  const std::string tmp = std::string(path) + ".tmp";
+  FILE* f = fopen(tmp.c_str(), "wb");
+  if (!f) return refuse("es_ctx_save: cannot open the file");
+  auto fail = [&](const char* m) { es_set_error(m); fclose(f); (void)remove(tmp.c_str()); return -1; };
+  auto wr = [&](const void* p, size_t n) { return fwrite(p, 1, n, f) == n; };
+  auto wr2 = [&](u64 a, u64 b) { const u64 r[2] = {a, b}; return wr(r, 16); };
+  const char* const werr = "es_ctx_save: write failed";
+  ImageOptions o;
+  memcpy(o.cond_scales, c->cond_scales, sizeof(o.cond_scales));
+  o.start = c->control_start; o.end = c->control_end; o.use_graphs = c->use_graphs; o.n_alphas = (unsigned)c->alphas_cumprod.size();
+  o.scheduler = c->scheduler; o.n_alphas_f64 = (unsigned)c->alphas_cumprod_f64.size();
+  if (!wr(&h, sizeof(h)) || !wr(&c->g, sizeof(c->g)) || !wr(&o, sizeof(o))) return fail(werr);
+  if (o.n_alphas && !wr(c->alphas_cumprod.data(), o.n_alphas * sizeof(float))) return fail(werr);
+  const unsigned zero4 = 0;
+  if ((o.n_alphas & 1) && !wr(&zero4, 4)) return fail(werr);
+  if (o.n_alphas_f64 && !wr(c->alphas_cumprod_f64.data(), o.n_alphas_f64 * sizeof(double))) return fail(werr);
+  for (const auto& s : segs) if (s.off != UNUSED && !wr2(s.off, s.bytes)) return fail(werr);
+  for (int which = 0; which < ES_PLAN_COUNT; ++which) {
+    const u64 pb = img[which].size();
+    if (!wr(&pb, 8)) return fail(werr);
+    if (!pb) continue;
+    const size_t blob0 = 16 + c->plan[which]->ops.size() * 24;
+    for (const auto& r : rel[which]) {                     // the image holds no absolute address: the same context saves to the same bytes
+      const u64 off = r.seg->off + r.delta;
+      memcpy(img[which].data() + blob0 + r.pos, &off, 8);
+    }
+    const u64 nrel = rel[which].size();
+    if (!wr(img[which].data(), img[which].size()) || !wr(&nrel, 8)) return fail(werr);
+    for (const auto& r : rel[which]) if (!wr2(r.pos, r.seg->off + r.delta)) return fail(werr);
+  }
+  for (int i = 0; i < ES_BUF_COUNT; ++i)
+    if (!(slot[i].seg ? wr2(slot[i].seg->off + slot[i].delta, c->bytes[i]) : wr2((u64)-1ll, 0))) return fail(werr);
+  const u64 n_ext = ext.size();
+  if (!wr(&n_ext, 8)) return fail(werr);
+  for (const auto& e : ext) if (!wr2(e.seg->off + e.delta, e.bytes)) return fail(werr);
+  if (data_bytes) {                                        // through a bounded staging buffer
+    if (hipSetDevice(c->device) != hipSuccess) return fail("es_ctx_save: hipSetDevice failed");
+    std::vector<char> buf(64u << 20);
+    for (const auto& e : ext)
+      for (u64 done = 0; done < e.bytes;) {
+        const size_t n = (size_t)std::min<u64>(e.bytes - done, buf.size());
+        if (hipMemcpy(buf.data(), (const void*)(e.src + done), n, hipMemcpyDeviceToHost) != hipSuccess) return fail("es_ctx_save: copy from the device failed");
+        if (!wr(buf.data(), n)) return fail(werr);
+        done += n;
+      }
+  }
+  if (fclose(f) != 0) { (void)remove(tmp.c_str()); return refuse(werr); }
+  if (rename(tmp.c_str(), path) != 0) { (void)remove(tmp.c_str()); return refuse("es_ctx_save: cannot rename the finished image to its final name"); }
   return 0;
+}
+}  // namespace
+
+extern "C" int es_ctx_save(const es_ctx* c, const char* path) {
+  if (!c || !path) { es_set_error("es_ctx_save: null argument"); return -1; }
+  if (!c->arena || c->arena_on_host) { es_set_error("es_ctx_save: the context does not own a device arena (built by a Python host: use es_ctx_save_ranges)"); return -1; }
+  const es_mem_range arena = {(uint64_t)c->arena, c->arena_bytes};
+  return write_image(c, path, &arena, 1, nullptr, 0, nullptr);
+}
+extern "C" int es_ctx_save_ranges(const es_ctx* c, const char* path, const es_mem_range* segments, int n_segments,
+                                  const es_mem_range* blocks, int n_blocks, es_ctx_image_info* info) {
+  if (!c || n_segments < 0 || (n_segments && !segments) || n_blocks < 0) { es_set_error("es_ctx_save_ranges: bad arguments"); return -1; }
+  if (!c->launchable) { es_set_error("es_ctx_save_ranges: an inspection build (es_load_weights device -1 / -2) holds no device memory to save"); return -1; }
+  return write_image(c, path, segments, n_segments, blocks, n_blocks, info);
 }
 
 extern "C" int es_ctx_plan_size(const es_ctx* c, int which) {

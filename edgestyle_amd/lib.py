@@ -66,6 +66,15 @@ SCHED_DDIM, SCHED_UNIPC = 0, 1
 OP_CONV_GEMM, OP_LINEAR_XS, OP_ATTENTION = 1, 2, 3      # csrc/plan.h es_op_kind (es_plan_count)
 
 
+class MemRange(C.Structure):        # es_mem_range
+    _fields_ = [("addr", C.c_uint64), ("bytes", C.c_uint64)]
+
+
+class CtxImageInfo(C.Structure):    # es_ctx_image_info
+    _fields_ = [("arena_bytes", C.c_uint64), ("data_bytes", C.c_uint64), ("segments", C.c_int32), ("extents", C.c_int32),
+                ("relocations", C.c_int32 * PLAN_COUNT)]
+
+
 class AttnDesc(C.Structure):
     _fields_ = [
         ("q", C.c_void_p), ("k", C.c_void_p), ("v", C.c_void_p), ("o", C.c_void_p),
@@ -278,6 +287,7 @@ SYMBOLS = {
     "es_ctx_plan": (_P, [_P, _I]),
     "es_ctx_load": (C.c_int, [C.c_char_p, _I, C.POINTER(_P)]),
     "es_ctx_save": (C.c_int, [_P, C.c_char_p]),
+    "es_ctx_save_ranges": (C.c_int, [_P, C.c_char_p, C.POINTER(MemRange), _I, C.POINTER(MemRange), _I, C.POINTER(CtxImageInfo)]),
     "es_plan_export": (C.c_size_t, [_P, _P, C.c_size_t]),
     "es_plan_import": (_P, [_P, C.c_size_t]),
     "es_plan_pointer_fields": (C.c_int, [_I, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _I, C.POINTER(C.c_int32)]),

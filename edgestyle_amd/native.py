@@ -7,13 +7,16 @@ es_denoise_loop (== the loop of model/edgestyle_pipeline.py:435-543) and es_vae_
 launch lists (es_plan) against static device buffers.  Something has to build those once: pack the weights, allocate the
 buffers and walk the model while the plans record.  That is this module; it is the only part that needs Python.  After
 `NativeEngine(...)` returns, `engine.ctx` is a plain `es_ctx*` that any host can drive with raw device pointers
-(INTEGRATION.md shows the C calls); the methods below do exactly that through ctypes and nothing else.
+(INTEGRATION.md shows the C calls); the methods of _Context, which both classes share, do exactly that through ctypes and
+nothing else.
 
 The recorded pointers live in torch's graph-private memory pools (every plan is recorded inside a `torch.cuda.graph`
 capture, which is also what keeps the activations of a plan from being handed to anybody else); the engine keeps those
-graphs alive for as long as the context exists.
+graphs alive for as long as the context exists.  A context image of such a context is written by the library
+(es_ctx_save_ranges): NativeEngine.save only tells it where torch's allocator keeps that memory.
 """
 import ctypes as C
+import struct
 from typing import Optional, Sequence
 
 import torch
@@ -28,26 +31,107 @@ def _p(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
-def _prepare_conds_u8(self, images, normalize, noise, nn: int, B: int, R: int, device):
-    """es_prepare_conds_u8 for either context class: images is nn x B uint8 HWC device tensors (net-major: a flat list, or one
-    list per net; any sizes), normalize one flag per net, noise per net None or device fp32 [N,L,h,w]."""
-    if len(images) == nn and not torch.is_tensor(images[0]):
-        images = [im for per_net in images for im in per_net]
-    if len(images) != nn * B:
-        raise EdgeStyleHipError(f"prepare_conds_u8: {nn} nets x batch {B} = {nn * B} images, got {len(images)}")
-    if len(normalize) != nn:
-        raise EdgeStyleHipError(f"prepare_conds_u8: one normalize flag per net ({nn}), got {len(normalize)}")
-    descs = ops.image_descriptors(images, "prepare_conds_u8")
-    need = ops.image_resize_workspace_bytes(descs, R)
-    ws = torch.empty((max(need, 1),), dtype=torch.uint8, device=device)
-    nz = [None if (noise is None or noise[i] is None) else noise[i].to(device, torch.float32).contiguous() for i in range(nn)]
-    npz = (C.c_void_p * nn)(*[None if z is None else z.data_ptr() for z in nz])
-    nrm = (C.c_int32 * nn)(*[1 if f else 0 for f in normalize])
-    L.check(self.lib.es_prepare_conds_u8(self.ctx, descs, nrm, npz, _p(ws), ws.numel(), self._stream()), "es_prepare_conds_u8")
-    self._live = (list(images), nz, ws)       # asynchronous: keep the sources and the scratch until the next call
+class _Context:
+    """What both builders end up with: an `es_ctx*` (self.ctx, of self.lib) and its geometry - B images per call, N = B or 2B
+    samples, T steps, latent h x w, nn condition slots, the compute dtype, out_channels of the noise prediction and the
+    (H, W) of an image.  The methods are thin ctypes drivers of the step-level entry points: raw device pointers in, raw
+    device pointers out, and what the library refuses surfaces as EdgeStyleHipError with its text."""
+
+    def set_options(self, cond_scales: Optional[Sequence[float]] = None, control_guidance_start: float = 0.0,
+                    control_guidance_end: float = 1.0, use_graphs=True):
+        """use_graphs: False = launch by launch, True = one hipGraph per plan, 2 = the whole loop as one hipGraph."""
+        arr = None if cond_scales is None else (C.c_float * 6)(*([float(s) for s in cond_scales] + [1.0] * (6 - len(cond_scales))))
+        L.check(self.lib.es_ctx_set_options(self.ctx, arr, control_guidance_start, control_guidance_end, int(use_graphs)),
+                "es_ctx_set_options")
+
+    def set_scheduler(self, scheduler: int):
+        """L.SCHED_DDIM | L.SCHED_UNIPC (UniPCMultistepScheduler with the SD1.5 config, TT:273): the update es_denoise_loop
+        applies (the recorded step list is the same)."""
+        L.check(self.lib.es_ctx_set_scheduler(self.ctx, int(scheduler)), "es_ctx_set_scheduler")
+
+    def set_alphas_cumprod(self, alphas_cumprod):
+        """The scheduler's schedule (default: the library's own SD1.5 table, which equals torch's cumprod to 1e-6 only - hand
+        over the scheduler's tensor where the DDIM coefficients must match a Python host's bit for bit)."""
+        ac = alphas_cumprod.float().contiguous()
+        L.check(self.lib.es_ctx_set_alphas_cumprod(self.ctx, ac.numpy().ctypes.data_as(C.POINTER(C.c_float)), ac.numel()),
+                "es_ctx_set_alphas_cumprod")
+
+    @staticmethod
+    def _stream():
+        return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def denoise_step(self, sample, t: float, ehs, cond_embeds, scales=None, out=None):
+        """sample [N,h,w,latent_pad], ehs [N,77,D], cond_embeds nn x [N,h,w,C0] (compute dtype, contiguous, device) -> [N,h,w,4]"""
+        if out is None:
+            out = torch.empty((self.N, self.h, self.w, self.out_channels), dtype=self.dtype, device=sample.device)
+        ptrs = (C.c_void_p * len(cond_embeds))(*[c.data_ptr() for c in cond_embeds])
+        sc = None if scales is None else (C.c_float * 6)(*([float(s) for s in scales] + [1.0] * (6 - len(scales))))
+        L.check(self.lib.es_denoise_step(self.ctx, _p(sample), float(t), _p(ehs), ptrs, sc, _p(out), self._stream()), "es_denoise_step")
+        return out
+
+    def prepare_conds(self, images, noise=None):
+        """images: nn x device fp32 [B,3,H,W]; noise: per slot None or device fp32 [N,L,h,w] (VAE-conditioned nets need it)"""
+        imgs = [im.contiguous() for im in images]
+        nz = [None if (noise is None or noise[i] is None) else noise[i].contiguous() for i in range(len(imgs))]
+        ip = (C.c_void_p * len(imgs))(*[im.data_ptr() for im in imgs])
+        npz = (C.c_void_p * len(imgs))(*[None if z is None else z.data_ptr() for z in nz])
+        L.check(self.lib.es_prepare_conds(self.ctx, ip, npz, self._stream()), "es_prepare_conds")
+        self._live = (imgs, nz)               # the copies are asynchronous: keep the sources until the next call
+
+    def prepare_conds_u8(self, images, normalize: Sequence[bool], noise=None):
+        """prepare_conds from decoded photos: nn x B uint8 HWC device tensors of any sizes (net-major: a flat list, or one list
+        per net), resized, cropped and converted on the device (TT:29-48); normalize[i]: net i takes [-1,1] (the VAE-conditioned
+        nets); noise as in prepare_conds."""
+        nn, B = self.nn, self.B
+        if len(images) == nn and not torch.is_tensor(images[0]):
+            images = [im for per_net in images for im in per_net]
+        if len(images) != nn * B:
+            raise EdgeStyleHipError(f"prepare_conds_u8: {nn} nets x batch {B} = {nn * B} images, got {len(images)}")
+        if len(normalize) != nn:
+            raise EdgeStyleHipError(f"prepare_conds_u8: one normalize flag per net ({nn}), got {len(normalize)}")
+        descs = ops.image_descriptors(images, "prepare_conds_u8")
+        device = images[0].device
+        need = ops.image_resize_workspace_bytes(descs, self.image_size[0])
+        ws = torch.empty((max(need, 1),), dtype=torch.uint8, device=device)
+        nz = [None if (noise is None or noise[i] is None) else noise[i].to(device, torch.float32).contiguous() for i in range(nn)]
+        npz = (C.c_void_p * nn)(*[None if z is None else z.data_ptr() for z in nz])
+        nrm = (C.c_int32 * nn)(*[1 if f else 0 for f in normalize])
+        L.check(self.lib.es_prepare_conds_u8(self.ctx, descs, nrm, npz, _p(ws), ws.numel(), self._stream()), "es_prepare_conds_u8")
+        self._live = (list(images), nz, ws)       # asynchronous: keep the sources and the scratch until the next call
+
+    def denoise_loop(self, latents, ehs, guidance_scale: float, timesteps):
+        """latents fp32 [B,h,w,L] NHWC device (updated in place and returned); ehs [N,77,D] dtype; timesteps: host list"""
+        ts = (C.c_float * len(timesteps))(*[float(t) for t in timesteps])
+        L.check(self.lib.es_denoise_loop(self.ctx, _p(latents), _p(ehs), float(guidance_scale), ts, len(timesteps), self._stream()),
+                "es_denoise_loop")
+        return latents
+
+    def vae_decode(self, latents, out=None):
+        if out is None:
+            out = torch.empty((self.B, 3) + self.image_size, dtype=torch.float32, device=latents.device)
+        L.check(self.lib.es_vae_decode(self.ctx, _p(latents), _p(out), self._stream()), "es_vae_decode")
+        return out
+
+    def vae_decode_u8(self, latents, out=None):
+        """vae_decode with the bytes of output_type "pil" as the result: uint8 [B,H,W,3] on the device."""
+        if out is None:
+            out = torch.empty((self.B,) + self.image_size + (3,), dtype=torch.uint8, device=latents.device)
+        L.check(self.lib.es_vae_decode_u8(self.ctx, _p(latents), _p(out), self._stream()), "es_vae_decode_u8")
+        return out
+
+    def close(self):
+        if getattr(self, "ctx", None):
+            self.lib.es_ctx_destroy(self.ctx)
+            self.ctx = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
-class NativeEngine:
+class NativeEngine(_Context):
     def __init__(self, pipe, batch_size: int = 1, guidance: bool = True, num_inference_steps: int = 50,
                  height: Optional[int] = None, width: Optional[int] = None, use_graphs: bool = True,
                  embed_conditions: bool = True, guess_mode: bool = False):
@@ -57,7 +141,6 @@ class NativeEngine:
         if not isinstance(pipe.scheduler, DDIMScheduler):
             raise EdgeStyleHipError("the native loop implements the DDIM update (the BASELINE metric's scheduler)")
         self.pipe, self.lib = pipe, L.load()
-        self._cond_scales = [1.0] * 6
         dev = pipe.device
         ucfg, vcfg = pipe.unet.cfg, pipe.vae.cfg
         h = (height // vcfg.scale) if height else ucfg.sample_size
@@ -84,7 +167,7 @@ class NativeEngine:
         self._coef[:T * 4].copy_(loop.coef.reshape(-1))
         loop.coef = self._coef[:T * 4].view(T, 4)
         self.B, self.N, self.T, self.h, self.w, self.nn = B, N, T, h, w, nn
-        self.dtype = pipe.dtype
+        self.dtype, self.out_channels, self.image_size = pipe.dtype, ucfg.out_channels, (h * vcfg.scale, w * vcfg.scale)
         self.ts_dev = torch.zeros((T,), dtype=torch.float32, device=dev)
         self.ts_dev.copy_(pipe.scheduler.set_timesteps(T).float())
         grouped_tables = runner.mode == "grouped" and not guess
@@ -123,7 +206,6 @@ class NativeEngine:
                             latent_pad=pipe.unet.engine.in_pad, n_conds=nn, n_steps=T, dtype=L.ES_F16 if self.dtype == torch.float16 else L.ES_BF16,
                             guess_mode=int(guess))
         L.check(self.lib.es_ctx_set_geometry(ctx, C.byref(geo)), "es_ctx_set_geometry")
-        self._geo = geo
         self.plan_sizes = {}
         todo = [(L.PLAN_PREP, prep), (L.PLAN_STEP, loop.one_step), (L.PLAN_STEP_GENERIC, generic), (L.PLAN_DECODE, decode)]
         if conds_fn is not None:
@@ -159,12 +241,9 @@ class NativeEngine:
                 binds[L.BUF_COND_IMG0 + i] = self.cond_img[i]
                 if self.cond_noise[i] is not None:
                     binds[L.BUF_COND_NOISE0 + i] = self.cond_noise[i]
-        self._binds = binds
         for slot, t in binds.items():
             L.check(self.lib.es_ctx_bind(ctx, slot, _p(t), t.numel() * t.element_size()), "es_ctx_bind")
-        ac = pipe.scheduler.alphas_cumprod.float().contiguous()
-        L.check(self.lib.es_ctx_set_alphas_cumprod(ctx, ac.numpy().ctypes.data_as(C.POINTER(C.c_float)), ac.numel()),
-                "es_ctx_set_alphas_cumprod")
+        self.set_alphas_cumprod(pipe.scheduler.alphas_cumprod)
         self.set_options(use_graphs=use_graphs)
         # The recorded plans hold raw pointers into this loop's static buffers and StepState tensors (time-projection table,
         # batch-concatenated conditions, text K/V projections): the loop becomes PRIVATE to the engine.  It leaves the
@@ -247,40 +326,14 @@ class NativeEngine:
                             ops.memcpy(loop.conds[i][B:], e)
         return fn
 
-    # -- thin ctypes drivers: raw device pointers in, raw device pointers out ------------------------------------------
-    def set_options(self, cond_scales: Optional[Sequence[float]] = None, control_guidance_start: float = 0.0,
-                    control_guidance_end: float = 1.0, use_graphs=True):
-        """use_graphs: False = launch by launch, True = one hipGraph per plan, 2 = the whole loop as one hipGraph."""
-        arr = None
-        if cond_scales is not None:
-            arr = (C.c_float * 6)(*([float(s) for s in cond_scales] + [1.0] * (6 - len(cond_scales))))
-            self._cond_scales = list(arr)
-        self._cg, self._use_graphs = (float(control_guidance_start), float(control_guidance_end)), int(use_graphs)
-        L.check(self.lib.es_ctx_set_options(self.ctx, arr, control_guidance_start, control_guidance_end, int(use_graphs)),
-                "es_ctx_set_options")
-
-    def set_scheduler(self, scheduler: int):
-        """L.SCHED_DDIM | L.SCHED_UNIPC: the update es_denoise_loop applies (the recorded step list is the same)."""
-        L.check(self.lib.es_ctx_set_scheduler(self.ctx, int(scheduler)), "es_ctx_set_scheduler")
-        self._scheduler = int(scheduler)
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
+    # -- the drivers of _Context, behind the checks this host can make: it holds the tensors the plans were recorded on ----------
     def denoise_step(self, sample: torch.Tensor, t: float, ehs: torch.Tensor, cond_embeds: Sequence[torch.Tensor],
                      scales: Optional[Sequence[float]] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """sample [N,h,w,latent_pad] dtype NHWC, ehs [N,77,D] dtype, cond_embeds n x [N,h,w,C0] dtype -> noise [N,h,w,4]."""
         loop = self.loop
         for a, b in [(sample, loop.model_in), (ehs, loop.ehs)] + list(zip(cond_embeds, loop.conds)):
             if a.shape != b.shape or a.dtype != b.dtype or not a.is_contiguous() or not a.is_cuda:
                 raise EdgeStyleHipError(f"denoise_step: expected a contiguous device tensor {tuple(b.shape)} {b.dtype}")
-        if out is None:
-            out = torch.empty_like(loop.noise)
-        ptrs = (C.c_void_p * len(cond_embeds))(*[c.data_ptr() for c in cond_embeds])
-        sc = None if scales is None else (C.c_float * 6)(*([float(s) for s in scales] + [1.0] * (6 - len(scales))))
-        L.check(self.lib.es_denoise_step(self.ctx, _p(sample), float(t), _p(ehs), ptrs, sc, _p(out), self._stream()),
-                "es_denoise_step")
-        return out
+        return super().denoise_step(sample, t, ehs, cond_embeds, scales, out)
 
     def set_conds(self, cond_embeds: Sequence[torch.Tensor]):
         """The loop reads the condition embeddings last placed in the context's slots."""
@@ -289,70 +342,39 @@ class NativeEngine:
 
     def denoise_loop(self, latents: torch.Tensor, ehs: torch.Tensor, guidance_scale: float,
                      timesteps: Optional[Sequence[float]] = None) -> torch.Tensor:
-        """latents fp32 [B,h,w,L] NHWC (updated in place and returned); ehs [N,77,D] dtype."""
         if timesteps is None:
             timesteps = self.pipe.scheduler.set_timesteps(self.T).tolist()
-        ts = (C.c_float * len(timesteps))(*[float(t) for t in timesteps])
         if latents.shape != self.loop.latents.shape or latents.dtype != torch.float32 or not latents.is_contiguous():
             raise EdgeStyleHipError(f"denoise_loop: latents must be fp32 contiguous {tuple(self.loop.latents.shape)}")
-        L.check(self.lib.es_denoise_loop(self.ctx, _p(latents), _p(ehs.contiguous()), float(guidance_scale), ts, len(timesteps),
-                                         self._stream()), "es_denoise_loop")
-        return latents
+        return super().denoise_loop(latents, ehs.contiguous(), guidance_scale, timesteps)
 
-    def prepare_conds(self, images: Sequence[torch.Tensor], noise: Optional[Sequence[Optional[torch.Tensor]]] = None):
-        """images: n x device fp32 [B,3,H,W]; noise: per net None or device fp32 [N,L,h,w] (VAE-conditioned nets need it)."""
+    def _need_conds_plan(self):
         if L.PLAN_CONDS not in self.plan_sizes:
             raise EdgeStyleHipError("this context was built without ES_PLAN_CONDS")
-        imgs = [im.to(self.pipe.device, torch.float32).contiguous() for im in images]
-        nz = [None if (noise is None or noise[i] is None) else noise[i].to(self.pipe.device, torch.float32).contiguous()
-              for i in range(len(imgs))]
+
+    def prepare_conds(self, images: Sequence[torch.Tensor], noise: Optional[Sequence[Optional[torch.Tensor]]] = None):
+        self._need_conds_plan()
+        imgs = [im.to(self.pipe.device, torch.float32) for im in images]
+        nz = [None if (noise is None or noise[i] is None) else noise[i].to(self.pipe.device, torch.float32) for i in range(len(imgs))]
         for i, im in enumerate(imgs):
             if im.shape != self.cond_img[i].shape:
                 raise EdgeStyleHipError(f"prepare_conds: image {i} must be {tuple(self.cond_img[i].shape)}")
             if nz[i] is not None and self.cond_noise[i] is not None and nz[i].shape != self.cond_noise[i].shape:
                 raise EdgeStyleHipError(f"prepare_conds: noise {i} must be {tuple(self.cond_noise[i].shape)}")
-        ip = (C.c_void_p * len(imgs))(*[im.data_ptr() for im in imgs])
-        npz = (C.c_void_p * len(imgs))(*[None if z is None else z.data_ptr() for z in nz])
-        L.check(self.lib.es_prepare_conds(self.ctx, ip, npz, self._stream()), "es_prepare_conds")
-        self._live = (imgs, nz)               # the copies are asynchronous: keep the sources until the next call
+        super().prepare_conds(imgs, nz)
 
     def prepare_conds_u8(self, images, normalize: Sequence[bool], noise: Optional[Sequence[Optional[torch.Tensor]]] = None):
-        """prepare_conds from decoded photos: n x B uint8 HWC device tensors of any sizes (net-major), resized, cropped and
-        converted on the device (TT:29-48); normalize[i]: net i takes [-1,1] (the VAE-conditioned nets)."""
-        if L.PLAN_CONDS not in self.plan_sizes:
-            raise EdgeStyleHipError("this context was built without ES_PLAN_CONDS")
-        _prepare_conds_u8(self, images, normalize, noise, self.nn, self.B, self.cond_img[0].shape[-1], self.pipe.device)
-
-    def vae_decode(self, latents: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        if out is None:
-            out = torch.empty_like(self.image)
-        L.check(self.lib.es_vae_decode(self.ctx, _p(latents), _p(out), self._stream()), "es_vae_decode")
-        return out
-
-    def vae_decode_u8(self, latents: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """vae_decode with the bytes of output_type "pil" as the result: uint8 [B,H,W,3] on the device."""
-        if out is None:
-            B, _, H, W = self.image.shape
-            out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=self.image.device)
-        L.check(self.lib.es_vae_decode_u8(self.ctx, _p(latents), _p(out), self._stream()), "es_vae_decode_u8")
-        return out
+        self._need_conds_plan()
+        super().prepare_conds_u8(images, normalize, noise)
 
     # -- context image: everything es_ctx_load needs to run this context without Python ---------------------------------
     def save(self, path: str) -> dict:
-        """Write a context image for es_ctx_load (include/edgestyle_hip.h).
-
-        Relocation is TYPED: the library names the pointer fields of every recorded call (es_plan_pointer_fields) and exactly
-        those 8-byte words are rewritten as offsets into one arena; a non-null pointer that is not inside a live allocator
-        segment of this device is an error here, not a fault at load time.  The arena keeps the layout of every referenced
-        allocator segment (an activation freed during a capture is an inactive block the captured kernels still write, and
-        may straddle today's block boundaries), but only memory that the plans READ and never WRITE - packed weights, norm
-        and fusion parameters, tables built at load time - is stored in the file; everything some call writes (activations,
-        split-K slabs, scratch, static input slots) is produced at run time and travels as zero-filled space."""
-        import struct
-        import numpy as np
+        """Write a context image for es_ctx_load (include/edgestyle_hip.h).  The library writes it (es_ctx_save_ranges: typed
+        relocation into one arena that keeps the layout of every referenced allocator segment; only memory that the plans
+        read and never write travels as data).  What only this host knows is where torch's allocator keeps the memory the
+        recorded pointers refer to: its segments, and the blocks inside them - an activation freed during a capture is an
+        inactive block the captured kernels still write."""
         torch.cuda.synchronize()
-        hip = C.CDLL("libamdhip64.so")
-        hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
         dev_index = self.pipe.device.index or 0
         segs, blks = [], []
         for seg in torch.cuda.memory_snapshot():
@@ -363,154 +385,15 @@ class NativeEngine:
             for bk in seg.get("blocks", []):
                 blks.append((bk.get("address", a), bk["size"]))
                 a = bk.get("address", a) + bk["size"]
-        segs.sort()
-        blks.sort()
-        starts = np.array([a for a, _ in segs], dtype=np.uint64)
-        ends = starts + np.array([n for _, n in segs], dtype=np.uint64)
-        bstarts = np.array([a for a, _ in blks], dtype=np.uint64)
-        bends = bstarts + np.array([n for _, n in blks], dtype=np.uint64)
-
-        def locate(addrs, st, en):
-            idx = np.searchsorted(st, addrs, side="right").astype(np.int64) - 1
-            ok = (idx >= 0) & (addrs < en[np.clip(idx, 0, len(en) - 1)])
-            return np.where(ok, idx, -1)
-
-        # pointer-field tables of the library, by op kind
-        fields = {}
-
-        def fields_of(kind):
-            if kind not in fields:
-                offs, uses = (C.c_int32 * 64)(), (C.c_int32 * 64)()
-                elem = C.c_int32(0)
-                n = self.lib.es_plan_pointer_fields(kind, offs, uses, 64, C.byref(elem))
-                if n > 64:
-                    raise EdgeStyleHipError("save: pointer-field table overflow")
-                fields[kind] = ([(offs[i], uses[i]) for i in range(n)], elem.value)
-            return fields[kind]
-
-        plans, used = {}, set()
-        blk_use = {}                                   # block index -> OR of the uses of every pointer into it
-        for which in range(L.PLAN_COUNT):
-            pl = self.lib.es_ctx_plan(self.ctx, which)
-            if not pl:
-                continue
-            n = self.lib.es_plan_export(pl, None, 0)
-            raw = (C.c_char * n)()
-            self.lib.es_plan_export(pl, raw, n)
-            img = np.frombuffer(raw, dtype=np.uint8).copy()
-            n_ops = int(img[:8].view(np.uint64)[0])
-            table = img[16:16 + 24 * n_ops].view(np.uint64).reshape(n_ops, 3)
-            blob0 = 16 + 24 * n_ops
-            rel = []
-            for kind, off, nbytes in table.tolist():
-                kind = int(np.int64(kind))
-                fl, elem = fields_of(kind)
-                if not fl:
-                    continue
-                reps = max(1, nbytes // elem) if elem else 1
-                for r in range(reps):
-                    for fo, use in fl:
-                        pos = int(off) + r * elem + fo
-                        if pos + 8 > int(off) + int(nbytes):
-                            raise EdgeStyleHipError("save: a pointer field lies outside its record (ABI mismatch)")
-                        addr = int(img[blob0 + pos:blob0 + pos + 8].view(np.uint64)[0])
-                        if addr == 0:
-                            continue
-                        a1 = np.array([addr], dtype=np.uint64)
-                        si = int(locate(a1, starts, ends)[0])
-                        if si < 0:
-                            raise EdgeStyleHipError(f"save: op kind {kind} holds a device pointer {addr:#x} outside every allocator "
-                                                    "segment of this device - it cannot be relocated")
-                        rel.append((pos, si, addr - int(starts[si])))
-                        used.add(si)
-                        bi = int(locate(a1, bstarts, bends)[0])
-                        if bi >= 0:
-                            blk_use[bi] = blk_use.get(bi, 0) | use
-            plans[which] = (img, rel)
-        binds = {}
-        for slot, t in self._binds.items():
-            a1 = np.array([t.data_ptr()], dtype=np.uint64)
-            si = int(locate(a1, starts, ends)[0])
-            if si < 0:
-                raise EdgeStyleHipError("save: a bound buffer is not a live allocation")
-            used.add(si)
-            binds[slot] = (si, t.data_ptr() - int(starts[si]), t.numel() * t.element_size())
-            bi = int(locate(a1, bstarts, bends)[0])
-            if bi >= 0:
-                blk_use[bi] = blk_use.get(bi, 0) | 2          # filled by the host entry points at run time
-        # arena layout: one slot per referenced segment
-        off, arena = {}, 0
-        for si in sorted(used):
-            off[si] = arena
-            arena += (int(ends[si] - starts[si]) + 255) // 256 * 256
-        # data extents: blocks that are only ever read (small blocks travel in any case: tables / flags a few KB large)
-        extents = []
-        for bi, use in sorted(blk_use.items()):
-            nb = int(bends[bi] - bstarts[bi])
-            if (use & 2) and nb > (64 << 10):
-                continue
-            si = int(locate(np.array([bstarts[bi]], dtype=np.uint64), starts, ends)[0])
-            extents.append((int(bstarts[bi]), off[si] + int(bstarts[bi]) - int(starts[si]), nb))
-        g = self._geo
-        ac = self.pipe.scheduler.alphas_cumprod.float().contiguous().numpy()
-        with open(path, "wb") as f:
-            f.write(b"ESCTX\x03\x00\x00" + struct.pack("<IIQ", L.ABI_VERSION, len(used), arena))
-            f.write(bytes(g))
-            # options record of format 3: + the scheduler es_denoise_loop applies and the length of an f64 schedule (none from
-            # this host: a loaded UniPC context derives its sigmas from the library's own SD1.5 table in double, as this one does)
-            f.write(struct.pack("<6fffiIiI", *self._cond_scales, self._cg[0], self._cg[1], int(self._use_graphs), len(ac),
-                                int(getattr(self, "_scheduler", L.SCHED_DDIM)), 0))
-            f.write(ac.tobytes())
-            if len(ac) & 1:
-                f.write(b"\0" * 4)
-            for si in sorted(used):
-                f.write(struct.pack("<QQ", off[si], int(ends[si] - starts[si])))
-            for which in range(L.PLAN_COUNT):
-                if which not in plans:
-                    f.write(struct.pack("<Q", 0))
-                    continue
-                img, rel = plans[which]
-                f.write(struct.pack("<Q", len(img)))
-                f.write(img.tobytes())
-                f.write(struct.pack("<Q", len(rel)))
-                for blob_off, si, o in rel:
-                    f.write(struct.pack("<QQ", blob_off, off[si] + o))
-            nslots = L.BUF_COUNT
-            for slot in range(nslots):
-                if slot in binds:
-                    si, o, nb = binds[slot]
-                    f.write(struct.pack("<qQ", off[si] + o, nb))
-                else:
-                    f.write(struct.pack("<qQ", -1, 0))
-            f.write(struct.pack("<Q", len(extents)))
-            for _, ao, nb in extents:
-                f.write(struct.pack("<QQ", ao, nb))
-            host = np.empty(64 << 20, dtype=np.uint8)
-            data_bytes = 0
-            for src, _, nb in extents:
-                done = 0
-                while done < nb:
-                    n = min(nb - done, host.nbytes)
-                    rc = hip.hipMemcpy(host.ctypes.data, C.c_void_p(src + done), n, 2)
-                    if rc != 0:
-                        raise EdgeStyleHipError(f"save: hipMemcpy failed ({rc})")
-                    f.write(host[:n].tobytes())
-                    done += n
-                data_bytes += nb
-        return dict(blocks=len(used), arena_bytes=arena, data_bytes=data_bytes, extents=len(extents),
-                    relocations={w: len(r) for w, (_, r) in plans.items()})
+        info = L.CtxImageInfo()
+        L.check(self.lib.es_ctx_save_ranges(self.ctx, str(path).encode(), (L.MemRange * len(segs))(*segs), len(segs),
+                                            (L.MemRange * len(blks))(*blks), len(blks), C.byref(info)), "es_ctx_save_ranges")
+        return dict(blocks=info.segments, arena_bytes=info.arena_bytes, data_bytes=info.data_bytes, extents=info.extents,
+                    relocations={w: info.relocations[w] for w in range(L.PLAN_COUNT) if self.lib.es_ctx_plan(self.ctx, w)})
 
     def close(self):
-        if self.ctx:
-            self.lib.es_ctx_destroy(self.ctx)
-            self.ctx = None
-            self._keep.clear()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().close()
+        self._keep.clear()
 
 
 # ======================================================================================================================
@@ -559,7 +442,7 @@ def state_dict_descriptors(sd):
     return L.StateDict(arr, len(sd)), keep
 
 
-class NativeContext:
+class NativeContext(_Context):
     """A context built by es_load_weights (include/edgestyle_hip.h) from state dicts in the reference's key layout, and thin
     ctypes drivers of the step-level entry points on raw device pointers.  Nothing of edgestyle_amd's model code (models.py,
     engine.py, ops.py) is involved: torch only hands over host pointers at build time and device pointers at run time.
@@ -579,6 +462,7 @@ class NativeContext:
         nn = len(net_of_cond)
         self.B, self.N, self.T, self.h, self.w, self.nn = batch_size, batch_size * (2 if guidance else 1), num_inference_steps, h, w, nn
         self.dtype, self.device = dtype, device
+        self.out_channels, self.image_size = ucfg.out_channels, (h * vcfg.scale, w * vcfg.scale)
         wts = L.Weights()
         keep = []
         for name in ("unet", "vae", "fusion"):
@@ -607,110 +491,37 @@ class NativeContext:
     def plan_size(self, which: int) -> int:
         return self.lib.es_ctx_plan_size(self.ctx, which)
 
-    def set_options(self, cond_scales: Optional[Sequence[float]] = None, control_guidance_start: float = 0.0,
-                    control_guidance_end: float = 1.0, use_graphs=True):
-        arr = None if cond_scales is None else (C.c_float * 6)(*([float(s) for s in cond_scales] + [1.0] * (6 - len(cond_scales))))
-        L.check(self.lib.es_ctx_set_options(self.ctx, arr, control_guidance_start, control_guidance_end, int(use_graphs)),
-                "es_ctx_set_options")
 
-    def set_scheduler(self, scheduler: int):
-        """L.SCHED_DDIM | L.SCHED_UNIPC (UniPCMultistepScheduler with the SD1.5 config, TT:273)."""
-        L.check(self.lib.es_ctx_set_scheduler(self.ctx, int(scheduler)), "es_ctx_set_scheduler")
-
-    def set_alphas_cumprod(self, alphas_cumprod):
-        """The scheduler's schedule (default: the library's own SD1.5 table, which equals torch's cumprod to 1e-6 only - hand
-        over the scheduler's tensor where the DDIM coefficients must match a Python host's bit for bit)."""
-        ac = alphas_cumprod.float().contiguous()
-        L.check(self.lib.es_ctx_set_alphas_cumprod(self.ctx, ac.numpy().ctypes.data_as(C.POINTER(C.c_float)), ac.numel()),
-                "es_ctx_set_alphas_cumprod")
-
-    @staticmethod
-    def _stream():
-        return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-    def denoise_step(self, sample, t: float, ehs, cond_embeds, scales=None, out=None):
-        """sample [N,h,w,latent_pad], ehs [N,77,D], cond_embeds 6 x [N,h,w,C0] (compute dtype, contiguous, device) -> [N,h,w,4]"""
-        if out is None:
-            out = torch.empty((self.N, self.h, self.w, self.ucfg.out_channels), dtype=self.dtype, device=sample.device)
-        ptrs = (C.c_void_p * self.nn)(*[c.data_ptr() for c in cond_embeds])
-        sc = None if scales is None else (C.c_float * self.nn)(*[float(s) for s in scales])
-        L.check(self.lib.es_denoise_step(self.ctx, _p(sample), float(t), _p(ehs), ptrs, sc, _p(out), self._stream()), "es_denoise_step")
-        return out
-
-    def prepare_conds(self, images, noise=None):
-        """images: 6 x device fp32 [B,3,H,W]; noise: per slot None or device fp32 [N,L,h,w]"""
-        self._live = ([im.contiguous() for im in images], [None if (noise is None or z is None) else z.contiguous() for z in (noise or [None] * self.nn)])
-        ip = (C.c_void_p * self.nn)(*[im.data_ptr() for im in self._live[0]])
-        npz = (C.c_void_p * self.nn)(*[None if z is None else z.data_ptr() for z in self._live[1]])
-        L.check(self.lib.es_prepare_conds(self.ctx, ip, npz, self._stream()), "es_prepare_conds")
-
-    def denoise_loop(self, latents, ehs, guidance_scale: float, timesteps):
-        """latents fp32 [B,h,w,L] NHWC device (in place); timesteps: host list of length n_steps"""
-        ts = (C.c_float * len(timesteps))(*[float(t) for t in timesteps])
-        L.check(self.lib.es_denoise_loop(self.ctx, _p(latents), _p(ehs), float(guidance_scale), ts, len(timesteps), self._stream()),
-                "es_denoise_loop")
-        return latents
-
-    def vae_decode(self, latents, out=None):
-        if out is None:
-            s = self.vcfg.scale
-            out = torch.empty((self.B, 3, self.h * s, self.w * s), dtype=torch.float32, device=latents.device)
-        L.check(self.lib.es_vae_decode(self.ctx, _p(latents), _p(out), self._stream()), "es_vae_decode")
-        return out
-
-    def prepare_conds_u8(self, images, normalize, noise=None):
-        """images: 6 x B uint8 HWC device tensors of any sizes (net-major); normalize: one flag per slot (the VAE-conditioned
-        nets take [-1,1], TT:29-48); noise as in prepare_conds"""
-        dev = images[0][0].device if not torch.is_tensor(images[0]) else images[0].device
-        _prepare_conds_u8(self, images, normalize, noise, self.nn, self.B, self.h * self.vcfg.scale, dev)
-
-    def vae_decode_u8(self, latents, out=None):
-        if out is None:
-            s = self.vcfg.scale
-            out = torch.empty((self.B, self.h * s, self.w * s, 3), dtype=torch.uint8, device=latents.device)
-        L.check(self.lib.es_vae_decode_u8(self.ctx, _p(latents), _p(out), self._stream()), "es_vae_decode_u8")
-        return out
-
-    def close(self):
-        if getattr(self, "ctx", None):
-            self.lib.es_ctx_destroy(self.ctx)
-            self.ctx = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+def plan_ops(lib, plan):
+    """[(op kind, argument record, [positions of its pointer fields inside the record])] of an es_plan*, array ops expanded:
+    the one reader in Python of an exported plan (es_plan_export: u64 n_ops, u64 blob bytes, n_ops x {i64 kind, u64 offset,
+    u64 bytes}, blob) and of the library's pointer-field tables (es_plan_pointer_fields)."""
+    if not plan:
+        return []
+    n = lib.es_plan_export(plan, None, 0)
+    raw = (C.c_char * n)()
+    lib.es_plan_export(plan, raw, n)
+    img = bytes(raw)
+    blob0 = 16 + 24 * int.from_bytes(img[:8], "little")
+    out, fields = [], {}
+    for kind, off, nbytes in struct.iter_unpack("<qQQ", img[16:blob0]):
+        if kind not in fields:
+            offs, uses, elem = (C.c_int32 * 64)(), (C.c_int32 * 64)(), C.c_int32(0)
+            k = lib.es_plan_pointer_fields(kind, offs, uses, 64, C.byref(elem))
+            fields[kind] = (offs[:k], elem.value)
+        fl, elem = fields[kind]
+        reps = max(1, nbytes // elem) if elem else 1
+        out.append((kind, img[blob0 + off:blob0 + off + nbytes], [r * elem + fo for r in range(reps) for fo in fl]))
+    return out
 
 
 def plan_records(lib, ctx, which: int):
     """[(op kind, argument record with every pointer field replaced by 0 / 1 = null / set)] of one plan of a context: what two
     builders must agree on call by call (the addresses themselves belong to each builder's allocator)."""
-    import numpy as np
-    pl = lib.es_ctx_plan(ctx, which)
-    if not pl:
-        return []
-    n = lib.es_plan_export(pl, None, 0)
-    raw = (C.c_char * n)()
-    lib.es_plan_export(pl, raw, n)
-    img = np.frombuffer(raw, dtype=np.uint8).copy()
-    n_ops = int(img[:8].view(np.uint64)[0])
-    table = img[16:16 + 24 * n_ops].view(np.uint64).reshape(n_ops, 3)
-    blob0 = 16 + 24 * n_ops
-    out, fields = [], {}
-    for kind, off, nbytes in table.tolist():
-        kind = int(np.int64(kind))
-        if kind not in fields:
-            offs, uses, elem = (C.c_int32 * 64)(), (C.c_int32 * 64)(), C.c_int32(0)
-            k = lib.es_plan_pointer_fields(kind, offs, uses, 64, C.byref(elem))
-            fields[kind] = ([offs[i] for i in range(k)], elem.value)
-        fl, elem = fields[kind]
-        rec = img[blob0 + int(off):blob0 + int(off) + int(nbytes)].copy()
-        for r in range(max(1, int(nbytes) // elem) if elem else 1):
-            for fo in fl:
-                pos = r * elem + fo
-                v = int(rec[pos:pos + 8].view(np.uint64)[0])
-                rec[pos:pos + 8] = 0
-                rec[pos] = 1 if v else 0
-        out.append((kind, rec.tobytes()))
+    out = []
+    for kind, rec, fields in plan_ops(lib, lib.es_ctx_plan(ctx, which)):
+        rec = bytearray(rec)
+        for pos in fields:
+            rec[pos:pos + 8] = bytes([1 if any(rec[pos:pos + 8]) else 0]) + bytes(7)
+        out.append((kind, bytes(rec)))
     return out

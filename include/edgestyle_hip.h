@@ -464,12 +464,12 @@ int es_plan_size(const es_plan* p);                    /* number of recorded cal
 int es_plan_count(const es_plan* p, int kind);         /* ... of one kind (csrc/plan.h: 1 = es_conv_gemm, 2 = es_linear_xs, ...) */
 int es_plan_launch(const es_plan* p, void* stream);
 /* flat image of a plan: returns the bytes needed; writes them when cap suffices.  The recorded device addresses inside
- * are NOT relocated (edgestyle_amd/native.py save() builds the relocation tables es_ctx_load applies) */
+ * are NOT relocated (es_ctx_save_ranges builds the relocation tables es_ctx_load applies) */
 size_t es_plan_export(const es_plan* p, void* out, size_t cap);
 /* The pointer fields of a recorded call, by op kind (csrc/plan.h es_op_kind): byte offsets inside the argument record and how
  * the op uses the memory behind each (1 = reads, 2 = writes, 3 = both); *elem_bytes != 0: the record is an array of elements
  * of that size (es_fusion_blocks).  Returns the field count and fills at most `cap` entries.  This is what relocates a plan:
- * exactly these words are device addresses (NativeEngine.save), nothing is guessed from bit patterns. */
+ * exactly these words are device addresses (es_ctx_save_ranges), nothing is guessed from bit patterns. */
 int es_plan_pointer_fields(int kind, int32_t* offsets, int32_t* uses, int cap, int32_t* elem_bytes);
 es_plan* es_plan_import(const void* data, size_t size);
 
@@ -538,14 +538,34 @@ int es_ctx_set_alphas_cumprod_f64(es_ctx* c, const double* alphas_cumprod, int n
 int es_unipc_coef_table(const double* alphas_cumprod, int n_alphas, const float* timesteps, int n, float* out);
 int es_ctx_plan_size(const es_ctx* c, int which);
 es_plan* es_ctx_plan(es_ctx* c, int which);             /* borrowed */
-/* Load a context image written by NativeEngine.save(path) (edgestyle_amd/native.py): packed weights, tables, static buffers,
- * the five launch lists and their pointer relocations.  No Python, torch or model code is needed to load or run it: build once
- * (es_load_weights or a Python host), ship the image, start in under a second. */
+/* Load a context image written by es_ctx_save / es_ctx_save_ranges: packed weights, tables, static buffers, the launch lists
+ * and their pointer relocations.  No Python, torch or model code is needed to load or run it: build once (es_load_weights or
+ * a Python host), ship the image, start in under a second. */
 int es_ctx_load(const char* path, int device, es_ctx** out);
 /* Write a context that owns its arena - one built by es_load_weights, or loaded by es_ctx_load - as such an image (same format):
- * build from checkpoints once (seconds), start from the image afterwards (one hipMalloc + copies).  Contexts of a Python host
- * hold pointers into the host's allocator pools instead of one arena: NativeEngine.save writes those. */
+ * build from checkpoints once (seconds), start from the image afterwards (one hipMalloc + copies).  It is es_ctx_save_ranges
+ * with the arena as the one segment.  Contexts of a Python host hold pointers into the host's allocator pools instead of one
+ * arena: those go through es_ctx_save_ranges. */
 int es_ctx_save(const es_ctx* c, const char* path);
+typedef struct { uint64_t addr, bytes; } es_mem_range;
+typedef struct {
+  uint64_t arena_bytes, data_bytes;       /* size of the arena es_ctx_load will allocate; bytes of it stored in the file */
+  int32_t segments, extents;              /* used segments (= arena slots); data extents */
+  int32_t relocations[ES_PLAN_COUNT];     /* non-null pointer fields per plan */
+} es_ctx_image_info;
+/* Write ANY launchable context as a context image; the one writer of the format.
+ * segments: the allocator segments the context's pointers may fall into (any order; overlapping ones are refused).
+ * blocks:   the allocator's blocks inside them, or NULL.
+ * Every non-null pointer field of every recorded call (es_plan_pointer_fields; nothing else in a record is read as an address)
+ * and every bound slot must lie in a segment: otherwise an error naming the op kind and the address.  The image's arena gets
+ * one slot per USED segment, in address order, each rounded up to 256 bytes, and every such pointer becomes an offset into it
+ * (the stored launch lists hold offsets too: no absolute address is written).  What travels as bytes: with `blocks`, every
+ * referenced block that no call writes (the OR of the uses of all pointers into it lacks 2; a bound slot counts as written,
+ * the host entry points fill it) and every referenced block of at most 64 KiB; without, the context's own recorded extents
+ * (es_load_weights / es_ctx_load).  All else is zero-filled space.  The file is written as `path`.tmp and renamed on success.
+ * path NULL: lay the image out and fill *info (may be NULL) only - no file, no HIP call. */
+int es_ctx_save_ranges(const es_ctx* c, const char* path, const es_mem_range* segments, int n_segments,
+                       const es_mem_range* blocks, int n_blocks, es_ctx_image_info* info);
 /* ---------------------------------------------------------------------------------------------------------
  * es_load_weights - build a context from the reference's state dicts, natively.
  * Replaces, on the loading side: EdgeStyleMultiControlNetModel.from_pretrained + load_state_dict

@@ -290,23 +290,15 @@ def plan_constants(lib, ctx, which):
     parameters - as host bytes, in call order.  Only for contexts whose recorded addresses are HOST addresses
     (python_dry_context, es_load_weights(device=-2))."""
     import ctypes as Ct
-    import numpy as np
     from edgestyle_amd import lib as L
-    pl = lib.es_ctx_plan(ctx, which)
-    n = lib.es_plan_export(pl, None, 0)
-    raw = (Ct.c_char * n)()
-    lib.es_plan_export(pl, raw, n)
-    img = bytes(raw)
-    n_ops = int.from_bytes(img[:8], "little")
-    blob0 = 16 + 24 * n_ops
+    from edgestyle_amd.native import plan_ops
     out = []
 
     def rd(addr, nbytes):
         if addr:
             out.append(Ct.string_at(addr, nbytes))
-    for i in range(n_ops):
-        kind, off, nb = (int.from_bytes(img[16 + 24 * i + 8 * j:24 + 24 * i + 8 * j], "little", signed=True) for j in range(3))
-        rec = img[blob0 + off:blob0 + off + nb]
+    for kind, rec, _ in plan_ops(lib, lib.es_ctx_plan(ctx, which)):
+        nb = len(rec)
         if kind == 1:
             d = L.GemmDesc.from_buffer_copy(rec)
             ws_ = [d.w] if d.ngroups <= 1 else list(d.w_g)[:d.ngroups]

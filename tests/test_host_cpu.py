@@ -82,6 +82,180 @@ def test_plan_image_round_trip_markers_and_context_image_errors(tmp_path):
     assert L.es_ctx_load(str(bad).encode(), 0, ctypes.byref(ctx)) != 0 and b"not a context image" in L.es_last_error()
 
 
+# ----------------------------------------------------------------------------------------------------------------
+# es_ctx_save_ranges, the one writer of a context image, on a host without a GPU: a context assembled from hand-made plans
+# and invented addresses.  With path NULL, or with an image that has no data extents, nothing dereferences them.
+# The memory map of these tests (S = allocator segment; S2 is used by nobody; 64 KiB = 0x10000):
+#   S0 0x10000 + 0x20001   -> arena 0x00000 (slot 0x20100: rounded up to 256)
+#   S1 0x30001 + 0x00100   -> arena 0x20100 (adjacent: S0's end is S1's first byte)
+#   S2 0x40000 + 0x01000   -> no slot
+#   S3 0x50000 + 0x40000   -> arena 0x20200; the arena is 0x60200 bytes
+# ----------------------------------------------------------------------------------------------------------------
+_SEGS = [(0x50000, 0x40000), (0x10000, 0x20001), (0x40000, 0x1000), (0x30001, 0x100)]        # handed over unsorted
+_ARENA_OF = {0x10000: 0x0, 0x10008: 0x8, 0x10010: 0x10, 0x30000: 0x20000,                    # S0 (0x30000: its last byte)
+             0x30001: 0x20100, 0x30100: 0x201FF,                                              # S1: first and last byte
+             0x50000: 0x20200, 0x50010: 0x20210, 0x50020: 0x20220, 0x50040: 0x20240, 0x50100: 0x20300,
+             0x60001: 0x30201, 0x60002: 0x30202, 0x60010: 0x30210, 0x70002: 0x40202}                            # S3
+
+
+def _image_plans(at):
+    """The two plans of these tests as {which: (plan image, [blob positions of the non-null pointer fields, in call order])};
+    `at` maps an address to what the image is to hold in its place."""
+    import struct
+    F = lib.FusionDesc
+    step = (struct.pack("<QQQ", at(0x50000), at(0x10000), 64)            # @0   es_memcpy {dst, src, bytes}
+            + struct.pack("<Q", at(0x30000))                             # @24  es_incr {ctr}
+            + struct.pack("<QQQii", at(0x30001), 0, at(0x60001), 5, 3)   # @32  es_gather_row {table, idx (null), out, row_len, nrows}
+            + struct.pack("<QQQ", at(0x50010), at(0x60002), 8)           # @64  es_memcpy
+            + struct.pack("<QQQ", at(0x50020), at(0x70002), 8))          # @88  es_memcpy
+    step_ops = [(18, 0, 24), (16, 24, 8), (17, 32, 32), (18, 64, 24), (18, 88, 24)]
+    a, b = F(), F()                                                       # es_fusion_blocks: two elements in one record
+    a.res[0], a.w1, a.out, a.C = at(0x30100), at(0x10008), at(0x50100), 320
+    b.res[5], b.u, b.HW = at(0x10010), at(0x60010), 64
+    sz = ctypes.sizeof(F)
+    out = {}
+    for which, ops_, blob, pos in ((lib.PLAN_STEP, step_ops, step, [0, 8, 24, 32, 48, 64, 72, 88, 96]),
+                                   (lib.PLAN_DECODE, [(8, 0, 2 * sz)], bytes(a) + bytes(b),
+                                    [F.res.offset, F.w1.offset, F.out.offset, sz + F.res.offset + 40, sz + F.u.offset])):
+        out[which] = (struct.pack("<QQ", len(ops_), len(blob)) + b"".join(struct.pack("<qQQ", *o) for o in ops_) + blob, pos)
+    return out
+
+
+def _image_ctx(L, plans, binds=()):
+    ctx = ctypes.c_void_p()
+    assert L.es_ctx_create(0, ctypes.byref(ctx)) == 0
+    for which, img in plans.items():
+        p = ctypes.c_void_p(L.es_plan_import((ctypes.c_char * len(img)).from_buffer_copy(img), len(img)))
+        assert p.value and L.es_ctx_set_plan(ctx, which, p) == 0
+    for slot, addr, nbytes in binds:
+        assert L.es_ctx_bind(ctx, slot, ctypes.c_void_p(addr), nbytes) == 0
+    return ctx
+
+
+def _ranges(r):
+    return (lib.MemRange * len(r))(*r), len(r)
+
+
+_BINDS = ((lib.BUF_SAMPLE, 0x70002, 16), (lib.BUF_IMAGE, 0x50040, 32))
+
+
+def test_context_image_layout_segments_extents_and_relocation_counts():
+    """Layout phase alone (path NULL): which segments get an arena slot, how large the arena is, which blocks travel as data
+    and how many pointer fields of each plan are relocated - against figures worked out by hand from the map above."""
+    L = lib.load()
+    ctx = _image_ctx(L, {w: img for w, (img, _) in _image_plans(lambda a: a).items()}, _BINDS)
+    blocks = [(0x10000, 0x10001),      # A: 64 KiB + 1, only read (memcpy src, fusion w1 and res)              -> data
+              (0x20001, 0x10000),      # B: 64 KiB, written (es_incr reads and writes it): small                 -> data
+              # S1 has no block: 0x30001 and 0x30100 are relocated and add nothing
+              (0x50000, 0x10001),      # C: 64 KiB + 1, only written (a bound slot lies in it, too)             -> space
+              (0x60001, 0x10001),      # D: 64 KiB + 1, written by es_gather_row, read by an es_memcpy (+ fusion u) -> space
+              (0x70002, 0x10001),      # E: 64 KiB + 1, only read by the plans, but ES_BUF_SAMPLE is bound here -> space
+              (0x80003, 0x100)]        # F: referenced by nobody                                                -> nothing
+    info = lib.CtxImageInfo()
+    assert L.es_ctx_save_ranges(ctx, None, *_ranges(_SEGS), *_ranges(blocks[::-1]), ctypes.byref(info)) == 0, L.es_last_error()
+    assert (info.segments, info.arena_bytes) == (3, 0x60200)
+    assert (info.extents, info.data_bytes) == (2, 0x10001 + 0x10000)
+    assert list(info.relocations) == [0, 0, 9, 5, 0, 0]            # null fields (es_gather_row's idx, most of a fusion element) skipped
+    # without ES_BUF_SAMPLE in it, E is only read: a third extent
+    ctx2 = _image_ctx(L, {w: img for w, (img, _) in _image_plans(lambda a: a).items()}, _BINDS[1:])
+    assert L.es_ctx_save_ranges(ctx2, None, *_ranges(_SEGS), *_ranges(blocks), ctypes.byref(info)) == 0
+    assert (info.extents, info.data_bytes, info.arena_bytes) == (3, 0x10001 + 0x10000 + 0x10001, 0x60200)
+    # no block table: only what the context's builder recorded as data travels - nothing, for a context assembled by hand
+    assert L.es_ctx_save_ranges(ctx, None, *_ranges(_SEGS), None, 0, ctypes.byref(info)) == 0
+    assert (info.segments, info.arena_bytes, info.extents, info.data_bytes) == (3, 0x60200, 0, 0) and list(info.relocations) == [0, 0, 9, 5, 0, 0]
+    # a context that uses S0 alone: one slot, rounded up to 256
+    ctx3 = _image_ctx(L, {lib.PLAN_PREP: _pointer_plan([(16, 0x10000)])})
+    assert L.es_ctx_save_ranges(ctx3, None, *_ranges(_SEGS), None, 0, ctypes.byref(info)) == 0
+    assert (info.segments, info.arena_bytes) == (1, 0x20100) and list(info.relocations) == [0, 1, 0, 0, 0, 0]
+    for c in (ctx, ctx2, ctx3):
+        L.es_ctx_destroy(c)
+
+
+def _pointer_plan(calls):
+    """a plan image of one-pointer calls [(kind, address)] (es_incr = 16 {ctr})"""
+    import struct
+    return (struct.pack("<QQ", len(calls), 8 * len(calls)) + b"".join(struct.pack("<qQQ", k, 8 * i, 8) for i, (k, _) in enumerate(calls))
+            + b"".join(struct.pack("<Q", a) for _, a in calls))
+
+
+def test_context_image_refusals_name_the_cause_and_leave_no_file(tmp_path):
+    import struct
+    L = lib.load()
+    path = tmp_path / "no.esctx"
+
+    def refused(ctx, segs, *words):
+        info = lib.CtxImageInfo()
+        for p in (None, str(path).encode()):                     # the same verdict with and without a file to write
+            assert L.es_ctx_save_ranges(ctx, p, *_ranges(segs), None, 0, ctypes.byref(info)) != 0
+            err = L.es_last_error().decode()
+            assert all(w in err for w in words), err
+            assert not path.exists() and not (tmp_path / "no.esctx.tmp").exists()
+        L.es_ctx_destroy(ctx)
+
+    # S1's end belongs to nobody (S2 begins later); S0's end is S1's first byte and is fine (the layout test relocates it)
+    refused(_image_ctx(L, {lib.PLAN_STEP: _pointer_plan([(16, 0x10000), (16, 0x30101)])}), _SEGS, "op kind 16", "0x30101", "outside every segment")
+    refused(_image_ctx(L, {lib.PLAN_STEP: _pointer_plan([(16, 0x30001)])}), [(0x10000, 0x20001), (0x30002, 0x100)], "op kind 16", "0x30001")
+    refused(_image_ctx(L, {}, [(lib.BUF_EHS, 0x41000, 8)]), _SEGS, "bound slot 2", "0x41000", "outside every segment")
+    refused(_image_ctx(L, {}, [(lib.BUF_EHS, 0x30100, 2)]), _SEGS, "bound slot 2", "outside every segment")       # runs past S1's last byte
+    refused(_image_ctx(L, {lib.PLAN_STEP: _pointer_plan([(16, 0x10000)])}), _SEGS + [(0x30000, 0x10)], "overlapping segments")
+    refused(_image_ctx(L, {lib.PLAN_STEP: _pointer_plan([(16, 0x10000)])}), [(0x10000, 0)], "empty")
+    # es_gather_row {table, idx, out, ...} recorded with 16 bytes: its third pointer field would lie behind the record
+    short = struct.pack("<QQ", 1, 16) + struct.pack("<qQQ", 17, 0, 16) + struct.pack("<QQ", 0x10000, 0x10008)
+    refused(_image_ctx(L, {lib.PLAN_STEP: short}), _SEGS, "pointer field lies outside its record")
+    # es_ctx_save is the same writer with the context's own arena as the one segment: a context without one is sent here
+    ctx = _image_ctx(L, {lib.PLAN_STEP: _pointer_plan([(16, 0x10000)])})
+    assert L.es_ctx_save(ctx, str(path).encode()) != 0
+    assert b"does not own a device arena" in L.es_last_error() and b"es_ctx_save_ranges" in L.es_last_error() and not path.exists()
+    L.es_ctx_destroy(ctx)
+
+
+def test_context_image_without_data_extents_byte_for_byte(tmp_path):
+    """An image whose referenced blocks are all large and written has no data, so writing it touches no GPU: the whole file
+    against one assembled here - magic and format 3, ABI 7, geometry, options, an odd fp32 schedule padded to 8 bytes, the f64
+    schedule, the block table of the used segments, per plan `size | image with arena offsets in the blob | n_rel | (position,
+    offset)` with a zero size for an absent plan, the slot table with -1 for unbound slots, zero extents."""
+    import struct
+    L = lib.load()
+    ctx = _image_ctx(L, {w: img for w, (img, _) in _image_plans(lambda a: a).items()}, _BINDS)
+    geo = lib.CtxGeometry(B=1, cfg=1, h=8, w=8, latent_channels=4, latent_pad=8, n_conds=6, n_steps=4, dtype=lib.ES_F16, guess_mode=0)
+    assert L.es_ctx_set_geometry(ctx, ctypes.byref(geo)) == 0
+    scales = [0.5, 1.0, 1.5, 2.0, 2.5, 3.0]
+    assert L.es_ctx_set_options(ctx, (ctypes.c_float * 6)(*scales), 0.25, 0.75, 2) == 0
+    ac, ac64 = [0.75, 0.5, 0.25], [0.875, 0.125]
+    assert L.es_ctx_set_alphas_cumprod(ctx, (ctypes.c_float * 3)(*ac), 3) == 0
+    assert L.es_ctx_set_alphas_cumprod_f64(ctx, (ctypes.c_double * 2)(*ac64), 2) == 0
+    blocks = [(0x10000, 0x20001), (0x50000, 0x40000)]              # S0 and S3 as one block each, both written; S1 without a block
+    path = tmp_path / "ctx.esctx"
+    info = lib.CtxImageInfo()
+    assert L.es_ctx_save_ranges(ctx, str(path).encode(), *_ranges(_SEGS), *_ranges(blocks), ctypes.byref(info)) == 0, L.es_last_error()
+    assert (info.segments, info.arena_bytes, info.extents, info.data_bytes) == (3, 0x60200, 0, 0)
+    want = b"ESCTX\x03\x00\x00" + struct.pack("<IIQ", 7, 3, 0x60200) + bytes(geo)
+    want += struct.pack("<6fffiIiI", *scales, 0.25, 0.75, 2, 3, lib.SCHED_DDIM, 2)
+    want += struct.pack("<3f4x2d", *ac, *ac64)
+    want += struct.pack("<QQQQQQ", 0x0, 0x20001, 0x20100, 0x100, 0x20200, 0x40000)
+    given, moved = _image_plans(lambda a: a), _image_plans(_ARENA_OF.__getitem__)
+    for which in range(lib.PLAN_COUNT):
+        if which not in moved:
+            want += struct.pack("<Q", 0)
+            continue
+        img, pos = moved[which]
+        blob0 = len(img) - struct.unpack("<Q", img[8:16])[0]
+        want += struct.pack("<Q", len(img)) + img + struct.pack("<Q", len(pos))
+        for p in pos:
+            addr = struct.unpack("<Q", given[which][0][blob0 + p:blob0 + p + 8])[0]
+            want += struct.pack("<QQ", p, _ARENA_OF[addr])
+    slots = {lib.BUF_SAMPLE: (0x40202, 16), lib.BUF_IMAGE: (0x20240, 32)}
+    for slot in range(lib.BUF_COUNT):
+        want += struct.pack("<qQ", *slots.get(slot, (-1, 0)))
+    want += struct.pack("<Q", 0)
+    got = path.read_bytes()
+    assert got == want, next(i for i, (x, y) in enumerate(zip(got, want)) if x != y) if len(got) == len(want) else (len(got), len(want))
+    assert not (tmp_path / "ctx.esctx.tmp").exists()
+    # the same context saves to the same bytes, in whatever order the segments are handed over
+    assert L.es_ctx_save_ranges(ctx, str(path).encode(), *_ranges(_SEGS[::-1]), *_ranges(blocks), None) == 0 and path.read_bytes() == want
+    L.es_ctx_destroy(ctx)
+
+
 def test_native_ddim_coefficients_match_the_host_scheduler():
     """es_ddim_coef_table (what es_denoise_loop derives from `timesteps`, host-only code) vs DDIMScheduler.coef_table():
     bit for bit with the scheduler's alphas_cumprod handed over, within 1e-6 with the library's own SD1.5 schedule."""
@@ -602,7 +776,7 @@ def test_best_embeddings_prompt_picker():
 
 
 def test_pointer_field_tables_match_the_descriptor_structs():
-    """es_plan_pointer_fields (what NativeEngine.save relocates by, instead of guessing pointers from bit patterns): for every
+    """es_plan_pointer_fields (what es_ctx_save_ranges relocates by, instead of guessing pointers from bit patterns): for every
     descriptor struct mirrored in edgestyle_amd/lib.py, the library's table names exactly the pointer-typed fields of the
     struct - no more, no fewer -, each 8-byte aligned and inside the record, each with a use (1 reads, 2 writes, 3 both)."""
     L = lib.load()

@@ -244,6 +244,25 @@ def test_es_prepare_conds_from_rgb_images_equals_the_pipeline_bitwise(built):
     eng.close()
 
 
+def test_saving_an_engine_twice_gives_the_same_image_and_it_holds_no_address(built, tmp_path):
+    """NativeEngine.save hands torch's segments and blocks to es_ctx_save_ranges, which stores arena offsets in every pointer
+    field: two saves of an engine that did not run in between are the same bytes, and no 8-byte word of the image is the
+    address of one of the engine's bound slots."""
+    import os
+    import numpy as np
+    pipe, eng, ws, ucfg, vcfg = built
+    a, b = str(tmp_path / "a.esctx"), str(tmp_path / "b.esctx")
+    info = eng.save(a)
+    assert eng.save(b) == info
+    raw = open(a, "rb").read()
+    assert raw == open(b, "rb").read()
+    assert info["data_bytes"] < os.path.getsize(a) < info["arena_bytes"]
+    slots = [eng.lib.es_ctx_buffer(eng.ctx, slot, None) for slot in range(L.BUF_COUNT)]
+    slots = np.array([p for p in slots if p], dtype=np.uint64)
+    assert len(slots) >= 18
+    assert not np.isin(np.frombuffer(raw[:len(raw) // 8 * 8], dtype=np.uint64), slots).any()
+
+
 def test_context_image_saved_here_runs_in_a_process_without_torch(built, tmp_path):
     """NativeEngine.save(path) -> es_ctx_load(path) in a child process that imports neither torch nor this package
     (tests/run_ctx_image.py: ctypes on the library and the HIP runtime only), and in a compiled C++ host
