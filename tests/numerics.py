@@ -999,10 +999,17 @@ def silu_maps(N, C, H, W, ratio, dtype, seed=0, outlier_frac=0.01, outlier_gain=
 
 
 def conv_case(N, H, W, C1, Cout, dtype, k=3, stride=1, pad=None, upsample=False, out_hw=None, C2=0, tails=(), temb=False, silu=False,
-              scale=1.0, residual=False, residual_lo=False, bias=True, inputs="randn", weights="randn", seed=0):
+              scale=1.0, residual=False, residual_lo=False, bias=True, inputs="randn", weights="randn", seed=0, rep=1, nsrc=None, src=None,
+              first=0, scale_dev=None):
     """One es_conv_gemm launch, everything seeded, NHWC and rounded to the storage dtype (returned in fp32): x [N, H, W, C1] (+ x2 with C2
     channels, + tail sources [N, Hout, Wout, Ct] of a 1x1 convolution summed in, + temb [N, Cout], + residual and its low word),
     w [Cout, C1 + C2, k, k], wt [Cout, sum(tails)], b fp32, and the geometry.
+    rep > 1: a shared source (es_gemm_desc.x_nmod, ops.conv_gemm(..., x_rep=)).  "x_src" holds the nsrc = N // rep samples the launch is
+             handed, "x" - what every reference reads - the N samples of the launch: sample i reads x_src[(first + i) % nsrc].  nsrc /
+             src / first: the case is one weight group of a grouped launch - nsrc source samples (or `src`, the tensor another group
+             of the same launch made) and `first`, the index of the group's first sample in the launch.
+    scale_dev: a device scalar (es_gemm_desc.out_scale_dev).  "scale" - what every reference multiplies by - is the fp32 product
+             float32(scale) * float32(scale_dev), as the kernels form it; the factors are kept as "scale_host" and "scale_dev".
     inputs:  "randn" zero-mean; "silu0" / "silu3" post-SiLU maps (silu_maps at ratio 0 / 3); "near_2^10" activations of magnitude about
              2^10 with random signs (for weights="subnormal"); "peak" randn scaled so that the largest fp64 OUTPUT lies at 2e4 .. 3e4.
     weights: "randn" / sqrt(fan-in); "subnormal" every |w| < 2^-14 (fp16 subnormals: a flush to zero returns the bias); "zero".
@@ -1012,16 +1019,31 @@ def conv_case(N, H, W, C1, Cout, dtype, k=3, stride=1, pad=None, upsample=False,
     pad = (1 if k == 3 else 0) if pad is None else pad
     Hout, Wout = conv_out_hw(H, W, k, stride, pad, upsample, out_hw)
     Ct, Ctot = sum(tails), C1 + C2
-    if inputs in ("silu0", "silu3"):
-        xa = silu_maps(N, Ctot, H, W, 0 if inputs == "silu0" else 3, dtype, seed=seed)
+    if src is not None:
+        nsrc = src.shape[0]
+    elif nsrc is None and rep > 1:
+        assert N % rep == 0, (N, rep)
+        nsrc = N // rep
+    if nsrc:
+        assert not C2 and not tails and inputs != "peak", "a shared source is a single source (gemm_check)"
+    Nx = nsrc or N                                # samples drawn for the source
+    if src is not None:
+        assert tuple(src.shape) == (nsrc, H, W, C1) and torch.equal(src, rnd(src, dtype))
+        xa = src
+    elif inputs in ("silu0", "silu3"):
+        xa = silu_maps(Nx, Ctot, H, W, 0 if inputs == "silu0" else 3, dtype, seed=seed)
     elif inputs == "near_2^10":
-        sgn = torch.where(torch.rand(N, H, W, Ctot, generator=g) < 0.5, -1.0, 1.0)
-        xa = rnd(sgn * 1024.0 * (1 + 0.1 * torch.randn(N, H, W, Ctot, generator=g)), dtype)
+        sgn = torch.where(torch.rand(Nx, H, W, Ctot, generator=g) < 0.5, -1.0, 1.0)
+        xa = rnd(sgn * 1024.0 * (1 + 0.1 * torch.randn(Nx, H, W, Ctot, generator=g)), dtype)
         assert float(xa.abs().min()) > 512.0 and float(xa.abs().max()) < 2048.0
     else:
-        xa = torch.randn(N, H, W, Ctot, generator=g)
+        xa = torch.randn(Nx, H, W, Ctot, generator=g)
         xa = rnd(xa - xa.mean(), dtype)
         assert abs(float(xa.double().mean())) < 1e-3
+    x_src = None
+    if nsrc:
+        x_src = xa.contiguous()
+        xa = x_src[(first + torch.arange(N)) % nsrc]
     fan = k * k * Ctot + Ct
     if weights == "subnormal":
         lim = 2.0 ** FP16_NORMAL_MIN_LOG2
@@ -1036,10 +1058,16 @@ def conv_case(N, H, W, C1, Cout, dtype, k=3, stride=1, pad=None, upsample=False,
         assert float(w.abs().max()) < 2.0 ** FP16_NORMAL_MIN_LOG2 and float((w != 0).double().mean()) > 0.99
     c = dict(dtype=dtype, N=N, H=H, W=W, C1=C1, C2=C2, Cout=Cout, k=k, stride=stride, pad=pad, upsample=bool(upsample),
              out_hw=(Hout, Wout), silu=bool(silu), scale=float(torch.tensor(scale, dtype=torch.float32)),
+             scale_host=float(torch.tensor(scale, dtype=torch.float32)), scale_dev=None, x_src=x_src, nsrc=nsrc or 0, first=first if nsrc else 0,
              x=xa[..., :C1].contiguous(), x2=xa[..., C1:].contiguous() if C2 else None, w=w, wt=wt,
              b=(0.1 * torch.randn(Cout, generator=g)) if bias else None,
              tails=[rnd(torch.randn(N, Hout, Wout, t, generator=g), dtype) for t in tails],
              temb=rnd(torch.randn(N, Cout, generator=g), dtype) if temb else None, res=None, res_lo=None)
+    if nsrc:
+        assert all(torch.equal(c["x"][i], x_src[(first + i) % nsrc]) for i in range(N))
+    if scale_dev is not None:   # scale *= *p.out_scale_dev: one fp32 product
+        c["scale_dev"] = float(torch.tensor(scale_dev, dtype=torch.float32))
+        c["scale"] = float(torch.tensor(scale, dtype=torch.float32) * torch.tensor(scale_dev, dtype=torch.float32))
     if residual:
         c["res"] = rnd(torch.randn(N, Hout, Wout, Cout, generator=g), dtype)
         if residual_lo:         # the low word of a value pair: what is left of a sum after its rounding - below half a unit of the high word
@@ -1133,7 +1161,8 @@ def conv_base_ref(c):
 def conv_epilogue(c, acc, wide=False, defect=None, temb_rows=None):
     """csrc/gemm_conv.hip's epilogue on the fp32 accumulators [N, Hout, Wout, Cout]: ((acc + bias) + temb), SiLU, * scale, ROUND, then
     + residual in fp32 and ROUND AGAIN.  wide: the two-word stream - the fp32 sum over the rounded value, the residual and its low
-    word, stored as hi = round(sum) and lo = round(sum - hi); returns (hi, lo)."""
+    word, stored as hi = round(sum) and lo = round(sum - hi); returns (hi, lo).
+    Planted: "scale_before_act" - silu(x * scale) where the design is silu(x) * scale."""
     dt = c["dtype"]
     y = acc.float()
     late_bias = defect == "late_bias" and c["b"] is not None
@@ -1141,9 +1170,11 @@ def conv_epilogue(c, acc, wide=False, defect=None, temb_rows=None):
         y = y + c["b"]
     if c["temb"] is not None:
         y = y + (c["temb"][:, None, None, :] if temb_rows is None else temb_rows)
-    if c["silu"]:
-        y = F.silu(y)
-    y = rnd(y * torch.tensor(c["scale"], dtype=torch.float32), dt)
+    sc = torch.tensor(c["scale"], dtype=torch.float32)
+    if c["silu"] and defect == "scale_before_act":
+        y = rnd(F.silu(y * sc), dt)
+    else:
+        y = rnd((F.silu(y) if c["silu"] else y) * sc, dt)
     if late_bias:
         y = rnd(y + c["b"], dt)
     if c["res"] is None:
@@ -1163,16 +1194,27 @@ def conv_im2col(c, korder=0, defect=None):
     (upsampled) image reads zero.  Geometry defects (planted):
       "hw_swapped"       the pixel decode divides by Hout where it should divide by Wout
       "right_tap"        the right-hand tap column (kx = k - 1) is dropped at ox == Wout - 1
-      "wrap_next_sample" a tap below the last row of sample n reads row 0 .. of sample n + 1 (a flat offset with no range check)"""
+      "wrap_next_sample" a tap below the last row of sample n reads row 0 .. of sample n + 1 (a flat offset with no range check)
+    With a shared source (conv_case(rep= | nsrc=)) row m of sample n reads source sample (first + n) % nsrc.  Planted there:
+      "mod_per_tile"     every row of a 128-row tile reads the source sample of the tile's FIRST row (modulo nsrc): the modulo taken once
+                         per workgroup.  Identical to the design where no tile straddles a sample (H * W % 128 == 0)
+      "mod_in_group"     the modulo is taken of the sample's index inside its weight group (n % nsrc, without `first`): identical to the
+                         design unless the group starts at a launch index that is no multiple of nsrc"""
     N, H, W, k, s, p = c["N"], c["H"], c["W"], c["k"], c["stride"], c["pad"]
     Hout, Wout = c["out_hw"]
     x = c["x"] if c["x2"] is None else torch.cat([c["x"], c["x2"]], dim=-1)
+    if defect in ("mod_per_tile", "mod_in_group"):
+        assert c.get("nsrc"), f"{defect} is a defect of the shared source"
     up = 1 if c["upsample"] else 0
     Hin, Win = H << up, W << up
     Ctot = x.shape[-1]
     m = torch.arange(N * Hout * Wout)
     n, rem = m // (Hout * Wout), m % (Hout * Wout)
     oy, ox = (rem // Wout, rem % Wout) if defect != "hw_swapped" else (rem // Hout, rem % Hout)
+    if defect == "mod_per_tile":                 # (groups start on whole tiles: the case's tiles are the launch's)
+        x, n, N = c["x_src"], (c["first"] + (m // BM_CONV) * BM_CONV // (Hout * Wout)) % c["nsrc"], c["nsrc"]
+    elif defect == "mod_in_group":
+        x, n, N = c["x_src"], n % c["nsrc"], c["nsrc"]
     cols = []
     for ky in range(k):
         for kx in range(k):
@@ -1234,10 +1276,14 @@ def conv_base_alg(c, chain=8, splitk=1, korder=0, wide=False, defect=None):
       "rounded_slabs"   the split-K slabs are rounded to the storage dtype before the reduce
       "late_bias"       the bias is added behind the rounding (and the sum rounded again)
       "tile_unwritten"  the second 128-pixel tile (the last, if there is one only) is never stored: NaN, as a sentinel-filled output shows it
-      "temb_first_pixel" every pixel of a 128-pixel tile takes the time-embedding row of the tile's FIRST pixel's sample"""
+      "temb_first_pixel" every pixel of a 128-pixel tile takes the time-embedding row of the tile's FIRST pixel's sample
+      "dev_scale_dropped_in_reduce"  with splitk > 1 (the epilogue is the reduce kernel's) only the host out_scale is applied
+      "scale_before_act" conv_epilogue's"""
     dt = c["dtype"]
     N, (Hout, Wout), Cout = c["N"], c["out_hw"], c["Cout"]
-    A, Wm = conv_im2col(c, korder, defect if defect in ("hw_swapped", "right_tap", "wrap_next_sample") else None)
+    A, Wm = conv_im2col(c, korder, defect if defect in ("hw_swapped", "right_tap", "wrap_next_sample", "mod_per_tile", "mod_in_group") else None)
+    if defect == "dev_scale_dropped_in_reduce" and splitk > 1:
+        c = dict(c, scale=c["scale_host"])
     acc = None
     for k0, k1 in conv_splitk_slices(A.shape[1], splitk):
         slab = _chain_dot(A[:, k0:k1], Wm[:, k0:k1], chain) if k1 > k0 else torch.zeros(A.shape[0], Cout)

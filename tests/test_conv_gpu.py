@@ -7,7 +7,7 @@ share among independent fp32 implementations of the same launch - base_alg with 
 F.unfold + torch.mm on the device's own matrix cores - all computed when the test runs; and the row_err bars of test_numerics_gpu.py.
 
 TABLE is not a cross product: every form (tile, ring depth, split-K, K order, XCD order, epilogue) meets every geometry class
-(non-square, odd, stride 2, upsample, W == 1, tiles that straddle samples) at least once where the form can run at all; that is
+(non-square, odd, stride 2, upsample, W == 1, tiles that straddle samples, linear rows) at least once where the form can run at all; that is
 asserted when the module is imported, and `coverage()` prints the matrix."""
 import math
 
@@ -37,11 +37,34 @@ GEOMS = {  # name -> H, W and the geometry arguments of nm.conv_case
     "up_5x7": dict(H=5, W=7, upsample=True), "up_3x8": dict(H=3, W=8, upsample=True), "up_12x10": dict(H=12, W=10, upsample=True),
     "up_4x8": dict(H=4, W=8, upsample=True),                         # (added: 128 output pixels per sample behind the upsample)
     "k1_9x7": dict(H=9, W=7, k=1), "k1_1x1": dict(H=1, W=1, k=1), "k1_13x1": dict(H=13, W=1, k=1),
+    # linear rows (ops.linear: [M, 1, 1, K], the sample count is the row count): the time-embedding MLP's 2 rows, one prompt's 77, 3 x 77 = 231
+    # (a ragged last 128-row tile and a ragged 256-row tile), 385 (the same at four tiles).  The entry names its own sample counts
+    "lin": dict(H=1, W=1, k=1, Ns=([2], [77], [231], [385])),
 }
 CHANNELS = {"8>64": (8, 0, 64), "16>32": (16, 0, 32), "64>64": (64, 0, 64), "128+64>320": (128, 64, 320), "320>4": (320, 0, 4),
-            "128>3": (128, 0, 3), "256>640": (256, 0, 640)}
-CLASSES = ("non-square", "odd", "stride 2", "upsample", "W == 1", "straddles samples")
-EPILOGUES = ("bias", "temb_tuni", "temb_pix", "temb_silu_res", "tail1", "tail2", "wide1", "wide2", "grouped", "gn_part")
+            "128>3": (128, 0, 3), "256>640": (256, 0, 640),
+            "8>320": (8, 0, 320),                 # conv_in: 4 latent channels padded to 8 (unaligned: the 4-wave 128-pixel tile only)
+            "768>640": (768, 0, 640)}             # the text K / V projection
+CLASSES = ("non-square", "odd", "stride 2", "upsample", "W == 1", "straddles samples", "linear rows")
+EPILOGUES = ("bias", "temb_tuni", "temb_pix", "temb_silu_res", "tail1", "tail2", "wide1", "wide2", "grouped",
+             # res: a plain residual (to_out, ff of an fp16 pipeline).  silu_scale: ES_ACT_SILU and out_scale = 1 / 1.702, nothing else (CLIP's
+             # quick_gelu, the time-embedding MLP).  shared: x_rep = 3 (es_gemm_desc.x_nmod).  scale_dev: out_scale = 0.5 times a device scalar 0.7
+             "res", "silu_scale", "shared", "scale_dev",
+             # single forms, each pinned to the geometry it exists at (not in FORMS): shared_grouped - a shared source of two samples under
+             # two weight sets over 3 + 5 samples, the second group starting at launch index 3 (gemm_check accepts the launch: no refusal to
+             # assert); conv_in - models.py's grouped conv_in exactly; scale_dev_res - scale, then a residual; scale_dev_gn - the device
+             # scale in splitk_reduce_gn_kernel
+             "shared_grouped", "conv_in", "scale_dev_res", "scale_dev_gn", "gn_part")
+SINGLE_FORMS = ("shared_grouped", "conv_in", "scale_dev_res", "scale_dev_gn", "gn_part")
+TEMB = ("temb_tuni", "temb_pix", "temb_silu_res")
+SILU = ("temb_silu_res", "silu_scale")
+RESIDUAL = ("temb_silu_res", "wide1", "wide2", "res", "conv_in", "scale_dev_res")
+WIDE = ("wide1", "wide2", "conv_in")
+GN_PART = ("gn_part", "scale_dev_gn")
+SHARED = {"shared": 3, "shared_grouped": 4, "conv_in": 4}            # form -> x_rep
+SCALES = {"temb_silu_res": (0.7, None), "silu_scale": (1 / 1.702, None), "scale_dev": (0.5, 0.7), "scale_dev_res": (0.5, 0.7),
+          "scale_dev_gn": (0.5, 0.7)}                                # form -> (out_scale, the device scalar)
+GROUPS = {"shared_grouped": [3, 5], "conv_in": [1, 1, 1, 1]}         # form -> group_n (the `grouped` form: sample_counts)
 
 
 def R(geom, chan, dt, tile, stages, splitk, korder, xcd, epi, inputs="randn", weights="randn"):
@@ -130,7 +153,51 @@ TABLE = [
     # GroupNorm statistics handed over: the gn_part table is guarded like the outputs
     R("s1_8x16", "128+64>320", "f", "t4w", 2, 1, 0, 0, "gn_part"),
     R("s2_15x16", "64>64", "b", "t64", 2, 2, 0, 0, "gn_part"),
+    # a plain residual, no time embedding, no activation (judged against base_alg like every form that rounds twice)
+    R("lin", "768>640", "f", "t8w", 2, 1, 0, 0, "res"),
+    R("s2_5x7", "64>64", "f", "t4w", 4, 1, 1, 1, "res"),
+    R("up_3x8", "128+64>320", "b", "t64", 2, 2, 0, 0, "res"),
+    R("lin", "768>640", "b", "t320", 2, 5, 0, 1, "res"),
+    # SiLU and a scale, nothing else.  The 256 x 320 tile has no SiLU epilogue (es_conv_gemm8p_form_ok sends the fused form to the
+    # 128 x 160 tile: asserted below, at import); with K split its partials go through the reduce, which has every form
+    R("lin", "768>640", "f", "t4w", 2, 1, 0, 0, "silu_scale"),
+    R("lin", "256>640", "b", "t64", 4, 2, 0, 1, "silu_scale"),
+    R("s2_9x12", "64>64", "f", "t8w", 4, 1, 1, 0, "silu_scale"),
+    R("up_5x7", "128+64>320", "f", "t320", 2, 2, 0, 0, "silu_scale"),
+    # a shared source, x_rep = 3: both loaders (aligned and not), both K orders, every tile; 33 x 31 and 17 x 16 pixels per sample put the
+    # wrap from source sample nsrc - 1 to 0 inside a tile; lin x 768>640 is the text K / V projection (231 rows: nsrc = 77)
+    R("lin", "768>640", "f", "t4w", 2, 1, 0, 0, "shared"),
+    R("s1_5x7", "64>64", "f", "t8w", 2, 1, 1, 1, "shared"),
+    R("s2_33x31", "256>640", "b", "t64", 2, 5, 0, 0, "shared"),
+    R("up_3x8", "256>640", "f", "t320", 2, 1, 0, 1, "shared"),
+    R("s1_33x31", "64>64", "f", "t4w", 4, 2, 1, 0, "shared"),
+    R("lin", "768>640", "b", "t320", 2, 1, 0, 0, "shared"),
+    R("s1_37x1", "8>64", "f", "t4w", 2, 1, 0, 0, "shared"),
+    # ... under two weight sets, the second group starting at launch index 3 of a source of 2: sample n of the LAUNCH reads n % x_nmod
+    R("s1_8x16", "64>64", "f", "t4w", 2, 1, 0, 0, "shared_grouped"),
+    R("up_4x8", "64>64", "b", "t64", 2, 2, 0, 1, "shared_grouped"),
+    # conv_in of all nets in one launch: four weight sets over one sample each, all reading the one latent, + condition, two-word output
+    R("s1_8x16", "8>320", "b", "t4w", 2, 1, 0, 0, "conv_in"),
+    # the device scalar at each of its read sites: the fused epilogue of every tile, the plain reduce (split in two, ragged), the reduce
+    # that hands GroupNorm statistics over; and followed by a residual in the same launch
+    R("s1_7x5", "64>64", "f", "t4w", 2, 1, 0, 0, "scale_dev"),
+    R("s2_15x16", "64>64", "b", "t8w", 2, 1, 1, 1, "scale_dev"),
+    R("up_5x7", "256>640", "f", "t64", 2, 1, 0, 0, "scale_dev"),
+    R("s1_37x1", "256>640", "f", "t320", 2, 1, 0, 1, "scale_dev"),
+    R("k1_9x7", "128+64>320", "f", "t4w", 2, 2, 0, 0, "scale_dev"),
+    R("s1_12x20", "256>640", "b", "t320", 2, 7, 1, 0, "scale_dev"),
+    R("lin", "768>640", "f", "t64", 2, 1, 0, 1, "scale_dev"),
+    R("s2_15x16", "64>64", "f", "t64", 2, 2, 0, 0, "scale_dev_gn"),
+    R("lin", "768>640", "f", "t4w", 4, 3, 0, 0, "scale_dev_res"),
+    # the other epilogue forms on linear rows
+    R("lin", "256>640", "f", "t8w", 2, 1, 0, 0, "temb_silu_res"),
+    R("lin", "768>640", "b", "t4w", 2, 2, 0, 1, "wide1"),
+    R("lin", "256>640", "b", "t64", 4, 1, 0, 0, "wide2"),
+    R("lin", "64>64", "f", "t4w", 4, 1, 0, 1, "tail1"),
+    R("lin", "64>64", "f", "t64", 2, 2, 0, 0, "tail2"),
 ]
+# the scale_dev row that is launched a second time with the device scalar at 0.0 (conditioning_scale = 0): every element == 0 and finite
+ZERO_SCALE = ("s1_7x5", "t4w", "scale_dev")
 
 
 def _tile_rows(row):
@@ -174,6 +241,8 @@ def row_classes(row):
         out.add("W == 1")
     if (Hout * Wout) % half:
         out.add("straddles samples")                                   # at N = 3 (grouped rows: inside a group)
+    if (g["H"], g["W"], g["k"]) == (1, 1, 1):
+        out.add("linear rows")                                         # the HWout == 1 branch of the pixel decode: n = m
     return out
 
 
@@ -190,11 +259,13 @@ def row_forms(row):
 
 
 FORMS = ("t4w", "t8w", "t64", "t320", "stages 2", "stages 4", "splitk 1", "splitk 2", "splitk ragged", "korder 0", "korder 1", "xcd 0", "xcd 1") \
-    + EPILOGUES[:-1]
-# (form, class) pairs no launch can realise: the form's own preconditions
+    + tuple(e for e in EPILOGUES if e not in SINGLE_FORMS)
+# (form, class) pairs no launch can realise: the form's own preconditions.  (The new forms - res, silu_scale, shared, scale_dev - have
+# none: each meets every geometry class, "linear rows" included.)
 IMPOSSIBLE = {("tail1", "stride 2"), ("tail1", "upsample"), ("tail2", "stride 2"), ("tail2", "upsample"),      # tails: same-size output
-              ("temb_tuni", "W == 1"), ("temb_tuni", "straddles samples"),                                      # H * W % tile rows == 0
-              ("grouped", "W == 1")}                                                                            # groups of whole 128-pixel tiles
+              ("temb_tuni", "W == 1"), ("temb_tuni", "straddles samples"), ("temb_tuni", "linear rows"),        # H * W % tile rows == 0
+              ("grouped", "W == 1"), ("grouped", "linear rows"),                                                # groups of whole 128-pixel tiles
+              ("korder 1", "linear rows")}                                                                      # chunk-major K: 3 x 3 only
 
 
 def row_id(row):
@@ -219,17 +290,24 @@ def route_desc(row):
     for i, ct in enumerate(tails):
         setattr(d, f"t{i + 1}", 1)
         setattr(d, f"Ct{i + 1}", ct)
-    d.temb = 1 if epi.startswith("temb") else None
-    d.act = lib.ACT_SILU if epi == "temb_silu_res" else lib.ACT_NONE
-    d.residual = 1 if epi in ("temb_silu_res", "wide1", "wide2") else None
-    d.out_lo, d.residual_lo = 1 if epi in ("wide1", "wide2") else None, 1 if epi == "wide2" else None
-    d.gn_part, d.gn_groups = 1 if epi == "gn_part" else None, 32
+    d.temb = 1 if epi in TEMB else None
+    d.act = lib.ACT_SILU if epi in SILU else lib.ACT_NONE
+    d.residual = 1 if epi in RESIDUAL else None
+    d.out_lo, d.residual_lo = 1 if epi in WIDE else None, 1 if epi == "wide2" else None
+    d.gn_part, d.gn_groups = 1 if epi in GN_PART else None, 32
+    d.out_scale = SCALES.get(epi, (1.0, None))[0]
+    d.out_scale_dev = 1 if SCALES.get(epi, (1.0, None))[1] is not None else None
+    d.x_nmod = 1 if epi in SHARED else 0                                   # (one sample: the source is that sample)
     return d
 
 
 def expected_kernel(row, bn):
-    """es_conv_gemm_last_kernel, unpacked (lib.gemm_kernel_fields), of the tile the row names: its pixels, waves, ring depth and K order"""
+    """es_conv_gemm_last_kernel, unpacked (lib.gemm_kernel_fields), of the tile the row names: its pixels, waves, ring depth and K order.
+    A row that names the 256 x 320 tile with an epilogue that tile lacks (es_conv_gemm8p_form_ok: a fused SiLU, ...) is expected where the
+    library sends it - the 128 x 160 tile on 4 waves; validate() refuses such a row in TABLE, so that none passes on another tile unseen"""
     C1, C2, _ = CHANNELS[row["chan"]]
+    if row["tile"] == "t320" and not nm.gemm_big_tile_takes(route_desc(row)):
+        return dict(bn=160, bm=128, stages=2, waves=4, aligned=True, ln=False, ko=bool(row["korder"]), geglu=False, bf16=row["dtype"] == torch.bfloat16)
     return dict(bn=bn, bm=_tile_rows(row), stages=row["stages"], waves={"t8w": 8, "t320": 8}.get(row["tile"], 4),
                 aligned=C1 % 64 == 0 and C2 % 64 == 0, ln=False, ko=bool(row["korder"]), geglu=False, bf16=row["dtype"] == torch.bfloat16)
 
@@ -253,18 +331,28 @@ def validate(row):
         assert hw % (128 if bn == 320 else _tile_rows(row)) == 0, name
     if row["epi"] == "temb_pix":
         assert hw % _tile_rows(row) != 0, name
-    if row["epi"] in ("wide1", "wide2"):
+    if row["epi"] in WIDE:
         assert row["dtype"] == torch.bfloat16 and Cout % 8 == 0, name
+    if row["epi"] in SHARED:
+        assert C2 == 0 and not _tails(row), name                         # gemm_check: x_nmod needs a single source
+    if row["epi"] in GROUPS:
+        assert hw % (256 if row["tile"] == "t320" else 128) == 0, name   # groups of whole tiles at any sample counts
+    if row["epi"] == "conv_in":
+        assert (row["geom"], row["chan"], row["tile"], g["k"]) == ("s1_8x16", "8>320", "t4w", 3), name
+    if "Ns" in GEOMS[row["geom"]]:
+        assert row["epi"] not in GROUPS and row["epi"] != "grouped" and all(len(ns) == 1 for ns in GEOMS[row["geom"]]["Ns"]), name
     # the tile the row names is the tile its descriptor reaches: the library's route (no GPU needed) and its Python mirror both say so.
     # A t320 row whose epilogue the 256-pixel kernel lacks would run - and pass - on the 128 x 160 tile
     d = route_desc(row)
     got, mirror = lib.gemm_route(d), nm.gemm_route(d)
     assert lib.gemm_kernel_fields(got["kernel"]) == lib.gemm_kernel_fields(mirror["kernel"]) == expected_kernel(row, d.bn), (name, got, mirror)
+    assert row["tile"] != "t320" or (got["family"] == 1 and expected_kernel(row, d.bn)["bm"] == 256), \
+        f"{name}: the 256 x 320 tile lacks this epilogue form, the row would run on the 128 x 160 tile"
     if row["inputs"] == "peak":
         assert row["dtype"] == torch.float16, name
     if row["weights"] == "zero":
         assert row["epi"] == "bias", name
-    if row["epi"] == "gn_part":
+    if row["epi"] in GN_PART:
         assert hw % 64 == 0 and Cout % 32 == 0 and Cout // 32 <= (160 if bn == 320 else bn) and (row["splitk"] == 1 or Cout // 32 <= 64), name
 
 
@@ -285,6 +373,19 @@ def coverage():
 
 for _row in TABLE:
     validate(_row)
+# a fused silu_scale launch recorded with bn = 320 lands on the 128 x 160 tile (which is why TABLE has that form on t320 with K split only):
+# the library's route and its mirror say so, expected_kernel says so, and validate() refuses the row
+_fused = dict([r for r in TABLE if r["epi"] == "silu_scale" and r["tile"] == "t320"][0], splitk=1)
+_d = route_desc(_fused)
+assert lib.gemm_kernel_fields(lib.gemm_route(_d)["kernel"]) == lib.gemm_kernel_fields(nm.gemm_route(_d)["kernel"]) == expected_kernel(_fused, 320) \
+    and expected_kernel(_fused, 320)["bn"] == 160 and lib.gemm_route(_d)["family"] == 0
+try:
+    validate(_fused)
+except AssertionError as _e:
+    assert "lacks this epilogue form" in str(_e), _e
+else:
+    raise AssertionError("validate() lets a fused SiLU row on the 256 x 320 tile pass")
+assert len([r for r in TABLE if (r["geom"], r["tile"], r["epi"]) == ZERO_SCALE]) == 1
 _matrix, _missing = coverage()
 assert not _missing, f"test_conv_gpu.TABLE leaves (form, geometry class) pairs unmet: {_missing}\n{_matrix}"
 assert len({row_id(r) for r in TABLE}) == len(TABLE)
@@ -318,9 +419,11 @@ def _pack(ops, c, korder):
         return ops.pack_weight(c["w"], c["b"], c["dtype"], DEV)
 
 
-def launch(row, cases):
+def launch(row, cases, dev_scale=None):
     """one es_conv_gemm launch over the concatenated samples of `cases` (one case; several = a grouped launch with one weight set per
-    case) into guarded buffers.  Returns dict(y, lo, desc, problems)."""
+    case) into guarded buffers.  A shared source: the launch is handed the cases' common "x_src" and x_rep.  A device scale: element
+    [1:2] of a 3-element fp32 vector whose neighbours are NaN (the engine passes scales_dev[0:1] of a longer vector); dev_scale
+    overrides its value.  Returns dict(y, lo, desc, problems)."""
     from edgestyle_amd import ops, lib
     c0, dt = cases[0], cases[0]["dtype"]
     Hout, Wout = c0["out_hw"]
@@ -342,9 +445,19 @@ def launch(row, cases):
         kw["temb"] = table[:, 64:]
     if c0["silu"]:
         kw["act"] = lib.ACT_SILU
-    if c0["scale"] != 1.0:
+    if c0["scale_dev"] is not None:
+        vec = torch.tensor([float("nan"), c0["scale_dev"] if dev_scale is None else dev_scale, float("nan")], dtype=torch.float32, device=DEV)
+        kw.update(out_scale=c0["scale_host"], out_scale_dev=vec[1:2])
+    elif c0["scale"] != 1.0:
         kw["out_scale"] = c0["scale"]
-    wide = row["epi"] in ("wide1", "wide2")
+    nsrc = c0["nsrc"]
+    if nsrc:
+        assert N % nsrc == 0 and all(c["x_src"] is c0["x_src"] for c in cases)
+        kw["x_rep"] = N // nsrc
+        xdev = c0["x_src"].to(DEV, dt)
+    else:
+        xdev = dev("x")
+    wide = row["epi"] in WIDE
     big_lo = None
     if c0["res"] is not None:
         kw["residual"] = dev("res")
@@ -354,7 +467,7 @@ def launch(row, cases):
             big_lo, lo2 = guarded(M, Cout, dt)
             kw.update(wide=True, out_lo=lo2.view(N, Hout, Wout, Cout))
     big_gn = None
-    if row["epi"] == "gn_part":
+    if row["epi"] in GN_PART:
         gshape = (N, 2 * (Hout * Wout // 64), 32, 2)
         big_gn, gn2 = guarded(gshape[0] * gshape[1], 64, torch.float32)
         kw.update(gn_groups=32, gn_part=gn2.view(gshape))
@@ -362,7 +475,7 @@ def launch(row, cases):
     if len(cases) > 1:
         kw["group_n"] = [c["N"] for c in cases]
     with knobs(**kn), launches() as rec:
-        y = ops.conv_gemm(dev("x"), pws if len(cases) > 1 else pws[0], **kw)
+        y = ops.conv_gemm(xdev, pws if len(cases) > 1 else pws[0], **kw)
     torch.cuda.synchronize()
     assert y.data_ptr() == out.data_ptr() and len(rec.descs) == 1
     d = rec.descs[0]
@@ -374,6 +487,10 @@ def launch(row, cases):
         problems.append(f"kernel {ran} ran, the row's tile is {expected_kernel(row, want['bn'])}")
     if len(cases) > 1 and int(d.ngroups) != len(cases):
         problems.append(f"ngroups {int(d.ngroups)}")
+    if int(d.x_nmod) != nsrc or int(d.N) != N:
+        problems.append(f"descriptor: x_nmod {int(d.x_nmod)} and N {int(d.N)}, the source holds {nsrc} samples (0: not shared) and the launch covers {N}")
+    if (int(d.out_scale_dev or 0) != 0) != (c0["scale_dev"] is not None):
+        problems.append("the device scale's pointer is not in the descriptor")
     if wide and not (int(d.out_lo or 0) and (int(d.residual_lo or 0) != 0) == (c0["res_lo"] is not None)):
         problems.append("the two-word stream's pointers are not in the descriptor")
     for name, b, t, rows, width in (("out", big, out2, M, Cout), ("out_lo", big_lo, kw.get("out_lo"), M, Cout),
@@ -470,17 +587,40 @@ def check(fails, name, row, c, y, lo):
 def make_cases(row, Ns, seed):
     g, (C1, C2, Cout) = _geometry(row), CHANNELS[row["chan"]]
     epi = row["epi"]
+    scale, scale_dev = SCALES.get(epi, (1.0, None))
     kw = dict(k=g["k"], stride=g["stride"], pad=g["pad"], upsample=g["upsample"], out_hw=g["out_hw"], C2=C2, tails=_tails(row),
-              temb=epi in ("temb_tuni", "temb_pix", "temb_silu_res"), silu=epi == "temb_silu_res", scale=0.7 if epi == "temb_silu_res" else 1.0,
-              residual=epi in ("temb_silu_res", "wide1", "wide2"), residual_lo=epi == "wide2", inputs=row["inputs"], weights=row["weights"])
+              temb=epi in TEMB, silu=epi in SILU, scale=scale, scale_dev=scale_dev,
+              residual=epi in RESIDUAL, residual_lo=epi == "wide2", inputs=row["inputs"], weights=row["weights"])
+    if epi in SHARED:                  # one source for the whole launch: the first case draws it, the other groups' cases are handed it
+        nsrc, cases = sum(Ns) // SHARED[epi], []
+        assert nsrc * SHARED[epi] == sum(Ns)
+        for i, n in enumerate(Ns):
+            cases.append(nm.conv_case(n, g["H"], g["W"], C1, Cout, row["dtype"], seed=seed + 7 * i, nsrc=nsrc, first=sum(Ns[:i]),
+                                      src=cases[0]["x_src"] if i else None, **kw))
+        assert len(Ns) == 1 or epi == "conv_in" or any(c["first"] % nsrc for c in cases)      # a group that starts off a multiple of nsrc
+        return cases
     return [nm.conv_case(n, g["H"], g["W"], C1, Cout, row["dtype"], seed=seed + 7 * i, **kw) for i, n in enumerate(Ns)]
 
 
 def sample_counts(row):
     """N = 1 and N = 3 (tiles straddle sample boundaries); one larger N where three samples are under CONV_MIN_ELEMENTS outputs, so
-    that the misrounded bar has something to bite on; grouped launches: two weight sets over whole tiles"""
+    that the misrounded bar has something to bite on; grouped launches: two weight sets over whole tiles.  A geometry that names its
+    sample counts (GEOMS[..]["Ns"]) gets those.  A shared source (x_rep = 3) takes multiples of 3: 3 and 6 samples (a source of one and
+    of two), a named count rounded down to one (3, 75 = 3 x 25, 231 = 3 x 77, 384 = 3 x 128 rows).  The single grouped forms: GROUPS"""
     Hout, Wout = _geometry(row)["out_hw"]
     hw, Cout = Hout * Wout, CHANNELS[row["chan"]][2]
+    rep = SHARED.get(row["epi"], 1)
+    if row["epi"] in GROUPS:
+        return [GROUPS[row["epi"]]]
+    if "Ns" in GEOMS[row["geom"]]:
+        return [[max(rep, n // rep * rep) for n in ns] for ns in GEOMS[row["geom"]]["Ns"]]
+    if rep > 1:
+        out = [[rep], [2 * rep]]
+        if 2 * rep * hw * Cout < nm.CONV_MIN_ELEMENTS:
+            big = -(-nm.CONV_MIN_ELEMENTS // (hw * Cout * rep)) * rep
+            if big <= 160:
+                out.append([big])
+        return out
     if row["epi"] == "grouped":
         gran = 256 if row["tile"] == "t320" else 128
         unit = gran // math.gcd(gran, hw)
@@ -496,7 +636,7 @@ def sample_counts(row):
 def twin_of(row):
     """the variant the existing tests require the row's tile to equal bit for bit (test_conv_gemm_small_tile_equals_default_tile,
     ..._eight_wave_tile_equals_four_wave_tile, ..._big_tile_equals_small_tile): the 4-wave 128-pixel tile, same K order and slices"""
-    if row["tile"] == "t4w" or row["epi"] == "gn_part":
+    if row["tile"] == "t4w" or row["epi"] in GN_PART:
         return None
     return dict(row, tile="t4w", stages=2)
 
@@ -515,6 +655,13 @@ def run_row(row):
             n = c["N"]
             check(fails, tag + (f" group {gi}" if len(cases) > 1 else ""), row, c, r["y"][a:a + n], None if r["lo"] is None else r["lo"][a:a + n])
             a += n
+        if (row["geom"], row["tile"], row["epi"]) == ZERO_SCALE:          # conditioning_scale = 0: the device scalar at 0.0
+            z = launch(row, cases, dev_scale=0.0)
+            zero = bool((z["y"] == 0).all()) and bool(torch.isfinite(z["y"]).all())
+            print(f"numerics: {tag}: device scale 0.0: every element == 0 and finite: {zero}", flush=True)
+            fails += [f"{tag} (device scale 0.0): {p}" for p in z["problems"]]
+            if not zero:
+                fails.append(f"{tag}: device scale 0.0 leaves {int((z['y'] != 0).sum())} elements that are not 0, {int((~torch.isfinite(z['y'])).sum())} not finite")
         tw = twin_of(row)
         if tw is not None and "non-square" in row_classes(row):
             r2 = launch(tw, cases)

@@ -482,6 +482,79 @@ def test_planted_geometry_defects_in_the_convolution_exceed_the_bars(defect, sha
         assert torch.equal(nm.conv_base_alg(sq, 8, defect=defect), nm.conv_base_alg(sq, 8))
 
 
+def _group_of_five(dtype):
+    """the second weight group of a grouped launch over a shared source of two samples: five samples that start at launch index 3"""
+    first = nm.conv_case(3, 8, 16, 64, 96, dtype, nsrc=2, seed=23)
+    return nm.conv_case(5, 8, 16, 64, 96, dtype, src=first["x_src"], first=3, seed=24)
+
+
+SOURCE_AND_SCALE_DEFECTS = [  # defect, the case it is planted in, split-K
+    ("mod_per_tile", lambda dt: nm.conv_case(6, 9, 12, 64, 96, dt, rep=3, seed=25), 1),         # 108 pixels per sample: tiles straddle samples
+    ("mod_in_group", _group_of_five, 1),                                                         # 3 % 2 != 0
+    ("dev_scale_dropped_in_reduce", lambda dt: nm.conv_case(3, 9, 12, 64, 96, dt, scale=0.5, scale_dev=0.7, seed=26), 2),
+    ("scale_before_act", lambda dt: nm.conv_case(3, 9, 12, 64, 96, dt, silu=True, scale=1 / 1.702, seed=27), 1),
+]
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("defect,make,splitk", SOURCE_AND_SCALE_DEFECTS, ids=[d for d, _, _ in SOURCE_AND_SCALE_DEFECTS])
+def test_planted_source_and_scale_defects_in_the_convolution_exceed_the_bars(defect, make, splitk, dtype):
+    """a shared source's modulo taken once per tile, or of the index inside the weight group; a device scale the split-K reduce forgets;
+    a scale applied in front of the SiLU: each is outside the misrounded bar AND outside the row_err bars at the shape it is planted
+    in, and the design - on the same case - is inside both"""
+    c = make(dtype)
+    ref = nm.conv_ref64(c)
+    assert ref.numel() >= nm.CONV_MIN_ELEMENTS
+    cnt = _conv_counts(c, ref, splitk)
+    bar = nm.misrounded_bar(cnt.values())
+    good, bad = nm.conv_base_alg(c, 8, splitk), nm.conv_base_alg(c, 8, splitk, defect=defect)
+    n_bad = nm.misrounded(bad, ref, dtype, count=True)
+    e_bad, e_alg, e_ref = nm.row_err(bad, ref), nm.row_err(good, ref), nm.row_err(nm.conv_base_ref(c), ref)
+    print(f"conv {defect} {dtype}: misrounded {n_bad / ref.numel():.2%} (design {cnt['alg8'] / ref.numel():.4%}, bar {bar / ref.numel():.3%})  "
+          f"row_err {e_bad:.2e} (design {e_alg:.2e}, base_ref {e_ref:.2e})")
+    assert cnt["alg8"] <= nm.misrounded_bar([cnt["alg32"], cnt["torch32"]]) and 0 < e_alg <= nm.MARGIN * e_ref, (defect, cnt, e_alg, e_ref)
+    assert n_bad > bar and n_bad > 0.01 * ref.numel(), (defect, n_bad, bar)
+    assert e_bad > _bar(e_alg, e_ref), (defect, e_bad, e_alg, e_ref)
+    if defect == "mod_per_tile":                 # ... and invisible where every tile lies inside one sample: why the straddling rows are needed
+        whole = nm.conv_case(6, 8, 16, 64, 96, dtype, rep=3, seed=25)
+        assert (whole["out_hw"][0] * whole["out_hw"][1]) % nm.BM_CONV == 0
+        assert torch.equal(nm.conv_base_alg(whole, 8, defect=defect), nm.conv_base_alg(whole, 8))
+    if defect == "mod_in_group":                 # ... and invisible in a group that starts on a multiple of nsrc
+        even = nm.conv_case(5, 8, 16, 64, 96, dtype, src=c["x_src"], first=2, seed=24)
+        assert torch.equal(nm.conv_base_alg(even, 8, defect=defect), nm.conv_base_alg(even, 8))
+    if defect == "dev_scale_dropped_in_reduce":  # ... and in the fused epilogue of an unsplit launch
+        assert torch.equal(nm.conv_base_alg(c, 8, 1, defect=defect), nm.conv_base_alg(c, 8, 1))
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_conv_case_with_a_shared_source_equals_the_repeated_tensor(dtype):
+    """conv_case(rep=3): "x" is "x_src" repeated along the batch, and every reference of the case equals that of a case that was handed
+    the repeated tensor as an ordinary source"""
+    for kw in [dict(H=5, W=7), dict(H=1, W=1, k=1), dict(H=9, W=12, stride=2), dict(H=3, W=8, upsample=True)]:
+        c = nm.conv_case(6, C1=64, Cout=24, dtype=dtype, rep=3, seed=28, **kw)
+        assert c["nsrc"] == 2 and c["x_src"].shape[0] == 2 and c["x"].shape[0] == 6 and torch.equal(c["x"], c["x_src"].repeat(3, 1, 1, 1))
+        plain = dict(c, x=c["x_src"].repeat(3, 1, 1, 1).contiguous(), x_src=None, nsrc=0)
+        for f in (nm.conv_ref64, nm.conv_base_ref, nm.conv_torch32, nm.conv_base_alg):
+            assert torch.equal(f(c), f(plain)), (kw, f.__name__)
+        assert all(torch.equal(a, b) for a, b in zip(nm.conv_im2col(c), nm.conv_im2col(plain)))
+    g = _group_of_five(dtype)
+    assert [int(i) for i in (3 + torch.arange(5)) % 2] == [1, 0, 1, 0, 1] and torch.equal(g["x"][0], g["x_src"][1]) and torch.equal(g["x"][1], g["x_src"][0])
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_conv_case_with_a_device_scale_equals_the_fp32_product_as_out_scale(dtype):
+    """scale_dev: the references multiply by float32(out_scale) * float32(dev), one fp32 product as `scale *= *p.out_scale_dev` forms it"""
+    kw = dict(N=3, H=9, W=12, C1=64, Cout=96, dtype=dtype, residual=True, seed=29)
+    c = nm.conv_case(scale=0.5, scale_dev=0.7, **kw)
+    prod = float(torch.tensor(0.5, dtype=torch.float32) * torch.tensor(0.7, dtype=torch.float32))
+    assert c["scale"] == prod and c["scale_host"] == 0.5 and c["scale_dev"] == float(torch.tensor(0.7, dtype=torch.float32))
+    one = nm.conv_case(scale=prod, **kw)
+    assert one["scale_dev"] is None and one["scale"] == one["scale_host"] == prod
+    for sk in (1, 3):
+        assert torch.equal(nm.conv_base_alg(c, 8, sk), nm.conv_base_alg(one, 8, sk))
+    assert torch.equal(nm.conv_ref64(c), nm.conv_ref64(one)) and torch.equal(nm.conv_base_ref(c), nm.conv_base_ref(one))
+
+
 # ----------------------------------------------------------------------------------------------------------------
 # the fusion block
 # ----------------------------------------------------------------------------------------------------------------
