@@ -151,6 +151,7 @@ class ClipVisionConfig(C.Structure):    # es_clip_vision_config
 
 FILTER_BILINEAR, FILTER_BICUBIC = 0, 1           # ES_FILTER_*
 CROP_TORCHVISION, CROP_TRANSFORMERS = 0, 1       # ES_CROP_*
+MASK_AND, MASK_OR, MASK_ANDNOT = 0, 1, 2         # ES_MASK_*
 
 
 class Tensor(C.Structure):          # es_tensor
@@ -368,6 +369,12 @@ SYMBOLS = {
     "es_prompt_table_destroy": (None, [_P]),
     "es_prompt_assemble": (C.c_int, [_P, _P, _I, _I, _P, _P, _P]),
     "es_prompt_assemble_host": (C.c_int, [_P, C.POINTER(C.c_int32), _I, _I, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "es_mask_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
+    "es_mask_morph": (C.c_int, [_P, _P, _I, _I, _I, C.POINTER(C.c_int32), _I, _P, C.c_size_t, _P]),
+    "es_mask_largest_component": (C.c_int, [_P, _P, _P, _I, _I, _I, _P, C.c_size_t, _P]),
+    "es_mask_logic": (C.c_int, [_P, _P, _P, _L, _I, _P]),
+    "es_image_mask_fill_u8": (C.c_int, [C.POINTER(ImageU8), _P, _P, _I, _I, _I, C.POINTER(C.c_uint8), _P]),
+    "es_sam_compose": (C.c_int, [C.POINTER(ImageU8), _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, C.c_size_t, _P]),
 }
 
 _lib = None

@@ -1216,6 +1216,117 @@ def image_f32_to_u8(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torc
 
 
 # ----------------------------------------------------------------------------------------------------------------
+# mask post-processing (csrc/mask.hip): bit-packed morphology, largest 8-connected component, boolean algebra, draw_binary_mask
+# and create_sam_images in one call.  Masks are uint8 (or bool) device tensors [count, H, W]; results are uint8 of 0 / 1.
+# ----------------------------------------------------------------------------------------------------------------
+def _mask_operand(t: torch.Tensor, what: str, shape=None) -> torch.Tensor:
+    if not torch.is_tensor(t) or t.dtype not in (torch.uint8, torch.bool) or not t.is_cuda:
+        raise L.EdgeStyleHipError(f"{what}: a mask must be a uint8 or bool device tensor")
+    if t.dim() != 3 or min(t.shape) < 1 or not t.is_contiguous():
+        raise L.EdgeStyleHipError(f"{what}: a mask must be a dense [count, H, W] tensor, got {tuple(t.shape)} with strides {t.stride()}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise L.EdgeStyleHipError(f"{what}: masks of one call must have one shape ({tuple(t.shape)} vs {tuple(shape)})")
+    return t.view(torch.uint8) if t.dtype == torch.bool else t
+
+
+def _mask_out(out: Optional[torch.Tensor], shape, dev, what: str) -> torch.Tensor:
+    if out is None:
+        return torch.empty(shape, dtype=torch.uint8, device=dev)
+    if out.dtype != torch.uint8 or out.device != dev or tuple(out.shape) != tuple(shape) or not out.is_contiguous():
+        raise L.EdgeStyleHipError(f"{what}: out must be a contiguous uint8 {tuple(shape)} tensor on {dev}")
+    return out
+
+
+def mask_workspace_bytes(H: int, W: int, count: int) -> int:
+    need = int(L.load().es_mask_workspace_bytes(int(H), int(W), int(count)))
+    if need == 0:
+        L.check(-1, "es_mask_workspace_bytes")
+    return need
+
+
+def _mask_workspace(workspace: Optional[torch.Tensor], H: int, W: int, count: int, dev, what: str) -> torch.Tensor:
+    if workspace is None:
+        return torch.empty((mask_workspace_bytes(H, W, count),), dtype=torch.uint8, device=dev)
+    if workspace.dtype != torch.uint8 or workspace.device != dev or not workspace.is_contiguous():
+        raise L.EdgeStyleHipError(f"{what}: workspace must be a contiguous uint8 tensor on {dev}")
+    return workspace
+
+
+def mask_morph(mask: torch.Tensor, radii: Sequence[int], out: Optional[torch.Tensor] = None,
+               workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The chain of clipped-window dilations (r > 0) and erosions (r < 0) `radii`, in order, on [count, H, W]; out may be mask."""
+    m = _mask_operand(mask, "mask_morph")
+    n, H, W = m.shape
+    out = _mask_out(out, m.shape, m.device, "mask_morph")
+    ws = _mask_workspace(workspace, H, W, n, m.device, "mask_morph")
+    arr = (C.c_int32 * max(len(radii), 1))(*[int(r) for r in radii])
+    L.check(L.load().es_mask_morph(_ptr(m), _ptr(out), n, H, W, arr, len(radii), _ptr(ws), ws.numel(), _stream()), "es_mask_morph")
+    return out
+
+
+def mask_largest_component(mask: torch.Tensor, out: Optional[torch.Tensor] = None, area_out: Optional[torch.Tensor] = None,
+                           workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The largest 8-connected component of each mask (ties: the one that starts first in row-major order; no true pixel: all
+    true, as the reference's labeled_array == 0).  area_out: int32 [count] device tensor that receives the winners' areas."""
+    m = _mask_operand(mask, "mask_largest_component")
+    n, H, W = m.shape
+    out = _mask_out(out, m.shape, m.device, "mask_largest_component")
+    if area_out is not None and (area_out.dtype != torch.int32 or area_out.device != m.device or tuple(area_out.shape) != (n,)
+                                 or not area_out.is_contiguous()):
+        raise L.EdgeStyleHipError(f"mask_largest_component: area_out must be a contiguous int32 [{n}] tensor on {m.device}")
+    ws = _mask_workspace(workspace, H, W, n, m.device, "mask_largest_component")
+    L.check(L.load().es_mask_largest_component(_ptr(m), _ptr(out), _ptr(area_out), n, H, W, _ptr(ws), ws.numel(), _stream()),
+            "es_mask_largest_component")
+    return out
+
+
+def mask_logic(a: torch.Tensor, b: torch.Tensor, op: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """a op b for op in L.MASK_AND | L.MASK_OR | L.MASK_ANDNOT (a & ~b); out may be a or b."""
+    a = _mask_operand(a, "mask_logic")
+    b = _mask_operand(b, "mask_logic", a.shape)
+    out = _mask_out(out, a.shape, a.device, "mask_logic")
+    L.check(L.load().es_mask_logic(_ptr(a), _ptr(b), _ptr(out), a.numel(), int(op), _stream()), "es_mask_logic")
+    return out
+
+
+def image_mask_fill_u8(images: Optional[Sequence[torch.Tensor]], mask: torch.Tensor, colour, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """draw_binary_mask for count images: [count, H, W, 3] that keeps images[i] where mask[i] is true and is `colour` elsewhere;
+    images None: images of zeros."""
+    m = _mask_operand(mask, "image_mask_fill_u8")
+    n, H, W = m.shape
+    descs = None
+    if images is not None:
+        if len(images) != n:
+            raise L.EdgeStyleHipError(f"image_mask_fill_u8: {len(images)} images for {n} masks")
+        descs = image_descriptors(images, "image_mask_fill_u8")
+    out = _mask_out(out, (n, H, W, 3), m.device, "image_mask_fill_u8")
+    col = (C.c_uint8 * 3)(*[int(c) for c in colour])
+    L.check(L.load().es_image_mask_fill_u8(descs, _ptr(m), _ptr(out), n, H, W, col, _stream()), "es_image_mask_fill_u8")
+    return out
+
+
+def sam_compose(images: Optional[Sequence[torch.Tensor]], subject: torch.Tensor, body: torch.Tensor, clothes: torch.Tensor,
+                head: torch.Tensor, want_masks: bool = True, want_images: bool = True, masks_out: Optional[torch.Tensor] = None,
+                images_out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
+    """create_sam_images after the networks, one call: -> (masks [count, 4, H, W]: all, agnostic, clothes, head | None,
+    images [count, 5, H, W, 3]: subject, mask, agnostic, clothes, head | None)."""
+    s = _mask_operand(subject, "sam_compose")
+    b, c, h = (_mask_operand(t, "sam_compose", s.shape) for t in (body, clothes, head))
+    n, H, W = s.shape
+    descs = None
+    if want_images:
+        if images is None or len(images) != n:
+            raise L.EdgeStyleHipError(f"sam_compose: {n} images are needed for {n} sets of masks")
+        descs = image_descriptors(images, "sam_compose")
+    masks_out = _mask_out(masks_out, (n, 4, H, W), s.device, "sam_compose") if want_masks else None
+    images_out = _mask_out(images_out, (n, 5, H, W, 3), s.device, "sam_compose") if want_images else None
+    ws = _mask_workspace(workspace, H, W, n, s.device, "sam_compose")
+    L.check(L.load().es_sam_compose(descs, _ptr(s), _ptr(b), _ptr(c), _ptr(h), n, H, W, _ptr(masks_out), _ptr(images_out), _ptr(ws),
+                                    ws.numel(), _stream()), "es_sam_compose")
+    return masks_out, images_out
+
+
+# ----------------------------------------------------------------------------------------------------------------
 # seeded noise: torch's device Philox stream restated (csrc/rng.hip)
 _ROUND = {None: L.ES_F32, torch.float32: L.ES_F32, torch.float16: L.ES_F16, torch.bfloat16: L.ES_BF16}
 

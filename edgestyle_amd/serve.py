@@ -7,8 +7,9 @@ GPU: the current pair is in the bench line, `value` against `throughput_mode.val
 within `max_wait_s` of each other run as ONE pipeline call of up to `max_batch` images, each with its own latents
 drawn from its own seed — a request's image does not depend on what it was batched with (tests/test_host_cpu.py).
 
-Host logic only (a queue, a worker thread, futures); the Gradio UI, the YOLO / OpenPose / SAM preprocessing and the
-CLIP prompt picker of app.py:125-149 are out of scope.  Multi-GPU: one `TryOnService` per rank, the
+Host logic only (a queue, a worker thread, futures); the Gradio UI, the YOLO / OpenPose / SAM networks of `preprocess`
+(app.py:125-149) and the CLIP prompt picker are out of scope here.  What `preprocess` computes AFTER its
+networks - from the four SAM masks to the images a request carries - is `edgestyle_amd.masks.create_sam_images`.  Multi-GPU: one `TryOnService` per rank, the
 front end deals requests round-robin (independent images) — no collective on the request path.
 """
 from __future__ import annotations

@@ -1022,6 +1022,56 @@ int es_prompt_assemble(const es_prompt_table* t, const int32_t* topk_dev, int n,
 /* the same rows from HOST topk into HOST memory, by the kernel's own index code */
 int es_prompt_assemble_host(const es_prompt_table* t, const int32_t* topk, int n, int k, int32_t* ids_out, int32_t* eos_pos);
 
+/* =========================================================================================================
+ * Mask post-processing (csrc/mask.hip): the arithmetic the reference runs between a segmenter's mask predictions and the images
+ * try_on takes (extract_dataset.py:316-351 and :394-502, composed differently in inference.py:322-447), restated.  All of it is
+ * integer-exact.  Masks are DEVICE uint8 [count, H, W]: nonzero reads as true, outputs are exactly 0 or 1.  H and W are each in
+ * 1..4096 (no alignment asked), count in 1..4096.  Inside the library a mask is bit-packed, 64 pixels per word.
+ *   Morphology: dilate by r = OR over the (2r+1)^2 window CLIPPED to the image, erode by r = AND over the clipped window; pixels
+ *   outside the image never contribute.  That is cv2.dilate / cv2.erode with their default border, with a full k x k kernel and
+ *   `iterations` = n at r = n(k-1)/2 (cv2 itself enlarges the kernel and runs once), and skimage's closing(x, square(k)) =
+ *   erode(dilate(x)) at r = (k-1)/2.  smooth_mask(kernel_size 3, iterations 3) is the chain {+3, -3, -3, +3}.
+ *   Largest component: 8-connectivity (skimage.measure.label's default in 2-D), area = pixel count, a tie goes to the component
+ *   whose first pixel in row-major order comes first (the reference keeps `region.area > largest_area` over regions in label order).
+ *   A mask with no true pixel gives an ALL-TRUE result: the reference then compares labeled_array == 0.  Restated, not repaired.
+ * Integer atomics only: a result does not depend on the order of execution.  The number of launches depends on the arguments
+ * alone, never on the pixels; nothing is allocated or read back: every call is capturable.  Like the byte-image calls none of
+ * these is part of a plan (-1 while one records on the thread), so ES_ABI_VERSION stays as it is.
+ * ========================================================================================================= */
+/* host-only: bytes of device scratch that every call below needs at most for `count` masks of H x W (es_sam_compose's need: ten
+ * packed masks and two int32 [H, W] arrays per image); 0 with es_last_error() set on bad arguments.  The workspace must be
+ * 8-byte aligned. */
+size_t es_mask_workspace_bytes(int H, int W, int count);
+/* radii: HOST int32 [n], n <= 16, applied in order: r > 0 dilates by r, r < 0 erodes by -r, 0 does nothing; |r| <= 15.
+ * in and out may be the same pointer.  One launch per nonzero radius, plus the packing and the unpacking. */
+int es_mask_morph(const uint8_t* in, uint8_t* out, int count, int H, int W, const int32_t* radii, int n, void* ws, size_t ws_bytes,
+                  void* stream);
+/* out = the largest 8-connected component of each mask (all true for a mask without a true pixel, see above); area_out: DEVICE
+ * int32 [count] or NULL, the winner's pixel count (0 for a mask without a true pixel).  in and out may be the same pointer.
+ * Union-find on an int32 [H, W] array whose links always point to a smaller linear index: the root of a component is its first
+ * pixel in row-major order. */
+int es_mask_largest_component(const uint8_t* in, uint8_t* out, int32_t* area_out, int count, int H, int W, void* ws, size_t ws_bytes,
+                              void* stream);
+enum { ES_MASK_AND = 0, ES_MASK_OR = 1, ES_MASK_ANDNOT = 2 };      /* a & b, a | b, a & ~b */
+/* out[i] = a[i] op b[i] over n bytes read as booleans; out may be a or b */
+int es_mask_logic(const uint8_t* a, const uint8_t* b, uint8_t* out, int64_t n, int op, void* stream);
+/* draw_binary_mask: out_hwc3 [count, H, W, 3] keeps the pixels of img[i] (H x W; a fourth channel is ignored and the row stride
+ * honoured, as in the byte-image calls) where mask [count, H, W] is true and is `colour` elsewhere.  img_or_null: HOST array of
+ * `count` descriptors, or NULL for images of zeros. */
+int es_image_mask_fill_u8(const es_image_u8* img_or_null, const uint8_t* mask, uint8_t* out_hwc3, int count, int H, int W,
+                          const uint8_t colour[3], void* stream);
+/* create_sam_images (app.py:125-149 -> extract_dataset.py:394-502) after the networks: with sm = {+3, -3, -3, +3} and cK =
+ * closing(square(K)) = {+(K-1)/2, -(K-1)/2},
+ *   S = sm(c3(subject))  A = sm(c3(body))  C = sm(c3(clothes))  Hd = sm(c7(head))  ALL = sm(largest(S | C | Hd))
+ *   agnostic = A & ~(A & C) & ALL   clothes_m = C & ~(A & C) & ALL   head_m = Hd & ALL
+ * imgs: HOST array of `count` descriptors of H x W photos; subject / body / clothes / head: [count, H, W] each.
+ * masks_out [count, 4, H, W]: ALL, agnostic, clothes_m, head_m.  images_out [count, 5, H, W, 3]: the photo where ALL holds and grey
+ * 127 elsewhere; the reference's `mask` (black where agnostic holds, white 255 elsewhere); the photo under agnostic,
+ * under clothes_m and under head_m on grey 127.  Either output may be NULL (not both).  The score test, getBox and which image goes
+ * to which slot stay with the caller. */
+int es_sam_compose(const es_image_u8* imgs, const uint8_t* subject, const uint8_t* body, const uint8_t* clothes, const uint8_t* head,
+                   int count, int H, int W, uint8_t* masks_out, uint8_t* images_out, void* ws, size_t ws_bytes, void* stream);
+
 
 #ifdef __cplusplus
 }
