@@ -752,25 +752,32 @@ struct Resnet {
     if (has_short && cout % 64 == 0 && cin % 64 == 0) conv2s = B.conv_tail(W, p + ".conv2", p + ".conv_shortcut");
     else { conv2 = B.conv(W, p + ".conv2"); if (has_short) shortc = B.conv(W, p + ".conv_shortcut"); }
   }
-  // tproj: [rows, width] table of all time projections (null: the VAE's resnets)
-  T run(Builder& B, const T& x, const T& tproj, const T& x2 = T()) const {
-    T h = B.group_norm(x, n1, groups, eps, true, x2);
-    CA a;
-    if (temb_off >= 0) { a.temb = tproj.chan(temb_off, tproj.c - temb_off); a.temb_stride = tproj.ld; }
-    a.gn_groups = groups;
-    h = B.conv_gemm(h, conv1, a);
-    h = B.group_norm(h, n2, groups, eps, true);
-    if (conv2s) {
-      if (x2 && (x.c % 64 || x2.c % 64)) fail("builder: skip concat with channels that are not multiples of 64");
-      CA t; t.tails.push_back(x); if (x2) t.tails.push_back(x2); t.gn_groups = groups;
-      return B.conv_gemm(h, conv2s, t);
-    }
-    T xs = x;
-    if (shortc) { CA s; s.x2 = x2; xs = B.conv_gemm(x, shortc, s); }
-    CA r; r.residual = xs; r.wide = true; r.gn_groups = groups;
-    return B.conv_gemm(h, conv2, r);
-  }
 };
+
+// ResnetBlock2D of every net in `rs` as one launch per layer (engine.resnet_block): x is the batch concatenation of the nets' activations,
+// `counts` the samples of each.  One net is a group of one with an empty `counts`: its launches carry no group table.
+// tproj: [rows, width] table of all time projections (null: the VAE's resnets); x2: the UNet decoder's skip concat
+T run_resnet(Builder& B, const std::vector<const Resnet*>& rs, const std::vector<int>& counts, const T& x, const T& tproj, const T& x2 = T()) {
+  const Resnet* r0 = rs[0];
+  if (x2 && rs.size() > 1) fail("builder: a skip concat with more than one group has no launch");
+  std::vector<Norm> n1, n2; PWs c1, c2, c2s, sh; bool all_s = true;
+  for (auto r : rs) { n1.push_back(r->n1); n2.push_back(r->n2); c1.push_back(r->conv1); c2.push_back(r->conv2); c2s.push_back(r->conv2s); sh.push_back(r->shortc); if (!r->conv2s) all_s = false; }
+  T h = B.group_norm(x, n1, r0->groups, r0->eps, true, x2, counts);
+  CA a; a.group_n = counts; a.gn_groups = r0->groups;
+  if (r0->temb_off >= 0) { a.temb = tproj.chan(r0->temb_off, tproj.c - r0->temb_off); a.temb_stride = tproj.ld; }
+  h = B.conv_gemm(h, c1, a);
+  h = B.group_norm(h, n2, r0->groups, r0->eps, true, T(), counts);
+  if (all_s) {
+    if (x2 && (x.c % 64 || x2.c % 64)) fail("builder: skip concat with channels that are not multiples of 64");
+    CA t; t.tails.push_back(x); if (x2) t.tails.push_back(x2); t.group_n = counts; t.gn_groups = r0->groups;
+    return B.conv_gemm(h, c2s, t);
+  }
+  for (auto r : rs) if (r->conv2s) fail("builder: grouped resnets must fold conv_shortcut all alike");
+  T xs = x;
+  if (r0->shortc) { CA s; s.x2 = x2; s.group_n = counts; xs = B.conv_gemm(x, sh, s); }
+  CA r; r.residual = xs; r.group_n = counts; r.wide = true; r.gn_groups = r0->groups;
+  return B.conv_gemm(h, c2, r);
+}
 
 struct Transformer {               // Transformer2DModel(use_linear_projection False) + one BasicTransformerBlock, all folds on
   Norm norm;
@@ -872,6 +879,57 @@ struct Encoder {                   // conv_in + time_embedding + down_blocks + m
     return B.linear(e, tproj);
   }
 };
+
+// Transformer2DModel of every net in `ts` in lockstep (engine.transformer_block, folded paths; run_resnet's conventions): attention is one
+// launch over the whole batch.  kv: Transformer::context of the same rows
+T run_transformer(Builder& B, const std::vector<const Transformer*>& ts, const std::vector<int>& counts, const T& x, const T& kv) {
+  const Transformer* t0 = ts[0];
+  const int Nn = x.n, H = x.h, Wd = x.w, C = x.c;
+  std::vector<int> rows;
+  for (int n : counts) rows.push_back(n * H * Wd);
+  std::vector<Norm> nl; PWs pin, qkv, o1, q2, o2, ff1, ffo;
+  for (auto t : ts) { nl.push_back(t->norm); pin.push_back(t->proj_in); qkv.push_back(t->qkv_ln); o1.push_back(t->o1); q2.push_back(t->q2_ln); o2.push_back(t->o2); ff1.push_back(t->ff1_ln); ffo.push_back(t->ffo); }
+  T tok = B.gn_proj_in(x, nl, t0->groups, 1e-6f, pin, counts).view(Nn, H * Wd, 1, C);
+  CA gr; gr.group_n = rows;
+  T q = B.linear(tok, qkv, gr);
+  T a = B.attention(q.chan(0, C), q.chan(C, C), q.chan(2 * C, C), t0->heads);
+  CA r1 = gr; r1.residual = tok; r1.wide = true;
+  tok = B.linear(a, o1, r1);
+  T qq = B.linear(tok, q2, gr);
+  a = B.attention(qq, kv.chan(0, C), kv.chan(C, C), t0->heads);
+  CA r2 = gr; r2.residual = tok; r2.wide = true;
+  tok = B.linear(a, o2, r2);
+  T f = B.linear(tok, ff1, gr);
+  CA fo; fo.x2 = tok.view(Nn, H, Wd, C); fo.residual = x; fo.group_n = counts; fo.wide = true; fo.gn_groups = t0->groups;
+  return B.conv_gemm(f.view(Nn, H, Wd, 4 * C), ffo, fo);
+}
+
+// down blocks + mid block of encoders of one architecture in lockstep (engine.encoder_pass).  hh: conv_in's output over the whole batch
+// (each group's conv_in(sample) + cond already applied) -> (skips, mid); ctx: one K/V tensor per transformer, same rows
+void run_encoder(Builder& B, const std::vector<const Encoder*>& es, const std::vector<int>& counts, T hh, const T& tproj, const std::vector<T>& ctx,
+                 std::vector<T>& skips, T& mid) {
+  const Encoder* e0 = es[0];
+  skips.push_back(hh);
+  int ci = 0;
+  auto rs_of = [&](auto f) { std::vector<const Resnet*> v; for (auto e : es) v.push_back(f(e)); return v; };
+  auto ts_of = [&](int ti) { std::vector<const Transformer*> v; for (auto e : es) v.push_back(&e->tr[ti]); return v; };
+  for (size_t i = 0; i < e0->down.size(); ++i) {
+    for (size_t j = 0; j < e0->down[i].size(); ++j) {
+      hh = run_resnet(B, rs_of([&](const Encoder* e) { return &e->down[i][j].first; }), counts, hh, tproj);
+      if (e0->down[i][j].second >= 0) { hh = run_transformer(B, ts_of(e0->down[i][j].second), counts, hh, ctx[ci]); ++ci; }
+      skips.push_back(hh);
+    }
+    if (e0->downsample[i]) {
+      PWs ds; for (auto e : es) ds.push_back(e->downsample[i]);
+      CA a; a.stride = 2; a.group_n = counts; a.gn_groups = e0->cfg.groups;
+      hh = B.conv_gemm(hh, ds, a);
+      skips.push_back(hh);
+    }
+  }
+  hh = run_resnet(B, rs_of([](const Encoder* e) { return &e->mid0; }), counts, hh, tproj);
+  hh = run_transformer(B, ts_of(e0->mid_attn), counts, hh, ctx[ci]);
+  mid = run_resnet(B, rs_of([](const Encoder* e) { return &e->mid1; }), counts, hh, tproj);
+}
 
 struct UNet : Encoder {
   std::vector<std::vector<std::pair<Resnet, int>>> up;
@@ -988,19 +1046,19 @@ struct VAE {
     d_out = B.conv(W, "decoder.conv_out");
   }
   T run_mid(Builder& B, const Mid& m, T h) const {
-    h = m.r0.run(B, h, T());
+    h = run_resnet(B, {&m.r0}, {}, h, T());
     const int N = h.n, H = h.h, Wd = h.w, C = h.c;
     T n = B.group_norm(h, m.gn, cfg.groups, cfg.eps, false).view(N, H * Wd, 1, C);
     T qkv = B.linear(n, m.qkv);
     T a = B.attention(qkv.chan(0, C), qkv.chan(C, C), qkv.chan(2 * C, C), 1);
     CA r; r.residual = h.view(N, H * Wd, 1, C);
     h = B.linear(a, m.o, r).view(N, H, Wd, C);
-    return m.r1.run(B, h, T());
+    return run_resnet(B, {&m.r1}, {}, h, T());
   }
   T encode_moments(Builder& B, const T& img) const {       // [N,H,W,8 (3 real)] -> moments [N,H/8,W/8,2L]
     T h = B.conv_gemm(img, e_in);
     for (const auto& blk : e_down) {
-      for (const auto& r : blk.first) h = r.run(B, h, T());
+      for (const auto& r : blk.first) h = run_resnet(B, {&r}, {}, h, T());
       if (blk.second) { CA a; a.stride = 2; a.pad = 0; a.out_h = h.h / 2; a.out_w = h.w / 2; h = B.conv_gemm(h, blk.second, a); }   // F.pad(0,1,0,1) + conv s2 p0
     }
     h = run_mid(B, e_mid, h);
@@ -1013,7 +1071,7 @@ struct VAE {
     h = B.conv_gemm(h, d_in);
     h = run_mid(B, d_mid, h);
     for (const auto& blk : d_up) {
-      for (const auto& r : blk.first) h = r.run(B, h, T());
+      for (const auto& r : blk.first) h = run_resnet(B, {&r}, {}, h, T());
       if (blk.second) { CA a; a.upsample = true; h = B.conv_gemm(h, blk.second, a); }
     }
     h = B.group_norm(h, d_norm, cfg.groups, cfg.eps, true);
@@ -1021,7 +1079,7 @@ struct VAE {
   }
 };
 
-// ---- GroupedEncoder (engine.py) + StepRunner (models.py), grouped lockstep mode ------------------------------------------------
+// ---- StepRunner (models.py) + pipeline._Loop: the steps, grouped lockstep mode (GroupedEncoder's tables; the walk is run_encoder) ----
 struct Model {
   Builder B;
   UCfg ucfg; VCfg vcfg;
@@ -1050,94 +1108,21 @@ struct Model {
   int Bc = 2;                                              // samples the ControlNets run on: the conditional half under CFG
   std::vector<std::vector<T>> ctx_guess;
 
-  std::vector<Norm> norms(const std::vector<const Resnet*>& rs, int which) const { std::vector<Norm> v; for (auto r : rs) v.push_back(which == 1 ? r->n1 : r->n2); return v; }
-
-  T g_resnet(const std::vector<const Resnet*>& rs, const T& x, const T& tproj) {
-    const Resnet* r0 = rs[0];
-    T hh = B.group_norm(x, norms(rs, 1), r0->groups, r0->eps, true, T(), counts);
-    PWs c1, c2, c2s, sh; bool all_s = true;
-    for (auto r : rs) { c1.push_back(r->conv1); c2.push_back(r->conv2); c2s.push_back(r->conv2s); sh.push_back(r->shortc); if (!r->conv2s) all_s = false; }
-    CA a; a.temb = tproj.chan(r0->temb_off, tproj.c - r0->temb_off); a.temb_stride = tproj.ld; a.group_n = counts; a.gn_groups = r0->groups;
-    hh = B.conv_gemm(hh, c1, a);
-    hh = B.group_norm(hh, norms(rs, 2), r0->groups, r0->eps, true, T(), counts);
-    if (all_s) { CA t; t.tails.push_back(x); t.group_n = counts; t.gn_groups = r0->groups; return B.conv_gemm(hh, c2s, t); }
-    for (auto r : rs) if (r->conv2s) fail("builder: grouped resnets must fold conv_shortcut all alike");
-    T xs = x;
-    if (r0->shortc) { CA s; s.group_n = counts; xs = B.conv_gemm(x, sh, s); }
-    CA r; r.residual = xs; r.group_n = counts; r.wide = true; r.gn_groups = r0->groups;
-    return B.conv_gemm(hh, c2, r);
-  }
-  T g_transformer(const std::vector<const Transformer*>& ts, const T& x, const T& kv) {
-    const Transformer* t0 = ts[0];
-    const int Nn = x.n, H = x.h, Wd = x.w, C = x.c;
-    std::vector<int> rows;
-    for (int n : counts) rows.push_back(n * H * Wd);
-    std::vector<Norm> nl; PWs pin, qkv, o1, q2, o2, ff1, ffo;
-    for (auto t : ts) { nl.push_back(t->norm); pin.push_back(t->proj_in); qkv.push_back(t->qkv_ln); o1.push_back(t->o1); q2.push_back(t->q2_ln); o2.push_back(t->o2); ff1.push_back(t->ff1_ln); ffo.push_back(t->ffo); }
-    T tok = B.gn_proj_in(x, nl, t0->groups, 1e-6f, pin, counts).view(Nn, H * Wd, 1, C);
-    CA gr; gr.group_n = rows;
-    T q = B.linear(tok, qkv, gr);
-    T a = B.attention(q.chan(0, C), q.chan(C, C), q.chan(2 * C, C), t0->heads);
-    CA r1 = gr; r1.residual = tok; r1.wide = true;
-    tok = B.linear(a, o1, r1);
-    T qq = B.linear(tok, q2, gr);
-    a = B.attention(qq, kv.chan(0, C), kv.chan(C, C), t0->heads);
-    CA r2 = gr; r2.residual = tok; r2.wide = true;
-    tok = B.linear(a, o2, r2);
-    T f = B.linear(tok, ff1, gr);
-    CA fo; fo.x2 = tok.view(Nn, H, Wd, C); fo.residual = x; fo.group_n = counts; fo.wide = true; fo.gn_groups = t0->groups;
-    return B.conv_gemm(f.view(Nn, H, Wd, 4 * C), ffo, fo);
-  }
-  // h: [ntot,H,W,C0] -> (skips, mid) over the whole batch (GroupedEncoder.run)
-  void g_run(T hh, const T& tproj, std::vector<T>& skips, T& mid) {
-    const Encoder* e0 = encs[0];
-    skips.push_back(hh);
-    int ci = 0;
-    auto rs_of = [&](const std::function<const Resnet*(const Encoder*)>& f) { std::vector<const Resnet*> v; for (auto e : encs) v.push_back(f(e)); return v; };
-    auto ts_of = [&](int ti) { std::vector<const Transformer*> v; for (auto e : encs) v.push_back(&e->tr[ti]); return v; };
-    for (size_t i = 0; i < e0->down.size(); ++i) {
-      for (size_t j = 0; j < e0->down[i].size(); ++j) {
-        hh = g_resnet(rs_of([&](const Encoder* e) { return &e->down[i][j].first; }), hh, tproj);
-        if (e0->down[i][j].second >= 0) { hh = g_transformer(ts_of(e0->down[i][j].second), hh, ctx_grouped[ci]); ++ci; }
-        skips.push_back(hh);
-      }
-      if (e0->downsample[i]) {
-        PWs ds; for (auto e : encs) ds.push_back(e->downsample[i]);
-        CA a; a.stride = 2; a.group_n = counts; a.gn_groups = ucfg.groups;
-        hh = B.conv_gemm(hh, ds, a);
-        skips.push_back(hh);
-      }
-    }
-    hh = g_resnet(rs_of([](const Encoder* e) { return &e->mid0; }), hh, tproj);
-    hh = g_transformer(ts_of(e0->mid_attn), hh, ctx_grouped[ci]);
-    mid = g_resnet(rs_of([](const Encoder* e) { return &e->mid1; }), hh, tproj);
-  }
-  // one transformer of the UNet decoder (engine.Transformer.__call__, folded paths)
-  T transformer(const Transformer& t, const T& x, const T& kv) {
-    const int Nn = x.n, H = x.h, Wd = x.w, C = x.c;
-    T tok = B.gn_proj_in(x, std::vector<Norm>{t.norm}, t.groups, 1e-6f, PWs{t.proj_in}).view(Nn, H * Wd, 1, C);
-    T q = B.linear(tok, t.qkv_ln);
-    T a = B.attention(q.chan(0, C), q.chan(C, C), q.chan(2 * C, C), t.heads);
-    CA r1; r1.residual = tok; r1.wide = true;
-    tok = B.linear(a, t.o1, r1);
-    T qq = B.linear(tok, t.q2_ln);
-    a = B.attention(qq, kv.chan(0, C), kv.chan(C, C), t.heads);
-    CA r2; r2.residual = tok; r2.wide = true;
-    tok = B.linear(a, t.o2, r2);
-    T f = B.linear(tok, t.ff1_ln);
-    CA fo; fo.x2 = tok.view(Nn, H, Wd, C); fo.residual = x; fo.wide = true; fo.gn_groups = t.groups;
-    return B.conv_gemm(f.view(Nn, H, Wd, 4 * C), t.ffo, fo);
-  }
-
   // StepRunner.set_context: every cross-attention K/V projection of the text states, once per call
+  // (guess_mode, StepRunner.set_context(guess_mode=True): the ControlNets see the last Bc rows - the conditional half under CFG - and
+  //  project into ctx_guess, after the UNet instead of before it)
   void set_context() {
+    auto unet_kv = [&] { for (size_t ti = 0; ti < unet.tr.size(); ++ti) unet.tr[ti].context(B, ehs, ctx_unet[ti], 1); };
+    const T ehs_cn = guess ? ehs.batch(N - Bc) : ehs;
+    std::vector<std::vector<T>>& dst = guess ? ctx_guess : ctx_nets;
+    if (guess) unet_kv();
     size_t gi = 0;
     for (const auto& g : groups) {
       const ControlNet& net = *nets[g.first];
-      for (int ti = 0; ti < net.n_enc_tr; ++ti) net.tr[ti].context(B, ehs, ctx_nets[gi][ti], (int)g.second.size());
+      for (int ti = 0; ti < net.n_enc_tr; ++ti) net.tr[ti].context(B, ehs_cn, dst[gi][ti], (int)g.second.size());
       ++gi;
     }
-    for (size_t ti = 0; ti < unet.tr.size(); ++ti) unet.tr[ti].context(B, ehs, ctx_unet[ti], 1);
+    if (!guess) unet_kv();
   }
   void set_conds() {
     int a = 0;
@@ -1215,7 +1200,7 @@ struct Model {
       tproj = tproj_cur;
     } else tproj = time_proj_generic();
     std::vector<T> skips; T mid;
-    g_run(h0, tproj, skips, mid);
+    run_encoder(B, encs, counts, h0, tproj, ctx_grouped, skips, mid);
     h0 = T();
     std::vector<T> srcs = skips; srcs.push_back(mid);
     std::vector<T> enc;
@@ -1246,6 +1231,13 @@ struct Model {
     srcs.clear(); skips.clear(); enc.clear(); mid = T();
     unet_decoder(fused, tproj.batch(ncn));                  // skip + residual already summed: PL:500-510
   }
+  // UNet.encode: conv_in + down blocks + mid block of the UNet alone, x -> skips (returned: the mid tensor)
+  T unet_encode(const T& x, const T& tp, std::vector<T>& skips) {
+    CA a; a.gn_groups = ucfg.groups;
+    T hh = B.conv_gemm(x, unet.conv_in, a);
+    run_encoder(B, {&unet}, {}, hh, tp, ctx_unet, skips, hh);
+    return hh;
+  }
   // UNet.forward from the (summed) skip / mid tensors on: `fused` = 12 skips + the mid tensor at the back
   void unet_decoder(std::vector<T>& fused, const T& tp) {
     T hh = fused.back();
@@ -1255,8 +1247,8 @@ struct Model {
       for (const auto& ra : unet.up[i]) {
         T skip = fused.back();
         fused.pop_back();
-        hh = ra.first.run(B, hh, tp, skip);
-        if (ra.second >= 0) { hh = transformer(unet.tr[ra.second], hh, ctx_unet[ci]); ++ci; }
+        hh = run_resnet(B, {&ra.first}, {}, hh, tp, skip);
+        if (ra.second >= 0) { hh = run_transformer(B, {&unet.tr[ra.second]}, {}, hh, ctx_unet[ci]); ++ci; }
       }
       if (unet.upsample[i]) { CA a; a.upsample = true; hh = B.conv_gemm(hh, unet.upsample[i], a); }
     }
@@ -1264,33 +1256,7 @@ struct Model {
     CA o; o.out = noise;
     B.conv_gemm(hh, unet.conv_out, o);
   }
-  // Encoder.run of ONE encoder (engine.Encoder.run): h -> (skips, mid)
-  void enc_run(const Encoder& e, T hh, const T& tp, const std::vector<T>& ctx, std::vector<T>& skips, T& mid) {
-    skips.push_back(hh);
-    int ci = 0;
-    for (size_t i = 0; i < e.down.size(); ++i) {
-      for (size_t j = 0; j < e.down[i].size(); ++j) {
-        hh = e.down[i][j].first.run(B, hh, tp);
-        if (e.down[i][j].second >= 0) { hh = transformer(e.tr[e.down[i][j].second], hh, ctx[ci]); ++ci; }
-        skips.push_back(hh);
-      }
-      if (e.downsample[i]) { CA a; a.stride = 2; a.gn_groups = ucfg.groups; hh = B.conv_gemm(hh, e.downsample[i], a); skips.push_back(hh); }
-    }
-    hh = e.mid0.run(B, hh, tp);
-    hh = transformer(e.tr[e.mid_attn], hh, ctx[ci]);
-    mid = e.mid1.run(B, hh, tp);
-  }
-  // ---- guess_mode (StepRunner.set_context(guess_mode=True) / _step_guess; CL:256-264, PL:453-459, 487-497) -------------------------
-  void set_context_guess() {
-    for (size_t ti = 0; ti < unet.tr.size(); ++ti) unet.tr[ti].context(B, ehs, ctx_unet[ti], 1);
-    const T ehs_c = ehs.batch(N - Bc);                      // the ControlNets see the last Bc rows: the conditional half under CFG
-    size_t gi = 0;
-    for (const auto& g : groups) {
-      const ControlNet& net = *nets[g.first];
-      for (int ti = 0; ti < net.n_enc_tr; ++ti) net.tr[ti].context(B, ehs_c, ctx_guess[gi][ti], (int)g.second.size());
-      ++gi;
-    }
-  }
+  // ---- guess_mode (StepRunner._step_guess; CL:256-264, PL:453-459, 487-497) ------------------------------------------------------
   // torch.logspace(-1, 0, n) of dtype float (ATen's CPU kernel fills the second half from the end), as models._guess_level_scales hands it over
   static std::vector<float> guess_level_scales(int n) {
     std::vector<float> ls((size_t)n);
@@ -1314,7 +1280,7 @@ struct Model {
       T h0 = B.empty(k * Bc, x.h, x.w, c0);
       for (int i = 0; i < k; ++i) { CA a; a.residual = conds[g.second[i]]; a.out = h0.batch(i * Bc, Bc); B.conv_gemm(xc, cn.conv_in, a); }
       std::vector<T> skips; T mid;
-      enc_run(cn, h0, tp, ctx_guess[gi], skips, mid);
+      run_encoder(B, {&cn}, {}, h0, tp, ctx_guess[gi], skips, mid);
       std::vector<T> res;
       // (one plain ControlNet: its conditioning scale rides on the same epilogue, StepRunner._cn_scale)
       for (size_t lvl = 0; lvl <= skips.size(); ++lvl) {
@@ -1327,15 +1293,19 @@ struct Model {
     }
     std::vector<T> fused = nn == 1 ? rpn[0] : fuse(rpn, Bc, nullptr);
     T tpu = unet.time_proj(B, t_rows, N);
-    CA ci_; ci_.gn_groups = ucfg.groups;
-    T hh = B.conv_gemm(x, unet.conv_in, ci_);
     std::vector<T> skips;
-    enc_run(unet, hh, tpu, ctx_unet, skips, hh);
+    T hh = unet_encode(x, tpu, skips);
     // torch.cat([zeros, d]) + skip == add into the conditional half (PL:487-497), in place
     for (size_t k2 = 0; k2 < skips.size(); ++k2) { T v = skips[k2].batch(Bh); B.add_into(v, fused[k2].view(v.n, v.h, v.w, v.c), v); }
     { T v = hh.batch(Bh); B.add_into(v, fused.back().view(v.n, v.h, v.w, v.c), v); }
     skips.push_back(hh);
     unet_decoder(skips, tpu);
+  }
+  // the noise prediction -> the next latents and model input, and the device step counter moves on (the tail of both _Loop steps)
+  void scheduler_step() {
+    Builder::ok(es_cfg_ddim_step(noise.ptr(), (float*)latents.ptr(), model_in.ptr(), (const float*)coef.ptr(), (const int32_t*)step_idx.ptr(), geo.cfg ? 7.5f : 1.0f,
+                                 B_, h * w, ucfg.in_ch, model_in.c, geo.cfg, T_, B.dt, nullptr), "es_cfg_ddim_step");
+    Builder::ok(es_incr((int32_t*)step_idx.ptr(), nullptr), "es_incr");
   }
   // pipeline._Loop.one_step_unet / StepRunner.step_unet_only: a step outside every control-guidance window (PL:419-427) - the UNet
   // alone, its skip / mid tensors plus the constant fusion-of-zeros residuals (a single ControlNet: plus nothing)
@@ -1343,10 +1313,8 @@ struct Model {
     B.gather_row(t_table, T_, step_idx, t_rows, kmax * N);
     B.gather_row(tproj_table, T_, step_idx, tproj_cur, (int)((long long)ntot * width * 2 / 4));
     T tp = tproj_cur.batch(ncn);
-    CA ci_; ci_.gn_groups = ucfg.groups;
-    T hh = B.conv_gemm(model_in, unet.conv_in, ci_);
     std::vector<T> skips;
-    enc_run(unet, hh, tp, ctx_unet, skips, hh);
+    T hh = unet_encode(model_in, tp, skips);
     if (nn != 1) {
       if (fused_zero.size() != skips.size() + 1) fail("builder: fusion-of-zeros constants do not match the residual levels");
       for (size_t k = 0; k < skips.size(); ++k) skips[k] = B.add(skips[k], fused_zero[k].view(skips[k].n, skips[k].h, skips[k].w, skips[k].c));
@@ -1354,17 +1322,13 @@ struct Model {
     }
     skips.push_back(hh);
     unet_decoder(skips, tp);
-    Builder::ok(es_cfg_ddim_step(noise.ptr(), (float*)latents.ptr(), model_in.ptr(), (const float*)coef.ptr(), (const int32_t*)step_idx.ptr(), geo.cfg ? 7.5f : 1.0f,
-                                 B_, h * w, ucfg.in_ch, model_in.c, geo.cfg, T_, B.dt, nullptr), "es_cfg_ddim_step");
-    Builder::ok(es_incr((int32_t*)step_idx.ptr(), nullptr), "es_incr");
+    scheduler_step();
   }
   void one_step() {                                         // pipeline._Loop.one_step: PL:435-522 for the step the device counter selects
     B.gather_row(t_table, T_, step_idx, t_rows, kmax * N);
     B.gather_row(scale_table, T_, step_idx, scales_cur, nn);
     if (guess) step_guess(); else step(true);
-    Builder::ok(es_cfg_ddim_step(noise.ptr(), (float*)latents.ptr(), model_in.ptr(), (const float*)coef.ptr(), (const int32_t*)step_idx.ptr(), geo.cfg ? 7.5f : 1.0f,
-                                 B_, h * w, ucfg.in_ch, model_in.c, geo.cfg, T_, B.dt, nullptr), "es_cfg_ddim_step");
-    Builder::ok(es_incr((int32_t*)step_idx.ptr(), nullptr), "es_incr");
+    scheduler_step();
   }
   void decode() {
     T dec = vae.decode(B, model_in.batch(0, B_));
@@ -1598,9 +1562,9 @@ extern "C" int es_load_weights(const es_weights* wts, const es_model_config* mc,
     if (M.guess) {
       // guess_mode: no lockstep tables - the ControlNets run on another batch than the UNet (NativeEngine with guess_mode=True).
       // ES_PLAN_STEP_UNET stays empty: steps outside the control-guidance window run ES_PLAN_STEP with all scales 0
-      { Recording r(plans[ES_PLAN_PREP]); M.set_context_guess(); }
+      { Recording r(plans[ES_PLAN_PREP]); M.set_context(); }
       { Recording r(plans[ES_PLAN_STEP]); M.one_step(); }
-      { Recording r(plans[ES_PLAN_STEP_GENERIC]); M.set_context_guess(); M.step_guess(); }
+      { Recording r(plans[ES_PLAN_STEP_GENERIC]); M.set_context(); M.step_guess(); }
     } else {
       { Recording r(plans[ES_PLAN_PREP]); M.set_context(); M.set_conds(); M.set_time_table(); }
       { Recording r(plans[ES_PLAN_STEP]); M.one_step(); }

@@ -116,16 +116,28 @@ class Resnet:
             self.conv2s = pk.conv_tail(p + ".conv2", p + ".conv_shortcut")
 
     def __call__(self, x, tproj, x2=None):
-        h = ops.group_norm(x, self.n1[0], self.n1[1], self.groups, self.eps, True, x2=x2)
-        temb = None if self.temb_off is None else tproj[:, self.temb_off:]
-        # (gn_groups: the launch's epilogue hands the GroupNorm statistics of its output over to the GroupNorm that reads it -
-        #  norm2 here, the next block's norm1 / Transformer2DModel.norm for the block's output; ops.GN_HANDOVER)
-        h = ops.conv_gemm(h, self.conv1, temb=temb, gn_groups=self.groups)
-        h = ops.group_norm(h, self.n2[0], self.n2[1], self.groups, self.eps, True)
-        if self.conv2s is not None and (x2 is None or (x.shape[3] % 64 == 0 and x2.shape[3] % 64 == 0)):
-            return ops.conv_gemm(h, self.conv2s, tail=(x, x2), gn_groups=self.groups)
-        xs = ops.conv_gemm(x, self.short, x2=x2) if self.short is not None else x
-        return ops.conv_gemm(h, self.conv2, residual=xs, wide=True, gn_groups=self.groups)   # x + h: a sum of the residual stream (ops.WIDE_STREAM)
+        return resnet_block([self], x, tproj, x2=x2)
+
+
+def resnet_block(rs: Sequence[Resnet], x, tproj, counts: Optional[Sequence[int]] = None, x2=None):
+    """ResnetBlock2D of every net in `rs` as one launch per layer: x is the batch concatenation [sum(counts),H,W,C] of the nets'
+    activations, `counts` the samples of each.  One net is a group of one: no `counts`, and the launches carry no group table.
+    x2: the UNet decoder's skip concat.  tproj: the table of time projections (None for the VAE's resnets, temb_off is None)."""
+    r0 = rs[0]
+    c = counts if len(rs) > 1 else None
+    if c is not None and x2 is not None:
+        raise L.EdgeStyleHipError("resnet_block: a skip concat (x2) with more than one group has no launch")
+    h = ops.group_norm(x, [r.n1[0] for r in rs], [r.n1[1] for r in rs], r0.groups, r0.eps, True, x2=x2, group_n=c)
+    temb = None if r0.temb_off is None else tproj[:, r0.temb_off:]
+    # (gn_groups: the launch's epilogue hands the GroupNorm statistics of its output over to the GroupNorm that reads it -
+    #  norm2 here, the next block's norm1 / Transformer2DModel.norm for the block's output; ops.GN_HANDOVER)
+    h = ops.conv_gemm(h, [r.conv1 for r in rs], temb=temb, group_n=c, gn_groups=r0.groups)
+    h = ops.group_norm(h, [r.n2[0] for r in rs], [r.n2[1] for r in rs], r0.groups, r0.eps, True, group_n=c)
+    if all(r.conv2s is not None for r in rs) and (x2 is None or (x.shape[3] % 64 == 0 and x2.shape[3] % 64 == 0)):
+        return ops.conv_gemm(h, [r.conv2s for r in rs], tail=(x, x2), group_n=c, gn_groups=r0.groups)
+    xs = ops.conv_gemm(x, [r.short for r in rs], x2=x2, group_n=c) if r0.short is not None else x
+    # x + h: a sum of the residual stream (ops.WIDE_STREAM)
+    return ops.conv_gemm(h, [r.conv2 for r in rs], residual=xs, group_n=c, wide=True, gn_groups=r0.groups)
 
 
 class Transformer:
@@ -172,20 +184,36 @@ class Transformer:
         return ops.linear(ehs, self.kv2, out=out, x_rep=rep)
 
     def __call__(self, x, kv):
-        N, H, W, C = x.shape
-        tok = ops.gn_proj_in(x, self.norm[0], self.norm[1], self.groups, 1e-6, self.proj_in).reshape(N, H * W, C)
-        fold = self.ln_fold
-        qkv = ops.linear(tok, self.qkv_ln) if fold else ops.linear(ops.layer_norm(tok, *self.ln1), self.qkv)
-        a = ops.attention(qkv[:, :, :C], qkv[:, :, C:2 * C], qkv[:, :, 2 * C:], self.heads)
-        tok = ops.linear(a, self.o1, residual=tok, wide=True)             # the three sums of the token stream and the block's own
-        q = ops.linear(tok, self.q2_ln) if fold else ops.linear(ops.layer_norm(tok, *self.ln2), self.q2)
-        a = ops.attention(q, kv[:, :, :C], kv[:, :, C:], self.heads)
-        tok = ops.linear(a, self.o2, residual=tok, wide=True)
-        f = ops.linear(tok, self.ff1_ln) if (fold and self.ff1_ln is not None) else ops.linear(ops.layer_norm(tok, *self.ln3), self.ff1)
-        if self.ffo is not None:
-            return ops.conv_gemm(f.reshape(N, H, W, 4 * C), self.ffo, x2=tok.reshape(N, H, W, C), residual=x, wide=True, gn_groups=self.groups)
-        tok = ops.linear(f, self.ff2, residual=tok, wide=True)
-        return ops.conv_gemm(tok.reshape(N, H, W, C), self.proj_out, residual=x, wide=True, gn_groups=self.groups)
+        return transformer_block([self], x, kv)
+
+
+def transformer_block(ts: Sequence[Transformer], x, kv, counts: Optional[Sequence[int]] = None):
+    """Transformer2DModel of every net in `ts` in lockstep over the batch concatenation x (resnet_block's conventions); attention is
+    one launch over the whole batch.  kv: Transformer.context of the same rows."""
+    t0 = ts[0]
+    N, H, W, C = x.shape
+    c = counts if len(ts) > 1 else None
+    rows = None if c is None else [n * H * W for n in c]
+    tok = ops.gn_proj_in(x, [t.norm[0] for t in ts], [t.norm[1] for t in ts], t0.groups, 1e-6, [t.proj_in for t in ts], group_n=c).reshape(N, H * W, C)
+    fold = all(t.ln_fold for t in ts)
+
+    def ln_linear(k, plain, folded):
+        if fold and folded is not None:
+            return ops.linear(tok, [getattr(t, folded) for t in ts], group_n=rows)
+        n = ops.layer_norm(tok, [getattr(t, k)[0] for t in ts], [getattr(t, k)[1] for t in ts], group_rows=rows)
+        return ops.linear(n, [getattr(t, plain) for t in ts], group_n=rows)
+    qkv = ln_linear("ln1", "qkv", "qkv_ln")
+    a = ops.attention(qkv[:, :, :C], qkv[:, :, C:2 * C], qkv[:, :, 2 * C:], t0.heads)
+    tok = ops.linear(a, [t.o1 for t in ts], residual=tok, group_n=rows, wide=True)     # the three sums of the token stream and the block's own
+    q = ln_linear("ln2", "q2", "q2_ln")
+    a = ops.attention(q, kv[:, :, :C], kv[:, :, C:], t0.heads)
+    tok = ops.linear(a, [t.o2 for t in ts], residual=tok, group_n=rows, wide=True)
+    f = ln_linear("ln3", "ff1", "ff1_ln" if all(t.ln_fold and t.ff1_ln is not None for t in ts) else None)
+    if all(t.ffo is not None for t in ts):
+        return ops.conv_gemm(f.reshape(N, H, W, 4 * C), [t.ffo for t in ts], x2=tok.reshape(N, H, W, C), residual=x, group_n=c, wide=True,
+                             gn_groups=t0.groups)
+    tok = ops.linear(f, [t.ff2 for t in ts], residual=tok, group_n=rows, wide=True)
+    return ops.conv_gemm(tok.reshape(N, H, W, C), [t.proj_out for t in ts], residual=x, group_n=c, wide=True, gn_groups=t0.groups)
 
 
 class Encoder:
@@ -251,21 +279,29 @@ class Encoder:
         return self.tproj.cout
 
     def run(self, h, tproj, ctx: List[torch.Tensor]):
-        skips = [h]
-        ci = 0
-        for i, blk in enumerate(self.down):
-            for r, a in blk:
-                h = r(h, tproj)
-                if a is not None:
-                    h = a(h, ctx[ci]); ci += 1
-                skips.append(h)
-            if self.downsample[i] is not None:
-                h = ops.conv_gemm(h, self.downsample[i], stride=2, gn_groups=self.cfg.norm_num_groups)
-                skips.append(h)
-        h = self.mid0(h, tproj)
-        h = self.mid_attn(h, ctx[ci])
-        h = self.mid1(h, tproj)
-        return skips, h
+        return encoder_pass([self], h, tproj, ctx)
+
+
+def encoder_pass(encs: Sequence[Encoder], h, tproj, ctx: List[torch.Tensor], counts: Optional[Sequence[int]] = None):
+    """Down blocks + mid block of encoders of one architecture in lockstep.  h: conv_in's output, [sum(counts),H,W,C0] (each group's
+    conv_in(sample) + cond already applied) -> (skips, mid) over the whole batch; ctx: one K/V tensor per transformer, same rows."""
+    e0 = encs[0]
+    c = counts if len(encs) > 1 else None
+    skips = [h]
+    ci = 0
+    for i, blk in enumerate(e0.down):
+        for j, (_, a) in enumerate(blk):
+            h = resnet_block([e.down[i][j][0] for e in encs], h, tproj, c)
+            if a is not None:
+                h = transformer_block([e.down[i][j][1] for e in encs], h, ctx[ci], c); ci += 1
+            skips.append(h)
+        if e0.downsample[i] is not None:
+            h = ops.conv_gemm(h, [e.downsample[i] for e in encs], stride=2, group_n=c, gn_groups=e0.cfg.norm_num_groups)
+            skips.append(h)
+    h = resnet_block([e.mid0 for e in encs], h, tproj, c)
+    h = transformer_block([e.mid_attn for e in encs], h, ctx[ci], c)
+    h = resnet_block([e.mid1 for e in encs], h, tproj, c)
+    return skips, h
 
 
 class UNet(Encoder):
@@ -515,58 +551,5 @@ class GroupedEncoder:
             a += n
         return out
 
-    def _resnet(self, rs, x, tproj):
-        c = self.counts
-        r0 = rs[0]
-        h = ops.group_norm(x, [r.n1[0] for r in rs], [r.n1[1] for r in rs], r0.groups, r0.eps, True, group_n=c)
-        h = ops.conv_gemm(h, [r.conv1 for r in rs], temb=tproj[:, r0.temb_off:], group_n=c, gn_groups=r0.groups)
-        h = ops.group_norm(h, [r.n2[0] for r in rs], [r.n2[1] for r in rs], r0.groups, r0.eps, True, group_n=c)
-        if all(r.conv2s is not None for r in rs):
-            return ops.conv_gemm(h, [r.conv2s for r in rs], tail=(x,), group_n=c, gn_groups=r0.groups)
-        xs = ops.conv_gemm(x, [r.short for r in rs], group_n=c) if r0.short is not None else x
-        return ops.conv_gemm(h, [r.conv2 for r in rs], residual=xs, group_n=c, wide=True, gn_groups=r0.groups)
-
-    def _transformer(self, ts, x, kv):
-        c = self.counts
-        t0 = ts[0]
-        N, H, W, C = x.shape
-        rows = [n * H * W for n in c]
-        tok = ops.gn_proj_in(x, [t.norm[0] for t in ts], [t.norm[1] for t in ts], t0.groups, 1e-6, [t.proj_in for t in ts], group_n=c).reshape(N, H * W, C)
-        fold = all(t.ln_fold for t in ts)
-
-        def ln_linear(k, plain, folded):
-            if fold and folded is not None:
-                return ops.linear(tok, [getattr(t, folded) for t in ts], group_n=rows)
-            n = ops.layer_norm(tok, [getattr(t, k)[0] for t in ts], [getattr(t, k)[1] for t in ts], group_rows=rows)
-            return ops.linear(n, [getattr(t, plain) for t in ts], group_n=rows)
-        qkv = ln_linear("ln1", "qkv", "qkv_ln")
-        a = ops.attention(qkv[:, :, :C], qkv[:, :, C:2 * C], qkv[:, :, 2 * C:], t0.heads)
-        tok = ops.linear(a, [t.o1 for t in ts], residual=tok, group_n=rows, wide=True)
-        q = ln_linear("ln2", "q2", "q2_ln")
-        a = ops.attention(q, kv[:, :, :C], kv[:, :, C:], t0.heads)
-        tok = ops.linear(a, [t.o2 for t in ts], residual=tok, group_n=rows, wide=True)
-        f = ln_linear("ln3", "ff1", "ff1_ln" if all(t.ln_fold and t.ff1_ln is not None for t in ts) else None)
-        if all(t.ffo is not None for t in ts):
-            return ops.conv_gemm(f.reshape(N, H, W, 4 * C), [t.ffo for t in ts], x2=tok.reshape(N, H, W, C), residual=x, group_n=c, wide=True,
-                                 gn_groups=t0.groups)
-        tok = ops.linear(f, [t.ff2 for t in ts], residual=tok, group_n=rows, wide=True)
-        return ops.conv_gemm(tok.reshape(N, H, W, C), [t.proj_out for t in ts], residual=x, group_n=c, wide=True, gn_groups=t0.groups)
-
     def run(self, h, tproj, ctx: List[torch.Tensor]):
-        """h: [ntot,H,W,C0] (each group's conv_in(sample)+cond already applied) -> (skips, mid) over the whole batch."""
-        skips = [h]
-        ci = 0
-        e0 = self.encs[0]
-        for i, blk in enumerate(e0.down):
-            for j, (r, a) in enumerate(blk):
-                h = self._resnet([e.down[i][j][0] for e in self.encs], h, tproj)
-                if a is not None:
-                    h = self._transformer([e.down[i][j][1] for e in self.encs], h, ctx[ci]); ci += 1
-                skips.append(h)
-            if e0.downsample[i] is not None:
-                h = ops.conv_gemm(h, [e.downsample[i] for e in self.encs], stride=2, group_n=self.counts, gn_groups=e0.cfg.norm_num_groups)
-                skips.append(h)
-        h = self._resnet([e.mid0 for e in self.encs], h, tproj)
-        h = self._transformer([e.mid_attn for e in self.encs], h, ctx[ci])
-        h = self._resnet([e.mid1 for e in self.encs], h, tproj)
-        return skips, h
+        return encoder_pass(self.encs, h, tproj, ctx, self.counts)

@@ -228,7 +228,7 @@ def test_a_dry_context_cannot_be_saved_or_run(tiny, tmp_path):
             c.close()
 
 
-def test_dry_recording_validates_but_does_not_launch():
+def test_dry_recording_validates_but_does_not_launch(monkeypatch):
     """es_plan_set_dry: a recording thread's calls are checked and recorded, nothing runs (no GPU here) - and a call the
     kernel would reject is rejected and NOT recorded."""
     lib = L.load()
@@ -253,6 +253,22 @@ def test_dry_recording_validates_but_does_not_launch():
         assert lib.es_plan_size(plan) == 1
         d.d, d.ldq, d.ldk, d.ldv, d.ldo = 40, 80, 80, 80, 80
         assert lib.es_attention(C.byref(d), None) == 0 and lib.es_plan_size(plan) == 2
+        # the model walk of the Python host: a skip concat (x2) over more than one weight group has no launch - refused before the
+        # first call of the block, nothing recorded
+        from edgestyle_amd import engine as E
+        g = torch.Generator().manual_seed(0)
+        sd = {f"r.{n}.{k}": torch.randn(s, generator=g) for n, k, s in
+              (("norm1", "weight", (128,)), ("norm1", "bias", (128,)), ("conv1", "weight", (64, 128, 3, 3)), ("conv1", "bias", (64,)),
+               ("norm2", "weight", (64,)), ("norm2", "bias", (64,)), ("conv2", "weight", (64, 64, 3, 3)), ("conv2", "bias", (64,)),
+               ("conv_shortcut", "weight", (64, 128, 1, 1)), ("conv_shortcut", "bias", (64,)))}
+        rs = [E.Resnet(E._Packer(sd, torch.float16, "cpu"), "r", 32, 1e-5, None) for _ in range(2)]
+        x, x2 = torch.zeros(4, 8, 8, 64, dtype=torch.float16), torch.zeros(4, 8, 8, 64, dtype=torch.float16)
+        with pytest.raises(L.EdgeStyleHipError, match="x2.*more than one group"):
+            E.resnet_block(rs, x, None, counts=[2, 2], x2=x2)
+        assert lib.es_plan_size(plan) == 2
+        monkeypatch.setattr(ops, "_stream", lambda: None)
+        y = rs[0](x, None, x2=x2)                   # one net, the same operands: GroupNorm, conv1, GroupNorm, conv2 + shortcut
+        assert lib.es_plan_size(plan) == 6 and y.shape == (4, 8, 8, 64)
     finally:
         assert lib.es_plan_set_dry(0) == 1
         lib.es_plan_end_record(plan)
