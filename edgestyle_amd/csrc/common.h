@@ -98,6 +98,12 @@ ES_DEVICE float wave_max(float v) {
 // v_rcp_f32 (1 ulp) instead of an IEEE division (~12 instructions): SiLU sits in the inner loop of GroupNorm-apply,
 // the fusion passes and GEMM epilogues, whose outputs are rounded to 16 bits anyway.
 ES_DEVICE float silu_f(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
+// tanh GELU, nn.GELU(approximate="tanh") of the EfficientViT blocks: 0.5 x (1 + tanh(u)) = x sigmoid(2 u), u = sqrt(2 / pi) (x + 0.044715 x^3):
+// one exp and one v_rcp_f32 like silu_f.  Large |x|: exp gives 0 or inf, the result is x or -0 - never NaN for a finite x.
+ES_DEVICE float gelu_tanh_f(float x) {
+  constexpr float C1 = 2.0f * 0.7978845608028654f, C3 = C1 * 0.044715f;
+  return x * __builtin_amdgcn_rcpf(1.0f + __expf(-(x * __builtin_fmaf(x * x, C3, C1))));
+}
 // exact (erf) GELU, as torch.nn.functional.gelu default used by diffusers GEGLU.  erf by Abramowitz-Stegun 7.1.26
 // (|abs err| <= 5e-7 against torch's erf GELU over [-12, 12], far below fp16/bf16 resolution), arranged for the GEGLU epilogue:
 //   gelu(x) = x * Phi(x),  Phi(x) = x >= 0 ? 1 - h : h,  h = 0.5 * poly(t) * exp(-x^2 / 2),  t = 1 / (1 + p |x| / sqrt 2)

@@ -677,6 +677,7 @@ __global__ __launch_bounds__(BM * 8 / FM, (STAGES == 2 && BM == 128) ? (FM == 2 
               if constexpr (LN) a = ln_rstd * (a - ln_mean * lncs[i][r]);
               float x = a + bias[i][r] + tv[r];
               if (p.act == ES_ACT_SILU) x = silu_f(x);
+              if constexpr (!LN) { if (p.act == ES_ACT_GELU_TANH) x = gelu_tanh_f(x); }      // (a LayerNorm-folded launch is no plain linear layer with it: gemm_check)
               pk[r] = from_f32<T>(x * scale);
             }
             *(typename Traits<T>::vec4*)(et + (prow + j * 16) * EROW + (pcol + i * 16) * 2) = pk;
@@ -824,6 +825,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const es_gemm_desc p
   for (int r = 0; r < 8; ++r) {
     float x = v[r] + bv[r] + tv[r];
     if (p.act == ES_ACT_SILU) x = silu_f(x);
+    else if (p.act == ES_ACT_GELU_TANH) x = gelu_tanh_f(x);
     x = to_f32(from_f32<T>(x * scale));                   // same rounding point as the fused epilogue
     v[r] = x + rv[r];
   }
@@ -920,6 +922,7 @@ __global__ __launch_bounds__(64 * (CB / 8)) void splitk_reduce_gn_kernel(const e
       for (int r = 0; r < 8; ++r) {
         float x = v[r] + bv[r] + tv[r];
         if (p.act == ES_ACT_SILU) x = silu_f(x);
+        else if (p.act == ES_ACT_GELU_TANH) x = gelu_tanh_f(x);
         x = to_f32(from_f32<T>(x * scale));
         v[r] = x + rv[r];
       }
@@ -1056,7 +1059,7 @@ const char* gemm_check(const es_gemm_desc* d) {
   if (d->stages != 0 && (d->stages < 2 || d->stages > 4)) return "es_conv_gemm: stages must be 0 (auto), 2, 3 or 4";
   if (d->waves != 0 && d->waves != 4 && d->waves != 8) return "es_conv_gemm: waves must be 0 (auto), 4 or 8";
   if (d->ln_colsum && (d->ksize != 1 || d->stride != 1 || d->C2 || d->C1 % BK || d->Kpad != d->C1 || d->splitk != 1 ||
-                       d->bn == 320 || d->upsample || d->temb || d->stages == 3))
+                       d->bn == 320 || d->upsample || d->temb || d->stages == 3 || d->act == ES_ACT_GELU_TANH))      // (no tanh-GELU in the folded kernels)
     return "es_conv_gemm: LayerNorm fold needs a plain linear layer: ksize 1, one source, K = C1 (multiple of 64), splitk 1, bn 64|128|160";
   if (d->ln_colsum && d->ngroups > 1)
     for (int g = 0; g < d->ngroups; ++g)

@@ -9,9 +9,12 @@
 // bytes EQUAL Pillow's.  The coefficient code is written once (resize_axis, __host__ __device__): es_image_resize_coeffs hands
 // the host build of it to the CPU tests, the kernels run the device build.  Built with -ffp-contract=off (csrc/Makefile): a
 // fused multiply-add in the weight arithmetic would round differently from Pillow's C.
+// es_sam_preprocess_u8 (EfficientViTSam.transform: long side -> S, no crop, normalise, pad) lives here as well: it resamples with the same
+// resize_axis, through kernels of its own (a rectangular result, every source row), so nothing the calls above compute changes.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
+#include <algorithm>
 #include <vector>
 
 #include "../../include/edgestyle_hip.h"
@@ -185,6 +188,101 @@ __global__ __launch_bounds__(256) void f32_to_u8_kernel(const float* __restrict_
     for (int q = 0; q < m; ++q)
       for (int c = 0; c < 3; ++c) dst[q * 3 + c] = (uint8_t)unit_to_u8(src[(long long)c * HW + q]);
   }
+}
+
+// ---- EfficientViTSam.transform --------------------------------------------------------------------------------------------------
+// torchvision's resize(PIL, (rh, rw)) without a crop: Pillow's horizontal pass over every source row, then its vertical pass, then
+// ToTensor / Normalize / SamPad.  `pix`: where the normalising kernel reads the resized bytes - the compact result of the passes, or the
+// source itself (its own stride and channel count) when the long side already is S and Pillow is never called.
+struct SamImg {
+  const uint8_t* src;
+  long long stride;
+  uint8_t* tmp;           // [in_h][rw][3]  (need_h)
+  uint8_t* res;           // [rh][rw][3]    (need_h or need_v)
+  const uint8_t* pix;
+  long long pix_pitch;
+  int32_t pix_step;
+  int32_t in_h, in_w, ch, rh, rw, need_h, need_v;
+};
+struct SamBatch { SamImg d[kImgPerLaunch]; float mean[3], std[3]; int32_t S, first; };
+
+__global__ __launch_bounds__(256) void sam_resize_h_kernel(const SamBatch b) {
+  const SamImg& d = b.d[blockIdx.y];
+  if (!d.need_h) return;
+  const int row3 = 3 * d.rw;
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (long long)d.in_h * row3) return;
+  const int r = (int)(idx / row3), j = (int)(idx - (long long)r * row3);
+  const int xx = j / 3, c = j - 3 * xx;
+  const uint8_t* row = d.src + (size_t)r * (size_t)d.stride + c;
+  int acc = 1 << (kPrecisionBits - 1), xmin;
+  const int ch = d.ch;
+  resize_axis(ES_FILTER_BILINEAR, d.in_w, d.rw, xx, &xmin, [&](int x0, int x, int k) { acc += k * (int)row[(size_t)(x0 + x) * ch]; });
+  d.tmp[idx] = clip8(acc);
+}
+
+__global__ __launch_bounds__(256) void sam_resize_v_kernel(const SamBatch b) {
+  const SamImg& d = b.d[blockIdx.y];
+  if (!d.need_v) return;        // (a horizontal pass alone wrote `res` itself: sam_plan points tmp at it)
+  const int row3 = 3 * d.rw;
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (long long)d.rh * row3) return;
+  const int yy = (int)(idx / row3), j = (int)(idx - (long long)yy * row3);
+  const int x = j / 3, c = j - 3 * x;
+  const uint8_t* base;
+  size_t pitch;
+  if (d.need_h) { base = d.tmp + j; pitch = (size_t)row3; }
+  else { base = d.src + (size_t)x * d.ch + c; pitch = (size_t)d.stride; }
+  int acc = 1 << (kPrecisionBits - 1), ymin;
+  resize_axis(ES_FILTER_BILINEAR, d.in_h, d.rh, yy, &ymin, [&](int y0, int y, int k) { acc += k * (int)base[(size_t)(y0 + y) * pitch]; });
+  d.res[idx] = clip8(acc);
+}
+
+// one thread per canvas pixel: (v / 255 - mean) / std, both divisions correctly rounded and nothing fused (torch's ToTensor and Normalize);
+// outside the resized image every output is exactly 0
+template <typename T>
+__global__ __launch_bounds__(256) void sam_normalize_kernel(const SamBatch b, T* out_nhwc, float* out_nchw, uint8_t* out_u8) {
+  const SamImg& d = b.d[blockIdx.y];
+  const int S = b.S;
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (long long)S * S) return;
+  const int y = (int)(idx / S), x = (int)(idx - (long long)y * S);
+  const size_t img = (size_t)(b.first + (int)blockIdx.y);
+  float f[3] = {0.f, 0.f, 0.f};
+  uint8_t v[3] = {0, 0, 0};
+  if (y < d.rh && x < d.rw) {
+    const uint8_t* px = d.pix + (size_t)y * (size_t)d.pix_pitch + (size_t)x * d.pix_step;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { v[c] = px[c]; f[c] = __fdiv_rn(__fdiv_rn((float)v[c], 255.0f) - b.mean[c], b.std[c]); }
+  }
+  if (out_nhwc) {
+    T* o = out_nhwc + (img * S * S + (size_t)idx) * 8;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) o[c] = (T)(c < 3 ? f[c] : 0.f);
+  }
+  if (out_nchw)
+    for (int c = 0; c < 3; ++c) out_nchw[(img * 3 + c) * S * S + (size_t)idx] = f[c];
+  if (out_u8)
+    for (int c = 0; c < 3; ++c) out_u8[(img * S * S + (size_t)idx) * 3 + c] = v[c];
+}
+
+void sam_shape(int h, int w, int S, int32_t out[2]) {      // SamResize: get_preprocess_shape, and no resize when the long side is S
+  const int lng = h > w ? h : w;
+  if (lng == S) { out[0] = h; out[1] = w; return; }
+  const double scale = (double)S * 1.0 / (double)lng;
+  out[0] = (int)((double)h * scale + 0.5);
+  out[1] = (int)((double)w * scale + 0.5);
+}
+size_t sam_plan(const es_image_u8& im, int S, SamImg& d) {  // bytes of workspace the image needs (tmp, then res, each 16-byte aligned)
+  int32_t hw[2];
+  sam_shape(im.height, im.width, S, hw);
+  d.src = im.data; d.stride = im.row_stride; d.in_h = im.height; d.in_w = im.width; d.ch = im.channels;
+  d.rh = hw[0]; d.rw = hw[1];
+  d.need_h = d.rw != d.in_w; d.need_v = d.rh != d.in_h;
+  d.tmp = nullptr; d.res = nullptr; d.pix = im.data; d.pix_pitch = im.row_stride; d.pix_step = im.channels;
+  const size_t a = d.need_h && d.need_v ? (((size_t)d.in_h * d.rw * 3 + 15) & ~(size_t)15) : 0;
+  const size_t r = d.need_h || d.need_v ? (((size_t)d.rh * d.rw * 3 + 15) & ~(size_t)15) : 0;
+  return a + r;
 }
 
 thread_local char g_msg[224];
@@ -389,5 +487,77 @@ extern "C" int es_image_f32_to_u8(const float* in_nchw, uint8_t* out_hwc, int B,
   const int vec = HW % 4 == 0 && (uintptr_t)in_nchw % 16 == 0 && (uintptr_t)out_hwc % 4 == 0;
   hipLaunchKernelGGL(f32_to_u8_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, in_nchw, out_hwc, (long long)B, HW, vec);
   if (hipGetLastError() != hipSuccess) { fail("es_image_f32_to_u8", "launch failed"); return -2; }
+  return 0;
+}
+
+extern "C" void es_sam_resize_shape(int height, int width, int S, int32_t out_hw[2]) {
+  if (out_hw) { out_hw[0] = out_hw[1] = 0; if (height >= 1 && width >= 1 && S >= 1) sam_shape(height, width, S, out_hw); }
+}
+
+static int sam_check(const char* who, const es_image_u8* imgs, int count, int S) {
+  if (check_images(who, imgs, count, S)) return -1;
+  for (int i = 0; i < count; ++i) {
+    int32_t hw[2];
+    sam_shape(imgs[i].height, imgs[i].width, S, hw);
+    if (hw[0] < 1 || hw[1] < 1) return fail_img(who, i, "the resized shorter side would be empty");
+  }
+  return 0;
+}
+
+extern "C" size_t es_sam_preprocess_u8_workspace_bytes(const es_image_u8* imgs, int count, int S) {
+  if (sam_check("es_sam_preprocess_u8_workspace_bytes", imgs, count, S)) return 0;
+  size_t need = 0;
+  SamImg d;
+  for (int i = 0; i < count; ++i) need += sam_plan(imgs[i], S, d);
+  return need;
+}
+
+extern "C" int es_sam_preprocess_u8(const es_image_u8* imgs, int count, int S, const float mean[3], const float std[3], int dtype, void* out_nhwc,
+                                    float* out_nchw, uint8_t* out_u8, int32_t* input_hw, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* who = "es_sam_preprocess_u8";
+  if (sam_check(who, imgs, count, S)) return -1;
+  if (!mean || !std) return fail(who, "null pointer (mean / std)");
+  if (!out_nhwc && !out_nchw && !out_u8) return fail(who, "null pointer (every output)");
+  if (dtype != ES_F16 && dtype != ES_BF16) return fail(who, "dtype must be ES_F16 or ES_BF16");
+  for (int c = 0; c < 3; ++c) if (!(std[c] > 0.f)) return fail(who, "std must be positive");
+  if (es_plan_recording()) return fail(who, "a plan is recording on this thread; the byte-image calls are never part of a plan");
+  std::vector<SamImg> ds((size_t)count);
+  size_t need = 0;
+  for (int i = 0; i < count; ++i) {
+    SamImg& d = ds[i];
+    const size_t bytes = sam_plan(imgs[i], S, d);
+    uint8_t* at = (uint8_t*)workspace + need;
+    if (d.need_h && d.need_v) { d.tmp = at; d.res = at + (((size_t)d.in_h * d.rw * 3 + 15) & ~(size_t)15); }
+    else if (d.need_h) { d.tmp = at; d.res = at; }        // the horizontal pass alone: its result is the resized image
+    else if (d.need_v) d.res = at;
+    if (d.need_h || d.need_v) { d.pix = d.res; d.pix_pitch = 3ll * d.rw; d.pix_step = 3; }
+    need += bytes;
+    if (input_hw) { input_hw[2 * i] = d.rh; input_hw[2 * i + 1] = d.rw; }
+  }
+  if (need && !workspace) return fail(who, "null pointer (workspace)");
+  if (workspace_bytes < need) {
+    snprintf(g_msg, sizeof(g_msg), "%s: workspace too small: %zu bytes given, %zu needed (es_sam_preprocess_u8_workspace_bytes)", who, workspace_bytes, need);
+    es_set_error(g_msg);
+    return -1;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  for (int first = 0; first < count; first += kImgPerLaunch) {
+    SamBatch b = {};
+    b.S = S; b.first = first;
+    for (int c = 0; c < 3; ++c) { b.mean[c] = mean[c]; b.std[c] = std[c]; }
+    const int n = count - first < kImgPerLaunch ? count - first : kImgPerLaunch;
+    long long hmax = 0, vmax = 0;
+    for (int i = 0; i < n; ++i) {
+      b.d[i] = ds[first + i];
+      if (b.d[i].need_h) hmax = std::max(hmax, 3ll * b.d[i].in_h * b.d[i].rw);
+      if (b.d[i].need_v) vmax = std::max(vmax, 3ll * b.d[i].rh * b.d[i].rw);
+    }
+    if (hmax) hipLaunchKernelGGL(sam_resize_h_kernel, dim3((unsigned)((hmax + 255) / 256), n), dim3(256), 0, st, b);
+    if (vmax) hipLaunchKernelGGL(sam_resize_v_kernel, dim3((unsigned)((vmax + 255) / 256), n), dim3(256), 0, st, b);
+    const dim3 grid((unsigned)(((long long)S * S + 255) / 256), n);
+    if (dtype == ES_F16) hipLaunchKernelGGL(sam_normalize_kernel<_Float16>, grid, dim3(256), 0, st, b, (_Float16*)out_nhwc, out_nchw, out_u8);
+    else hipLaunchKernelGGL(sam_normalize_kernel<__bf16>, grid, dim3(256), 0, st, b, (__bf16*)out_nhwc, out_nchw, out_u8);
+  }
+  if (hipGetLastError() != hipSuccess) { fail(who, "launch failed"); return -2; }
   return 0;
 }

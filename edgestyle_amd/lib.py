@@ -11,7 +11,7 @@ LIB_PATH = os.environ.get("ES_HIP_LIB") or os.path.join(_HERE, "lib", "libedgest
 
 ES_F16, ES_BF16, ES_F32 = 0, 1, 2
 ABI_VERSION = 7          # include/edgestyle_hip.h ES_ABI_VERSION
-ACT_NONE, ACT_SILU, ACT_GEGLU = 0, 1, 2
+ACT_NONE, ACT_SILU, ACT_GEGLU, ACT_GELU_TANH = 0, 1, 2, 3
 
 
 class GemmDesc(C.Structure):
@@ -147,6 +147,12 @@ class TextConfig(C.Structure):      # es_text_config
 class ClipVisionConfig(C.Structure):    # es_clip_vision_config
     _fields_ = [(n, C.c_int32) for n in ("image_size", "patch_size", "hidden", "heads", "layers", "intermediate", "projection_dim")] + \
         [("ln_eps", C.c_float), ("act", C.c_int32), ("image_mean", C.c_float * 3), ("image_std", C.c_float * 3)]
+
+
+class SamConfig(C.Structure):       # es_sam_config
+    _fields_ = [("image_size", C.c_int32), ("width", C.c_int32 * 5), ("depth", C.c_int32 * 5), ("qkv_dim", C.c_int32), ("head_width", C.c_int32),
+                ("head_depth", C.c_int32), ("out_dim", C.c_int32), ("bn_eps", C.c_float), ("ln_eps", C.c_float),
+                ("pixel_mean", C.c_float * 3), ("pixel_std", C.c_float * 3)]
 
 
 FILTER_BILINEAR, FILTER_BICUBIC = 0, 1           # ES_FILTER_*
@@ -375,6 +381,20 @@ SYMBOLS = {
     "es_mask_logic": (C.c_int, [_P, _P, _P, _L, _I, _P]),
     "es_image_mask_fill_u8": (C.c_int, [C.POINTER(ImageU8), _P, _P, _I, _I, _I, C.POINTER(C.c_uint8), _P]),
     "es_sam_compose": (C.c_int, [C.POINTER(ImageU8), _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, C.c_size_t, _P]),
+    "es_dwconv": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "es_relu_linear_attention": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _P]),
+    "es_sam_neck_merge": (C.c_int, [C.POINTER(_P), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _I, _P, _I, _I, _I, _P]),
+    "es_sam_resize_shape": (None, [_I, _I, _I, C.POINTER(C.c_int32)]),
+    "es_sam_preprocess_u8_workspace_bytes": (C.c_size_t, [C.POINTER(ImageU8), _I, _I]),
+    "es_sam_preprocess_u8": (C.c_int, [C.POINTER(ImageU8), _I, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _I, _P, _P, _P, C.POINTER(C.c_int32), _P,
+                                       C.c_size_t, _P]),
+    "es_sam_encoder_create": (C.c_int, [C.POINTER(StateDict), C.POINTER(SamConfig), _I, _I, _I, C.POINTER(_P)]),
+    "es_sam_encoder_destroy": (None, [_P]),
+    "es_sam_encoder_arena_bytes": (C.c_size_t, [_P]),
+    "es_sam_encode": (C.c_int, [_P, _P, _I, _P, _P]),
+    "es_sam_encoder_stage": (C.c_int, [_P, _I, _I, _P, _P]),
+    "es_sam_encode_u8_workspace_bytes": (C.c_size_t, [_P, C.POINTER(ImageU8), _I]),
+    "es_sam_encode_u8": (C.c_int, [_P, C.POINTER(ImageU8), _I, _P, C.POINTER(C.c_int32), _P, C.c_size_t, _P]),
 }
 
 _lib = None

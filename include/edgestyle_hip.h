@@ -21,7 +21,10 @@ extern "C" {
 #endif
 
 enum { ES_F16 = 0, ES_BF16 = 1, ES_F32 = 2 /* es_tensor sources only: the kernels compute in ES_F16 / ES_BF16 */ };
-enum { ES_ACT_NONE = 0, ES_ACT_SILU = 1, ES_ACT_GEGLU = 2 };
+enum { ES_ACT_NONE = 0, ES_ACT_SILU = 1, ES_ACT_GEGLU = 2,
+       ES_ACT_GELU_TANH = 3 /* nn.GELU(approximate="tanh"); es_conv_gemm on the 64- / 128- / 160-wide tiles and the split-K reduce only:
+                               es_conv_gemm8p_form_ok and es_linear_xs refuse it, so the launch policy never routes it to them, and a
+                               LayerNorm-folded launch (ln_colsum) with it is refused */ };
 
 /* 7 (round 5): es_gemm_desc.bn = 256; es_xs_desc.gn_* and es_gn_desc.stats_only (both structs grew: GroupNorm in front of a row-stationary
  * projection); es_conv_gemm8p_form_ok, es_ctx_graph_hazard, es_linear_xs_set_pp, es_attention_set_kvres, es_set_operand_limit,
@@ -1071,6 +1074,64 @@ int es_image_mask_fill_u8(const es_image_u8* img_or_null, const uint8_t* mask, u
  * to which slot stay with the caller. */
 int es_sam_compose(const es_image_u8* imgs, const uint8_t* subject, const uint8_t* body, const uint8_t* clothes, const uint8_t* head,
                    int count, int H, int W, uint8_t* masks_out, uint8_t* images_out, void* ws, size_t ws_bytes, void* stream);
+
+
+/* =========================================================================================================
+ * EfficientViT-SAM image encoder (csrc/sam.hip; the preprocessing in csrc/image_io.hip): photo bytes -> the image embedding a SAM mask
+ * decoder takes.  Replaces the reference's EfficientViTSamImageEncoder forward (efficientvit/models/efficientvit/sam.py:174-190:
+ * EfficientViTLargeBackbone -> SamNeck -> LayerNorm2d) and EfficientViTSam.transform (sam.py:211-221) that EfficientViTSamPredictor.set_image
+ * (sam.py:274-293) runs per photo and per predictor (extract_dataset.py:371-425: five predictors whose fine-tuned models share ONE frozen
+ * image encoder - one embedding per photo serves all five decoders).  The mask decoder and the prompt encoder stay with the caller.
+ * Like the text and CLIP objects none of these calls is ever part of a plan (-1 while one records on the thread), so ES_ABI_VERSION stays.
+ * All tensors are DEVICE memory, NHWC in the storage dtype (ES_F16 | ES_BF16) unless stated otherwise.
+ * ========================================================================================================= */
+/* Depthwise convolution with "same" padding (k / 2): out[n, oy, ox, c] = act(sum_{ky, kx} x[n, oy s + ky - k/2, ox s + kx - k/2, c] w[ky k + kx, c] + bias[c]),
+ * fp32 accumulation in tap order, one rounding.  x [N, H, W, C], w [k * k, C] (dtype), bias fp32 [C] or NULL, out [N, Ho, Wo, C] with
+ * Ho = (H + 2 (k / 2) - k) / s + 1.  k = 3 with stride 1 | 2, k = 5 with stride 1; C a multiple of 8; act ES_ACT_NONE | ES_ACT_GELU_TANH.
+ * Pointers 16-byte aligned.  A result does not depend on N or on how the launch is cut. */
+int es_dwconv(const void* x, const void* w, const float* bias, void* out, int N, int H, int W, int C, int k, int stride, int act, int dtype,
+              void* stream);
+/* LiteMLA.relu_linear_att (efficientvit/models/nn/ops.py:397-434) over the concatenation [qkv ; aggreg(qkv)], which is never written:
+ * a, b [N, HW, 3 * heads * 32] are its two halves (groups 0 .. heads - 1 read a, groups heads .. 2 heads - 1 read b; a group is 96 channels:
+ * q, k, v of 32), out [N, HW, 2 * heads * 32], channel g * 32 + d.  Per (n, g), all in fp32: kv = relu(k)^T [v | 1] over the tokens in order,
+ * o = relu(q) kv, out = o[:32] / (o[32] + 1e-15), one rounding.  A group whose relu(k) or relu(q) is all zero gives exactly 0.
+ * HW >= 1 (no multiple of anything), heads in 1..1024. */
+int es_relu_linear_attention(const void* a, const void* b, void* out, int N, int HW, int heads, int dtype, void* stream);
+/* SamNeck's merge: out [N, 64, 64, C] = m0 + (m1 + m2) (list_sum's order; fp32, one rounding), each map [N, h_i, w_i, C] resampled to 64 x 64
+ * with torch's bicubic (A = -0.75, align_corners = False, indices clamped at the border) in fp32; a map that already is 64 x 64 is read as
+ * it is.  count in 1..3 maps, C a multiple of 8, h_i, w_i in 1..64. */
+int es_sam_neck_merge(const void* const* maps, const int32_t* hs, const int32_t* ws, int count, void* out, int N, int C, int dtype, void* stream);
+/* EfficientViTSam.transform.  Per image (HOST descriptors, device bytes, any size, 3 or 4 channels of which 3 are read): resized so that the
+ * long side is S with Pillow's antialiased bilinear filter (target sizes int(x * S / long + 0.5); no resize when the long side is S),
+ * x / 255, (x - mean) / std in fp32 (both divisions correctly rounded), placed at the top left of an S x S canvas whose remainder is
+ * exactly 0.0.  Outputs, each optional: out_nhwc [count, S, S, 8] in `dtype` (channels 3..7 zero: the stem's input), out_nchw fp32
+ * [count, 3, S, S] (the reference's tensor), out_u8 [count, S, S, 3] (the resized bytes, 0 outside them).  input_hw: HOST [count, 2] or
+ * NULL, the resized (h, w) - the input_size postprocess_masks needs; es_sam_resize_shape is the same rule, host-only. */
+void es_sam_resize_shape(int height, int width, int S, int32_t out_hw[2]);
+size_t es_sam_preprocess_u8_workspace_bytes(const es_image_u8* imgs, int count, int S);
+int es_sam_preprocess_u8(const es_image_u8* imgs, int count, int S, const float mean[3], const float std[3], int dtype, void* out_nhwc,
+                         float* out_nchw, uint8_t* out_u8, int32_t* input_hw, void* workspace, size_t workspace_bytes, void* stream);
+typedef struct { int32_t image_size, width[5], depth[5], qkv_dim, head_width, head_depth, out_dim;
+                 float bn_eps, ln_eps, pixel_mean[3], pixel_std[3]; } es_sam_config;
+typedef struct es_sam_encoder es_sam_encoder;
+/* sd: the reference's state_dict() names, bare (backbone.*, neck.*, norm.*) or with the `image_encoder.` prefix of an EfficientViTSam
+ * checkpoint; unknown keys (num_batches_tracked) are ignored, a missing key or a wrong shape is an error that names the key.  Whether a
+ * ConvLayer has a bias and / or a BatchNorm is read from which keys exist.  BatchNorm (eval form) is folded into its convolution in fp64 and
+ * rounded once; one arena holds the packed weights, the activations of max_n images and the split-K workspace.  device -1: a dry build
+ * that reports the arena size.  Scope: widths multiples of 32, qkv_dim 32, head_width and out_dim multiples of 8, image_size a multiple of
+ * 32 in [64, 512] (the neck's 64 x 64 output is hard-wired in the reference, sam.py:127), max_n >= 1. */
+int es_sam_encoder_create(const es_state_dict* sd, const es_sam_config* cfg, int dtype, int max_n, int device, es_sam_encoder** out);
+void es_sam_encoder_destroy(es_sam_encoder* e);
+size_t es_sam_encoder_arena_bytes(const es_sam_encoder* e);
+/* x_nchw fp32 [n, 3, S, S], already normalised and padded (the reference's tensor) -> out_nchw fp32 [n, out_dim, 64, 64].  Nothing is
+ * allocated or staged: a capturing stream is accepted.  Image i of a batch equals the same image encoded alone bit for bit. */
+int es_sam_encode(es_sam_encoder* e, const float* x_nchw, int n, float* out_nchw, void* stream);
+/* the backbone's stage2 | stage3 | stage4 map of the last encode as fp32 NCHW [n, width[stage], S / 2^(stage+1), ...] (what the neck read) */
+int es_sam_encoder_stage(es_sam_encoder* e, int stage, int n, float* out_nchw, void* stream);
+size_t es_sam_encode_u8_workspace_bytes(const es_sam_encoder* e, const es_image_u8* imgs, int count);
+/* es_sam_preprocess_u8 + es_sam_encode: imgs HOST array, device bytes, any size; input_hw HOST [count, 2] or NULL */
+int es_sam_encode_u8(es_sam_encoder* e, const es_image_u8* imgs, int count, float* out_nchw, int32_t* input_hw, void* workspace,
+                     size_t workspace_bytes, void* stream);
 
 
 #ifdef __cplusplus
