@@ -155,6 +155,32 @@ class SamConfig(C.Structure):       # es_sam_config
                 ("pixel_mean", C.c_float * 3), ("pixel_std", C.c_float * 3)]
 
 
+class SamPromptDesc(C.Structure):  # es_sam_prompt_desc
+    _fields_ = [(n, C.c_void_p) for n in ("gauss", "point_embeddings", "not_a_point", "iou_token", "mask_tokens", "points", "labels", "boxes",
+                                          "tokens", "query_pe")] + \
+        [(n, C.c_int32) for n in ("n", "P", "embed_dim", "n_mask_tokens", "frame", "orig_h", "orig_w", "dtype")]
+
+
+class LinearTokensDesc(C.Structure):    # es_linear_tokens_desc
+    _fields_ = [(n, C.c_void_p) for n in ("x", "w", "bias", "residual", "out")] + \
+        [(n, C.c_int32) for n in ("n", "rows", "K", "N", "ldx", "ldr", "ldo")] + [(n, C.c_int64) for n in ("bsx", "bsr", "bso")] + \
+        [(n, C.c_int32) for n in ("per_row_weights", "relu", "dtype")]
+
+
+class SamDecoderConfig(C.Structure):    # es_sam_decoder_config
+    _fields_ = [(n, C.c_int32) for n in ("embed_dim", "heads", "mlp_dim", "depth", "grid", "frame", "n_mask_tokens", "iou_hidden", "iou_depth",
+                                         "attn_downsample")] + [("ln_eps", C.c_float), ("ln2d_eps", C.c_float)]
+
+
+class SamPrompts(C.Structure):          # es_sam_prompts
+    _fields_ = [(n, C.c_void_p) for n in ("points", "labels", "boxes", "mask_input")] + [(n, C.c_int32) for n in ("P", "orig_h", "orig_w")]
+
+
+class SamUpscaleDesc(C.Structure):  # es_sam_upscale_desc
+    _fields_ = [(n, C.c_void_p) for n in ("g", "w_packed", "ln_gamma", "ln_beta", "bias2", "hyper", "out")] + \
+        [(n, C.c_int32) for n in ("n", "grid_h", "grid_w", "C1", "M", "ldh")] + [("bsh", C.c_int64), ("ln_eps", C.c_float), ("dtype", C.c_int32)]
+
+
 FILTER_BILINEAR, FILTER_BICUBIC = 0, 1           # ES_FILTER_*
 CROP_TORCHVISION, CROP_TRANSFORMERS = 0, 1       # ES_CROP_*
 MASK_AND, MASK_OR, MASK_ANDNOT = 0, 1, 2         # ES_MASK_*
@@ -395,6 +421,21 @@ SYMBOLS = {
     "es_sam_encoder_stage": (C.c_int, [_P, _I, _I, _P, _P]),
     "es_sam_encode_u8_workspace_bytes": (C.c_size_t, [_P, C.POINTER(ImageU8), _I]),
     "es_sam_encode_u8": (C.c_int, [_P, C.POINTER(ImageU8), _I, _P, C.POINTER(C.c_int32), _P, C.c_size_t, _P]),
+    "es_sam_prompt_token_count": (C.c_int, [_I, _I]),
+    "es_sam_prompt_tokens": (C.c_int, [C.POINTER(SamPromptDesc), _P]),
+    "es_sam_prompt_tokens_host": (C.c_int, [C.POINTER(SamPromptDesc), _P]),
+    "es_linear_tokens": (C.c_int, [C.POINTER(LinearTokensDesc), _P]),
+    "es_sam_upscale_pack": (C.c_int, [_P, _I, _I, _P]),
+    "es_sam_upscale_masks": (C.c_int, [C.POINTER(SamUpscaleDesc), _P]),
+    "es_sam_decoder_create": (C.c_int, [C.POINTER(StateDict), C.POINTER(SamDecoderConfig), _I, _I, _I, _I, C.POINTER(_P)]),
+    "es_sam_decoder_destroy": (None, [_P]),
+    "es_sam_decoder_arena_bytes": (C.c_size_t, [_P]),
+    "es_sam_decode": (C.c_int, [_P, _P, C.POINTER(SamPrompts), _I, _I, _P, _P, _P]),
+    "es_sam_predict": (C.c_int, [_P, _P, C.POINTER(SamPrompts), _I, _I, _P, _P, _P, _P, _P]),
+    "es_sam_postprocess_masks": (C.c_int, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "es_sam_postprocess_masks_host": (C.c_int, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "es_mask_bbox": (C.c_int, [_P, _P, _I, _I, _I, _I, _P]),
+    "es_mask_bbox_host": (C.c_int, [_P, _P, _I, _I, _I, _I]),
 }
 
 _lib = None

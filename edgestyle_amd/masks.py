@@ -5,8 +5,10 @@ returns device uint8 tensors: masks of 0 / 1 (a `.bool()` view away from the ref
 pipeline.preprocess_images and NativeBestEmbeddings take unchanged.
 
 A mask is [H, W] or a batch [count, H, W]; the result has the shape of the input.  The networks (YOLOv5, OpenPose,
-EfficientViT-SAM), the `subject_scores < 0.5` test, getBox and the choice of which image goes to which slot stay with the caller.
+EfficientViT-SAM), the `subject_scores < 0.5` test and the choice of which image goes to which slot stay with the caller; getBox is
+`get_box` (csrc/sam_decoder.hip), which leaves the box on the device for the next decode's prompt.
 """
+import ctypes as C
 from typing import Optional, Sequence
 
 import numpy as np
@@ -92,6 +94,18 @@ def largest_component(mask, return_area: bool = False):
     return (out, area[0] if single else area) if return_area else out
 
 
+def get_box(mask, margin: int = 20) -> torch.Tensor:
+    """extract_dataset.py:298-313: [max(0, xmin - margin), max(0, ymin - margin), min(W, xmax + margin), min(H, ymax + margin)] over the true
+    pixels, zeros for a mask without one -> fp32 [4] (or [count, 4]) on the device, never read back here"""
+    m, single = to_mask(mask)
+    count, H, W = m.shape
+    boxes = torch.empty((count, 4), dtype=torch.float32, device=m.device)
+    with torch.cuda.device(m.device):
+        L.check(L.load().es_mask_bbox(C.c_void_p(m.data_ptr()), C.c_void_p(boxes.data_ptr()), count, H, W, int(margin),
+                                      C.c_void_p(torch.cuda.current_stream(m.device).cuda_stream)), "es_mask_bbox")
+    return boxes[0] if single else boxes
+
+
 def draw_binary_mask(image, mask, mask_color=(0, 0, 255)) -> torch.Tensor:
     """extract_dataset.py:316-331: `image` where `mask` is true, mask_color elsewhere; image None = zeros (np.zeros_like(image))"""
     m, single = to_mask(mask)
@@ -115,6 +129,28 @@ def create_sam_images(image, subject, body, clothes, head, return_masks: bool = 
     pick = (lambda t, k: t[0, k]) if single else (lambda t, k: t[:, k])
     out = tuple(pick(images, k) for k in range(5))
     return (out, tuple(pick(masks, k) for k in range(4))) if return_masks else out
+
+
+def segment(photo, points, predictors, labels=None, margin: int = 20):
+    """The network half of create_sam_images (extract_dataset.py:371-429) and its device arithmetic, without a host visit between the
+    decodes: one encode, the point-prompted base decode (multimask, mask 0), its box with `margin` (get_box), four box-prompted decodes
+    (subject, body, clothes, head; single mask), then create_sam_images.  predictors: five sam.NativeSamPredictor in that order (base
+    first) that share one encoder.  points: [P, 2] pose key points in the photo's pixels (labels: all foreground unless given).
+    -> (create_sam_images' five images, the subject score as a device scalar: the caller's `< SUBJECT_SCORE_THRESHOLD` test)"""
+    if len(predictors) != 5:
+        raise _bad("segment takes five predictors: base, subject, body, clothes, head")
+    img = to_image(photo)
+    base = predictors[0]
+    feats, _ = base.encoder.encode_u8([img])
+    for p in predictors:
+        p.set_features(feats, img.shape[:2])
+    pts = torch.as_tensor(np.asarray(points, dtype=np.float32))
+    lab = torch.ones(pts.shape[0], dtype=torch.int32) if labels is None else torch.as_tensor(labels)
+    all_masks, _, _ = base.predict_device(pts, lab, multimask_output=True)
+    box = get_box(all_masks[0], margin)
+    outs = [p.predict_device(box=box, multimask_output=False) for p in predictors[1:]]
+    subject, body, clothes, head = (o[0][0] for o in outs)
+    return create_sam_images(img, subject, body, clothes, head), outs[0][1][0]
 
 
 def subject_image_masks(subject, body, clothes, kernel_size: int = 3, iterations: int = 3):

@@ -1077,11 +1077,11 @@ int es_sam_compose(const es_image_u8* imgs, const uint8_t* subject, const uint8_
 
 
 /* =========================================================================================================
- * EfficientViT-SAM image encoder (csrc/sam.hip; the preprocessing in csrc/image_io.hip): photo bytes -> the image embedding a SAM mask
- * decoder takes.  Replaces the reference's EfficientViTSamImageEncoder forward (efficientvit/models/efficientvit/sam.py:174-190:
+ * EfficientViT-SAM image encoder (csrc/sam.hip; the preprocessing in csrc/image_io.hip): photo bytes -> the image embedding the SAM mask
+ * decoder (next section) takes.  Replaces the reference's EfficientViTSamImageEncoder forward (efficientvit/models/efficientvit/sam.py:174-190:
  * EfficientViTLargeBackbone -> SamNeck -> LayerNorm2d) and EfficientViTSam.transform (sam.py:211-221) that EfficientViTSamPredictor.set_image
  * (sam.py:274-293) runs per photo and per predictor (extract_dataset.py:371-425: five predictors whose fine-tuned models share ONE frozen
- * image encoder - one embedding per photo serves all five decoders).  The mask decoder and the prompt encoder stay with the caller.
+ * image encoder - one embedding per photo serves all five decoders). 
  * Like the text and CLIP objects none of these calls is ever part of a plan (-1 while one records on the thread), so ES_ABI_VERSION stays.
  * All tensors are DEVICE memory, NHWC in the storage dtype (ES_F16 | ES_BF16) unless stated otherwise.
  * ========================================================================================================= */
@@ -1132,6 +1132,121 @@ size_t es_sam_encode_u8_workspace_bytes(const es_sam_encoder* e, const es_image_
 /* es_sam_preprocess_u8 + es_sam_encode: imgs HOST array, device bytes, any size; input_hw HOST [count, 2] or NULL */
 int es_sam_encode_u8(es_sam_encoder* e, const es_image_u8* imgs, int count, float* out_nchw, int32_t* input_hw, void* workspace,
                      size_t workspace_bytes, void* stream);
+
+
+/* =========================================================================================================
+ * SAM prompt encoder and mask decoder, the pieces that are no big GEMM (csrc/sam_decoder.hip): the prompt tokens, the token-side linear
+ * layers of the TwoWayTransformer, the fused upscaling tail, postprocess_masks and getBox of segment_anything 1.0's PromptEncoder / MaskDecoder as EfficientViT-SAM
+ * builds them (efficientvit/models/efficientvit/sam.py:522-540) and as extract_dataset.py:371-429 chains them: a decode's mask gives the box
+ * of the next decode without a host visit.  es_sam_decoder strings them together with es_conv_gemm, es_layer_norm,
+ * es_add and es_attention: a C++ host needs only the pose key points from outside.
+ * No float atomics, nothing allocated or read back (capturable), image i of a batch equals the image alone bit for bit; never part of a
+ * plan (-1 while one records on the thread), so ES_ABI_VERSION stays.  The *_host twins run the kernels' own index and weight code on the CPU.
+ * ========================================================================================================= */
+typedef struct {
+  /* weights, fp32: PromptEncoder.pe_layer.positional_encoding_gaussian_matrix [2, embed_dim / 2], point_embeddings.{0..3}.weight as
+   * [4, embed_dim], not_a_point_embed.weight [embed_dim]; MaskDecoder.iou_token.weight [embed_dim], mask_tokens.weight [n_mask_tokens, embed_dim] */
+  const float *gauss, *point_embeddings, *not_a_point, *iou_token, *mask_tokens;
+  /* prompts of n images in ORIGINAL-image pixels: points fp32 [n, P, 2] (x, y), labels int32 [n, P] (1 foreground, 0 background, -1 not a
+   * point), boxes fp32 [n, 4] (x0, y0, x1, y1; what es_mask_bbox writes) or NULL: no box.  P == 0: points and labels are not read. */
+  const float* points;
+  const int32_t* labels;
+  const float* boxes;
+  void* tokens;      /* out, dtype [n, 1 + n_mask_tokens + T, embed_dim], T = es_sam_prompt_token_count(P, boxes != NULL) */
+  void* query_pe;    /* out or NULL: the same values once more (the decoder's query_pe is its token matrix) */
+  int32_t n, P, embed_dim, n_mask_tokens;
+  int32_t frame;     /* the prompt frame's long side (1024) */
+  int32_t orig_h, orig_w, dtype;
+} es_sam_prompt_desc;
+/* sparse tokens of a prompt: P points, then the box's two corners, or ONE padding point where there are points and no box; -1 for P < 0 */
+int es_sam_prompt_token_count(int P, int has_box);
+/* tokens = [iou_token; mask_tokens; sparse].  Sparse token of a point c with label 0 | 1: pe(c) + point_embeddings[label]; label -1:
+ * not_a_point alone; any other label: pe(c) alone, which is what segment_anything's _embed_points leaves for it (the labels are device
+ * memory and cannot be refused on the host); a box corner k: pe(corner) + point_embeddings[2 + k]; the padding point: not_a_point.  Coordinates go through
+ * apply_coords first (x * (new_w / orig_w) in double, rounded once to fp32, (new_h, new_w) = es_sam_resize_shape(orig_h, orig_w, frame)); then
+ * pe(c) = [sin | cos](2 pi ((2 (c + 0.5) / frame - 1) @ gauss)) in fp32 with the precise sinf / cosf.  One rounding to dtype.  All pointers
+ * DEVICE memory.  Refused: no prompt at all, more than 32 tokens, an odd embed_dim. */
+int es_sam_prompt_tokens(const es_sam_prompt_desc* d, void* stream);
+/* the same values in fp32 from HOST pointers into HOST memory [n, 1 + n_mask_tokens + T, embed_dim] (tokens, query_pe and dtype are not read) */
+int es_sam_prompt_tokens_host(const es_sam_prompt_desc* d, float* tokens_f32);
+typedef struct {
+  const void* x;           /* dtype, row r of sample i at x + i * bsx + r * ldx (elements); 16-byte aligned */
+  const void* w;           /* dtype [N, K] (nn.Linear's layout), or [rows, N, K] with per_row_weights; 16-byte aligned */
+  const float* bias;       /* fp32 [N] ([rows, N] with per_row_weights) or NULL */
+  const void* residual;    /* dtype or NULL, addressed like out with bsr / ldr */
+  void* out;               /* dtype, row r of sample i at out + i * bso + r * ldo */
+  int32_t n, rows, K, N;   /* rows in 1..32; K a multiple of 8 in 8..2048; N a multiple of 4 in 4..2048 */
+  int32_t ldx, ldr, ldo;   /* 0: dense (K, N, N); ldx a multiple of 8 */
+  int64_t bsx, bsr, bso;   /* 0: dense (rows * ld); bsx a multiple of 8 */
+  int32_t per_row_weights; /* 1: row r has weights and a bias of its own (MaskDecoder.output_hypernetworks_mlps as one launch) */
+  int32_t relu, dtype;
+} es_linear_tokens_desc;
+/* out[i, r, :] = act(x[i, r, :] W^T + b) (+ residual[i, r, :]): fp32 accumulation in an order that depends on K alone, bias, ReLU and the
+ * residual in fp32, one rounding.  The weights are shared by all samples. */
+int es_linear_tokens(const es_linear_tokens_desc* d, void* stream);
+typedef struct {
+  const void* g;            /* dtype [n, grid_h * grid_w, 4 * C1]: MaskDecoder.output_upscaling.0 (ConvTranspose2d k2 s2) as a 1x1 GEMM with its bias,
+                             * column (2 dy + dx) * C1 + c; 16-byte aligned */
+  const void* w_packed;     /* dtype, C1 * 2 * C1 elements: output_upscaling.3.weight through es_sam_upscale_pack; 16-byte aligned */
+  const float *ln_gamma, *ln_beta;      /* fp32 [C1]: output_upscaling.1 (LayerNorm2d) */
+  const float* bias2;       /* fp32 [C1 / 2]: output_upscaling.3.bias */
+  const void* hyper;        /* dtype, row m of image i at hyper + i * bsh + m * ldh, C1 / 2 values: the hypernetwork MLPs' outputs */
+  float* out;               /* fp32 [n, M, 4 * grid_h, 4 * grid_w] */
+  int32_t n, grid_h, grid_w, C1, M;     /* C1 = embed_dim / 4 in {32, 64}; M in 1..4 */
+  int32_t ldh;              /* 0: dense (C1 / 2) */
+  int64_t bsh;              /* 0: dense (M * ldh) */
+  float ln_eps;
+  int32_t dtype;
+} es_sam_upscale_desc;
+/* host-only: w fp32 [C1, C1 / 2, 2, 2] (ConvTranspose2d's layout) -> the MFMA B fragments es_sam_upscale_masks loads, C1 * 2 * C1 elements of dtype */
+int es_sam_upscale_pack(const float* w, int C1, int dtype, void* out);
+/* The mask decoder's tail behind ConvT1, fused: per (source pixel, sub-pixel) LayerNorm over the C1 channels (two-pass, eps ln_eps), erf-GELU,
+ * rounded once to dtype, ConvT2 on the matrix core (K = C1, N = 2 * 2 * C1 / 2), bias and erf-GELU in fp32, and the dot with hyper[m]:
+ * out[i, m, 4 py + 2 dy + dy2, 4 px + 2 dx + dx2].  The [C1 / 2, 4 grid, 4 grid] tensor is never written.  Fixed summation order: a result
+ * does not depend on n. */
+int es_sam_upscale_masks(const es_sam_upscale_desc* d, void* stream);
+/* ---- the decoder object: prompts + embedding -> low-res logits / masks, one arena, nothing allocated or read back in a call ---- */
+typedef struct { int32_t embed_dim, heads, mlp_dim, depth, grid, frame, n_mask_tokens, iou_hidden, iou_depth, attn_downsample;
+                 float ln_eps, ln2d_eps; } es_sam_decoder_config;        /* EfficientViT-SAM: 256, 8, 2048, 2, 64, 1024, 4, 256, 3, 2, 1e-5, 1e-6 */
+typedef struct {
+  const float* points;      /* DEVICE fp32 [n, P, 2] in original-image pixels, or NULL with P == 0 */
+  const int32_t* labels;    /* DEVICE int32 [n, P]: 1 | 0 | -1 (any other label gets the positional encoding alone, as segment_anything does) */
+  const float* boxes;       /* DEVICE fp32 [n, 4] or NULL (es_mask_bbox's output) */
+  const void* mask_input;   /* must be NULL: refused (the reference never passes one) */
+  int32_t P, orig_h, orig_w;
+} es_sam_prompts;
+typedef struct es_sam_decoder es_sam_decoder;
+/* sd: segment_anything 1.0's names (prompt_encoder.*, mask_decoder.*), bare or under one prefix that ends in "prompt_encoder." / "mask_decoder."
+ * being stripped (e.g. "sam."); prompt_encoder.mask_downscaling.* is ignored; a missing key or a wrong shape is an error that names the key.
+ * device -1: a dry build that reports the arena size.  Refused with the reason before anything is launched: embed_dim not a multiple of 64
+ * (and, narrower, not 128 | 256: es_sam_upscale_masks), head widths other than es_attention's, more than 32 tokens
+ * (1 + n_mask_tokens + max_points + 2), grid outside 1..64.  The image-side GEMMs take the tile es_launch_choose gives for ONE image, so image i
+ * of a batch equals the image alone bit for bit. */
+int es_sam_decoder_create(const es_state_dict* sd, const es_sam_decoder_config* cfg, int dtype, int max_n, int max_points, int device,
+                          es_sam_decoder** out);
+void es_sam_decoder_destroy(es_sam_decoder* d);
+size_t es_sam_decoder_arena_bytes(const es_sam_decoder* d);
+/* emb_nchw DEVICE fp32 [n, embed_dim, grid, grid] -> low_res DEVICE fp32 [n, M, 4 grid, 4 grid], iou DEVICE fp32 [n, M]; M = n_mask_tokens - 1
+ * with multimask (rows 1..), else 1 (row 0); only those rows are computed.  A capturing stream is accepted. */
+int es_sam_decode(es_sam_decoder* d, const float* emb_nchw, const es_sam_prompts* prompts, int n, int multimask, float* low_res, float* iou,
+                  void* stream);
+/* es_sam_decode + es_sam_postprocess_masks at (orig_h, orig_w): masks DEVICE uint8 [n, M, H, W] and / or mask_logits fp32 [n, M, H, W]
+ * (either may be NULL, not both); low_res may be NULL (the arena then holds it) */
+int es_sam_predict(es_sam_decoder* d, const float* emb_nchw, const es_sam_prompts* prompts, int n, int multimask, float* low_res, float* iou,
+                   uint8_t* masks, float* mask_logits, void* stream);
+/* EfficientViTSam.postprocess_masks (sam.py:223-239) and the predictor's `> mask_threshold` (0): logits fp32 [count, L, L] -> bilinear
+ * (align_corners=False) to S x S, cropped to [:new_h, :new_w], bilinear to H x W, in torch's fp32 index and weight arithmetic (scale = in /
+ * out, source = scale (dst + 0.5) - 0.5 clamped at 0); the S x S canvas is never stored.  out_f32 [count, H, W] and out_u8 [count, H, W]
+ * (1 where the value is > 0, else 0): either may be NULL, not both.  One (new_h, new_w, H, W) per call, as for es_sam_compose. */
+int es_sam_postprocess_masks(const float* logits, int count, int L, int S, int new_h, int new_w, int H, int W, float* out_f32, uint8_t* out_u8,
+                             void* stream);
+int es_sam_postprocess_masks_host(const float* logits, int count, int L, int S, int new_h, int new_w, int H, int W, float* out_f32,
+                                  uint8_t* out_u8);
+/* getBox (extract_dataset.py:298-313) of masks uint8 [count, H, W]: boxes fp32 [count, 4] = {max(0, xmin - margin), max(0, ymin - margin),
+ * min(W, xmax + margin), min(H, ymax + margin)} over the nonzero pixels, zeros for a mask without one.  Integer min / max atomics on the box
+ * buffer itself (int32 between the three launches), so there is no workspace. */
+int es_mask_bbox(const uint8_t* masks, float* boxes, int count, int H, int W, int margin, void* stream);
+int es_mask_bbox_host(const uint8_t* masks, float* boxes, int count, int H, int W, int margin);
 
 
 #ifdef __cplusplus
