@@ -13,8 +13,55 @@
 #include "common.h"
 #include "../../include/edgestyle_hip.h"
 #include "plan.h"
+#include "gn_index.h"
 
 namespace {
+
+// s += a[0], a[stride], ... a[(n - 1) * stride] and ss += b[...] likewise, strictly in that order - the adds of the plain loop, on
+// the same values.  The loads of NB elements are issued before the first of their adds: n / NB dependent round trips to LDS (or
+// to memory), not n.  The last, partial batch reads element k again where it has none left (always a valid address) and leaves
+// those values out of the sum, so it is one round trip too and needs no branch.
+template <int NB>
+ES_DEVICE void fold2_ordered(const float* a, const float* b, const int stride, const int n, float& s, float& ss) {
+  float x[NB], y[NB];
+  int k = 0;
+  for (; k + NB <= n; k += NB) {
+#pragma unroll
+    for (int u = 0; u < NB; ++u) { x[u] = a[(k + u) * stride]; y[u] = b[(k + u) * stride]; }
+    __builtin_amdgcn_sched_barrier(0);           // (keeps the reads together: hipcc otherwise pairs each with its add to save registers)
+#pragma unroll
+    for (int u = 0; u < NB; ++u) { s += x[u]; ss += y[u]; }
+  }
+  if (k < n) {
+    const int rem = n - k;
+#pragma unroll
+    for (int u = 0; u < NB - 1; ++u) { const int i = (u < rem ? k + u : k) * stride; x[u] = a[i]; y[u] = b[i]; }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int u = 0; u < NB - 1; ++u) if (u < rem) { s += x[u]; ss += y[u]; }
+  }
+}
+template <int NB>
+ES_DEVICE float fold_ordered(const float* a, const int stride, const int n, float s) {
+  float x[NB];
+  int k = 0;
+  for (; k + NB <= n; k += NB) {
+#pragma unroll
+    for (int u = 0; u < NB; ++u) x[u] = a[(k + u) * stride];
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int u = 0; u < NB; ++u) s += x[u];
+  }
+  if (k < n) {
+    const int rem = n - k;
+#pragma unroll
+    for (int u = 0; u < NB - 1; ++u) x[u] = a[(u < rem ? k + u : k) * stride];
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int u = 0; u < NB - 1; ++u) if (u < rem) s += x[u];
+  }
+  return s;
+}
 
 constexpr int GN_MAX_CHUNK = 64;
 constexpr int GN_MAX_GROUPS = 64;
@@ -43,8 +90,9 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const es_gn_desc p) {
   const int PS = CH8 <= 256 ? 256 / CH8 : 1;          // pixel slots processed concurrently
   float* csum = (float*)smem;                        // [PS][C]
   float* csq = csum + PS * C;                        // [PS][C]
+  const float inv_ch8 = 1.0f / (float)CH8;
   for (int q = threadIdx.x; q < PS * CH8; q += 256) {
-    const int ps = q / CH8, qq = q - ps * CH8;
+    const int ps = gn_div(q, CH8, inv_ch8), qq = q - ps * CH8;
     const int c = qq * 8;
     const bool second = c >= p.C1;
     const T* src = second ? (const T*)p.x2 : (const T*)p.x;
@@ -66,10 +114,21 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const es_gn_desc p) {
         for (int e = 0; e < 8; ++e) { const float f = to_f32(v[e]); s[e] += f; ss[e] += f * f; }
       }
     }
-    for (; px < p1; px += PS) {
-      const auto v = as_vec8<T>(*(const u32x4*)(src + ((size_t)n * p.HW + px) * cs + cc));
+    if (px < p1) {
+      // the last GNU - 1 pixels or fewer as ONE more round trip (a load-add loop pays one each: at 64 x 64 a thread has 10 or 11 pixels,
+      // two whole batches and up to three of these).  A slot past the end loads pixel px again and is zeroed: zeros add nothing to either
+      // sum (the slab kernel's pad pixels rely on the same), so the accumulation over the real pixels is what it was, in the same order.
+      u32x4 raw[GNU > 1 ? GNU - 1 : 1];
 #pragma unroll
-      for (int e = 0; e < 8; ++e) { const float f = to_f32(v[e]); s[e] += f; ss[e] += f * f; }
+      for (int u = 0; u < GNU - 1; ++u) raw[u] = *(const u32x4*)(src + ((size_t)n * p.HW + (px + u * PS < p1 ? px + u * PS : px)) * cs + cc);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int u = 0; u < GNU - 1; ++u) {
+        if (px + u * PS >= p1) raw[u] = u32x4{0u, 0u, 0u, 0u};
+        const auto v = as_vec8<T>(raw[u]);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { const float f = to_f32(v[e]); s[e] += f; ss[e] += f * f; }
+      }
     }
 #pragma unroll
     for (int e = 0; e < 8; ++e) { csum[ps * C + c + e] = s[e]; csq[ps * C + c + e] = ss[e]; }
@@ -81,11 +140,22 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const es_gn_desc p) {
   const int gi = threadIdx.x / L, l = threadIdx.x % L;
   float s = 0.f, ss = 0.f;
   if (gi < p.groups) {
+    // a lane's items l, l + L, ... in that order, eight items' LDS reads issued before the first of their adds; an item past the
+    // end reads the batch's first item again and is left out of the sum.  Item -> (slot, channel) by gn_div: no integer division in the loop.
     const int items = PS * cpg;
-    for (int it = l; it < items; it += L) {
-      const int ps = it / cpg, c = gi * cpg + (it - ps * cpg);
-      s += csum[ps * C + c];
-      ss += csq[ps * C + c];
+    const float inv_cpg = 1.0f / (float)cpg;
+    for (int it = l; it < items; it += 8 * L) {
+      float a[8], b[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int i = it + u * L < items ? it + u * L : it;
+        const int ps = gn_div(i, cpg, inv_cpg), c = gi * cpg + (i - ps * cpg);
+        a[u] = csum[ps * C + c];
+        b[u] = csq[ps * C + c];
+      }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int u = 0; u < 8; ++u) if (it + u * L < items) { s += a[u]; ss += b[u]; }
     }
   }
   // fold the L (4 or 8) lanes of a group: DPP quad steps, then the half-row mirror pairs the two quads (no LDS)
@@ -107,16 +177,22 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const es_gn_desc p, const
   float* shift = scale + C;            // [C]
   float* gstat = shift + C;            // [groups*2] mean, rstd
   float* red = gstat + 2 * p.groups;   // [slices][groups*2] partial sums of the partials
-  // gamma / beta go into the tables first (raw): their HBM round trip overlaps the partials' one
-  {
-    const float* gam = p.gamma;
-    const float* bet = p.beta;
-    if (p.ngroups > 1) {
-      const int g = (n >= p.n_end[0]) + (n >= p.n_end[1]) + (n >= p.n_end[2]);
-      gam = p.gamma_g[g];
-      bet = p.beta_g[g];
-    }
-    for (int c = threadIdx.x; c < C; c += 256) { scale[c] = gam[c]; shift[c] = bet[c]; }
+  // gamma / beta go into the tables first (raw).  Their HBM round trip overlaps the partials' one: a thread's first four channels
+  // (C <= 1024) are loaded here and written to LDS behind the partials' fold - a loop that loads and stores channel by channel waits
+  // for each load before the partials' loads are even issued.  A channel past C loads channel 0 and is not stored.
+  const float* gam = p.gamma;
+  const float* bet = p.beta;
+  if (p.ngroups > 1) {
+    const int g = (n >= p.n_end[0]) + (n >= p.n_end[1]) + (n >= p.n_end[2]);
+    gam = p.gamma_g[g];
+    bet = p.beta_g[g];
+  }
+  float gpre[4], bpre[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int c = threadIdx.x + 256 * j;
+    gpre[j] = gam[c < C ? c : 0];
+    bpre[j] = bet[c < C ? c : 0];
   }
   {
     // all 256 threads reduce the [nchunk][groups*2] partials: column = (group, stat), rows split into slices;
@@ -125,15 +201,22 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const es_gn_desc p, const
     const int slices = 256 / cols;
     const int col = threadIdx.x % cols, sl = threadIdx.x / cols;
     if (sl < slices) {
-      float acc = 0.f;
+      // rows sl, sl + slices, ... in that order, eight rows' loads in flight (fold_ordered): nchunk reaches 64, and 128 with the
+      // producer's statistics - up to 32 rows per thread, which a load-add loop would fetch one round trip after another
       const float* pp = p.partials + (size_t)n * nchunk * cols + col;
-      for (int k = sl; k < nchunk; k += slices) acc += pp[(size_t)k * cols];
-      red[sl * cols + col] = acc;
+      const int rows = nchunk > sl ? (nchunk - sl + slices - 1) / slices : 0;
+      red[sl * cols + col] = fold_ordered<8>(pp + (size_t)sl * cols, slices * cols, rows, 0.f);
     }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int c = threadIdx.x + 256 * j;
+      if (c < C) { scale[c] = gpre[j]; shift[c] = bpre[j]; }
+    }
+    for (int c = threadIdx.x + 1024; c < C; c += 256) { scale[c] = gam[c]; shift[c] = bet[c]; }
     __syncthreads();
     for (int gi = threadIdx.x; gi < p.groups; gi += 256) {
       float s = 0.f, ss = 0.f;
-      for (int k = 0; k < slices; ++k) { s += red[k * cols + gi * 2]; ss += red[k * cols + gi * 2 + 1]; }
+      fold2_ordered<4>(red + gi * 2, red + gi * 2 + 1, cols, slices, s, ss);
       const float cnt = (float)cpg * (float)p.HW;
       const float mean = s / cnt;
       float var = ss / cnt - mean * mean;
@@ -143,8 +226,9 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const es_gn_desc p, const
     }
   }
   __syncthreads();
+  const float inv_cpg = 1.0f / (float)cpg;
   for (int c = threadIdx.x; c < C; c += 256) {           // same thread wrote scale[c] / shift[c] above
-    const int gi = c / cpg;
+    const int gi = gn_div(c, cpg, inv_cpg);
     const float sc = scale[c] * gstat[gi * 2 + 1];
     scale[c] = sc;
     shift[c] = shift[c] - gstat[gi * 2] * sc;
@@ -249,7 +333,7 @@ __global__ __launch_bounds__(256) void gn_slab_kernel(const es_gn_desc p, const 
   float* csq = csum + PS * W;            // [PS][W]
   float* gstat = csq + PS * W;           // [gpb][2] mean, rstd
   const int t = threadIdx.x;
-  const int ps = t / W8, cq = t - ps * W8;
+  const int ps = gn_div(t, W8, 1.0f / (float)W8), cq = t - ps * W8;
   const bool active = ps < PS;
   const int c = gb * W + cq * 8;         // first channel of this thread's chunk
   const bool second = c >= p.C1;
@@ -264,15 +348,25 @@ __global__ __launch_bounds__(256) void gn_slab_kernel(const es_gn_desc p, const 
   }
   u32x4 raw[CPT];
   f32x4 ga[2], be[2];
+  int lgs[8];                            // the local group of each of this thread's 8 channels
   if (active) {
+    // every load of the thread is issued here, before anything waits: a pad pixel (px >= HW) loads the sample's last pixel - a valid
+    // address - and is zeroed behind the scheduling barrier.  (Under `if (px < HW)` hipcc moved each pixel's conversion and sums into the
+    // branch beside its load: the CPT = 8 form waited for one memory round trip per pixel, up to eight in a row.)
 #pragma unroll
     for (int k = 0; k < CPT; ++k) {
       const int px = ps + k * PS;
-      raw[k] = u32x4{0u, 0u, 0u, 0u};
-      if (px < p.HW) raw[k] = *(const u32x4*)(src + ((size_t)n * p.HW + px) * cs + cc);
+      raw[k] = *(const u32x4*)(src + ((size_t)n * p.HW + (px < p.HW ? px : p.HW - 1)) * cs + cc);
     }
     ga[0] = *(const f32x4*)(gam + c); ga[1] = *(const f32x4*)(gam + c + 4);
     be[0] = *(const f32x4*)(bet + c); be[1] = *(const f32x4*)(bet + c + 4);
+    // the group indices need no statistics: they are worked out here, while the loads are in flight (eight integer divisions stood
+    // between the last barrier and the first store)
+    gn_chunk_groups(cq * 8, cpg, lgs);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int k = 0; k < CPT; ++k)
+      if (ps + k * PS >= p.HW) raw[k] = u32x4{0u, 0u, 0u, 0u};
     float s[8], ss[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) { s[e] = 0.f; ss[e] = 0.f; }
@@ -288,10 +382,11 @@ __global__ __launch_bounds__(256) void gn_slab_kernel(const es_gn_desc p, const 
   __syncthreads();
   {
     // two fixed-order steps: (1) one thread per channel folds the PS pixel slots (conflict-free LDS columns, no
-    // integer division), (2) one wave per local group folds its cpg channel sums with an xor tree
+    // integer division; PS is 51 or 25 on the pipeline's shapes and reaches 256: sixteen slots' reads per round trip,
+    // fold2_ordered), (2) one wave per local group folds its cpg channel sums with an xor tree
     for (int ch = t; ch < W; ch += 256) {
       float s = 0.f, ss = 0.f;
-      for (int q = 0; q < PS; ++q) { s += csum[q * W + ch]; ss += csq[q * W + ch]; }
+      fold2_ordered<16>(csum + ch, csq + ch, W, PS, s, ss);
       csum[ch] = s;                      // row 0 is only read by this same thread above
       csq[ch] = ss;
     }
@@ -316,7 +411,7 @@ __global__ __launch_bounds__(256) void gn_slab_kernel(const es_gn_desc p, const 
     float sc[8], sh[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      const int lg = (cq * 8 + e) / cpg;
+      const int lg = lgs[e];
       const float g = e < 4 ? ga[0][e & 3] : ga[1][e & 3], b = e < 4 ? be[0][e & 3] : be[1][e & 3];
       sc[e] = g * gstat[lg * 2 + 1];
       sh[e] = b - gstat[lg * 2] * sc[e];
