@@ -26,9 +26,16 @@ namespace {
 
 constexpr int kPrecisionBits = 32 - 8 - 2;      // Pillow's PRECISION_BITS for 8-bit channels
 
-// Pillow's filters (Resample.c): the triangle of BILINEAR (support 1) and the Keys cubic of BICUBIC (a = -0.5, support 2)
-__host__ __device__ inline double filter_support(int filter) { return filter == ES_FILTER_BICUBIC ? 2.0 : 1.0; }
+// Pillow's filters (Resample.c): the triangle of BILINEAR (support 1), the Keys cubic of BICUBIC (a = -0.5, support 2) and the
+// truncated sinc of LANCZOS (sinc(x) * sinc(x / 3) on [-3, 3), support 3; sinc(x) = sin(pi x) / (pi x))
+__host__ __device__ inline double filter_support(int filter) { return filter == ES_FILTER_LANCZOS ? 3.0 : (filter == ES_FILTER_BICUBIC ? 2.0 : 1.0); }
+__host__ __device__ inline double sinc_pi(double x) {
+  if (x == 0.0) return 1.0;
+  x = x * 3.14159265358979323846;
+  return sin(x) / x;
+}
 __host__ __device__ inline double filter_weight(int filter, double x) {
+  if (filter == ES_FILTER_LANCZOS) return -3.0 <= x && x < 3.0 ? sinc_pi(x) * sinc_pi(x / 3) : 0.0;
   if (x < 0.0) x = -x;
   if (filter == ES_FILTER_BICUBIC) {
     const double a = -0.5;
@@ -285,6 +292,90 @@ size_t sam_plan(const es_image_u8& im, int S, SamImg& d) {  // bytes of workspac
   return a + r;
 }
 
+
+// ---- create_processed_image: resize to any (new_h, new_w), keep a window that may hang outside ------------------------------------
+// The two passes of the calls above with a rectangular window instead of the centre square: only the columns [x0, x0 + ncols) and the
+// rows the window keeps are produced (the source rows the kept rows' taps reach, for the horizontal pass), and a pixel of the window
+// that lies outside the resized image is 0, as PIL's crop pads it.
+struct WinDesc {
+  const uint8_t* src;
+  long long stride;
+  uint8_t* tmp;           // horizontal pass result: source rows [y0, y0 + nrows) x the ncols kept columns x 3 (need_h only)
+  uint8_t* out;           // [out_h, out_w, 3]
+  int32_t in_h, in_w, ch;
+  int32_t rh, rw, top, left;
+  int32_t y0, nrows, x0, ncols;
+  int32_t need_h, need_v;
+};
+struct WinBatch { WinDesc d[kImgPerLaunch]; int32_t out_h, out_w, filter; };
+
+__global__ __launch_bounds__(256) void window_h_kernel(const WinBatch b) {
+  const WinDesc& d = b.d[blockIdx.y];
+  if (!d.need_h) return;
+  const int row3 = 3 * d.ncols;
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (long long)d.nrows * row3) return;
+  const int r = (int)(idx / row3), j = (int)(idx - (long long)r * row3);
+  const int xx = d.x0 + j / 3, c = j % 3;
+  const uint8_t* row = d.src + (size_t)(d.y0 + r) * (size_t)d.stride + c;
+  int acc = 1 << (kPrecisionBits - 1), xmin;
+  const int ch = d.ch;
+  resize_axis(b.filter, d.in_w, d.rw, xx, &xmin, [&](int x0, int x, int k) { acc += k * (int)row[(size_t)(x0 + x) * ch]; });
+  d.tmp[idx] = clip8(acc);
+}
+
+__global__ __launch_bounds__(256) void window_v_kernel(const WinBatch b) {
+  const WinDesc& d = b.d[blockIdx.y];
+  const int row3 = 3 * b.out_w;
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (long long)b.out_h * row3) return;
+  const int yy = (int)(idx / row3), j = (int)(idx - (long long)yy * row3);
+  const int x = j / 3, c = j - 3 * x;
+  const int ry = d.top + yy, rx = d.left + x;             // the pixel of the resized image this byte shows
+  uint8_t v = 0;
+  if (ry >= 0 && ry < d.rh && rx >= 0 && rx < d.rw) {     // (inside: rx is one of the kept columns, ry one of the kept rows)
+    const uint8_t* base;                                  // row 0 of the column the taps run down
+    long long pitch, first;                               // `first`: the source row that base points at
+    if (d.need_h) { base = d.tmp + (size_t)(rx - d.x0) * 3 + c; pitch = 3ll * d.ncols; first = d.y0; }
+    else { base = d.src + (size_t)rx * d.ch + c; pitch = d.stride; first = 0; }
+    if (d.need_v) {
+      int acc = 1 << (kPrecisionBits - 1), ymin;
+      resize_axis(b.filter, d.in_h, d.rh, ry, &ymin, [&](int y0, int y, int k) { acc += k * (int)base[(size_t)((long long)(y0 + y) - first) * (size_t)pitch]; });
+      v = clip8(acc);
+    } else {
+      v = base[(size_t)((long long)ry - first) * (size_t)pitch];
+    }
+  }
+  d.out[idx] = v;
+}
+
+// create_processed_image's geometry (extract_dataset.py:118-164) in double, in its order of operations and with its int() truncations
+// (Python's max(0, v) / min(n, v) keep v unless the bound is strictly better: the same values).  false: no positive scale comes out.
+bool person_fit(int height, int width, const double box[4], int final_w, int final_h, double margin, int32_t out[4]) {
+  double xmin = box[0], ymin = box[1], xmax = box[2], ymax = box[3];
+  const double bbox_width = xmax - xmin, bbox_height = ymax - ymin;
+  const double margin_width = bbox_width * margin, margin_height = bbox_height * margin;
+  xmin = xmin - margin_width; if (0.0 > xmin) xmin = 0.0;
+  xmax = xmax + margin_width; if ((double)width < xmax) xmax = (double)width;
+  ymin = ymin - margin_height; if (0.0 > ymin) ymin = 0.0;
+  ymax = ymax + margin_height; if ((double)height < ymax) ymax = (double)height;
+  const double bbox_center_x = (xmin + xmax) / 2.0, bbox_center_y = (ymin + ymax) / 2.0;
+  if (!(xmax - xmin > 0.0) || !(ymax - ymin > 0.0)) return false;
+  const double scale_x = (double)final_w / (xmax - xmin), scale_y = (double)final_h / (ymax - ymin);
+  const double scale = scale_y < scale_x ? scale_y : scale_x;
+  const double nw = (double)width * scale, nh = (double)height * scale;
+  if (!(nw >= 1.0 && nw <= 16777216.0 && nh >= 1.0 && nh <= 16777216.0)) return false;
+  const int new_width = (int)nw, new_height = (int)nh;
+  const int new_bbox_center_x = (int)(bbox_center_x * scale), new_bbox_center_y = (int)(bbox_center_y * scale);
+  int left = new_bbox_center_x - final_w / 2, top = new_bbox_center_y - final_h / 2;
+  if (left < 0) left = 0;
+  if (top < 0) top = 0;
+  if (left + final_w > new_width) left = new_width - final_w;
+  if (top + final_h > new_height) top = new_height - final_h;
+  out[0] = new_width; out[1] = new_height; out[2] = left; out[3] = top;
+  return true;
+}
+
 thread_local char g_msg[224];
 int fail(const char* who, const char* what) {
   snprintf(g_msg, sizeof(g_msg), "%s: %s", who, what);
@@ -344,6 +435,13 @@ bool known_rules(const char* who, int filter, int crop) {
   if (filter != ES_FILTER_BILINEAR && filter != ES_FILTER_BICUBIC) { fail(who, "filter must be ES_FILTER_BILINEAR or ES_FILTER_BICUBIC"); return false; }
   if (crop != ES_CROP_TORCHVISION && crop != ES_CROP_TRANSFORMERS) { fail(who, "crop rule must be ES_CROP_TORCHVISION or ES_CROP_TRANSFORMERS"); return false; }
   return true;
+}
+
+// the windowed calls and es_image_resize_coeffs_ex also take ES_FILTER_LANCZOS (the centre-crop calls above keep their two filters)
+bool known_filter(const char* who, int filter) {
+  if (filter == ES_FILTER_BILINEAR || filter == ES_FILTER_BICUBIC || filter == ES_FILTER_LANCZOS) return true;
+  fail(who, "filter must be ES_FILTER_BILINEAR, ES_FILTER_BICUBIC or ES_FILTER_LANCZOS");
+  return false;
 }
 
 int resize_coeffs(const char* who, int filter, int in, int out, int32_t* xmin, int32_t* ntaps, int32_t* k, int cap) {
@@ -440,7 +538,7 @@ extern "C" int es_image_resize_coeffs(int in, int out, int32_t* xmin, int32_t* n
 }
 
 extern "C" int es_image_resize_coeffs_ex(int filter, int in, int out, int32_t* xmin, int32_t* ntaps, int32_t* k, int cap) {
-  if (!known_rules("es_image_resize_coeffs_ex", filter, ES_CROP_TORCHVISION)) return -1;
+  if (!known_filter("es_image_resize_coeffs_ex", filter)) return -1;
   return resize_coeffs("es_image_resize_coeffs_ex", filter, in, out, xmin, ntaps, k, cap);
 }
 
@@ -560,4 +658,143 @@ extern "C" int es_sam_preprocess_u8(const es_image_u8* imgs, int count, int S, c
   }
   if (hipGetLastError() != hipSuccess) { fail(who, "launch failed"); return -2; }
   return 0;
+}
+
+// ---- the windowed resize and create_processed_image ---------------------------------------------------------------------------------
+namespace {
+
+int window_check(const char* who, const es_image_u8* imgs, int count, const int32_t* geom, int out_h, int out_w, int filter) {
+  if (!geom) return fail(who, "null pointer (geom)");
+  if (out_h < 1 || out_w < 1) return fail(who, "out_h or out_w < 1");
+  if (out_h > 16384 || out_w > 16384) return fail(who, "out_h or out_w > 16384");
+  if (check_images(who, imgs, count, 1)) return -1;
+  if (!known_filter(who, filter)) return -1;
+  for (int i = 0; i < count; ++i) {
+    const int32_t* g = geom + 4 * i;
+    if (g[0] < 1 || g[1] < 1) return fail_img(who, i, "new_w or new_h < 1");
+    if (g[0] > (1 << 24) || g[1] > (1 << 24)) return fail_img(who, i, "the resized image would pass 2^24 pixels on a side");
+    if (g[2] < -(1 << 24) || g[2] > (1 << 24) || g[3] < -(1 << 24) || g[3] > (1 << 24)) return fail_img(who, i, "left or top beyond +-2^24");
+  }
+  return 0;
+}
+
+// geometry of one image: the kept columns and rows of the resized image, which passes run, the source rows the kept rows read
+void window_plan(const es_image_u8& im, const int32_t g[4], int out_h, int out_w, int filter, WinDesc& d) {
+  d.src = im.data; d.stride = im.row_stride;
+  d.in_h = im.height; d.in_w = im.width; d.ch = im.channels;
+  d.rw = g[0]; d.rh = g[1]; d.left = g[2]; d.top = g[3];
+  d.need_h = d.rw != d.in_w;
+  d.need_v = d.rh != d.in_h;
+  const int x0 = d.left > 0 ? d.left : 0, x1 = std::min(d.left + out_w, d.rw);
+  const int r0 = d.top > 0 ? d.top : 0, r1 = std::min(d.top + out_h, d.rh);
+  d.x0 = x0; d.ncols = x1 > x0 ? x1 - x0 : 0;
+  d.y0 = r0; d.nrows = r1 > r0 ? r1 - r0 : 0;
+  if (d.ncols == 0 || d.nrows == 0) { d.ncols = d.nrows = 0; d.need_h = 0; }      // the window misses the image: all zeros
+  else if (d.need_v) {
+    int lo = d.in_h, hi = 0;
+    for (int yy = r0; yy < r1; ++yy) {
+      int ymin;
+      const int n = resize_axis(filter, d.in_h, d.rh, yy, &ymin, [](int, int, int) {});
+      lo = ymin < lo ? ymin : lo;
+      hi = ymin + n > hi ? ymin + n : hi;
+    }
+    d.y0 = lo; d.nrows = hi - lo;
+  }
+  d.tmp = nullptr; d.out = nullptr;
+}
+size_t window_tmp_bytes(const WinDesc& d) { return d.need_h ? (size_t)d.nrows * 3 * (size_t)d.ncols : 0; }
+
+int window_resize(const char* who, const es_image_u8* imgs, int count, const int32_t* geom, uint8_t* out, int out_h, int out_w, int filter,
+                  void* workspace, size_t workspace_bytes, void* stream) {
+  if (window_check(who, imgs, count, geom, out_h, out_w, filter)) return -1;
+  if (!out) return fail(who, "null pointer (out)");
+  if (es_plan_recording()) return fail(who, "a plan is recording on this thread; the byte-image calls are never part of a plan");
+  std::vector<WinDesc> ds((size_t)count);
+  size_t need = 0;
+  for (int i = 0; i < count; ++i) {
+    window_plan(imgs[i], geom + 4 * i, out_h, out_w, filter, ds[i]);
+    ds[i].tmp = (uint8_t*)workspace + need;
+    need += window_tmp_bytes(ds[i]);
+    ds[i].out = out + (size_t)i * 3 * out_h * out_w;
+  }
+  if (need && !workspace) return fail(who, "null pointer (workspace)");
+  if (workspace_bytes < need) {
+    snprintf(g_msg, sizeof(g_msg), "%s: workspace too small: %zu bytes given, %zu needed", who, workspace_bytes, need);
+    es_set_error(g_msg);
+    return -1;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const long long vtotal = 3ll * out_h * out_w;
+  for (int first = 0; first < count; first += kImgPerLaunch) {
+    WinBatch b = {};
+    b.out_h = out_h; b.out_w = out_w; b.filter = filter;
+    const int n = count - first < kImgPerLaunch ? count - first : kImgPerLaunch;
+    long long hmax = 0;
+    for (int i = 0; i < n; ++i) {
+      b.d[i] = ds[first + i];
+      if (b.d[i].need_h) hmax = std::max(hmax, 3ll * b.d[i].nrows * b.d[i].ncols);
+    }
+    if ((hmax + 255) / 256 > 0x7fffffffll) return fail(who, "too many elements for one launch");
+    if (hmax) hipLaunchKernelGGL(window_h_kernel, dim3((unsigned)((hmax + 255) / 256), n), dim3(256), 0, st, b);
+    hipLaunchKernelGGL(window_v_kernel, dim3((unsigned)((vtotal + 255) / 256), n), dim3(256), 0, st, b);
+  }
+  if (hipGetLastError() != hipSuccess) { fail(who, "launch failed"); return -2; }
+  return 0;
+}
+
+size_t window_workspace(const char* who, const es_image_u8* imgs, int count, const int32_t* geom, int out_h, int out_w, int filter) {
+  if (window_check(who, imgs, count, geom, out_h, out_w, filter)) return 0;
+  size_t need = 0;
+  WinDesc d;
+  for (int i = 0; i < count; ++i) { window_plan(imgs[i], geom + 4 * i, out_h, out_w, filter, d); need += window_tmp_bytes(d); }
+  return need;
+}
+
+constexpr int kPersonSize = 512;             // IMAGE_WIDTH = IMAGE_HEIGHT of extract_dataset.py
+constexpr double kPersonMargin = 0.1;        // BOX_MARGIN
+
+int person_geom(const char* who, const es_image_u8* imgs, int count, const double* boxes, std::vector<int32_t>& geom) {
+  if (!boxes) return fail(who, "null pointer (boxes)");
+  if (check_images(who, imgs, count, 1)) return -1;
+  geom.resize((size_t)count * 4);
+  for (int i = 0; i < count; ++i)
+    if (!person_fit(imgs[i].height, imgs[i].width, boxes + 4 * i, kPersonSize, kPersonSize, kPersonMargin, &geom[(size_t)i * 4]))
+      return fail_img(who, i, "the box (with its margin, inside the photo) is empty or gives a resized photo beyond 1 .. 2^24 pixels");
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int es_person_crop_fit(int height, int width, const double box[4], int final_w, int final_h, double margin, int32_t out[4]) {
+  const char* who = "es_person_crop_fit";
+  if (!box || !out) return fail(who, "null pointer");
+  if (height < 1 || width < 1) return fail(who, "height or width < 1");
+  if (final_w < 1 || final_h < 1 || final_w > 16384 || final_h > 16384) return fail(who, "final_w or final_h outside 1 .. 16384");
+  if (!(margin >= 0.0 && margin <= 16.0)) return fail(who, "margin outside 0 .. 16");
+  for (int k = 0; k < 4; ++k) if (!(box[k] >= -1e9 && box[k] <= 1e9)) return fail(who, "a box coordinate is not a finite number of pixels");
+  if (!person_fit(height, width, box, final_w, final_h, margin, out))
+    return fail(who, "the box (with its margin, inside the photo) is empty or gives a resized photo beyond 1 .. 2^24 pixels");
+  return 0;
+}
+
+extern "C" size_t es_image_resize_window_u8_workspace_bytes(const es_image_u8* imgs, int count, const int32_t* geom, int out_h, int out_w, int filter) {
+  return window_workspace("es_image_resize_window_u8_workspace_bytes", imgs, count, geom, out_h, out_w, filter);
+}
+
+extern "C" int es_image_resize_window_u8(const es_image_u8* imgs, int count, const int32_t* geom, uint8_t* out, int out_h, int out_w, int filter,
+                                         void* workspace, size_t workspace_bytes, void* stream) {
+  return window_resize("es_image_resize_window_u8", imgs, count, geom, out, out_h, out_w, filter, workspace, workspace_bytes, stream);
+}
+
+extern "C" size_t es_person_crop_u8_workspace_bytes(const es_image_u8* imgs, int count, const double* boxes) {
+  std::vector<int32_t> geom;
+  if (person_geom("es_person_crop_u8_workspace_bytes", imgs, count, boxes, geom)) return 0;
+  return window_workspace("es_person_crop_u8_workspace_bytes", imgs, count, geom.data(), kPersonSize, kPersonSize, ES_FILTER_LANCZOS);
+}
+
+extern "C" int es_person_crop_u8(const es_image_u8* imgs, int count, const double* boxes, uint8_t* out, void* workspace, size_t workspace_bytes,
+                                 void* stream) {
+  std::vector<int32_t> geom;
+  if (person_geom("es_person_crop_u8", imgs, count, boxes, geom)) return -1;
+  return window_resize("es_person_crop_u8", imgs, count, geom.data(), out, kPersonSize, kPersonSize, ES_FILTER_LANCZOS, workspace, workspace_bytes, stream);
 }

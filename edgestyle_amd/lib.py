@@ -182,6 +182,7 @@ class SamUpscaleDesc(C.Structure):  # es_sam_upscale_desc
 
 
 FILTER_BILINEAR, FILTER_BICUBIC = 0, 1           # ES_FILTER_*
+FILTER_LANCZOS = 2                               # ... es_image_resize_coeffs_ex and the windowed calls only
 CROP_TORCHVISION, CROP_TRANSFORMERS = 0, 1       # ES_CROP_*
 MASK_AND, MASK_OR, MASK_ANDNOT = 0, 1, 2         # ES_MASK_*
 
@@ -436,6 +437,15 @@ SYMBOLS = {
     "es_sam_postprocess_masks_host": (C.c_int, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "es_mask_bbox": (C.c_int, [_P, _P, _I, _I, _I, _I, _P]),
     "es_mask_bbox_host": (C.c_int, [_P, _P, _I, _I, _I, _I]),
+    "es_person_crop_fit": (C.c_int, [_I, _I, C.POINTER(C.c_double), _I, _I, C.c_double, C.POINTER(C.c_int32)]),
+    "es_image_resize_window_u8_workspace_bytes": (C.c_size_t, [C.POINTER(ImageU8), _I, C.POINTER(C.c_int32), _I, _I, _I]),
+    "es_image_resize_window_u8": (C.c_int, [C.POINTER(ImageU8), _I, C.POINTER(C.c_int32), _P, _I, _I, _I, _P, C.c_size_t, _P]),
+    "es_person_crop_u8_workspace_bytes": (C.c_size_t, [C.POINTER(ImageU8), _I, C.POINTER(C.c_double)]),
+    "es_person_crop_u8": (C.c_int, [C.POINTER(ImageU8), _I, C.POINTER(C.c_double), _P, _P, C.c_size_t, _P]),
+    "es_pose_draw": (C.c_int, [_P, _P, _I, _I, _I, _P]),
+    "es_pose_draw_host": (C.c_int, [_P, _P, _I, _I, _I]),
+    "es_pose_select_host": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), _I]),
+    "es_pose_points_host": (C.c_int, [_P, _I, _I, _P]),
 }
 
 _lib = None

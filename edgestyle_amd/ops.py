@@ -1215,6 +1215,87 @@ def image_f32_to_u8(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torc
     return out
 
 
+def person_crop_fit(height: int, width: int, box, final_width: int = 512, final_height: int = 512, margin: float = 0.1):
+    """create_processed_image's geometry (extract_dataset.py:118-164) -> (new_w, new_h, left, top); left / top may be negative"""
+    out = (C.c_int32 * 4)()
+    b = (C.c_double * 4)(*[float(v) for v in box])
+    L.check(L.load().es_person_crop_fit(int(height), int(width), b, int(final_width), int(final_height), float(margin), out), "es_person_crop_fit")
+    return tuple(out)
+
+
+def _u8_out_and_workspace(what, out, shape, need, workspace, dev):
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=dev)
+    elif out.dtype != torch.uint8 or out.device != dev or tuple(out.shape) != tuple(shape) or not out.is_contiguous():
+        raise L.EdgeStyleHipError(f"{what}: out must be a contiguous uint8 {list(shape)} tensor on {dev}")
+    if workspace is None:
+        workspace = torch.empty((max(need, 1),), dtype=torch.uint8, device=dev)
+    elif workspace.dtype != torch.uint8 or workspace.device != dev or not workspace.is_contiguous() or workspace.numel() < need:
+        raise L.EdgeStyleHipError(f"{what}: workspace must be a contiguous uint8 tensor of at least {need} bytes on {dev}")
+    return out, workspace
+
+
+def image_resize_window_u8(images: Sequence[torch.Tensor], geom, out_h: int, out_w: int, filter: int = L.FILTER_LANCZOS,
+                           out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Each uint8 HWC device image resized to geom[i] = (new_w, new_h, left, top)'s size with Pillow's `filter`, of which the out_h x out_w
+    window at (top, left) is kept (zeros where it hangs outside), as ONE call: -> uint8 [count, out_h, out_w, 3]."""
+    what = "image_resize_window_u8"
+    descs = image_descriptors(images, what)
+    n, dev = len(images), images[0].device
+    flat = [int(v) for g in geom for v in g]
+    if len(flat) != 4 * n:
+        raise L.EdgeStyleHipError(f"{what}: geom must hold (new_w, new_h, left, top) for each of the {n} images")
+    g = (C.c_int32 * (4 * n))(*flat)
+    lib = L.load()
+    need = int(lib.es_image_resize_window_u8_workspace_bytes(descs, n, g, int(out_h), int(out_w), int(filter)))
+    out, workspace = _u8_out_and_workspace(what, out, (n, int(out_h), int(out_w), 3), need, workspace, dev)
+    L.check(lib.es_image_resize_window_u8(descs, n, g, _ptr(out), int(out_h), int(out_w), int(filter), _ptr(workspace), workspace.numel(), _stream()),
+            "es_image_resize_window_u8")
+    return out
+
+
+def person_crop_u8(images: Sequence[torch.Tensor], boxes, out: Optional[torch.Tensor] = None,
+                   workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """create_processed_image (extract_dataset.py:112-171) for a list of uint8 HWC device photos and their person boxes
+    (xmin, ymin, xmax, ymax) as ONE call: -> uint8 [count, 512, 512, 3]."""
+    what = "person_crop_u8"
+    descs = image_descriptors(images, what)
+    n, dev = len(images), images[0].device
+    flat = [float(v) for b in boxes for v in b]
+    if len(flat) != 4 * n:
+        raise L.EdgeStyleHipError(f"{what}: boxes must hold (xmin, ymin, xmax, ymax) for each of the {n} images")
+    b = (C.c_double * (4 * n))(*flat)
+    lib = L.load()
+    out4 = (C.c_int32 * 4)()
+    for i in range(n):                                     # (a refused box is reported before anything is allocated)
+        L.check(lib.es_person_crop_fit(descs[i].height, descs[i].width, (C.c_double * 4)(*flat[4 * i:4 * i + 4]), 512, 512, 0.1, out4),
+                "es_person_crop_fit")
+    need = int(lib.es_person_crop_u8_workspace_bytes(descs, n, b))
+    out, workspace = _u8_out_and_workspace(what, out, (n, 512, 512, 3), need, workspace, dev)
+    L.check(lib.es_person_crop_u8(descs, n, b, _ptr(out), _ptr(workspace), workspace.numel(), _stream()), "es_person_crop_u8")
+    return out
+
+
+def pose_draw(keypoints: torch.Tensor, H: int, W: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """draw_poses(.., draw_body=True) on black canvases (csrc/pose.hip): fp32 device key points [count, 18, 3] = (x, y, score), x and y in
+    [0, 1], score not > 0 = absent -> uint8 [count, H, W, 3], one launch."""
+    what = "pose_draw"
+    kp = keypoints
+    if not torch.is_tensor(kp) or kp.dtype != torch.float32 or not kp.is_cuda:
+        raise L.EdgeStyleHipError(f"{what}: keypoints must be an fp32 device tensor")
+    if kp.dim() != 3 or tuple(kp.shape[1:]) != (18, 3) or kp.shape[0] < 1 or not kp.is_contiguous():
+        raise L.EdgeStyleHipError(f"{what}: keypoints must be a dense [count, 18, 3] tensor, got {tuple(kp.shape)}")
+    n, H, W = kp.shape[0], int(H), int(W)
+    if H < 1 or W < 1:
+        raise L.EdgeStyleHipError(f"{what}: H or W < 1")
+    if out is None:
+        out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=kp.device)
+    elif out.dtype != torch.uint8 or out.device != kp.device or tuple(out.shape) != (n, H, W, 3) or not out.is_contiguous():
+        raise L.EdgeStyleHipError(f"{what}: out must be a contiguous uint8 [{n}, {H}, {W}, 3] tensor on {kp.device}")
+    L.check(L.load().es_pose_draw(_ptr(kp), _ptr(out), n, H, W, _stream()), "es_pose_draw")
+    return out
+
+
 # ----------------------------------------------------------------------------------------------------------------
 # mask post-processing (csrc/mask.hip): bit-packed morphology, largest 8-connected component, boolean algebra, draw_binary_mask
 # and create_sam_images in one call.  Masks are uint8 (or bool) device tensors [count, H, W]; results are uint8 of 0 / 1.

@@ -773,7 +773,7 @@ int es_image_f32_to_u8(const float* in_nchw, uint8_t* out_hwc, int B, int H, int
  * through CLIPProcessor); its wider support widens the range of source rows the horizontal pass keeps for the vertical one.
  * ES_CROP_TRANSFORMERS is transformers.image_transforms.center_crop: top = (rh - R) // 2, left = (rw - R) // 2 (the half is dropped,
  * where torchvision rounds it to even).  The size rule is the same for both: shortest edge -> R, the other (int)(R * long / short). */
-enum { ES_FILTER_BILINEAR = 0, ES_FILTER_BICUBIC = 1 };
+enum { ES_FILTER_BILINEAR = 0, ES_FILTER_BICUBIC = 1, ES_FILTER_LANCZOS = 2 /* coeffs_ex and the windowed calls below only */ };
 enum { ES_CROP_TORCHVISION = 0, ES_CROP_TRANSFORMERS = 1 };
 int es_image_fit_ex(int height, int width, int R, int crop, int32_t out[4]);
 int es_image_resize_coeffs_ex(int filter, int in, int out, int32_t* xmin, int32_t* ntaps, int32_t* k, int cap);
@@ -790,6 +790,85 @@ int es_prepare_conds_u8(es_ctx* c, const es_image_u8* images, const int32_t* nor
 /* es_vae_decode to bytes: the unchanged decode plan into ES_BUF_IMAGE, then es_image_f32_to_u8 from there;
  * out_hwc device uint8 [B,8h,8w,3].  Capturable like es_vae_decode. */
 int es_vae_decode_u8(es_ctx* c, const float* latents, uint8_t* out_hwc, void* stream);
+
+/* =========================================================================================================
+ * Person crop (csrc/image_io.hip): create_processed_image (extract_dataset.py:112-171) - the photo resized with Pillow's LANCZOS so that
+ * the person box with a 10 % margin fits 512 x 512, and a 512 x 512 window cut around the box centre - from a decoded photo and the
+ * detector's box.  ES_FILTER_LANCZOS is Pillow's LANCZOS: sinc(x) * sinc(x / 3) on [-3, 3), support 3.0 (stretched by the scale when
+ * shrinking), through the same coefficient code, 22-bit quantisation and two uint8 passes as the other filters: the bytes equal Pillow's.
+ * es_image_resize_coeffs_ex and the windowed calls take it; the centre-crop calls above keep their two filters.
+ * Opt-in: no existing call changes its bytes; never part of a plan (-1 while one records on the thread), ES_ABI_VERSION stays.
+ * ========================================================================================================= */
+/* host-only: lines 118-164 in double, in the reference's order of operations and with its int() truncations.  box = {xmin, ymin, xmax,
+ * ymax} in pixels of the height x width photo; out = {new_w, new_h, left, top}: the size the photo is resized to and where the
+ * final_w x final_h window starts in it.  left / top are NEGATIVE when the resized photo is smaller than the window (a tall narrow
+ * photo: new_w - final_w < 0), as in the reference, whose PIL crop then pads with zeros.  -1: bad arguments, or a box that is empty
+ * once the margin is added and it is cut to the photo (the reference divides by zero there). */
+int es_person_crop_fit(int height, int width, const double box[4], int final_w, int final_h, double margin, int32_t out[4]);
+/* imgs: HOST array of `count` descriptors (device bytes, any sizes, pitched rows, 3 | 4 channels); geom: HOST int32 [count][4] =
+ * {new_w, new_h, left, top} per image.  Image i is resized to new_h x new_w with `filter` (any ES_FILTER_*; an axis whose size stays is
+ * skipped, as Pillow skips it) and out[i] - device uint8 [count, out_h, out_w, 3] - receives the window whose corner is (top, left);
+ * bytes of the window outside the resized image are 0.  Only the columns the window shows and the source rows its rows read are
+ * computed.  workspace: the uint8 image between the passes, es_image_resize_window_u8_workspace_bytes (may be 0).  Asynchronous on
+ * `stream`, nothing is allocated: capturable.  Two launches per 16 images. */
+size_t es_image_resize_window_u8_workspace_bytes(const es_image_u8* imgs, int count, const int32_t* geom, int out_h, int out_w, int filter);
+int es_image_resize_window_u8(const es_image_u8* imgs, int count, const int32_t* geom, uint8_t* out, int out_h, int out_w, int filter,
+                              void* workspace, size_t workspace_bytes, void* stream);
+/* create_processed_image in one call: es_person_crop_fit(.., 512, 512, 0.1) per image, then es_image_resize_window_u8(.., 512, 512,
+ * ES_FILTER_LANCZOS).  boxes: HOST double [count][4]; out: device uint8 [count, 512, 512, 3] - the "processed" photo the SAM encoder,
+ * es_sam_compose and es_clip_pick take. */
+size_t es_person_crop_u8_workspace_bytes(const es_image_u8* imgs, int count, const double* boxes);
+int es_person_crop_u8(const es_image_u8* imgs, int count, const double* boxes, uint8_t* out, void* workspace, size_t workspace_bytes,
+                      void* stream);
+
+/* =========================================================================================================
+ * Pose rendering (csrc/pose.hip): controlnet_aux's draw_poses(.., draw_body=True, draw_hand=False, draw_face=False) on a black canvas,
+ * as create_openpose calls it after detect_poses (extract_dataset.py:222-295), and the host logic around it.  The detectors themselves
+ * (YOLOv5, OpenPose) are not part of this library.
+ * KEY POINTS: fp32 [count, 18, 3] = (x, y, score), x and y normalised to [0, 1] as in the reference's JSON (OpenPose body order: nose,
+ * neck, r-shoulder, r-elbow, r-wrist, l-shoulder, l-elbow, l-wrist, r-hip, r-knee, r-ankle, l-hip, l-knee, l-ankle, r-eye, l-eye, r-ear,
+ * l-ear).  A key point is ABSENT iff its score is not > 0 (NaN counts as absent).  es_pose_draw moreover does not draw a present point
+ * whose pixel position |x * W| or |y * H| is not below 65536 (or is NaN): it lies at least three canvases outside.
+ * WHAT IS DRAWN, in this order, the last writer winning, clipped at the canvas edge:
+ *  - limbs 1 .. 17 = (from, to), 1-based: (2,3) (2,6) (3,4) (4,5) (6,7) (7,8) (2,9) (9,10) (10,11) (2,12) (12,13) (13,14) (2,1) (1,15)
+ *    (15,17) (1,16) (16,18), skipped when either end is absent, in colour int(c * 0.6) per channel of
+ *    colours 1 .. 18 = (255,0,0) (255,85,0) (255,170,0) (255,255,0) (170,255,0) (85,255,0) (0,255,0) (0,255,85) (0,255,170) (0,255,255)
+ *    (0,170,255) (0,85,255) (0,0,255) (85,0,255) (170,0,255) (255,0,255) (255,0,170) (255,0,85);
+ *  - then every present key point i as a disc of radius 4 in colour i.
+ * The result is uint8 HWC [count, H, W, 3], what es_prepare_conds_u8 takes (normalize 0) as it lies; the reference's trailing cv2.resize
+ * to the same size is the identity.
+ * WHICH PIXELS A SHAPE COVERS is OpenCV's polygon and circle rasteriser in the reference; here it is this rule, in integers:
+ *  - X = (double)x * W, Y = (double)y * H (one IEEE product each).  A limb from P to Q has centre (cx, cy) = ((int)((X_P + X_Q) / 2),
+ *    (int)((Y_P + Y_Q) / 2)); qx = (int64)((X_P - X_Q) * 256), qy likewise (every cast truncates toward zero, like Python's int());
+ *    a = isqrt(qx^2 + qy^2) >> 9 is int(length / 2); its angle t = int(degrees(atan2(dy, dx))) is found without atan2: with
+ *    S(t) = round(sin(t deg) * 2^30) from a fixed 91-entry table (and its symmetries; C(t) = S(t + 90)), t' is the first of 0 .. 180
+ *    for which t' = 180 or C(t' + 1) * |qy| - S(t' + 1) * qx < 0, and t = t' or, when qy < 0, -t'.
+ *  - The limb is the ellipse with semi-axes a + 1/2 along (C(t), S(t)) and 4 + 1/2 across it (the half pixel stands for the boundary
+ *    OpenCV's fill includes); a point is the disc of radius 4 around ((int)X, (int)Y), rim included.  With A = 2a + 1, B = 9 (A = B = 8
+ *    and t = 0 for a disc), pixel (px, py) is covered iff, for u = px - cx, v = py - cy,
+ *      al = (u * C + v * S + 2^21) >> 22,  ac = (v * C - u * S + 2^21) >> 22      (floor; 1/256 pixel along and across)
+ *      |al| <= 128 A  and  |ac| <= 128 B  and  al^2 B^2 + ac^2 A^2 <= 16384 A^2 B^2      (64-bit integers).
+ *    A limb whose ends coincide (a = 0) is a stroke one pixel wide and nine long across its direction.
+ * No atan2, sqrt, sin or cos is evaluated anywhere, so es_pose_draw_host - the same __host__ __device__ code - and the kernel agree bit
+ * for bit.  Against the reference's own renderings of docs/test/{source,target}/openpose/N.json the rule reaches a whole-image PSNR of
+ * 34.3 - 34.6 dB and an IoU of 0.93 (pixels whose largest channel exceeds 40), as tests/test_pose_cpu.py asserts; it is not OpenCV's
+ * rasteriser byte for byte.
+ * Never part of a plan (-1 while one records on the thread); ES_ABI_VERSION stays.
+ * ========================================================================================================= */
+/* kp: DEVICE fp32 [count, 18, 3]; out: DEVICE uint8 [count, H, W, 3], every byte written.  1 <= H, W <= 16384, count <= 65535.  One
+ * launch for the whole batch, no atomics, nothing allocated: capturable. */
+int es_pose_draw(const float* kp, uint8_t* out, int count, int H, int W, void* stream);
+/* host-only: the same on HOST memory */
+int es_pose_draw_host(const float* kp, uint8_t* out, int count, int H, int W);
+/* host-only: create_openpose's filters and choice (lines 222-268) over n candidates - kps HOST fp32 [n, 18, 3], total_score and
+ * total_parts HOST double [n].  Kept: score > 10, parts > 5, any of nose / neck / eyes / ears present, a shoulder present, a hip present.
+ * Chosen: the largest area of the box around the present key points (in normalised coordinates), ties in input order.  Returns its
+ * index, -1 when none remains (n = 0 included), -2 on bad arguments. */
+int es_pose_select_host(const float* kps, const double* total_score, const double* total_parts, int n);
+/* host-only: the SAM point prompt of create_sam_images:361-365 - the present key points of one pose (kp HOST fp32 [18, 3]) times (W, H),
+ * in order, into out (HOST fp32 [18, 2], the first `count` rows written); returns count, -1 on bad arguments.  The rows are what
+ * es_sam_prompts.points takes, with label 1 each. */
+int es_pose_points_host(const float* kp, int W, int H, float* out);
 
 /* =========================================================================================================
  * Seeded noise (csrc/rng.hip): the normal stream of torch's DEVICE generator, restated, so that a host without Python can take
@@ -1139,7 +1218,8 @@ int es_sam_encode_u8(es_sam_encoder* e, const es_image_u8* imgs, int count, floa
  * layers of the TwoWayTransformer, the fused upscaling tail, postprocess_masks and getBox of segment_anything 1.0's PromptEncoder / MaskDecoder as EfficientViT-SAM
  * builds them (efficientvit/models/efficientvit/sam.py:522-540) and as extract_dataset.py:371-429 chains them: a decode's mask gives the box
  * of the next decode without a host visit.  es_sam_decoder strings them together with es_conv_gemm, es_layer_norm,
- * es_add and es_attention: a C++ host needs only the pose key points from outside.
+ * es_add and es_attention: a C++ host needs only the person box and the pose key points from outside (the two detectors' results;
+ * es_pose_points_host turns the key points into the point prompt, es_person_crop_u8 the box into the photo these calls take).
  * No float atomics, nothing allocated or read back (capturable), image i of a batch equals the image alone bit for bit; never part of a
  * plan (-1 while one records on the thread), so ES_ABI_VERSION stays.  The *_host twins run the kernels' own index and weight code on the CPU.
  * ========================================================================================================= */
