@@ -130,6 +130,13 @@ class ImageU8(C.Structure):         # es_image_u8
     _fields_ = [("data", C.c_void_p), ("height", C.c_int32), ("width", C.c_int32), ("channels", C.c_int32), ("row_stride", C.c_int64)]
 
 
+class JpegInfo(C.Structure):        # es_jpeg_info
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("components", C.c_int32), ("h", C.c_int32 * 3), ("v", C.c_int32 * 3),
+                ("tq", C.c_int32 * 3), ("td", C.c_int32 * 3), ("ta", C.c_int32 * 3), ("hmax", C.c_int32), ("vmax", C.c_int32),
+                ("mcus_x", C.c_int32), ("mcus_y", C.c_int32), ("blocks_w", C.c_int32 * 3), ("blocks_h", C.c_int32 * 3),
+                ("restart_interval", C.c_int32)]
+
+
 class Philox(C.Structure):          # es_philox
     _fields_ = [("seed", C.c_uint64), ("offset", C.c_uint64)]
 
@@ -446,6 +453,14 @@ SYMBOLS = {
     "es_pose_draw_host": (C.c_int, [_P, _P, _I, _I, _I]),
     "es_pose_select_host": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), _I]),
     "es_pose_points_host": (C.c_int, [_P, _I, _I, _P]),
+    "es_jpeg_info_host": (C.c_int, [_P, C.c_size_t, C.POINTER(JpegInfo)]),
+    "es_jpeg_coeff_count": (C.c_size_t, [C.POINTER(JpegInfo)]),
+    "es_jpeg_entropy_decode_host": (C.c_int, [_P, C.c_size_t, C.POINTER(JpegInfo), _P, _P]),
+    "es_jpeg_reconstruct_workspace_bytes": (C.c_size_t, [C.POINTER(JpegInfo), _I]),
+    "es_jpeg_reconstruct": (C.c_int, [C.POINTER(JpegInfo), _I, C.POINTER(_P), C.POINTER(_P), C.POINTER(ImageU8), _P, C.c_size_t, _P]),
+    "es_jpeg_reconstruct_host": (C.c_int, [C.POINTER(JpegInfo), _I, C.POINTER(_P), C.POINTER(_P), C.POINTER(ImageU8)]),
+    "es_jpeg_decode_staging_bytes": (C.c_size_t, [C.POINTER(JpegInfo), _I]),
+    "es_jpeg_decode_u8": (C.c_int, [C.POINTER(_P), C.POINTER(C.c_size_t), _I, C.POINTER(ImageU8), _P, _P, C.c_size_t, _P, C.c_size_t, _P]),
 }
 
 _lib = None

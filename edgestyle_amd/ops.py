@@ -1297,6 +1297,96 @@ def pose_draw(keypoints: torch.Tensor, H: int, W: int, out: Optional[torch.Tenso
 
 
 # ----------------------------------------------------------------------------------------------------------------
+# JPEG reconstruction (csrc/jpeg.hip): quantised DCT coefficients -> RGB bytes.  The host half (headers, Huffman decoding) is wrapped in
+# edgestyle_amd/jpeg.py, which also owns the convenient entry points; these two take what it prepared.
+# ----------------------------------------------------------------------------------------------------------------
+def _jpeg_outputs(what, infos, out, dev):
+    n = len(infos)
+    if out is None:
+        out = [torch.empty((infos[i].height, infos[i].width, 3), dtype=torch.uint8, device=dev) for i in range(n)]
+    if len(out) != n:
+        raise L.EdgeStyleHipError(f"{what}: {n} outputs expected")
+    descs = (L.ImageU8 * n)()
+    for i, t in enumerate(out):
+        H, W = infos[i].height, infos[i].width
+        if (not torch.is_tensor(t) or t.dtype != torch.uint8 or t.device != dev or tuple(t.shape) != (H, W, 3) or t.stride(2) != 1
+                or t.stride(1) != 3 or (H > 1 and t.stride(0) < W * 3)):
+            raise L.EdgeStyleHipError(f"{what}: output {i} must be a uint8 [{H}, {W}, 3] tensor on {dev} with dense pixels")
+        descs[i].data, descs[i].height, descs[i].width, descs[i].channels = t.data_ptr(), H, W, 3
+        descs[i].row_stride = t.stride(0) if H > 1 else W * 3
+    return out, descs
+
+
+def _jpeg_bytes_buffer(what, t, need, dev, name):
+    if t is None:
+        return torch.empty((max(need, 1),), dtype=torch.uint8, device=dev)
+    if t.dtype != torch.uint8 or t.device != dev or not t.is_contiguous() or t.numel() < need:
+        raise L.EdgeStyleHipError(f"{what}: {name} must be a contiguous uint8 tensor of at least {need} bytes on {dev}")
+    return t
+
+
+def jpeg_reconstruct(infos, coeffs: Sequence[torch.Tensor], qtables: Sequence[torch.Tensor], out=None,
+                     workspace: Optional[torch.Tensor] = None):
+    """infos: an array of L.JpegInfo; coeffs[i] / qtables[i]: device int16 tensors holding what es_jpeg_entropy_decode_host wrote for image
+    i (the tables' uint16 values as their int16 bit patterns).  -> a list of uint8 [H, W, 3] device tensors (`out`, when given: rows may
+    be pitched).  Images of different sizes and samplings are ONE call: two launches per 16 images."""
+    what = "jpeg_reconstruct"
+    n = len(infos)
+    if n < 1 or len(coeffs) != n or len(qtables) != n:
+        raise L.EdgeStyleHipError(f"{what}: one coefficient and one table tensor per image expected")
+    dev = coeffs[0].device
+    lib = L.load()
+    for i in range(n):
+        for t, count, name in ((coeffs[i], int(lib.es_jpeg_coeff_count(C.byref(infos[i]))), "coefficients"), (qtables[i], 64 * infos[i].components, "tables")):
+            if count == 0:
+                L.check(-1, "es_jpeg_coeff_count")
+            if not torch.is_tensor(t) or t.dtype != torch.int16 or t.device != dev or not t.is_cuda or not t.is_contiguous() or t.numel() < count:
+                raise L.EdgeStyleHipError(f"{what}: {name} {i} must be a contiguous int16 device tensor of at least {count} values")
+    need = int(lib.es_jpeg_reconstruct_workspace_bytes(infos, n))
+    if need == 0:
+        L.check(-1, "es_jpeg_reconstruct_workspace_bytes")
+    out, descs = _jpeg_outputs(what, infos, out, dev)
+    workspace = _jpeg_bytes_buffer(what, workspace, need, dev, "workspace")
+    cp = (C.c_void_p * n)(*[t.data_ptr() for t in coeffs])
+    qp = (C.c_void_p * n)(*[t.data_ptr() for t in qtables])
+    L.check(lib.es_jpeg_reconstruct(infos, n, cp, qp, descs, _ptr(workspace), workspace.numel(), _stream()), "es_jpeg_reconstruct")
+    return out
+
+
+def jpeg_decode_u8(datas: Sequence[bytes], infos, device, out=None, staging_host: Optional[torch.Tensor] = None,
+                   staging_dev: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
+    """es_jpeg_decode_u8: parse + upload + reconstruct of up to 64 files (bytes objects; infos: their L.JpegInfo array) in one call ->
+    a list of uint8 [H, W, 3] tensors on `device`.  staging_host: a pinned uint8 host tensor the caller keeps untouched until the stream has
+    passed the upload; when None one is allocated and the call waits for the stream before it returns."""
+    what = "jpeg_decode_u8"
+    n = len(datas)
+    if n < 1 or len(infos) != n:
+        raise L.EdgeStyleHipError(f"{what}: one info per file expected")
+    dev = torch.device(device)
+    if dev.type == "cuda" and dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    lib = L.load()
+    stage, need = int(lib.es_jpeg_decode_staging_bytes(infos, n)), int(lib.es_jpeg_reconstruct_workspace_bytes(infos, n))
+    if stage == 0 or need == 0:
+        L.check(-1, "es_jpeg_decode_staging_bytes")
+    out, descs = _jpeg_outputs(what, infos, out, dev)
+    own = staging_host is None
+    if own:
+        staging_host = torch.empty((stage,), dtype=torch.uint8, pin_memory=True)
+    elif staging_host.dtype != torch.uint8 or staging_host.is_cuda or not staging_host.is_contiguous() or staging_host.numel() < stage:
+        raise L.EdgeStyleHipError(f"{what}: staging_host must be a contiguous uint8 host tensor of at least {stage} bytes")
+    staging_dev = _jpeg_bytes_buffer(what, staging_dev, stage, dev, "staging_dev")
+    workspace = _jpeg_bytes_buffer(what, workspace, need, dev, "workspace")
+    bp = (C.c_void_p * n)(*[C.cast(C.c_char_p(d), C.c_void_p) for d in datas])
+    ln = (C.c_size_t * n)(*[len(d) for d in datas])
+    L.check(lib.es_jpeg_decode_u8(bp, ln, n, descs, C.c_void_p(staging_host.data_ptr()), _ptr(staging_dev), min(staging_host.numel(), staging_dev.numel()),
+                                  _ptr(workspace), workspace.numel(), _stream()), "es_jpeg_decode_u8")
+    if own:                                       # the upload reads the staging memory on the stream: it must not be freed before
+        torch.cuda.current_stream().synchronize()
+    return out
+
+
+# ----------------------------------------------------------------------------------------------------------------
 # mask post-processing (csrc/mask.hip): bit-packed morphology, largest 8-connected component, boolean algebra, draw_binary_mask
 # and create_sam_images in one call.  Masks are uint8 (or bool) device tensors [count, H, W]; results are uint8 of 0 / 1.
 # ----------------------------------------------------------------------------------------------------------------

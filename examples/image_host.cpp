@@ -7,7 +7,7 @@
 //   hipcc -O2 -Iinclude examples/image_host.cpp -Ledgestyle_amd/lib -ledgestyle_hip -Wl,-rpath,$PWD/edgestyle_amd/lib -o image_host
 //   ./image_host ctx.esctx cond0.ppm cond1.ppm cond2.ppm cond3.ppm cond4.ppm cond5.ppm inputs.bin out.ppm [--seed S [--cond-seed S2]]
 //
-// cond<i>.ppm: binary PPM (P6, maxval 255), the condition image of net i in the reference's order (agnostic, subject pose,
+// cond<i>.ppm: binary PPM (P6, maxval 255) or a baseline JPEG file (told by its first two bytes, decoded by es_jpeg_decode_u8), the condition image of net i in the reference's order (agnostic, subject pose,
 // clothes 1, pose 1, clothes 2, pose 2); a context of batch B > 1 takes the same six photos for every image of the batch.
 // inputs.bin (little endian, written by tests/test_image_io_gpu.py):
 //   int32 B, h, w, L, D, n_conds, n_steps, has_noise[n_conds], normalize[n_conds]; float guidance_scale; float timesteps[n_steps];
@@ -61,6 +61,41 @@ static bool read_ppm(const char* path, std::vector<uint8_t>& px, int* H, int* W)
   return ok;
 }
 
+// A photo that starts FF D8 is a JPEG file: decoded on the device by es_jpeg_decode_u8 (headers and Huffman decoding on this thread) into
+// [H, W, 3] device bytes, the bytes Pillow's Image.open(..).convert("RGB") gives.  0, or the exit status.
+static bool is_jpeg(const char* path) {
+  FILE* f = fopen(path, "rb");
+  if (!f) return false;
+  const bool yes = fgetc(f) == 0xFF && fgetc(f) == 0xD8;
+  fclose(f);
+  return yes;
+}
+static int load_jpeg(const char* path, uint8_t** d_px, int* H, int* W) {
+  std::vector<uint8_t> file;
+  FILE* f = fopen(path, "rb");
+  if (!f) { perror(path); return 1; }
+  uint8_t buf[65536];
+  size_t got;
+  while ((got = fread(buf, 1, sizeof(buf), f)) > 0) file.insert(file.end(), buf, buf + got);
+  fclose(f);
+  es_jpeg_info info;
+  ES_OK(es_jpeg_info_host(file.data(), file.size(), &info));
+  const size_t stage = es_jpeg_decode_staging_bytes(&info, 1), need = es_jpeg_reconstruct_workspace_bytes(&info, 1);
+  void *h_stage = nullptr, *d_stage = nullptr, *d_ws = nullptr;
+  HIP_OK(hipMalloc((void**)d_px, (size_t)info.height * info.width * 3));
+  HIP_OK(hipHostMalloc(&h_stage, stage));
+  HIP_OK(hipMalloc(&d_stage, stage));
+  HIP_OK(hipMalloc(&d_ws, need));
+  const es_image_u8 out = {*d_px, info.height, info.width, 3, (int64_t)info.width * 3};
+  const uint8_t* files[1] = {file.data()};
+  const size_t sizes[1] = {file.size()};
+  ES_OK(es_jpeg_decode_u8(files, sizes, 1, &out, h_stage, d_stage, stage, d_ws, need, nullptr));
+  HIP_OK(hipDeviceSynchronize());
+  (void)hipFree(d_ws); (void)hipFree(d_stage); (void)hipHostFree(h_stage);
+  *H = info.height; *W = info.width;
+  return 0;
+}
+
 int main(int argc, char** argv) {
   bool seeded = false, usage = argc < 10 || (argc - 10) % 2 != 0;
   es_philox lat_gen = {0, 0}, cond_gen = {0, 0};
@@ -111,10 +146,14 @@ int main(int argc, char** argv) {
   std::vector<uint8_t> px;
   for (int i = 0; i < nc; ++i) {
     int H = 0, W = 0;
-    if (!read_ppm(argv[2 + i], px, &H, &W)) return 1;
     uint8_t* p = nullptr;
-    HIP_OK(hipMalloc(&p, px.size()));
-    HIP_OK(hipMemcpy(p, px.data(), px.size(), hipMemcpyHostToDevice));
+    if (is_jpeg(argv[2 + i])) {
+      if (const int rc = load_jpeg(argv[2 + i], &p, &H, &W)) return rc;
+    } else {
+      if (!read_ppm(argv[2 + i], px, &H, &W)) return 1;
+      HIP_OK(hipMalloc(&p, px.size()));
+      HIP_OK(hipMemcpy(p, px.data(), px.size(), hipMemcpyHostToDevice));
+    }
     for (int b = 0; b < B; ++b) imgs[(size_t)i * B + b] = es_image_u8{p, H, W, 3, (int64_t)W * 3};
   }
   const int R = 8 * h;

@@ -7,7 +7,7 @@
 //   hipcc -O2 -Iinclude examples/pose_host.cpp -Ledgestyle_amd/lib -ledgestyle_hip -Wl,-rpath,$PWD/edgestyle_amd/lib -o pose_host
 //   ./pose_host photo.ppm xmin ymin xmax ymax keypoints.txt out
 //
-// photo.ppm: binary PPM (P6, maxval 255) of any size.  xmin .. ymax: the person detector's box in the photo's pixels.  keypoints.txt: 18
+// photo.ppm: binary PPM (P6, maxval 255) of any size, or a baseline JPEG file (told by its first two bytes, decoded by es_jpeg_decode_u8).  xmin .. ymax: the person detector's box in the photo's pixels.  keypoints.txt: 18
 // lines "x y score" in OpenPose body order, x and y normalised to [0, 1] of the processed photo, score 0 for a point that was not found.
 // Writes out_processed.ppm and out_pose.ppm (512 x 512 each) and prints the point prompt; both images are device memory that
 // es_sam_encode_u8, es_sam_compose and es_prepare_conds_u8 take as they are (examples/mask_host.cpp, examples/image_host.cpp) - this host
@@ -60,11 +60,50 @@ static bool write_ppm(const std::string& path, const uint8_t* px, int H, int W) 
   return true;
 }
 
+// A photo that starts FF D8 is a JPEG file: decoded on the device by es_jpeg_decode_u8 (headers and Huffman decoding on this thread) into
+// [H, W, 3] device bytes, the bytes Pillow's Image.open(..).convert("RGB") gives.  0, or the exit status.
+static bool is_jpeg(const char* path) {
+  FILE* f = fopen(path, "rb");
+  if (!f) return false;
+  const bool yes = fgetc(f) == 0xFF && fgetc(f) == 0xD8;
+  fclose(f);
+  return yes;
+}
+static int load_jpeg(const char* path, uint8_t** d_px, int* H, int* W) {
+  std::vector<uint8_t> file;
+  FILE* f = fopen(path, "rb");
+  if (!f) { perror(path); return 1; }
+  uint8_t buf[65536];
+  size_t got;
+  while ((got = fread(buf, 1, sizeof(buf), f)) > 0) file.insert(file.end(), buf, buf + got);
+  fclose(f);
+  es_jpeg_info info;
+  ES_OK(es_jpeg_info_host(file.data(), file.size(), &info));
+  const size_t stage = es_jpeg_decode_staging_bytes(&info, 1), need = es_jpeg_reconstruct_workspace_bytes(&info, 1);
+  void *h_stage = nullptr, *d_stage = nullptr, *d_ws = nullptr;
+  HIP_OK(hipMalloc((void**)d_px, (size_t)info.height * info.width * 3));
+  HIP_OK(hipHostMalloc(&h_stage, stage));
+  HIP_OK(hipMalloc(&d_stage, stage));
+  HIP_OK(hipMalloc(&d_ws, need));
+  const es_image_u8 out = {*d_px, info.height, info.width, 3, (int64_t)info.width * 3};
+  const uint8_t* files[1] = {file.data()};
+  const size_t sizes[1] = {file.size()};
+  ES_OK(es_jpeg_decode_u8(files, sizes, 1, &out, h_stage, d_stage, stage, d_ws, need, nullptr));
+  HIP_OK(hipDeviceSynchronize());
+  (void)hipFree(d_ws); (void)hipFree(d_stage); (void)hipHostFree(h_stage);
+  *H = info.height; *W = info.width;
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (argc != 8) { fprintf(stderr, "usage: %s photo.ppm xmin ymin xmax ymax keypoints.txt out\n", argv[0]); return 1; }
   std::vector<uint8_t> photo;
   int H = 0, W = 0;
-  if (!read_ppm(argv[1], photo, &H, &W)) return 1;
+  uint8_t* d_photo = nullptr;
+  const bool jpeg = is_jpeg(argv[1]);
+  if (jpeg) {
+    if (const int rc = load_jpeg(argv[1], &d_photo, &H, &W)) return rc;
+  } else if (!read_ppm(argv[1], photo, &H, &W)) return 1;
   const double box[4] = {atof(argv[2]), atof(argv[3]), atof(argv[4]), atof(argv[5])};
   float kp[18 * 3];
   {
@@ -77,11 +116,13 @@ int main(int argc, char** argv) {
   }
   const int S = 512;                            // the reference's IMAGE_WIDTH = IMAGE_HEIGHT: what es_person_crop_u8 writes
   const size_t out_bytes = (size_t)S * S * 3;
-  uint8_t *d_photo = nullptr, *d_processed = nullptr, *d_pose = nullptr;
+  uint8_t *d_processed = nullptr, *d_pose = nullptr;
   float* d_kp = nullptr;
   void* d_ws = nullptr;
-  HIP_OK(hipMalloc((void**)&d_photo, photo.size()));
-  HIP_OK(hipMemcpy(d_photo, photo.data(), photo.size(), hipMemcpyHostToDevice));
+  if (!jpeg) {
+    HIP_OK(hipMalloc((void**)&d_photo, photo.size()));
+    HIP_OK(hipMemcpy(d_photo, photo.data(), photo.size(), hipMemcpyHostToDevice));
+  }
   HIP_OK(hipMalloc((void**)&d_kp, sizeof(kp)));
   HIP_OK(hipMemcpy(d_kp, kp, sizeof(kp), hipMemcpyHostToDevice));
   HIP_OK(hipMalloc((void**)&d_processed, out_bytes));

@@ -871,6 +871,71 @@ int es_pose_select_host(const float* kps, const double* total_score, const doubl
 int es_pose_points_host(const float* kp, int W, int H, float* out);
 
 /* =========================================================================================================
+ * JPEG decoding (csrc/jpeg.h, csrc/jpeg.hip): the bytes of a baseline JPEG file -> uint8 [H, W, 3] RGB on the device, what Pillow's
+ * Image.open(..).convert("RGB") gives (libjpeg's default decoder settings: JDCT_ISLOW, fancy upsampling), byte for byte.  Two halves that
+ * meet at the quantised DCT coefficients: header parsing and Huffman decoding are serial and stay on the host (plain C++, csrc/jpeg.h);
+ * dequantisation, the 8x8 inverse DCT, chroma upsampling and YCbCr -> RGB are two launches on the device, and es_jpeg_reconstruct_host
+ * runs the same __host__ __device__ integer code on the CPU, bit for bit.
+ * SUPPORTED: SOF0 / SOF1, 8-bit samples, Huffman coding, one interleaved scan; 1 component (gray -> R = G = B) or 3 components YCbCr
+ * (JFIF, Adobe transform 1, or neither marker and component ids other than 'R','G','B') with luma sampling 1x1, 2x1 or 2x2 and chroma
+ * 1x1 (4:4:4, 4:2:2, 4:2:0); 8- and 16-bit quantisation tables, any number of DQT / DHT segments, DRI with RST0-7, 0xFF fill bytes; APPn
+ * and COM are skipped (EXIF orientation is not applied, as Pillow's open does not apply it).
+ * REFUSED, with the reason in es_last_error(): progressive (SOF2), lossless, arithmetic coding, 12-bit samples, 4 components (CMYK),
+ * Adobe transform 0 or RGB ids, other sampling factors, multi-scan files, a height or width of 0, anything truncated or malformed (a
+ * bad Huffman code, a missing table, a run past coefficient 63, a missing or misnumbered RST, no EOI after the scan).  The parser never
+ * reads past n and never writes outside the coefficient buffer, on any input.
+ * THE ARITHMETIC: coef * q; the 13-bit fixed-point "islow" inverse DCT (columns descaled by (x + 1024) >> 11, rows by (x + 2^17) >> 18,
+ * + 128, clamped to 0 .. 255); a component has ceil(W * h / hmax) x ceil(H * v / vmax) samples, the rest of its padded blocks is never
+ * read.  Chroma of width dw > 2 is upsampled with libjpeg's triangle filters - 4:2:2: out[2i] = (3 in[i] + in[i-1] + 1) >> 2,
+ * out[2i+1] = (3 in[i] + in[i+1] + 2) >> 2; 4:2:0: s[i] = 3 near[i] + far[i] (far: the chroma row above for even output rows, below for
+ * odd ones), out[2i] = (3 s[i] + s[i-1] + 8) >> 4, out[2i+1] = (3 s[i] + s[i+1] + 7) >> 4 - every index clamped to the real samples;
+ * dw <= 2: plain replication.  R = Y + ((91881 cr + 32768) >> 16), G = Y + ((-22554 cb - 46802 cr + 32768) >> 16),
+ * B = Y + ((116130 cb + 32768) >> 16) with cb, cr less 128, arithmetic shifts, clamped.
+ * HOSTILE COEFFICIENTS: the inverse DCT is computed modulo 2^32 (unsigned arithmetic, reinterpreted as two's complement before each
+ * descaling shift): what the encoder of a real image wrote never gets near the limit, anything else gives defined, identical bytes on
+ * both sides instead of undefined behaviour.
+ * Opt-in: no existing call changes its bytes; never part of a plan (-1 while one records on the thread), ES_ABI_VERSION stays.
+ * ========================================================================================================= */
+typedef struct {
+  int32_t width, height;
+  int32_t components;              /* 1 | 3 */
+  int32_t h[3], v[3];              /* sampling factors per component (a single component counts as 1 x 1: its scan is not interleaved) */
+  int32_t tq[3], td[3], ta[3];     /* quantisation, DC and AC Huffman table selectors per component */
+  int32_t hmax, vmax;
+  int32_t mcus_x, mcus_y;          /* MCU grid: ceil(width / (8 hmax)) x ceil(height / (8 vmax)) */
+  int32_t blocks_w[3], blocks_h[3];/* padded block grid per component: mcus_x * h x mcus_y * v */
+  int32_t restart_interval;        /* MCUs between RSTn markers, 0: none */
+} es_jpeg_info;
+/* host-only: reads the headers up to the scan.  0, or -1 with the reason for a file this decoder refuses */
+int es_jpeg_info_host(const uint8_t* bytes, size_t n, es_jpeg_info* info);
+/* host-only: int16 coefficients of one image: 64 per block of every component's padded grid (0 with es_last_error() on a bad info) */
+size_t es_jpeg_coeff_count(const es_jpeg_info* info);
+/* host-only: Huffman decoding.  coeffs: HOST int16 [es_jpeg_coeff_count] - component after component, within one the blocks row by row
+ * (block (by, bx) of component c at 64 * (by * blocks_w[c] + bx) past the component's start), each block in natural (row-major,
+ * de-zigzagged) order, every value written.  qtables: HOST uint16 [components][64], the table of each COMPONENT in natural order.
+ * `info` must be what es_jpeg_info_host gave for these bytes. */
+int es_jpeg_entropy_decode_host(const uint8_t* bytes, size_t n, const es_jpeg_info* info, int16_t* coeffs, uint16_t* qtables);
+/* bytes of device scratch es_jpeg_reconstruct needs (the uint8 component planes between its two launches); 0 with es_last_error() */
+size_t es_jpeg_reconstruct_workspace_bytes(const es_jpeg_info* infos, int count);
+/* infos: HOST array of `count` descriptors (images of different sizes and samplings in one call: two launches per 16 images);
+ * coeffs_dev[i] / qtables_dev[i]: DEVICE copies of what es_jpeg_entropy_decode_host wrote for image i, each 16-byte aligned;
+ * out[i]: DEVICE memory (`data` is written) of infos[i].height x infos[i].width, channels 3, any row_stride >= width * 3 - exactly
+ * width * 3 bytes of each row are written.  Asynchronous on `stream`, nothing is allocated: capturable. */
+int es_jpeg_reconstruct(const es_jpeg_info* infos, int count, const int16_t* const* coeffs_dev, const uint16_t* const* qtables_dev,
+                        const es_image_u8* out, void* workspace, size_t workspace_bytes, void* stream);
+/* host-only: the same on HOST memory (out[i].data included); needs no workspace */
+int es_jpeg_reconstruct_host(const es_jpeg_info* infos, int count, const int16_t* const* coeffs, const uint16_t* const* qtables,
+                             const es_image_u8* out);
+/* Parse + upload + reconstruct for up to 64 files.  bytes[i] / n[i]: the files (HOST).  out[i]: as above, sized from
+ * es_jpeg_info_host.  staging_host (HOST, pinned for an asynchronous upload) and staging_dev (DEVICE, 16-byte aligned) hold
+ * es_jpeg_decode_staging_bytes each: the coefficients and tables of all images, copied by one hipMemcpyAsync on `stream`; staging_host
+ * must stay untouched until that copy has run.  workspace: es_jpeg_reconstruct_workspace_bytes.  Nothing is allocated.  The Huffman
+ * decoding runs on the calling thread, so this call is not one to capture. */
+size_t es_jpeg_decode_staging_bytes(const es_jpeg_info* infos, int count);
+int es_jpeg_decode_u8(const uint8_t* const* bytes, const size_t* n, int count, const es_image_u8* out, void* staging_host,
+                      void* staging_dev, size_t staging_bytes, void* workspace, size_t workspace_bytes, void* stream);
+
+/* =========================================================================================================
  * Seeded noise (csrc/rng.hip): the normal stream of torch's DEVICE generator, restated, so that a host without Python can take
  * "seed 42" as an input and get the latents torch.randn(shape, generator=torch.Generator(device).manual_seed(42), device=device)
  * gives the reference's callers (test_text2image_pretrained_openpose.py:274, app.py:119).  The generator is Philox4x32-10 (ten
