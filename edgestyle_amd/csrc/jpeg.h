@@ -446,4 +446,434 @@ inline void reconstruct(const es_jpeg_info& I, const int16_t* coeffs, const uint
   }
 }
 
+// =====================================================================================================================================
+// The encoder: RGB (or gray) bytes -> the file Pillow's Image.save(f, "JPEG", quality=, subsampling=[, restart_marker_blocks=]) writes,
+// byte for byte (libjpeg's defaults: JFIF 1.01, the Annex K tables scaled by the quality, "islow" forward DCT, h2v1 / h2v2 box
+// downsampling with the alternating bias, the standard Huffman tables, one interleaved scan).  As above, the per-sample and per-block
+// rules are ES_JPEG_HD functions that csrc/jpeg_encode.hip's kernels and the host twin both call; the tables they read are one constexpr
+// value (kEnc here, a __constant__ copy of it on the device) passed by reference.
+// =====================================================================================================================================
+struct HuffEnc { uint32_t e[256]; };              // symbol -> code length << 16 | code, 0: the table has no such symbol
+struct EncConst {
+  uint8_t base_q[2][64];                          // Annex K.1 / K.2, natural order
+  uint8_t dc_bits[2][16], dc_vals[2][12];         // Annex K.3: codes per length, symbols in code order
+  uint8_t ac_bits[2][16], ac_vals[2][162];
+  uint8_t zigzag[64];                             // scan position -> natural index (kNatural)
+  HuffEnc dc[2], ac[2];
+};
+constexpr uint8_t kBaseLuma[64] = {16, 11, 10, 16, 24,  40,  51,  61,  12, 12, 14, 19, 26,  58,  60,  55,  14, 13, 16, 24, 40,  57,
+                                   69, 56, 14, 17, 22,  29,  51,  87,  80, 62, 18, 22, 37,  56,  68,  109, 103, 77, 24, 35, 55,  64,
+                                   81, 104, 113, 92, 49, 64, 78,  87,  103, 121, 120, 101, 72, 92,  95,  98,  112, 100, 103, 99};
+constexpr uint8_t kBaseChroma[64] = {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99,
+                                     99, 99, 47, 66, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99,
+                                     99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99};
+constexpr uint8_t kDcBits[2][16] = {{0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0}, {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0}};
+constexpr uint8_t kAcBits[2][16] = {{0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d}, {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77}};
+constexpr uint8_t kAcVals[2][162] = {
+    {0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81, 0x91, 0xa1,
+     0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18, 0x19, 0x1a, 0x25, 0x26,
+     0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56,
+     0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x83, 0x84, 0x85,
+     0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa,
+     0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6,
+     0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9,
+     0xfa},
+    {0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08, 0x14, 0x42,
+     0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25, 0xf1, 0x17, 0x18, 0x19,
+     0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55,
+     0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x82, 0x83,
+     0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8,
+     0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4,
+     0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9,
+     0xfa}};
+constexpr uint8_t kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                                 41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                                 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+// canonical codes (Annex C): the codes of one length are consecutive, the first of the next length is (last + 1) << 1
+constexpr void fill_huff_enc(HuffEnc& t, const uint8_t bits[16], const uint8_t* vals) {
+  uint32_t code = 0;
+  int k = 0;
+  for (int l = 1; l <= 16; ++l) {
+    for (int i = 0; i < bits[l - 1]; ++i, ++k, ++code) t.e[vals[k]] = (uint32_t)l << 16 | code;
+    code <<= 1;
+  }
+}
+constexpr EncConst make_enc_const() {
+  EncConst T{};
+  for (int i = 0; i < 64; ++i) { T.base_q[0][i] = kBaseLuma[i]; T.base_q[1][i] = kBaseChroma[i]; T.zigzag[i] = kZigzag[i]; }
+  for (int t = 0; t < 2; ++t) {
+    for (int i = 0; i < 16; ++i) { T.dc_bits[t][i] = kDcBits[t][i]; T.ac_bits[t][i] = kAcBits[t][i]; }
+    for (int i = 0; i < 12; ++i) T.dc_vals[t][i] = (uint8_t)i;
+    for (int i = 0; i < 162; ++i) T.ac_vals[t][i] = kAcVals[t][i];
+    fill_huff_enc(T.dc[t], T.dc_bits[t], T.dc_vals[t]);
+    fill_huff_enc(T.ac[t], T.ac_bits[t], T.ac_vals[t]);
+  }
+  return T;
+}
+constexpr EncConst kEnc = make_enc_const();
+
+// ---- the shared integer rules of the encoder -----------------------------------------------------------------------------------------
+// jcparam.c: jpeg_quality_scaling and jpeg_add_quant_table with force_baseline
+ES_JPEG_HD inline int quant_entry(int base, int quality) {
+  const int scale = quality < 50 ? 5000 / quality : 200 - 2 * quality;
+  const int v = (base * scale + 50) / 100;
+  return v < 1 ? 1 : v > 255 ? 255 : v;
+}
+// q: natural order; which: 0 luma, 1 chroma
+ES_JPEG_HD inline void quality_table(const EncConst& T, int which, int quality, uint16_t q[64]) {
+  for (int i = 0; i < 64; ++i) q[i] = (uint16_t)quant_entry(T.base_q[which][i], quality);
+}
+// jccolor.c, 16-bit fixed point; component c of one pixel
+ES_JPEG_HD inline int rgb_to_ycc(int r, int g, int b, int c) {
+  if (c == 0) return (19595 * r + 38470 * g + 7471 * b + 32768) >> 16;
+  if (c == 1) return (-11059 * r - 21709 * g + 32768 * b + (128 << 16) + 32767) >> 16;
+  return (32768 * r - 27439 * g - 5329 * b + (128 << 16) + 32767) >> 16;
+}
+ES_JPEG_HD inline int pixel_component(const uint8_t* img, size_t stride, int channels, int c, int x, int y) {
+  const uint8_t* p = img + (size_t)y * stride + (size_t)x * channels;
+  return channels == 1 ? p[0] : rgb_to_ycc(p[0], p[1], p[2], c);
+}
+// Sample (x, y) of component c's (downsampled) plane, for any x, y >= 0 inside the component's own blocks.  mode: kUpNone for luma and
+// for 4:4:4 chroma.  Edges as libjpeg pads them: columns and rows are replicated at FULL resolution (rows only up to a multiple of the
+// vertical factor), then the plane is downsampled, then ITS last row (dh - 1) is replicated down to whole blocks - so a row below the
+// last real chroma row repeats that row's average of two source rows, not the last source row alone.
+ES_JPEG_HD inline int enc_sample(const uint8_t* img, size_t stride, int channels, int W, int H, int c, int mode, int dh, int x, int y) {
+  if (mode == kUpNone) return pixel_component(img, stride, channels, c, x < W ? x : W - 1, y < H ? y : H - 1);
+  const int x0 = 2 * x < W ? 2 * x : W - 1, x1 = 2 * x + 1 < W ? 2 * x + 1 : W - 1;
+  if (mode == kUpH2V1) {
+    const int yy = y < H ? y : H - 1;
+    return (pixel_component(img, stride, channels, c, x0, yy) + pixel_component(img, stride, channels, c, x1, yy) + (x & 1)) >> 1;
+  }
+  const int cy = y < dh ? y : dh - 1;
+  const int y0 = 2 * cy < H ? 2 * cy : H - 1, y1 = 2 * cy + 1 < H ? 2 * cy + 1 : H - 1;
+  return (pixel_component(img, stride, channels, c, x0, y0) + pixel_component(img, stride, channels, c, x1, y0) +
+          pixel_component(img, stride, channels, c, x0, y1) + pixel_component(img, stride, channels, c, x1, y1) + 1 + (x & 1)) >> 2;
+}
+// One 8-point pass of jfdctint.c (CONST_BITS 13, PASS1_BITS 2).  first pass (rows): on sample - 128, outputs scaled by 4; second pass
+// (columns): the outputs are 8 x the DCT.
+ES_JPEG_HD inline int32_t fdescale(int32_t x, int n) { return (x + (1 << (n - 1))) >> n; }
+ES_JPEG_HD inline void fdct_1d(const int32_t d[8], int32_t o[8], bool second) {
+  const int32_t t0 = d[0] + d[7], t7 = d[0] - d[7], t1 = d[1] + d[6], t6 = d[1] - d[6];
+  const int32_t t2 = d[2] + d[5], t5 = d[2] - d[5], t3 = d[3] + d[4], t4 = d[3] - d[4];
+  const int32_t t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+  const int n = second ? 15 : 11;
+  o[0] = second ? fdescale(t10 + t11, 2) : (t10 + t11) * 4;
+  o[4] = second ? fdescale(t10 - t11, 2) : (t10 - t11) * 4;
+  int32_t z1 = (t12 + t13) * 4433;
+  o[2] = fdescale(z1 + t13 * 6270, n);
+  o[6] = fdescale(z1 - t12 * 15137, n);
+  z1 = t4 + t7;
+  int32_t z2 = t5 + t6, z3 = t4 + t6, z4 = t5 + t7;
+  const int32_t z5 = (z3 + z4) * 9633;
+  const int32_t a4 = t4 * 2446, a5 = t5 * 16819, a6 = t6 * 25172, a7 = t7 * 12299;
+  z1 *= -7373; z2 *= -20995; z3 *= -16069; z4 *= -3196;
+  z3 += z5; z4 += z5;
+  o[7] = fdescale(a4 + z1 + z3, n);
+  o[5] = fdescale(a5 + z2 + z4, n);
+  o[3] = fdescale(a6 + z2 + z3, n);
+  o[1] = fdescale(a7 + z1 + z4, n);
+}
+// jcdctmgr.c: the DCT output carries a factor 8, so the divisor is 8 q; round half away from zero
+ES_JPEG_HD inline int16_t quantise(int32_t c, uint16_t q) {
+  const int32_t d = 8 * (int32_t)q, a = c < 0 ? -c : c, v = (a + d / 2) / d;
+  return (int16_t)(c < 0 ? -v : v);
+}
+// jccoefct.c's dummy blocks.  (bx, by): a block of the MCU-padded grid of a component with rbw x rbh real blocks and h blocks per MCU
+// row.  -> the REAL block whose DC it carries ((bx, by) itself for a real block); true for a dummy block, whose AC is all zero.
+// Right of the last real block: the DC of the block to its left.  Below the last real block row: the DC of the previous block in MCU
+// order, which is the last block of the row above within the MCU - itself possibly a dummy, hence the clamp.
+ES_JPEG_HD inline bool dummy_source(int bx, int by, int rbw, int rbh, int h, int* sx, int* sy) {
+  *sx = bx; *sy = by;
+  if (bx < rbw && by < rbh) return false;
+  if (by >= rbh) { *sy = rbh - 1; *sx = (bx / h) * h + h - 1; }
+  else *sx = bx - 1;
+  if (*sx > rbw - 1) *sx = rbw - 1;
+  return true;
+}
+// real blocks of component c: its own ceil(samples / 8)
+ES_JPEG_HD inline int real_blocks_w(const es_jpeg_info& I, int c) { return ceil_div(comp_w(I, c), 8); }
+ES_JPEG_HD inline int real_blocks_h(const es_jpeg_info& I, int c) { return ceil_div(comp_h(I, c), 8); }
+
+// All a block of the padded grid needs, by value (what a kernel gets as its argument)
+struct EncGeom {
+  int32_t width, height, channels, components, mode;   // mode: the chroma planes' downsampling (kUp*)
+  int32_t h, v;                                         // luma blocks per MCU
+  int32_t mcus_x, mcus_y;
+  int32_t blocks_w[3], rbw[3], rbh[3], dh;              // padded and real block grids, real chroma rows
+  uint32_t nblk[3];                                     // blocks per component (padded)
+  int32_t restart_interval;
+};
+inline EncGeom enc_geom(const es_jpeg_info& I, int channels) {
+  EncGeom G;
+  memset(&G, 0, sizeof(G));
+  G.width = I.width; G.height = I.height; G.channels = channels; G.components = I.components;
+  G.mode = I.components == 3 ? up_mode(I.hmax, I.vmax) : kUpNone;
+  G.h = I.h[0]; G.v = I.v[0];
+  G.mcus_x = I.mcus_x; G.mcus_y = I.mcus_y;
+  for (int c = 0; c < I.components; ++c) {
+    G.blocks_w[c] = I.blocks_w[c];
+    G.rbw[c] = real_blocks_w(I, c); G.rbh[c] = real_blocks_h(I, c);
+    G.nblk[c] = (uint32_t)component_blocks(I, c);
+  }
+  G.dh = I.components == 3 ? comp_h(I, 1) : 0;
+  G.restart_interval = I.restart_interval;
+  return G;
+}
+// Row j of block (bx, by) of component c, before the DCT: sample - 128 of the block's source (dummy_source)
+ES_JPEG_HD inline void gather_row(const EncGeom& G, const uint8_t* img, size_t stride, int c, int sx, int sy, int j, int32_t row[8]) {
+  const int mode = c == 0 ? (int)kUpNone : G.mode;
+  for (int k = 0; k < 8; ++k) row[k] = enc_sample(img, stride, G.channels, G.width, G.height, c, mode, G.dh, sx * 8 + k, sy * 8 + j) - 128;
+}
+
+// ---- the scan's geometry: block s of the scan (MCU after MCU, inside one luma row by row, then Cb, then Cr) -------------------------------
+struct ScanBlock {
+  int c;                                          // component
+  uint32_t block;                                 // its number in the coefficient buffer (all components, 64 values each)
+  uint32_t pred;                                  // the block whose DC is the predictor, ~0u: the predictor is 0
+  bool boundary;                                  // the first block after a restart marker
+};
+ES_JPEG_HD inline uint32_t blocks_per_mcu(const EncGeom& G) { return G.components == 1 ? 1u : (uint32_t)(G.h * G.v + 2); }
+ES_JPEG_HD inline ScanBlock scan_block(const EncGeom& G, uint32_t s) {
+  const uint32_t bpm = blocks_per_mcu(G), luma = (uint32_t)(G.h * G.v);
+  const uint32_t m = s / bpm, k = s - m * bpm;
+  const uint32_t my = m / (uint32_t)G.mcus_x, mx = m - my * (uint32_t)G.mcus_x;
+  const bool first = G.restart_interval > 0 ? m % (uint32_t)G.restart_interval == 0 : m == 0;     // no predecessor in this interval
+  ScanBlock b;
+  b.boundary = first && m > 0 && k == 0;
+  if (k < luma) {
+    const uint32_t vy = k / (uint32_t)G.h, hx = k - vy * (uint32_t)G.h;
+    b.c = 0;
+    b.block = (my * G.v + vy) * (uint32_t)G.blocks_w[0] + mx * G.h + hx;
+    if (k > 0) {
+      const uint32_t pv = (k - 1) / (uint32_t)G.h, ph = (k - 1) - pv * (uint32_t)G.h;
+      b.pred = (my * G.v + pv) * (uint32_t)G.blocks_w[0] + mx * G.h + ph;
+    } else if (first) b.pred = ~0u;
+    else {
+      const uint32_t pm = m - 1, py = pm / (uint32_t)G.mcus_x, px = pm - py * (uint32_t)G.mcus_x;
+      b.pred = (py * G.v + G.v - 1) * (uint32_t)G.blocks_w[0] + px * G.h + G.h - 1;
+    }
+  } else {
+    b.c = (int)(k - luma) + 1;
+    const uint32_t base = G.nblk[0] + (b.c == 2 ? G.nblk[1] : 0u);
+    b.block = base + my * (uint32_t)G.blocks_w[b.c] + mx;
+    b.pred = first ? ~0u : b.block - 1;           // chroma has one block per MCU and rows of mcus_x blocks: the previous MCU's is the previous block
+  }
+  return b;
+}
+
+// ---- the block coder (jchuff.c with the standard tables) ------------------------------------------------------------------------------
+ES_JPEG_HD inline int bit_length(uint32_t v) {
+  int n = 0;
+  while (v) { ++n; v >>= 1; }
+  return n;
+}
+// Codes one block into a sink with put(bits, count) (count <= 16) and bad().  blk: natural order; t: 0 luma, 1 chroma tables.  A DC
+// difference above category 11 or an AC value above category 10 has no code in a baseline file: the sink is told (bad) and the value
+// is coded as if cut to the largest category, so that the bits written are bounded for ANY int16 input:
+// kMaxBlockBits = 11 + 11 + 63 * (16 + 10).
+constexpr uint32_t kMaxBlockBits = 11 + 11 + 63 * (16 + 10);
+template <class Sink>
+ES_JPEG_HD inline void code_block(const EncConst& T, int t, const int16_t* blk, int pred, Sink& s) {
+  int diff = (int)blk[0] - pred;
+  uint32_t mag = (uint32_t)(diff < 0 ? -diff : diff);
+  int nb = bit_length(mag);
+  if (nb > 11) { s.bad(); nb = 11; }
+  uint32_t e = T.dc[t].e[nb];
+  s.put(e & 0xffffu, (int)(e >> 16));
+  if (nb) s.put((uint32_t)(diff < 0 ? diff - 1 : diff) & ((1u << nb) - 1u), nb);
+  int run = 0;
+  for (int k = 1; k < 64; ++k) {
+    const int v = blk[T.zigzag[k]];
+    if (v == 0) { ++run; continue; }
+    for (; run > 15; run -= 16) { e = T.ac[t].e[0xf0]; s.put(e & 0xffffu, (int)(e >> 16)); }
+    mag = (uint32_t)(v < 0 ? -v : v);
+    nb = bit_length(mag);
+    if (nb > 10) { s.bad(); nb = 10; }
+    e = T.ac[t].e[run << 4 | nb];
+    s.put(e & 0xffffu, (int)(e >> 16));
+    s.put((uint32_t)(v < 0 ? v - 1 : v) & ((1u << nb) - 1u), nb);
+    run = 0;
+  }
+  if (run > 0) { e = T.ac[t].e[0]; s.put(e & 0xffffu, (int)(e >> 16)); }
+}
+struct LengthSink {
+  uint32_t bits = 0;
+  bool is_bad = false;
+  ES_JPEG_HD inline void put(uint32_t, int n) { bits += (uint32_t)n; }
+  ES_JPEG_HD inline void bad() { is_bad = true; }
+};
+
+// ---- the header (SOI .. SOS) into a sink with byte(b) -----------------------------------------------------------------------------------
+// at most 2 + 18 + 2 * 69 + 19 + 2 * 33 + 2 * 183 + 6 + 14 = 629 bytes
+constexpr int kMaxHeaderBytes = 629;
+template <class Bytes>
+ES_JPEG_HD inline void write_header(const EncConst& T, int width, int height, int components, int h, int v, int quality, int restart_interval,
+                                    Bytes& o) {
+  const uint8_t app0[18] = {0xFF, 0xE0, 0, 16, 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
+  o.byte(0xFF); o.byte(0xD8);
+  for (int i = 0; i < 18; ++i) o.byte(app0[i]);
+  const int tables = components == 1 ? 1 : 2;
+  for (int t = 0; t < tables; ++t) {
+    o.byte(0xFF); o.byte(0xDB); o.byte(0); o.byte(67); o.byte((uint8_t)t);
+    for (int i = 0; i < 64; ++i) o.byte((uint8_t)quant_entry(T.base_q[t][T.zigzag[i]], quality));
+  }
+  o.byte(0xFF); o.byte(0xC0); o.byte(0); o.byte((uint8_t)(8 + 3 * components)); o.byte(8);
+  o.byte((uint8_t)(height >> 8)); o.byte((uint8_t)height); o.byte((uint8_t)(width >> 8)); o.byte((uint8_t)width);
+  o.byte((uint8_t)components);
+  for (int c = 0; c < components; ++c) {
+    o.byte((uint8_t)(c + 1));
+    o.byte((uint8_t)(c == 0 ? (h << 4 | v) : 0x11));
+    o.byte((uint8_t)(c == 0 ? 0 : 1));
+  }
+  for (int t = 0; t < tables; ++t)
+    for (int ac = 0; ac < 2; ++ac) {
+      const uint8_t* bits = ac ? T.ac_bits[t] : T.dc_bits[t];
+      const uint8_t* vals = ac ? T.ac_vals[t] : T.dc_vals[t];
+      const int n = ac ? 162 : 12;
+      o.byte(0xFF); o.byte(0xC4); o.byte(0); o.byte((uint8_t)(2 + 1 + 16 + n)); o.byte((uint8_t)(ac << 4 | t));
+      for (int i = 0; i < 16; ++i) o.byte(bits[i]);
+      for (int i = 0; i < n; ++i) o.byte(vals[i]);
+    }
+  if (restart_interval > 0) {
+    o.byte(0xFF); o.byte(0xDD); o.byte(0); o.byte(4); o.byte((uint8_t)(restart_interval >> 8)); o.byte((uint8_t)restart_interval);
+  }
+  o.byte(0xFF); o.byte(0xDA); o.byte(0); o.byte((uint8_t)(6 + 2 * components)); o.byte((uint8_t)components);
+  for (int c = 0; c < components; ++c) { o.byte((uint8_t)(c + 1)); o.byte((uint8_t)(c == 0 ? 0x00 : 0x11)); }
+  o.byte(0); o.byte(63); o.byte(0);
+}
+ES_JPEG_HD inline uint32_t header_bytes(int components, int restart_interval) {
+  return (components == 1 ? 2u + 18 + 69 + 13 + 33 + 183 + 10 : 2u + 18 + 2 * 69 + 19 + 2 * 33 + 2 * 183 + 14) + (restart_interval > 0 ? 6u : 0u);
+}
+// counts every byte, stores those below cap
+struct BoundedBytes {
+  uint8_t* out;
+  size_t cap, n;
+  ES_JPEG_HD inline void byte(uint8_t b) {
+    if (n < cap) out[n] = b;
+    ++n;
+  }
+};
+
+// ---- parameters, geometry and the size bound ------------------------------------------------------------------------------------------
+inline bool encode_geometry(int width, int height, int channels, const es_jpeg_encode_params* P, es_jpeg_info& I, const char** why) {
+  if (!P) { *why = "null params"; return false; }
+  if (channels == 4) { *why = "cannot write mode RGBA as JPEG"; return false; }
+  if (channels != 1 && channels != 3) { *why = "1 or 3 channels expected"; return false; }
+  if (P->quality < 1 || P->quality > 100) { *why = "quality outside 1 .. 100"; return false; }
+  if (P->restart_interval < 0 || P->restart_interval > 65535) { *why = "restart interval outside 0 .. 65535"; return false; }
+  if (channels == 3 && P->subsampling != ES_JPEG_444 && P->subsampling != ES_JPEG_422 && P->subsampling != ES_JPEG_420) {
+    *why = "unknown subsampling (ES_JPEG_444, ES_JPEG_422 or ES_JPEG_420)";
+    return false;
+  }
+  memset(&I, 0, sizeof(I));
+  I.width = width; I.height = height; I.components = channels;
+  for (int c = 0; c < channels; ++c) { I.h[c] = I.v[c] = 1; I.tq[c] = I.td[c] = I.ta[c] = c ? 1 : 0; }
+  if (channels == 3) {
+    I.h[0] = P->subsampling == ES_JPEG_444 ? 1 : 2;
+    I.v[0] = P->subsampling == ES_JPEG_420 ? 2 : 1;
+  }
+  I.restart_interval = P->restart_interval;
+  return derive_geometry(I, why);
+}
+// what the encoder takes back as an info: one of encode_geometry's
+inline bool encode_info_ok(const es_jpeg_info* info, const es_jpeg_encode_params* P, const char** why) {
+  if (!info_ok(info, why)) return false;
+  es_jpeg_info I;
+  es_jpeg_encode_params Q;
+  if (!P) { *why = "null params"; return false; }
+  Q = *P;
+  Q.subsampling = info->components == 3 ? (info->h[0] == 1 ? ES_JPEG_444 : info->v[0] == 1 ? ES_JPEG_422 : ES_JPEG_420) : ES_JPEG_444;
+  if (!encode_geometry(info->width, info->height, info->components, &Q, I, why)) return false;
+  if (info->components == 3 && P->subsampling != Q.subsampling) { *why = "the info's sampling is not the params' subsampling"; return false; }
+  if (memcmp(&I, info, sizeof(I)) != 0) { *why = "the info is not what es_jpeg_encode_info_host gives for these params"; return false; }
+  return true;
+}
+inline uint64_t restart_intervals(const es_jpeg_info& I) {
+  const uint64_t mcus = (uint64_t)I.mcus_x * (uint64_t)I.mcus_y;
+  return I.restart_interval > 0 ? (mcus + I.restart_interval - 1) / I.restart_interval : 1;
+}
+// The bit stream before byte stuffing, restart markers included, is at most this many bytes: a block codes into at most kMaxBlockBits
+// (DC: the longest DC code, 11 bits in the chroma table, + 11 value bits; each of the 63 AC values: a 16-bit code + 10 value bits; the
+// ZRL and EOB symbols only ever replace longer codes of non-zero values), every interval is padded to a byte (< 1 byte each) and every
+// interval but the first is preceded by a 2-byte marker.
+inline uint64_t unstuffed_bound(const es_jpeg_info& I) {
+  uint64_t blocks = 0;
+  for (int c = 0; c < I.components; ++c) blocks += component_blocks(I, c);
+  const uint64_t n = restart_intervals(I);
+  return (blocks * kMaxBlockBits + 7) / 8 + n + 2 * (n - 1);
+}
+// The file is at most: the header + twice the data bytes (every data byte may be 0xFF and then takes a stuffed 0x00; counting the
+// marker bytes twice as well only loosens the bound) + EOI.
+inline uint64_t capacity_bound(const es_jpeg_info& I) { return header_bytes(I.components, I.restart_interval) + 2 * unstuffed_bound(I) + 2; }
+
+// ---- the host encoder ---------------------------------------------------------------------------------------------------------------
+// coeffs: [coeff_count(I)], every value written (the decoder's layout, dummy blocks included)
+inline void forward_host(const es_jpeg_info& I, int quality, const uint8_t* img, size_t stride, int16_t* coeffs) {
+  const EncGeom G = enc_geom(I, I.components);
+  uint16_t q[2][64];
+  quality_table(kEnc, 0, quality, q[0]);
+  quality_table(kEnc, 1, quality, q[1]);
+  int16_t* dst = coeffs;
+  for (int c = 0; c < I.components; ++c)
+    for (int by = 0; by < I.blocks_h[c]; ++by)
+      for (int bx = 0; bx < I.blocks_w[c]; ++bx, dst += 64) {
+        int sx, sy;
+        const bool dummy = dummy_source(bx, by, G.rbw[c], G.rbh[c], I.h[c], &sx, &sy);
+        int32_t ws[8][8], col[8], o[8];
+        for (int j = 0; j < 8; ++j) {
+          int32_t row[8];
+          gather_row(G, img, stride, c, sx, sy, j, row);
+          fdct_1d(row, ws[j], false);
+        }
+        for (int x = 0; x < 8; ++x) {
+          for (int k = 0; k < 8; ++k) col[k] = ws[k][x];
+          fdct_1d(col, o, true);
+          for (int k = 0; k < 8; ++k) dst[8 * k + x] = dummy && (k || x) ? (int16_t)0 : quantise(o[k], q[c ? 1 : 0][8 * k + x]);
+        }
+      }
+}
+// serial bit writer: MSB first, a 0x00 after every 0xFF
+struct StuffedBits {
+  BoundedBytes& o;
+  uint64_t acc = 0;
+  int cnt = 0;
+  bool is_bad = false;
+  explicit StuffedBits(BoundedBytes& o_) : o(o_) {}
+  inline void put(uint32_t bits, int n) {
+    acc = acc << n | bits;
+    cnt += n;
+    while (cnt >= 8) {
+      const uint8_t b = (uint8_t)(acc >> (cnt - 8));
+      o.byte(b);
+      if (b == 0xFF) o.byte(0);
+      cnt -= 8;
+    }
+  }
+  inline void bad() { is_bad = true; }
+  inline void flush() { if (cnt) put((1u << (8 - cnt)) - 1u, 8 - cnt); }
+};
+// The whole file into out (the bytes below cap are stored); returns its length.  *bad: a coefficient outside the baseline categories.
+inline size_t entropy_encode_host(const es_jpeg_info& I, int quality, const int16_t* coeffs, uint8_t* out, size_t cap, bool* bad) {
+  BoundedBytes o{out, cap, 0};
+  write_header(kEnc, I.width, I.height, I.components, I.h[0], I.v[0], quality, I.restart_interval, o);
+  const EncGeom G = enc_geom(I, I.components);
+  const uint32_t total = G.nblk[0] + G.nblk[1] + G.nblk[2];
+  StuffedBits w(o);
+  uint32_t rst = 0;
+  for (uint32_t s = 0; s < total; ++s) {
+    const ScanBlock b = scan_block(G, s);
+    if (b.boundary) {
+      w.flush();
+      o.byte(0xFF);
+      o.byte((uint8_t)(0xD0 + (rst++ & 7)));
+    }
+    code_block(kEnc, b.c ? 1 : 0, coeffs + (size_t)b.block * 64, b.pred == ~0u ? 0 : coeffs[(size_t)b.pred * 64], w);
+  }
+  w.flush();
+  o.byte(0xFF);
+  o.byte(0xD9);
+  *bad = w.is_bad;
+  return o.n;
+}
+
 }  // namespace esjpeg

@@ -5,6 +5,9 @@ refused; a refused file raises EdgeStyleHipError with the reason.
 
 decode returns device uint8 [H, W, 3] tensors: what ops.person_crop_u8, pipeline.preprocess_images, masks.segment and
 NativeBestEmbeddings take unchanged.
+
+The other direction (csrc/jpeg_encode.hip): encode / encode_device / encode_host turn RGB or gray bytes into the bytes of the file Pillow's
+Image.save(f, "JPEG", quality=, subsampling=, restart_marker_blocks=) writes; the device writes the whole file, header and EOI included.
 """
 import ctypes as C
 import os
@@ -115,3 +118,111 @@ def decode(data, device=DEVICE):
         part = raws[first:first + 64]
         out += ops.jpeg_decode_u8(part, _infos(part), device)
     return out[0] if single else out
+
+
+# ---- encoding (csrc/jpeg_encode.hip) ----------------------------------------------------------------------------------------------
+# RGB or gray bytes -> the bytes Pillow's Image.fromarray(a).save(f, "JPEG", quality=, subsampling=[, restart_marker_blocks=]) writes.
+_SUBSAMPLING = {0: 0, 1: 1, 2: 2, "4:4:4": 0, "4:2:2": 1, "4:2:0": 2, "4:1:1": 2}       # Pillow's spellings (its "4:1:1" is 4:2:0)
+
+
+def encode_params(quality=75, subsampling="4:2:0", restart_marker_blocks=0, **other) -> L.JpegEncodeParams:
+    """Pillow's save arguments as es_jpeg_encode_params.  Anything else Pillow would take (optimize, progressive, dpi, exif, ...) is
+    refused, never approximated."""
+    if other:
+        raise L.EdgeStyleHipError(f"jpeg.encode: {', '.join(sorted(other))} not supported (baseline files with the standard tables only)")
+    if isinstance(subsampling, bool) or subsampling not in _SUBSAMPLING:
+        raise L.EdgeStyleHipError(f"jpeg.encode: unknown subsampling {subsampling!r} (0, 1, 2, '4:4:4', '4:2:2' or '4:2:0')")
+    for name, v in (("quality", quality), ("restart_marker_blocks", restart_marker_blocks)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise L.EdgeStyleHipError(f"jpeg.encode: {name} must be an integer")
+    return L.JpegEncodeParams(int(quality), _SUBSAMPLING[subsampling], int(restart_marker_blocks))
+
+
+def _images(images):
+    """-> (list of [H, W, 3] / [H, W] arrays, whether the input was one image)"""
+    if isinstance(images, (list, tuple)):
+        if not images:
+            raise L.EdgeStyleHipError("jpeg.encode: no images")
+        return list(images), False
+    if images.ndim == 4:
+        return [images[i] for i in range(images.shape[0])], False
+    return [images], True
+
+
+def forward_host(arrays, params):
+    """es_jpeg_forward_host -> (infos, a list of int16 coefficient arrays in the decoder's layout)"""
+    descs = ops.jpeg_image_descs("jpeg.forward_host", arrays)
+    infos = ops.jpeg_encode_infos("jpeg.forward_host", descs, params)
+    lib = L.load()
+    coeffs = [np.empty((int(lib.es_jpeg_coeff_count(C.byref(infos[i]))),), dtype=np.int16) for i in range(len(arrays))]
+    cp = (C.c_void_p * len(arrays))(*[c.ctypes.data for c in coeffs])
+    L.check(lib.es_jpeg_forward_host(descs, len(arrays), C.byref(params), cp), "es_jpeg_forward_host")
+    return infos, coeffs
+
+
+def entropy_encode_host(infos, params, coeffs):
+    """es_jpeg_entropy_encode_host -> a list of bytes: the whole files"""
+    lib = L.load()
+    n = len(coeffs)
+    arr = (L.JpegInfo * n)(*infos)
+    coeffs = [np.ascontiguousarray(c, dtype=np.int16) for c in coeffs]
+    caps = [int(lib.es_jpeg_encode_capacity(C.byref(arr[i]), C.byref(params))) for i in range(n)]
+    if 0 in caps:
+        L.check(-1, "es_jpeg_encode_capacity")
+    for i in range(n):
+        if coeffs[i].size < int(lib.es_jpeg_coeff_count(C.byref(arr[i]))):
+            raise L.EdgeStyleHipError(f"jpeg: the coefficients of image {i} are shorter than its info asks for")
+    out = [np.empty((c,), dtype=np.uint8) for c in caps]
+    lengths = np.zeros((n,), dtype=np.uint32)
+    L.check(lib.es_jpeg_entropy_encode_host(arr, n, C.byref(params), (C.c_void_p * n)(*[c.ctypes.data for c in coeffs]),
+                                            (C.c_void_p * n)(*[o.ctypes.data for o in out]), (C.c_size_t * n)(*caps), lengths.ctypes.data),
+            "es_jpeg_entropy_encode_host")
+    return [o[:int(k)].tobytes() for o, k in zip(out, lengths)]
+
+
+def encode_host(arrays, quality=75, subsampling="4:2:0", restart_marker_blocks=0, **other):
+    """numpy uint8 [H, W, 3], [H, W], [B, H, W, 3] or a list -> bytes | list[bytes], computed on the CPU by the twin of the device code"""
+    params = encode_params(quality, subsampling, restart_marker_blocks, **other)
+    arrays, single = _images(arrays)
+    what = "jpeg.encode_host"
+    descs = ops.jpeg_image_descs(what, arrays)
+    infos = ops.jpeg_encode_infos(what, descs, params)
+    lib = L.load()
+    n = len(arrays)
+    caps = [int(lib.es_jpeg_encode_capacity(C.byref(infos[i]), C.byref(params))) for i in range(n)]
+    if 0 in caps:
+        L.check(-1, "es_jpeg_encode_capacity")
+    out = [np.empty((c,), dtype=np.uint8) for c in caps]
+    lengths = np.zeros((n,), dtype=np.uint32)
+    L.check(lib.es_jpeg_encode_host(descs, n, C.byref(params), (C.c_void_p * n)(*[o.ctypes.data for o in out]), (C.c_size_t * n)(*caps),
+                                    lengths.ctypes.data), "es_jpeg_encode_host")
+    files = [o[:int(k)].tobytes() for o, k in zip(out, lengths)]
+    return files[0] if single else files
+
+
+def encode_device(images, quality=75, subsampling="4:2:0", restart_marker_blocks=0, **other):
+    """device uint8 [H, W, 3], [H, W], [B, H, W, 3] or a list -> (a list of uint8 buffer tensors, one uint32 lengths tensor), all on the
+    device: buffer i holds file i in its first lengths[i] bytes.  Nothing is read back and nothing synchronises; one es_jpeg_encode_u8
+    call per 64 images, 8 launches per 16."""
+    params = encode_params(quality, subsampling, restart_marker_blocks, **other)
+    images, _ = _images(images)
+    out, lengths = [], []
+    for first in range(0, len(images), 64):
+        o, k = ops.jpeg_encode_u8(images[first:first + 64], params)
+        out += o
+        lengths.append(k)
+    return out, lengths[0] if len(lengths) == 1 else torch.cat([k.view(torch.int32) for k in lengths]).view(torch.uint32)
+
+
+def encode(images, quality=75, subsampling="4:2:0", restart_marker_blocks=0, **other):
+    """device uint8 [H, W, 3], [H, W], [B, H, W, 3] or a list -> bytes | list[bytes]: the files Pillow would write.  One download of the
+    lengths, then one of the finished files (gathered on the device); the pixels never leave it."""
+    single = not isinstance(images, (list, tuple)) and images.ndim != 4
+    out, lengths = encode_device(images, quality, subsampling, restart_marker_blocks, **other)
+    sizes = [int(k) for k in lengths.cpu().view(torch.int32).tolist()]
+    blob = torch.cat([o[:k] for o, k in zip(out, sizes)]).cpu().numpy().tobytes()
+    files, at = [], 0
+    for k in sizes:
+        files.append(blob[at:at + k])
+        at += k
+    return files[0] if single else files

@@ -137,6 +137,10 @@ class JpegInfo(C.Structure):        # es_jpeg_info
                 ("restart_interval", C.c_int32)]
 
 
+class JpegEncodeParams(C.Structure):    # es_jpeg_encode_params
+    _fields_ = [("quality", C.c_int32), ("subsampling", C.c_int32), ("restart_interval", C.c_int32)]
+
+
 class Philox(C.Structure):          # es_philox
     _fields_ = [("seed", C.c_uint64), ("offset", C.c_uint64)]
 
@@ -461,6 +465,17 @@ SYMBOLS = {
     "es_jpeg_reconstruct_host": (C.c_int, [C.POINTER(JpegInfo), _I, C.POINTER(_P), C.POINTER(_P), C.POINTER(ImageU8)]),
     "es_jpeg_decode_staging_bytes": (C.c_size_t, [C.POINTER(JpegInfo), _I]),
     "es_jpeg_decode_u8": (C.c_int, [C.POINTER(_P), C.POINTER(C.c_size_t), _I, C.POINTER(ImageU8), _P, _P, C.c_size_t, _P, C.c_size_t, _P]),
+    "es_jpeg_encode_info_host": (C.c_int, [_I, _I, _I, C.POINTER(JpegEncodeParams), C.POINTER(JpegInfo)]),
+    "es_jpeg_header_host": (C.c_int, [C.POINTER(JpegInfo), C.POINTER(JpegEncodeParams), _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "es_jpeg_encode_capacity": (C.c_size_t, [C.POINTER(JpegInfo), C.POINTER(JpegEncodeParams)]),
+    "es_jpeg_encode_workspace_bytes": (C.c_size_t, [C.POINTER(JpegInfo), _I, C.POINTER(JpegEncodeParams)]),
+    "es_jpeg_forward": (C.c_int, [C.POINTER(ImageU8), _I, C.POINTER(JpegEncodeParams), C.POINTER(_P), _P, C.c_size_t, _P]),
+    "es_jpeg_forward_host": (C.c_int, [C.POINTER(ImageU8), _I, C.POINTER(JpegEncodeParams), C.POINTER(_P)]),
+    "es_jpeg_entropy_encode": (C.c_int, [C.POINTER(JpegInfo), _I, C.POINTER(JpegEncodeParams), C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_size_t), _P, _P,
+                                         C.c_size_t, _P]),
+    "es_jpeg_entropy_encode_host": (C.c_int, [C.POINTER(JpegInfo), _I, C.POINTER(JpegEncodeParams), C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_size_t), _P]),
+    "es_jpeg_encode_u8": (C.c_int, [C.POINTER(ImageU8), _I, C.POINTER(JpegEncodeParams), C.POINTER(_P), C.POINTER(C.c_size_t), _P, _P, C.c_size_t, _P]),
+    "es_jpeg_encode_host": (C.c_int, [C.POINTER(ImageU8), _I, C.POINTER(JpegEncodeParams), C.POINTER(_P), C.POINTER(C.c_size_t), _P]),
 }
 
 _lib = None

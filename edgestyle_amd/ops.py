@@ -1387,6 +1387,121 @@ def jpeg_decode_u8(datas: Sequence[bytes], infos, device, out=None, staging_host
 
 
 # ----------------------------------------------------------------------------------------------------------------
+# JPEG encoding (csrc/jpeg_encode.hip): RGB or gray bytes -> the bytes of Pillow's file, written by the device.  edgestyle_amd/jpeg.py
+# owns the convenient entry points (Pillow's argument spellings, the download); these take an L.JpegEncodeParams.
+# ----------------------------------------------------------------------------------------------------------------
+def jpeg_image_descs(what, images):
+    """uint8 tensors or numpy arrays [H, W, 3] / [H, W] with dense pixels (rows may be pitched) -> the es_image_u8 array"""
+    n = len(images)
+    if n < 1:
+        raise L.EdgeStyleHipError(f"{what}: no images")
+    descs = (L.ImageU8 * n)()
+    for i, t in enumerate(images):
+        tensor = torch.is_tensor(t)
+        shape = tuple(t.shape)
+        stride = tuple(t.stride()) if tensor else tuple(t.strides)
+        if ((t.dtype != torch.uint8 if tensor else str(t.dtype) != "uint8") or len(shape) not in (2, 3) or min(shape) < 1):
+            raise L.EdgeStyleHipError(f"{what}: image {i} must be a uint8 [H, W, 3] or [H, W] array, got {shape}")
+        ch = 1 if len(shape) == 2 else shape[2]
+        if ((shape[1] > 1 and stride[1] != ch) or (len(shape) == 3 and ch > 1 and stride[2] != 1)
+                or (shape[0] > 1 and stride[0] < shape[1] * ch)):      # (the stride of an axis of one element says nothing)
+            raise L.EdgeStyleHipError(f"{what}: image {i} must have dense pixels (rows may be pitched), got strides {stride}")
+        descs[i].data = t.data_ptr() if tensor else t.ctypes.data
+        descs[i].height, descs[i].width, descs[i].channels = shape[0], shape[1], ch
+        descs[i].row_stride = stride[0] if shape[0] > 1 else shape[1] * ch
+    return descs
+
+
+def jpeg_encode_infos(what, descs, params):
+    lib = L.load()
+    infos = (L.JpegInfo * len(descs))()
+    for i, d in enumerate(descs):
+        L.check(lib.es_jpeg_encode_info_host(d.width, d.height, d.channels, C.byref(params), C.byref(infos[i])), "es_jpeg_encode_info_host")
+    return infos
+
+
+def _jpeg_encode_buffers(what, infos, params, dev, out, lengths, workspace):
+    lib = L.load()
+    n = len(infos)
+    caps = []
+    for i in range(n):
+        caps.append(int(lib.es_jpeg_encode_capacity(C.byref(infos[i]), C.byref(params))))
+        if caps[-1] == 0:
+            L.check(-1, "es_jpeg_encode_capacity")
+    need = int(lib.es_jpeg_encode_workspace_bytes(infos, n, C.byref(params)))
+    if need == 0:
+        L.check(-1, "es_jpeg_encode_workspace_bytes")
+    if out is None:
+        out = [torch.empty((c,), dtype=torch.uint8, device=dev) for c in caps]
+    if len(out) != n or any(o.dtype != torch.uint8 or o.device != dev or not o.is_contiguous() for o in out):
+        raise L.EdgeStyleHipError(f"{what}: {n} contiguous uint8 output tensors on {dev} expected")
+    if lengths is None:
+        lengths = torch.empty((n,), dtype=torch.uint32, device=dev)
+    if lengths.dtype != torch.uint32 or lengths.device != dev or not lengths.is_contiguous() or lengths.numel() < n:
+        raise L.EdgeStyleHipError(f"{what}: lengths must be a contiguous uint32 tensor of {n} values on {dev}")
+    workspace = _jpeg_bytes_buffer(what, workspace, need, dev, "workspace")
+    op = (C.c_void_p * n)(*[o.data_ptr() for o in out])
+    cp = (C.c_size_t * n)(*[o.numel() for o in out])
+    return out, lengths, workspace, op, cp
+
+
+def jpeg_forward(images: Sequence[torch.Tensor], params, coeffs=None):
+    """es_jpeg_forward: device uint8 images -> (infos, a list of int16 coefficient tensors in the decoder's layout).  One launch per 16."""
+    what = "jpeg_forward"
+    descs = jpeg_image_descs(what, images)
+    infos = jpeg_encode_infos(what, descs, params)
+    dev = images[0].device
+    lib = L.load()
+    n = len(images)
+    counts = [int(lib.es_jpeg_coeff_count(C.byref(infos[i]))) for i in range(n)]
+    if coeffs is None:
+        coeffs = [torch.empty((c,), dtype=torch.int16, device=dev) for c in counts]
+    if len(coeffs) != n or any(t.dtype != torch.int16 or t.device != dev or not t.is_contiguous() or t.numel() < c for t, c in zip(coeffs, counts)):
+        raise L.EdgeStyleHipError(f"{what}: one contiguous int16 coefficient tensor per image on {dev} expected")
+    if any(not t.is_cuda or t.device != dev for t in images):
+        raise L.EdgeStyleHipError(f"{what}: the images must be on one device")
+    cp = (C.c_void_p * n)(*[t.data_ptr() for t in coeffs])
+    L.check(lib.es_jpeg_forward(descs, n, C.byref(params), cp, None, 0, _stream()), "es_jpeg_forward")
+    return infos, coeffs
+
+
+def jpeg_entropy_encode(infos, params, coeffs: Sequence[torch.Tensor], out=None, lengths=None, workspace=None):
+    """es_jpeg_entropy_encode: coefficient tensors -> (uint8 buffers holding the whole files, uint32 lengths), all on the device; nothing
+    is read back.  7 launches per 16 images."""
+    what = "jpeg_entropy_encode"
+    n = len(infos)
+    if n < 1 or len(coeffs) != n:
+        raise L.EdgeStyleHipError(f"{what}: one coefficient tensor per image expected")
+    dev = coeffs[0].device
+    lib = L.load()
+    for i, t in enumerate(coeffs):
+        if not torch.is_tensor(t) or t.dtype != torch.int16 or t.device != dev or not t.is_cuda or not t.is_contiguous() \
+                or t.numel() < int(lib.es_jpeg_coeff_count(C.byref(infos[i]))):
+            raise L.EdgeStyleHipError(f"{what}: coefficients {i} must be a contiguous int16 device tensor of es_jpeg_coeff_count values")
+    out, lengths, workspace, op, cap = _jpeg_encode_buffers(what, infos, params, dev, out, lengths, workspace)
+    cp = (C.c_void_p * n)(*[t.data_ptr() for t in coeffs])
+    L.check(lib.es_jpeg_entropy_encode(infos, n, C.byref(params), cp, op, cap, _ptr(lengths), _ptr(workspace), workspace.numel(), _stream()),
+            "es_jpeg_entropy_encode")
+    return out, lengths
+
+
+def jpeg_encode_u8(images: Sequence[torch.Tensor], params, out=None, lengths=None, workspace=None):
+    """es_jpeg_encode_u8: up to 64 device uint8 images -> (uint8 buffers holding the files, uint32 lengths) on the device; nothing is read
+    back and nothing synchronises.  8 launches per 16 images."""
+    what = "jpeg_encode_u8"
+    descs = jpeg_image_descs(what, images)
+    dev = images[0].device
+    if any(not torch.is_tensor(t) or not t.is_cuda or t.device != dev for t in images):
+        raise L.EdgeStyleHipError(f"{what}: the images must be tensors on one device")
+    infos = jpeg_encode_infos(what, descs, params)
+    n = len(images)
+    out, lengths, workspace, op, cap = _jpeg_encode_buffers(what, infos, params, dev, out, lengths, workspace)
+    L.check(L.load().es_jpeg_encode_u8(descs, n, C.byref(params), op, cap, _ptr(lengths), _ptr(workspace), workspace.numel(), _stream()),
+            "es_jpeg_encode_u8")
+    return out, lengths
+
+
+# ----------------------------------------------------------------------------------------------------------------
 # mask post-processing (csrc/mask.hip): bit-packed morphology, largest 8-connected component, boolean algebra, draw_binary_mask
 # and create_sam_images in one call.  Masks are uint8 (or bool) device tensors [count, H, W]; results are uint8 of 0 / 1.
 # ----------------------------------------------------------------------------------------------------------------

@@ -936,6 +936,76 @@ int es_jpeg_decode_u8(const uint8_t* const* bytes, const size_t* n, int count, c
                       void* staging_dev, size_t staging_bytes, void* workspace, size_t workspace_bytes, void* stream);
 
 /* =========================================================================================================
+ * JPEG encoding (csrc/jpeg.h, csrc/jpeg_encode.hip): uint8 [H, W, 3] RGB (or [H, W] gray) on the device -> the bytes of the file that
+ * Pillow's Image.fromarray(a).save(f, "JPEG", quality=q, subsampling=s[, restart_marker_blocks=r]) writes (Pillow 12.2 over
+ * libjpeg-turbo 3: the pair tests/golden/jpeg_encode.safetensors is pinned to), byte for byte.  The whole file is written by the device:
+ * what crosses the bus afterwards is the finished file and its length.  Two stages that meet at the decoder's coefficient buffer
+ * (es_jpeg_coeff_count int16: block-major per component, MCU-padded grid, natural order inside a block, dummy blocks included):
+ *  FORWARD  colour conversion (Y = (19595 R + 38470 G + 7471 B + 32768) >> 16, Cb = (-11059 R - 21709 G + 32768 B + 128 << 16 + 32767)
+ *   >> 16, Cr = (32768 R - 27439 G - 5329 B + 128 << 16 + 32767) >> 16; one channel is its own luma), edge replication at full
+ *   resolution (rows only to a multiple of the vertical factor), box downsampling ((a + b + {0,1,0,1..}) >> 1 for 4:2:2,
+ *   (a + b + c + d + {1,2,1,2..}) >> 2 for 4:2:0), replication of the downsampled plane's last row to whole blocks, the 13-bit "islow"
+ *   forward DCT on sample - 128 and coef = sign(c) (|c| + 4 q) / (8 q) with the Annex K tables scaled by the quality
+ *   (scale = q < 50 ? 5000 / q : 200 - 2 q; entry = clamp((base * scale + 50) / 100, 1, 255)).  A dummy block (luma of 4:2:2 / 4:2:0
+ *   with an odd block count) has zero AC and the DC of the block to its left, or, below the last row, of the last block of the row above
+ *   within its MCU.
+ *  ENTROPY  the standard Huffman tables of Annex K.3, one interleaved scan; SOI, APP0 (JFIF 1.01, density 1 x 1), one DQT per table,
+ *   SOF0, four DHT (two for gray), DRI when a restart interval is set, SOS, data, EOI; nothing else.
+ * On the device the entropy stage is parallel over blocks: code length per block (the DC predecessor from the scan geometry), a prefix
+ * sum that also byte-aligns every restart interval, emission with atomicOr into zeroed words, a second count-and-scan for the 0x00 after
+ * every 0xFF, and a scatter that bounds every store by the capacity.  8 launches per 16 images for es_jpeg_encode_u8 (1 forward + 7
+ * entropy), images of different sizes and samplings share each launch.  Nothing is allocated, nothing synchronises: capturable.
+ * LIMITS: 1 or 3 channels (4: "cannot write mode RGBA as JPEG"), sides of 1 .. 65535, and es_jpeg_encode_capacity below 2^30 (the
+ * device counts the bits of one file in 32: about 2.5 million blocks - 160 megapixels at 4:4:4); no optimised tables, no
+ * progressive or arithmetic coding, no EXIF / ICC / comment / dpi.  Opt-in: no existing call changes; never part of a plan (-1 while
+ * one records on the thread), ES_ABI_VERSION stays.
+ * ========================================================================================================= */
+enum { ES_JPEG_444 = 0, ES_JPEG_422 = 1, ES_JPEG_420 = 2 };   /* Pillow's subsampling numbers */
+typedef struct {
+  int32_t quality;                 /* 1 .. 100 (Pillow's default: 75) */
+  int32_t subsampling;             /* ES_JPEG_444 | ES_JPEG_422 | ES_JPEG_420 (Pillow's default); ignored for one channel */
+  int32_t restart_interval;        /* MCUs between RSTn markers (Pillow's restart_marker_blocks), 0: none */
+} es_jpeg_encode_params;
+/* host-only: the geometry of the file these pixels become, in the decoder's struct.  0, or -1 with the reason */
+int es_jpeg_encode_info_host(int width, int height, int channels, const es_jpeg_encode_params* params, es_jpeg_info* info);
+/* host-only: SOI through SOS into out[0 .. cap); *n = their number (at most 629).  -1 if cap is short (*n is still set) */
+int es_jpeg_header_host(const es_jpeg_info* info, const es_jpeg_encode_params* params, uint8_t* out, size_t cap, size_t* n);
+/* host-only: an upper bound of the file's size, never a guess: header + 2 x (ceil(blocks x 1660 bits / 8) + one padding byte per restart
+ * interval + 2 marker bytes per interval after the first) + EOI.  1660 = 11 + 11 (the longest DC code and the largest DC category) +
+ * 63 x (16 + 10) (the longest AC code and the largest AC category for every coefficient); x 2: every byte may be 0xFF and take a stuffed
+ * 0x00.  0 with es_last_error() on bad arguments or when the bound reaches 2^30. */
+size_t es_jpeg_encode_capacity(const es_jpeg_info* info, const es_jpeg_encode_params* params);
+/* host-only: bytes of device scratch es_jpeg_encode_u8 needs for these images (es_jpeg_forward and es_jpeg_entropy_encode need no more);
+ * 0 with es_last_error() */
+size_t es_jpeg_encode_workspace_bytes(const es_jpeg_info* infos, int count, const es_jpeg_encode_params* params);
+/* Pixels -> coefficients.  images: HOST array of `count` descriptors of DEVICE pixels, 1 or 3 channels, any row_stride >= width *
+ * channels (only width * channels bytes of a row are read); coeffs_dev[i]: DEVICE int16 [es_jpeg_coeff_count], 16-byte aligned, every
+ * value written.  One launch per 16 images.  Asynchronous on `stream`; the workspace is not used by this stage (may be NULL / 0). */
+int es_jpeg_forward(const es_image_u8* images, int count, const es_jpeg_encode_params* params, int16_t* const* coeffs_dev, void* workspace,
+                    size_t workspace_bytes, void* stream);
+/* host-only: the same integer code on HOST memory */
+int es_jpeg_forward_host(const es_image_u8* images, int count, const es_jpeg_encode_params* params, int16_t* const* coeffs);
+/* Coefficients -> the whole file, header and EOI included.  infos: what es_jpeg_encode_info_host gave; coeffs_dev[i]: DEVICE, 16-byte
+ * aligned; out_dev[i]: DEVICE memory of capacity[i] bytes (any alignment); lengths_dev: DEVICE uint32 [count]; workspace: DEVICE,
+ * es_jpeg_encode_workspace_bytes.  lengths_dev[i] always receives the number of bytes the file needs; if that exceeds capacity[i]
+ * nothing at or beyond out_dev[i] + capacity[i] is written, the content below is unspecified and the caller must check.  A coefficient
+ * outside the baseline categories (|DC difference| >= 2048, |AC| >= 1024: no forward stage produces one) is coded as its low bits:
+ * the bounds hold, the file is not a valid one.  7 launches per 16 images.  Asynchronous on `stream`. */
+int es_jpeg_entropy_encode(const es_jpeg_info* infos, int count, const es_jpeg_encode_params* params, const int16_t* const* coeffs_dev,
+                           uint8_t* const* out_dev, const size_t* capacity, uint32_t* lengths_dev, void* workspace, size_t workspace_bytes,
+                           void* stream);
+/* host-only: the same on HOST memory; lengths: HOST uint32 [count].  -1 for a coefficient outside the baseline categories. */
+int es_jpeg_entropy_encode_host(const es_jpeg_info* infos, int count, const es_jpeg_encode_params* params, const int16_t* const* coeffs,
+                                uint8_t* const* out, const size_t* capacity, uint32_t* lengths);
+/* Both stages for up to 64 images: 8 launches per 16 images.  Contracts as above; nothing outside [0, capacity[i]) of an output and
+ * nothing outside the workspace is written. */
+int es_jpeg_encode_u8(const es_image_u8* images, int count, const es_jpeg_encode_params* params, uint8_t* const* out_dev,
+                      const size_t* capacity, uint32_t* lengths_dev, void* workspace, size_t workspace_bytes, void* stream);
+/* host-only: the twin, pixels and files in HOST memory */
+int es_jpeg_encode_host(const es_image_u8* images, int count, const es_jpeg_encode_params* params, uint8_t* const* out, const size_t* capacity,
+                        uint32_t* lengths);
+
+/* =========================================================================================================
  * Seeded noise (csrc/rng.hip): the normal stream of torch's DEVICE generator, restated, so that a host without Python can take
  * "seed 42" as an input and get the latents torch.randn(shape, generator=torch.Generator(device).manual_seed(42), device=device)
  * gives the reference's callers (test_text2image_pretrained_openpose.py:274, app.py:119).  The generator is Philox4x32-10 (ten
