@@ -1,7 +1,8 @@
 // Baseline JPEG, the host half and the shared integer rules (include/edgestyle_hip.h states format, limits and arithmetic in full):
 // the marker parser and the Huffman decoder - serial by nature, plain C++ - and, behind ES_JPEG_HD, the per-sample rules that
 // csrc/jpeg.hip's kernels and the host twin both run: the 1-D pass of the "islow" inverse DCT, its two descalings, libjpeg's triangle
-// chroma upsampling and YCbCr -> RGB.  Everything is integer arithmetic.  Any C++17 compiler can compile this header alone
+// chroma upsampling and YCbCr -> RGB; and the per-symbol code of the opt-in parallel Huffman decoder (csrc/jpeg_entropy.hip and its host
+// twin; the serial decoder stays the default).  Everything is integer arithmetic.  Any C++17 compiler can compile this header alone
 // (examples/jpeg_host.cpp -DJPEG_HOST_DRY does, under a host sanitizer for instance): no HIP, no library.
 //
 // Safety on hostile bytes: every read of the file is bounds-checked against n (BitReader feeds zero bits once it has met a marker or the
@@ -407,6 +408,383 @@ inline bool entropy_decode(const uint8_t* p, size_t n, const Header& H, int16_t*
 // qtables: uint16 [components][64], per component, natural order
 inline void component_qtables(const Header& H, uint16_t* qtables) {
   for (int c = 0; c < H.info.components; ++c) memcpy(qtables + 64 * c, H.qt[H.info.tq[c]], 64 * sizeof(uint16_t));
+}
+
+// ---- parallel entropy decoding (csrc/jpeg_entropy.hip and its host twin) ----------------------------------------------------------------
+// A SEGMENT is the stretch of entropy-coded bytes between restart markers; it is cut into subsequences of S raw bytes, one decoder
+// each.  Huffman streams re-synchronise, so a decoder started at a guessed state falls into step with the true symbol boundaries; the
+// subsequences exchange their exit states until nothing changes (at most J + 1 rounds for J subsequences), then decode once more from
+// the true states and write.  The per-symbol code below is what the kernel and the twin (entropy_decode_parallel) both compile.
+//
+// Bits are read from the RAW bytes, with no compaction pass.  Inside a segment a byte carries data unless it is a 00 that follows an FF
+// (the stuffed byte) or an FF that is followed by an FF (a fill byte): FF 00 is the data byte FF and FF FF 00 is ONE data byte FF, as
+// BitReader reads them.  A position is (raw byte, bit in it); it is kept canonical - on a data byte, or at the segment's end with bit
+// 0 - so that two decoders that meet at a symbol boundary hold the same number.
+//
+// Safety: every loop is bounded by the segment's length; a symbol takes at least one bit; a table entry the host would never build
+// (length 0 or above 16) counts as "no code"; table indices are masked; coefficient addresses come from block counters that are
+// checked against the geometry, never from the stream.
+inline uint64_t restart_intervals(const es_jpeg_info& I);       // (below, with the encoder's geometry)
+struct HuffFlat {                                 // Huff without `present`, plain data
+  uint16_t look[512];
+  int32_t maxcode[18];
+  int32_t valoff[17];
+  uint8_t vals[256];
+};
+struct ScanTables {                               // what es_jpeg_scan_prepare_host writes: ES_JPEG_TABLES_BYTES
+  HuffFlat t[6];                                  // [2 c]: the DC table of component c, [2 c + 1]: its AC table
+  int32_t components;
+  int32_t td[3], ta[3];                           // the selectors the scan named (for the record: t[] is already per component)
+  int32_t pad[3];
+};
+static_assert(sizeof(ScanTables) == ES_JPEG_TABLES_BYTES, "ES_JPEG_TABLES_BYTES");
+static_assert(sizeof(es_jpeg_segment) == 8, "es_jpeg_segment");
+
+enum { kStOk = 0, kStBadDC = 1, kStBadAC = 2, kStRun = 3, kStDCRange = 4, kStTruncated = 5 };
+inline const char* status_text(int code) {
+  switch (code) {
+    case kStOk: return "no defect";
+    case kStBadDC: return "a bit pattern that is no Huffman code (DC)";
+    case kStBadAC: return "a bit pattern that is no Huffman code (AC)";
+    case kStRun: return "a zero run past coefficient 63";
+    case kStDCRange: return "a DC coefficient outside 16 bits";
+    case kStTruncated: return "truncated: the entropy-coded data ends before the last MCU";
+    default: return "unknown JPEG status";
+  }
+}
+constexpr uint32_t kDefaultSubseq = 128;          // raw bytes per subsequence when the caller passes 0: the reference's 512 x 512 photo
+                                                  // settles in 4 rounds at 128 (11 at 32, 6 at 64, 3 at 256): rounds x bytes is lowest near here
+constexpr uint32_t kMinSubseq = 4;
+constexpr size_t kMaxParallelFile = (size_t)1 << 28;   // bit positions are 32-bit numbers
+
+// The decoder's state at a symbol boundary.  pos: raw byte * 8 + bit inside the segment; bk: block within the MCU << 8 | next zigzag
+// index (0: a DC symbol comes next).  kDead: where a speculative decode ends that met an impossible code - a pure function of the entry.
+// A decoder handed a dead entry proposes from its own guess again (else one impossible code would silence every decoder after it
+// until the true state arrives).  Once the rounds have settled, the entries up to the first dead one are the true ones; that one and
+// every entry behind it (guesses, not true states) count as dead in the count and write passes: they decode and write nothing.  The
+// true decode dies only on a defect, which the decoder before the dead entry reports if its block lies inside the segment's share -
+// stray bytes behind the last block are the usual cause, and are no error.
+struct ScanState { uint32_t pos, bk; };
+constexpr uint32_t kDeadPos = 0xFFFFFFFFu;
+ES_JPEG_HD inline ScanState dead_state() { return ScanState{kDeadPos, 0xFFFFu}; }
+ES_JPEG_HD inline bool same_state(const ScanState& a, const ScanState& b) { return a.pos == b.pos && a.bk == b.bk; }
+
+// the first data byte at or after j (len: none)
+ES_JPEG_HD inline uint32_t next_data(const uint8_t* p, uint32_t len, uint32_t j) {
+  while (j < len) {
+    const uint8_t b = p[j];
+    if (b == 0xFF) {
+      if (j + 1 < len && p[j + 1] != 0xFF) return j;     // FF 00: the data byte FF
+    } else if (!(b == 0 && j > 0 && p[j - 1] == 0xFF)) return j;
+    ++j;
+  }
+  return len;
+}
+struct RawBits {
+  const uint8_t* p;                               // the segment's raw bytes
+  uint32_t len;
+  uint32_t i, bit;                                // the next bit: bit `bit` (from the top) of data byte i; or i == len, bit == 0
+  uint32_t w, n1, n2;                             // the window: data bytes i, n1, n2 in bits 23 .. 0 (zero past the end), and where they lie
+  ES_JPEG_HD inline void window() {
+    if (i + 2 < len) {
+      const uint32_t b0 = p[i], b1 = p[i + 1], b2 = p[i + 2];
+      if (b0 != 0xFF && b1 != 0xFF && b2 != 0xFF) { w = b0 << 16 | b1 << 8 | b2; n1 = i + 1; n2 = i + 2; return; }
+    }
+    w = 0; n1 = n2 = len;
+    if (i >= len) return;
+    w = (uint32_t)p[i] << 16;
+    n1 = next_data(p, len, i + 1);
+    if (n1 >= len) return;
+    w |= (uint32_t)p[n1] << 8;
+    n2 = next_data(p, len, n1 + 1);
+    if (n2 < len) w |= p[n2];
+  }
+  ES_JPEG_HD inline uint32_t peek16() const { return (w >> (8 - bit)) & 0xFFFFu; }                    // after window()
+  ES_JPEG_HD inline uint32_t peek(int n) const { return (w >> (24 - (int)bit - n)) & ((1u << n) - 1u); }   // 1 <= n <= 16
+  // consumes n <= 16 bits of the window; false: they reach past the segment's real bits
+  ES_JPEG_HD inline bool skip(int n) {
+    const uint32_t have = 8u * ((i < len) + (n1 < len) + (n2 < len));
+    const uint32_t total = bit + (uint32_t)n;
+    if (total > have) { i = len; bit = 0; return false; }
+    const uint32_t adv = total >> 3;
+    i = adv == 0 ? i : adv == 1 ? n1 : n2;
+    bit = total & 7u;
+    return true;
+  }
+};
+// >= 0: the symbol; -1: no code of up to 16 bits matches; -2: the code ends past the segment's real bits
+ES_JPEG_HD inline int take_code(RawBits& r, const HuffFlat& t) {
+  r.window();
+  const uint32_t v = r.peek16();
+  const uint32_t e = t.look[v >> 7];
+  int l = (int)(e >> 8), sym = (int)(e & 255u);
+  if (!e) {
+    l = 0;
+    for (int q = 10; q <= 16; ++q) {
+      const int32_t code = (int32_t)(v >> (16 - q));
+      if (code <= t.maxcode[q]) { l = q; sym = t.vals[(uint32_t)(code + t.valoff[q]) & 255u]; break; }
+    }
+    if (!l) return -1;
+  } else if (l < 1 || l > 9) return -1;
+  return r.skip(l) ? sym : -2;
+}
+// the s extra bits of a coefficient, 1 <= s <= 15, extended; false: they reach past the segment's real bits
+ES_JPEG_HD inline bool take_value(RawBits& r, int s, int* out) {
+  r.window();
+  const int v = (int)r.peek(s);
+  if (!r.skip(s)) return false;
+  *out = v < (1 << (s - 1)) ? v - (1 << s) + 1 : v;
+  return true;
+}
+
+// The geometry the passes need, by value (what a kernel gets as its argument)
+struct ScanGeom {
+  uint64_t off[3];                                // first coefficient of each component
+  int32_t components, h, v, hv, bpm, mcus_x;      // luma blocks per MCU, blocks per MCU
+  int32_t blocks_w[3];
+  uint32_t mcus, ri;                              // MCUs of the image, MCUs per segment
+};
+inline ScanGeom scan_geom(const es_jpeg_info& I) {
+  ScanGeom G;
+  memset(&G, 0, sizeof(G));
+  for (int c = 1; c < I.components; ++c) G.off[c] = G.off[c - 1] + component_blocks(I, c - 1) * 64;
+  G.components = I.components; G.h = I.h[0]; G.v = I.v[0];
+  G.hv = I.components == 1 ? 1 : I.h[0] * I.v[0];
+  G.bpm = I.components == 1 ? 1 : G.hv + 2;
+  G.mcus_x = I.mcus_x;
+  for (int c = 0; c < 3; ++c) G.blocks_w[c] = I.blocks_w[c];
+  G.mcus = (uint32_t)I.mcus_x * (uint32_t)I.mcus_y;
+  G.ri = I.restart_interval > 0 ? (uint32_t)I.restart_interval : G.mcus;
+  return G;
+}
+// blocks segment `seg` must hold (seg < ceil(mcus / ri))
+ES_JPEG_HD inline uint32_t segment_blocks(const ScanGeom& G, uint32_t seg) {
+  const uint32_t left = G.mcus - seg * G.ri;
+  return (left < G.ri ? left : G.ri) * (uint32_t)G.bpm;
+}
+// where block `o` (o < segment_blocks) of segment `seg` lies in the coefficient buffer: entropy_decode's own formula
+ES_JPEG_HD inline uint64_t segment_block_offset(const ScanGeom& G, uint32_t seg, uint32_t o) {
+  const uint32_t mcu = seg * G.ri + o / (uint32_t)G.bpm, blk = o % (uint32_t)G.bpm;
+  const uint32_t my = mcu / (uint32_t)G.mcus_x, mx = mcu - my * (uint32_t)G.mcus_x;
+  if (blk < (uint32_t)G.hv) {
+    const uint32_t vy = blk / (uint32_t)G.h, hx = blk - vy * (uint32_t)G.h;
+    return ((uint64_t)(my * G.v + vy) * (uint32_t)G.blocks_w[0] + (mx * G.h + hx)) * 64u;
+  }
+  const int c = (int)(blk - (uint32_t)G.hv) + 1;
+  return G.off[c] + ((uint64_t)my * (uint32_t)G.blocks_w[c] + mx) * 64u;
+}
+
+// Decodes the symbols whose first bit lies in raw bytes [.., bound) from state st; returns the state at the first symbol boundary at or
+// past bound (or the segment's end), dead_state() after a defect.  The sink sees dc(component, difference), ac(zigzag index, value),
+// and defect(status, whether a DC symbol was due).
+template <class Sink>
+ES_JPEG_HD inline ScanState decode_subsequence(const ScanTables& T, const ScanGeom& G, const uint8_t* p, uint32_t len, ScanState st, uint32_t bound,
+                                               Sink& sink) {
+  uint32_t b = st.bk >> 8, k = st.bk & 255u;
+  if (st.pos == kDeadPos || (st.pos >> 3) > len || b >= (uint32_t)G.bpm || k > 63u) return dead_state();
+  RawBits r{p, len, st.pos >> 3, st.pos & 7u, 0, 0, 0};
+  if (bound > len) bound = len;
+  const uint32_t most = bound > r.i ? (bound - r.i) * 8u : 0u;   // every symbol takes at least one bit
+  for (uint32_t it = 0; it < most && r.i < bound; ++it) {
+    const int c = b < (uint32_t)G.hv ? 0 : (int)(b - (uint32_t)G.hv) + 1;
+    if (k == 0) {
+      int s = take_code(r, T.t[2 * c]);
+      if (s < 0) { sink.defect(s == -1 ? kStBadDC : kStTruncated, true); return dead_state(); }
+      s &= 15;
+      int diff = 0;
+      if (s && !take_value(r, s, &diff)) { sink.defect(kStTruncated, true); return dead_state(); }
+      sink.dc(c, diff);
+      k = 1;
+    } else {
+      const int rs = take_code(r, T.t[2 * c + 1]);
+      if (rs < 0) { sink.defect(rs == -1 ? kStBadAC : kStTruncated, false); return dead_state(); }
+      const uint32_t run = (uint32_t)rs >> 4;
+      const int s = rs & 15;
+      if (s == 0) {
+        if (run != 15u) k = 64;                   // EOB
+        else {
+          k += 16;
+          if (k > 64u) { sink.defect(kStRun, false); return dead_state(); }
+        }
+      } else {
+        k += run;
+        if (k > 63u) { sink.defect(kStRun, false); return dead_state(); }
+        int val = 0;
+        if (!take_value(r, s, &val)) { sink.defect(kStTruncated, false); return dead_state(); }
+        sink.ac(k, val);
+        ++k;
+      }
+    }
+    if (k >= 64u) { k = 0; b = b + 1 == (uint32_t)G.bpm ? 0 : b + 1; }
+  }
+  return ScanState{r.i * 8u + r.bit, b << 8 | k};
+}
+// the synchronise rounds: how many blocks start in the subsequence and what their DC differences sum to, modulo 2^32
+struct CountSink {
+  uint32_t dcs, sum[3];
+  ES_JPEG_HD inline void clear() { dcs = sum[0] = sum[1] = sum[2] = 0; }
+  ES_JPEG_HD inline void dc(int c, int diff) {      // (selects, not sum[c]: a dynamic index would put the array into scratch on the device)
+    ++dcs;
+    sum[0] += c == 0 ? (uint32_t)diff : 0u; sum[1] += c == 1 ? (uint32_t)diff : 0u; sum[2] += c == 2 ? (uint32_t)diff : 0u;
+  }
+  ES_JPEG_HD inline void ac(uint32_t, int) {}
+  ES_JPEG_HD inline void defect(int, bool) {}
+};
+// The write pass.  next: the ordinal of the next block to start; cur: the ordinal of the block the decoder is inside (~0u: none, its
+// values are dropped); blocks at or past `expected` are dropped and report nothing.  err: the first defect as ordinal << 3 | status.
+struct WriteSink {
+  const ScanGeom* G;
+  const uint8_t* natural;
+  int16_t* coeffs;
+  uint32_t seg, expected, next, cur, pred[3], err;
+  int16_t* blk;
+  ES_JPEG_HD inline void enter(uint32_t o) {
+    cur = o;
+    blk = o < expected ? coeffs + segment_block_offset(*G, seg, o) : nullptr;
+  }
+  ES_JPEG_HD inline void note(uint32_t o, int status) {
+    if (o >= expected) return;
+    const uint32_t key = o << 3 | (uint32_t)status;
+    if (key < err) err = key;
+  }
+  ES_JPEG_HD inline void dc(int c, int diff) {
+    enter(next++);
+    pred[0] += c == 0 ? (uint32_t)diff : 0u; pred[1] += c == 1 ? (uint32_t)diff : 0u; pred[2] += c == 2 ? (uint32_t)diff : 0u;
+    const int32_t v = (int32_t)(c == 0 ? pred[0] : c == 1 ? pred[1] : pred[2]);
+    if (v < -32768 || v > 32767) note(cur, kStDCRange);
+    if (blk) blk[0] = (int16_t)v;
+  }
+  ES_JPEG_HD inline void ac(uint32_t k, int val) {
+    if (blk) blk[natural[k & 63u] & 63u] = (int16_t)val;
+  }
+  ES_JPEG_HD inline void defect(int status, bool at_dc) { note(at_dc ? next : cur, status); }
+};
+// S and J of a segment of len raw bytes for a workgroup of T decoders: S = max(subseq, ceil(len / T)), J = ceil(len / S) <= T
+ES_JPEG_HD inline uint32_t subsequence_bytes(uint32_t len, uint32_t subseq, uint32_t T) {
+  const uint32_t per = (len + T - 1) / T;
+  return subseq > per ? subseq : per;
+}
+// the guessed entry of subsequence j > 0 before the first round: a DC symbol of the MCU's first block at its first data byte
+ES_JPEG_HD inline ScanState guessed_entry(const uint8_t* p, uint32_t len, uint32_t at) { return ScanState{next_data(p, len, at) * 8u, 0u}; }
+// what the last decoder adds after the write pass: a block left unfinished at the segment's end, or fewer blocks than expected
+ES_JPEG_HD inline void close_segment(WriteSink& w, const ScanState& exit) {
+  if (exit.pos != kDeadPos && (exit.bk & 255u) != 0u && w.cur != ~0u) w.note(w.cur, kStTruncated);
+  if (w.next < w.expected) w.note(w.next, kStTruncated);
+}
+
+// the marker that follows position pos, as next_marker; *ff: the first FF of the run that opens it (where the bit reader stops)
+inline int next_marker_at(const uint8_t* p, size_t n, size_t& pos, size_t* ff) {
+  for (;;) {
+    if (pos >= n) { *ff = n; return -1; }
+    if (p[pos] != 0xFF) { ++pos; continue; }
+    size_t q = pos + 1;
+    while (q < n && p[q] == 0xFF) ++q;
+    if (q >= n) { *ff = pos; return -1; }
+    if (p[q] != 0) { *ff = pos; pos = q + 1; return p[q]; }
+    pos = q + 1;
+  }
+}
+// The host preparation: one walk over the scan that finds the segments and checks what the serial decoder checks around them (RSTn
+// present and numbered, EOI after the last segment); no Huffman decoding.  segments: [restart_intervals(H.info)], offsets from p.
+inline bool scan_prepare(const uint8_t* p, size_t n, const Header& H, es_jpeg_segment* segments, ScanTables* tables, const char** why) {
+  if (n >= kMaxParallelFile) { *why = "a file of 256 MiB or more is not decoded in parallel"; return false; }
+  const es_jpeg_info& I = H.info;
+  memset(tables, 0, sizeof(*tables));
+  tables->components = I.components;
+  for (int c = 0; c < I.components; ++c) {
+    tables->td[c] = I.td[c]; tables->ta[c] = I.ta[c];
+    const Huff* src[2] = {&H.dc[I.td[c]], &H.ac[I.ta[c]]};
+    for (int a = 0; a < 2; ++a) {
+      HuffFlat& t = tables->t[2 * c + a];
+      memcpy(t.look, src[a]->look, sizeof(t.look));
+      memcpy(t.maxcode, src[a]->maxcode, sizeof(t.maxcode));
+      memcpy(t.valoff, src[a]->valoff, sizeof(t.valoff));
+      memcpy(t.vals, src[a]->vals, sizeof(t.vals));
+    }
+  }
+  const uint64_t count = restart_intervals(I);
+  size_t pos = H.scan_pos;
+  for (uint64_t k = 0; k < count; ++k) {
+    const size_t begin = pos;
+    size_t ff = n;
+    const int m = next_marker_at(p, n, pos, &ff);
+    segments[k].begin = (uint32_t)begin;
+    segments[k].end = (uint32_t)ff;
+    if (k + 1 < count) {
+      if (m != 0xD0 + (int)(k & 7)) { *why = m < 0 ? "truncated: the file ends where an RSTn marker must stand" : "a missing or misnumbered RSTn marker"; return false; }
+    } else {
+      if (m < 0) { *why = "truncated: no EOI marker after the scan"; return false; }
+      if (m != 0xD9) { *why = "multi-scan files are not supported (a segment follows the scan)"; return false; }
+    }
+  }
+  return true;
+}
+
+// The twin of csrc/jpeg_entropy.hip: the same rounds over the same states, `threads` standing for the workgroup's size, run one
+// decoder after the other.  coeffs: [coeff_count(I)], every value written.  Returns the status (kSt*); *rounds receives the largest
+// number of synchronise rounds a segment took.  p / n: the bytes the segments' offsets refer to.
+inline int entropy_decode_parallel(const uint8_t* p, size_t n, const es_jpeg_info& I, const es_jpeg_segment* segments, const ScanTables& T,
+                                   uint32_t subseq, uint32_t threads, int16_t* coeffs, uint32_t* rounds) {
+  memset(coeffs, 0, coeff_count(I) * sizeof(int16_t));
+  const ScanGeom G = scan_geom(I);
+  const uint32_t count = (uint32_t)restart_intervals(I);
+  if (n >= kMaxParallelFile) n = kMaxParallelFile - 1;
+  if (subseq == 0) subseq = kDefaultSubseq;
+  *rounds = 0;
+  int status = kStOk;
+  std::vector<ScanState> in, prop;
+  std::vector<CountSink> cnt;
+  std::vector<uint8_t> dirty;
+  for (uint32_t seg = 0; seg < count; ++seg) {
+    uint32_t end = segments[seg].end < n ? segments[seg].end : (uint32_t)n;
+    uint32_t begin = segments[seg].begin < end ? segments[seg].begin : end;
+    const uint8_t* s = p + begin;
+    const uint32_t len = end - begin;
+    const uint32_t S = subsequence_bytes(len, subseq, threads), J = len ? (len + S - 1) / S : 0;
+    const uint32_t expected = segment_blocks(G, seg);
+    uint32_t err = ~0u;
+    in.assign(J, dead_state()); prop.assign(J + 1, dead_state()); cnt.resize(J); dirty.assign(J, 1);
+    for (uint32_t j = 0; j < J; ++j) prop[j] = in[j] = guessed_entry(s, len, j * S);
+    uint32_t r = 0;
+    for (bool changed = J > 0; changed && r <= J;) {
+      for (uint32_t j = 0; j < J; ++j)
+        if (dirty[j]) {                             // a dead entry (the neighbour met an impossible code): propose from the own guess again
+          const bool dead = in[j].pos == kDeadPos;
+          cnt[j].clear();
+          prop[j + 1] = decode_subsequence(T, G, s, len, dead ? guessed_entry(s, len, j * S) : in[j], (j + 1) * S, cnt[j]);
+          if (dead) cnt[j].clear();                 // (what follows a dead entry is dropped by the write pass)
+        }
+      changed = false;
+      for (uint32_t j = 1; j < J; ++j) {
+        dirty[j] = !same_state(prop[j], in[j]);
+        in[j] = prop[j];
+        changed = changed || dirty[j];
+      }
+      if (J) dirty[0] = 0;
+      ++r;
+    }
+    if (r > *rounds) *rounds = r;
+    // Behind the first dead entry nothing is a true state (the decoder after it proposed from a guess): all of it is dead in the write pass
+    bool cut = false;
+    for (uint32_t j = 0; j < J; ++j) {
+      cut = cut || in[j].pos == kDeadPos;
+      if (cut) { in[j] = dead_state(); cnt[j].clear(); }
+    }
+    uint32_t ord = 0, pred[3] = {0, 0, 0};
+    WriteSink w;
+    for (uint32_t j = 0; j < J; ++j) {
+      w = WriteSink{&G, kNatural, coeffs, seg, expected, ord, ~0u, {pred[0], pred[1], pred[2]}, ~0u, nullptr};
+      if ((in[j].bk & 255u) != 0u && in[j].pos != kDeadPos && ord > 0) w.enter(ord - 1);
+      const ScanState exit = decode_subsequence(T, G, s, len, in[j], (j + 1) * S, w);
+      if (j + 1 == J) close_segment(w, exit);
+      if (w.err < err) err = w.err;
+      ord += cnt[j].dcs;
+      for (int c = 0; c < 3; ++c) pred[c] += cnt[j].sum[c];
+    }
+    if (J == 0) err = kStTruncated;               // an empty segment: block 0 is missing
+    if (err != ~0u && status == kStOk) status = (int)(err & 7u);      // segments in order: the first defect by (segment, block)
+  }
+  return status;
 }
 
 // ---- the host twin of the two kernels -------------------------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
 """Baseline JPEG files to RGB bytes (csrc/jpeg.h, csrc/jpeg.hip): what Pillow's Image.open(..).convert("RGB") returns, byte for byte,
 without Pillow.  Headers and Huffman decoding run on the host, dequantisation, inverse DCT, chroma upsampling and YCbCr -> RGB on the
-device (decode) or, through the same integer code, on the CPU (decode_host).  include/edgestyle_hip.h lists what is supported and what is
+device (decode) or, through the same integer code, on the CPU (decode_host).  Opt-in, decode(entropy="device") moves the Huffman
+decoding onto the device as well (csrc/jpeg_entropy.hip); the default is still the host decoder.  include/edgestyle_hip.h lists what is supported and what is
 refused; a refused file raises EdgeStyleHipError with the reason.
 
 decode returns device uint8 [H, W, 3] tensors: what ops.person_crop_u8, pipeline.preprocess_images, masks.segment and
@@ -109,15 +110,83 @@ def upload(coeffs: np.ndarray, qtables: np.ndarray, device=DEVICE):
             torch.from_numpy(np.ascontiguousarray(qtables, dtype=np.uint16).view(np.int16).reshape(-1)).to(device))
 
 
-def decode(data, device=DEVICE):
+def decode(data, device=DEVICE, entropy="host"):
     """bytes, a path, or a list of either -> device uint8 [H, W, 3] tensor(s).  A list is decoded by one es_jpeg_decode_u8 call per 64
-    files: the Huffman decoding on this thread, one upload, two launches per 16 images."""
+    files: the Huffman decoding on this thread, one upload, two launches per 16 images.  That is the default.  entropy="device" (opt-in)
+    takes es_jpeg_decode_dev_u8 instead: the files are uploaded as they are and the Huffman decoding runs on the device too
+    (csrc/jpeg_entropy.hip); the status words are read back before the images are returned, and a defect raises with its text."""
+    if entropy not in ("host", "device"):
+        raise L.EdgeStyleHipError(f"jpeg.decode: entropy must be 'host' or 'device', not {entropy!r}")
     raws, single = _items(data)
     out = []
     for first in range(0, len(raws), 64):
         part = raws[first:first + 64]
-        out += ops.jpeg_decode_u8(part, _infos(part), device)
+        if entropy == "host":
+            out += ops.jpeg_decode_u8(part, _infos(part), device)
+        else:
+            images, status = ops.jpeg_decode_dev_u8(part, _infos(part), device)
+            ops.jpeg_status_check(status, "jpeg.decode")
+            out += images
     return out[0] if single else out
+
+
+# ---- Huffman decoding in parallel (csrc/jpeg_entropy.hip and its host twin), opt-in ----------------------------------------------------
+def scan_prepare(data, jpeg_info: L.JpegInfo = None):
+    """es_jpeg_scan_prepare_host: the host half of the parallel decoder -> (info, segments int32 [n, 2] - [begin, end) offsets into the
+    file -, tables uint8 [L.JPEG_TABLES_BYTES], uint16 quantisation tables [components, 64]) as numpy arrays.  Refuses what the serial
+    decoder refuses around the segments (a missing or misnumbered RSTn marker, no EOI after the scan)."""
+    raw = _read(data)
+    lib = L.load()
+    if jpeg_info is None:
+        jpeg_info = info(raw)
+    count = int(lib.es_jpeg_segment_count(C.byref(jpeg_info)))
+    if count == 0:
+        L.check(-1, "es_jpeg_segment_count")
+    segments = np.zeros((count, 2), dtype=np.int32)
+    tables = np.zeros((L.JPEG_TABLES_BYTES,), dtype=np.uint8)
+    qtables = np.zeros((jpeg_info.components, 64), dtype=np.uint16)
+    L.check(lib.es_jpeg_scan_prepare_host(raw, len(raw), C.byref(jpeg_info), segments.ctypes.data, tables.ctypes.data, qtables.ctypes.data),
+            "es_jpeg_scan_prepare_host")
+    return jpeg_info, segments, tables, qtables
+
+
+def status_text(code: int) -> str:
+    return L.load().es_jpeg_status_text(int(code)).decode()
+
+
+def entropy_decode_parallel_host(data, threads, subseq_bytes=0, check=True):
+    """The twin of the device decoder on the CPU (es_jpeg_entropy_decode_parallel_host), `threads` standing for the workgroup's size ->
+    (info, int16 coefficients, uint16 tables [components, 64], status, synchronise rounds); the coefficients are what entropy_decode
+    gives, whatever threads and subseq_bytes are.  A non-zero status raises with its text unless check is False."""
+    raw = _read(data)
+    jpeg_info, segments, tables, qtables = scan_prepare(raw)
+    lib = L.load()
+    coeffs = np.empty((int(lib.es_jpeg_coeff_count(C.byref(jpeg_info))),), dtype=np.int16)
+    status = np.zeros((1,), dtype=np.int32)
+    rounds = C.c_int32(0)
+    buf = np.frombuffer(raw, dtype=np.uint8)
+    L.check(lib.es_jpeg_entropy_decode_parallel_host(C.byref(jpeg_info), 1, (C.c_void_p * 1)(buf.ctypes.data), (C.c_size_t * 1)(len(raw)),
+                                                     (C.c_void_p * 1)(segments.ctypes.data), (C.c_void_p * 1)(tables.ctypes.data), int(subseq_bytes),
+                                                     int(threads), (C.c_void_p * 1)(coeffs.ctypes.data), status.ctypes.data, C.byref(rounds)),
+            "es_jpeg_entropy_decode_parallel_host")
+    if check and status[0] != 0:
+        raise L.EdgeStyleHipError(f"jpeg.entropy_decode_parallel_host: {status_text(status[0])} (status {int(status[0])})")
+    return jpeg_info, coeffs, qtables, int(status[0]), int(rounds.value)
+
+
+def entropy_decode_device(data, subseq_bytes=0, device=DEVICE):
+    """bytes, a path, or a list of either -> (infos, a list of device int16 coefficient tensors, a list of device int16 table tensors -
+    both as ops.jpeg_reconstruct takes them -, the device int32 status tensor).  The host parses and prepares, the files are uploaded as
+    they are, es_jpeg_entropy_decode decodes them.  Nothing is read back: ops.jpeg_status_check(status) does that."""
+    raws, _ = _items(data)
+    parts = [scan_prepare(raw) for raw in raws]
+    infos = (L.JpegInfo * len(raws))(*[p[0] for p in parts])
+    files = [torch.from_numpy(np.frombuffer(raw, dtype=np.uint8).copy()).to(device) for raw in raws]
+    segments = [torch.from_numpy(p[1].reshape(-1)).to(device) for p in parts]
+    tables = [torch.from_numpy(p[2]).to(device) for p in parts]
+    qtables = [torch.from_numpy(np.ascontiguousarray(p[3]).view(np.int16).reshape(-1)).to(device) for p in parts]
+    coeffs, status = ops.jpeg_entropy_decode(infos, files, segments, tables, subseq_bytes)
+    return infos, coeffs, qtables, status
 
 
 # ---- encoding (csrc/jpeg_encode.hip) ----------------------------------------------------------------------------------------------

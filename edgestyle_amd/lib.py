@@ -141,6 +141,9 @@ class JpegEncodeParams(C.Structure):    # es_jpeg_encode_params
     _fields_ = [("quality", C.c_int32), ("subsampling", C.c_int32), ("restart_interval", C.c_int32)]
 
 
+JPEG_TABLES_BYTES = 8560            # ES_JPEG_TABLES_BYTES
+
+
 class Philox(C.Structure):          # es_philox
     _fields_ = [("seed", C.c_uint64), ("offset", C.c_uint64)]
 
@@ -465,6 +468,17 @@ SYMBOLS = {
     "es_jpeg_reconstruct_host": (C.c_int, [C.POINTER(JpegInfo), _I, C.POINTER(_P), C.POINTER(_P), C.POINTER(ImageU8)]),
     "es_jpeg_decode_staging_bytes": (C.c_size_t, [C.POINTER(JpegInfo), _I]),
     "es_jpeg_decode_u8": (C.c_int, [C.POINTER(_P), C.POINTER(C.c_size_t), _I, C.POINTER(ImageU8), _P, _P, C.c_size_t, _P, C.c_size_t, _P]),
+    "es_jpeg_segment_count": (C.c_size_t, [C.POINTER(JpegInfo)]),
+    "es_jpeg_scan_prepare_host": (C.c_int, [_P, C.c_size_t, C.POINTER(JpegInfo), _P, _P, _P]),
+    "es_jpeg_entropy_decode_workspace_bytes": (C.c_size_t, [C.POINTER(JpegInfo), _I]),
+    "es_jpeg_entropy_decode": (C.c_int, [C.POINTER(JpegInfo), _I, C.POINTER(_P), C.POINTER(C.c_size_t), C.POINTER(_P), C.POINTER(_P), _I,
+                                         C.POINTER(_P), _P, _P, C.c_size_t, _P]),
+    "es_jpeg_entropy_decode_parallel_host": (C.c_int, [C.POINTER(JpegInfo), _I, C.POINTER(_P), C.POINTER(C.c_size_t), C.POINTER(_P), C.POINTER(_P), _I, _I,
+                                                       C.POINTER(_P), _P, C.POINTER(C.c_int32)]),
+    "es_jpeg_status_text": (C.c_char_p, [_I]),
+    "es_jpeg_decode_dev_staging_bytes": (C.c_size_t, [C.POINTER(JpegInfo), C.POINTER(C.c_size_t), _I, C.POINTER(C.c_size_t)]),
+    "es_jpeg_decode_dev_u8": (C.c_int, [C.POINTER(_P), C.POINTER(C.c_size_t), _I, C.POINTER(ImageU8), _I, _P, _P, C.c_size_t, _P, C.c_size_t, _P,
+                                        C.c_size_t, _P]),
     "es_jpeg_encode_info_host": (C.c_int, [_I, _I, _I, C.POINTER(JpegEncodeParams), C.POINTER(JpegInfo)]),
     "es_jpeg_header_host": (C.c_int, [C.POINTER(JpegInfo), C.POINTER(JpegEncodeParams), _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "es_jpeg_encode_capacity": (C.c_size_t, [C.POINTER(JpegInfo), C.POINTER(JpegEncodeParams)]),

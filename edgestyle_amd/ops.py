@@ -1387,6 +1387,103 @@ def jpeg_decode_u8(datas: Sequence[bytes], infos, device, out=None, staging_host
 
 
 # ----------------------------------------------------------------------------------------------------------------
+# Huffman decoding on the device (csrc/jpeg_entropy.hip), opt-in: the default decoder is still the host one above.  The host half
+# (es_jpeg_scan_prepare_host) is wrapped in edgestyle_amd/jpeg.py; these take what it prepared.
+# ----------------------------------------------------------------------------------------------------------------
+def jpeg_status_check(status: torch.Tensor, what="jpeg"):
+    """reads the status words back (this waits for the stream) and raises EdgeStyleHipError with the text of the first defect"""
+    words = status.cpu().tolist()
+    for i, code in enumerate(words):
+        if code != 0:
+            text = L.load().es_jpeg_status_text(int(code)).decode()
+            raise L.EdgeStyleHipError(f"{what}: image {i}: {text} (status {code})")
+
+
+def jpeg_entropy_decode(infos, files: Sequence[torch.Tensor], segments: Sequence[torch.Tensor], tables: Sequence[torch.Tensor], subseq_bytes: int = 0,
+                        coeffs=None, status: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
+    """es_jpeg_entropy_decode.  infos: an array of L.JpegInfo; files[i]: device uint8 tensor holding file i (all of it is readable; the
+    segments' offsets are cut to its length); segments[i]: device int32 tensor, the pairs es_jpeg_scan_prepare_host wrote; tables[i]:
+    device uint8 tensor of L.JPEG_TABLES_BYTES.  -> (a list of int16 coefficient tensors, the int32 status tensor [n]), nothing is read
+    back.  Images of different sizes, samplings and segment counts are ONE call: two launches per 16 images."""
+    what = "jpeg_entropy_decode"
+    n = len(infos)
+    if n < 1 or len(files) != n or len(segments) != n or len(tables) != n:
+        raise L.EdgeStyleHipError(f"{what}: one file, one segment and one table tensor per image expected")
+    dev = files[0].device
+    lib = L.load()
+    counts = [int(lib.es_jpeg_coeff_count(C.byref(infos[i]))) for i in range(n)]
+    nseg = [int(lib.es_jpeg_segment_count(C.byref(infos[i]))) for i in range(n)]
+    if 0 in counts or 0 in nseg:
+        L.check(-1, "es_jpeg_coeff_count")
+    for i in range(n):
+        for t, dtype, least, name in ((files[i], torch.uint8, 1, "file"), (segments[i], torch.int32, 2 * nseg[i], "segments"),
+                                      (tables[i], torch.uint8, L.JPEG_TABLES_BYTES, "tables")):
+            if not torch.is_tensor(t) or t.dtype != dtype or t.device != dev or not t.is_cuda or not t.is_contiguous() or t.numel() < least:
+                raise L.EdgeStyleHipError(f"{what}: {name} {i} must be a contiguous {dtype} device tensor of at least {least} values")
+    if coeffs is None:
+        coeffs = [torch.empty((c,), dtype=torch.int16, device=dev) for c in counts]
+    for i, t in enumerate(coeffs):
+        if not torch.is_tensor(t) or t.dtype != torch.int16 or t.device != dev or not t.is_contiguous() or t.numel() < counts[i]:
+            raise L.EdgeStyleHipError(f"{what}: coefficients {i} must be a contiguous int16 device tensor of at least {counts[i]} values")
+    if status is None:
+        status = torch.empty((n,), dtype=torch.int32, device=dev)
+    elif status.dtype != torch.int32 or status.device != dev or not status.is_contiguous() or status.numel() < n:
+        raise L.EdgeStyleHipError(f"{what}: status must be a contiguous int32 device tensor of at least {n} values")
+    need = int(lib.es_jpeg_entropy_decode_workspace_bytes(infos, n))
+    if need == 0:
+        L.check(-1, "es_jpeg_entropy_decode_workspace_bytes")
+    workspace = _jpeg_bytes_buffer(what, workspace, need, dev, "workspace")
+    fp = (C.c_void_p * n)(*[t.data_ptr() for t in files])
+    fn = (C.c_size_t * n)(*[t.numel() for t in files])
+    sp = (C.c_void_p * n)(*[t.data_ptr() for t in segments])
+    tp = (C.c_void_p * n)(*[t.data_ptr() for t in tables])
+    cp = (C.c_void_p * n)(*[t.data_ptr() for t in coeffs])
+    L.check(lib.es_jpeg_entropy_decode(infos, n, fp, fn, sp, tp, int(subseq_bytes), cp, _ptr(status), _ptr(workspace), workspace.numel(), _stream()),
+            "es_jpeg_entropy_decode")
+    return coeffs, status
+
+
+def jpeg_decode_dev_u8(datas: Sequence[bytes], infos, device, subseq_bytes: int = 0, out=None, status: Optional[torch.Tensor] = None,
+                       staging_host: Optional[torch.Tensor] = None, staging_dev: Optional[torch.Tensor] = None,
+                       workspace: Optional[torch.Tensor] = None):
+    """es_jpeg_decode_dev_u8: parse + prepare on the host, one upload of the files, Huffman decoding and reconstruction on the device, up
+    to 64 files (bytes objects; infos: their L.JpegInfo array) -> (a list of uint8 [H, W, 3] tensors on `device`, the int32 status
+    tensor).  staging_host: a pinned uint8 host tensor the caller keeps untouched until the stream has passed the upload; when None one is
+    allocated and the call waits for the stream before it returns.  The status is NOT read here (jpeg_status_check does)."""
+    what = "jpeg_decode_dev_u8"
+    n = len(datas)
+    if n < 1 or len(infos) != n:
+        raise L.EdgeStyleHipError(f"{what}: one info per file expected")
+    dev = torch.device(device)
+    if dev.type == "cuda" and dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    lib = L.load()
+    ln = (C.c_size_t * n)(*[len(d) for d in datas])
+    up = C.c_size_t(0)
+    stage, need = int(lib.es_jpeg_decode_dev_staging_bytes(infos, ln, n, C.byref(up))), int(lib.es_jpeg_reconstruct_workspace_bytes(infos, n))
+    if stage == 0 or need == 0:
+        L.check(-1, "es_jpeg_decode_dev_staging_bytes")
+    out, descs = _jpeg_outputs(what, infos, out, dev)
+    own = staging_host is None
+    if own:
+        staging_host = torch.empty((up.value,), dtype=torch.uint8, pin_memory=True)
+    elif staging_host.dtype != torch.uint8 or staging_host.is_cuda or not staging_host.is_contiguous() or staging_host.numel() < up.value:
+        raise L.EdgeStyleHipError(f"{what}: staging_host must be a contiguous uint8 host tensor of at least {up.value} bytes")
+    staging_dev = _jpeg_bytes_buffer(what, staging_dev, stage, dev, "staging_dev")
+    workspace = _jpeg_bytes_buffer(what, workspace, need, dev, "workspace")
+    if status is None:
+        status = torch.empty((n,), dtype=torch.int32, device=dev)
+    elif status.dtype != torch.int32 or status.device != dev or not status.is_contiguous() or status.numel() < n:
+        raise L.EdgeStyleHipError(f"{what}: status must be a contiguous int32 device tensor of at least {n} values")
+    bp = (C.c_void_p * n)(*[C.cast(C.c_char_p(d), C.c_void_p) for d in datas])
+    L.check(lib.es_jpeg_decode_dev_u8(bp, ln, n, descs, int(subseq_bytes), _ptr(status), C.c_void_p(staging_host.data_ptr()), staging_host.numel(),
+                                      _ptr(staging_dev), staging_dev.numel(), _ptr(workspace), workspace.numel(), _stream()), "es_jpeg_decode_dev_u8")
+    if own:                                       # the upload reads the staging memory on the stream: it must not be freed before
+        torch.cuda.current_stream().synchronize()
+    return out, status
+
+
+# ----------------------------------------------------------------------------------------------------------------
 # JPEG encoding (csrc/jpeg_encode.hip): RGB or gray bytes -> the bytes of Pillow's file, written by the device.  edgestyle_amd/jpeg.py
 # owns the convenient entry points (Pillow's argument spellings, the download); these take an L.JpegEncodeParams.
 # ----------------------------------------------------------------------------------------------------------------

@@ -873,7 +873,8 @@ int es_pose_points_host(const float* kp, int W, int H, float* out);
 /* =========================================================================================================
  * JPEG decoding (csrc/jpeg.h, csrc/jpeg.hip): the bytes of a baseline JPEG file -> uint8 [H, W, 3] RGB on the device, what Pillow's
  * Image.open(..).convert("RGB") gives (libjpeg's default decoder settings: JDCT_ISLOW, fancy upsampling), byte for byte.  Two halves that
- * meet at the quantised DCT coefficients: header parsing and Huffman decoding are serial and stay on the host (plain C++, csrc/jpeg.h);
+ * meet at the quantised DCT coefficients: header parsing and Huffman decoding are serial and stay on the host (plain C++, csrc/jpeg.h;
+ * that is the default - the Huffman decoding on the device, below es_jpeg_decode_u8, is opt-in);
  * dequantisation, the 8x8 inverse DCT, chroma upsampling and YCbCr -> RGB are two launches on the device, and es_jpeg_reconstruct_host
  * runs the same __host__ __device__ integer code on the CPU, bit for bit.
  * SUPPORTED: SOF0 / SOF1, 8-bit samples, Huffman coding, one interleaved scan; 1 component (gray -> R = G = B) or 3 components YCbCr
@@ -934,6 +935,62 @@ int es_jpeg_reconstruct_host(const es_jpeg_info* infos, int count, const int16_t
 size_t es_jpeg_decode_staging_bytes(const es_jpeg_info* infos, int count);
 int es_jpeg_decode_u8(const uint8_t* const* bytes, const size_t* n, int count, const es_image_u8* out, void* staging_host,
                       void* staging_dev, size_t staging_bytes, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * Huffman decoding on the device (csrc/jpeg_entropy.hip), opt-in: THE DEFAULT IS STILL THE HOST DECODER - es_jpeg_decode_u8 and every
+ * call above keep their code paths and bytes.  The file's bytes in device memory -> the int16 coefficient buffer that
+ * es_jpeg_entropy_decode_host writes, bit for bit, in the layout es_jpeg_reconstruct takes.  The host keeps the header parse and one
+ * walk over the scan that finds the SEGMENTS (the entropy-coded bytes between restart markers; a file without DRI has one) and checks
+ * what the serial decoder checks around them (RSTn present and numbered, EOI after the last one) - no Huffman decoding.
+ * One workgroup of 1024 decoders owns one segment (grid.y = image, 16 images per launch; sizes, samplings and segment counts mix).  The
+ * segment's `len` raw bytes are cut into J = ceil(len / S) subsequences, S = max(subseq_bytes, ceil(len / 1024)), one decoder each.
+ * Bits are read from the raw bytes (a byte carries data unless it is a 00 after an FF or an FF before an FF).  Huffman streams
+ * re-synchronise: every decoder starts from a guessed state (position, block within the MCU, zigzag index), proposes its exit state to
+ * its neighbour, and the rounds repeat until no entry changes - at most J + 1, a handful on real files (a decoder handed
+ * the dead state of a neighbour that met an impossible code proposes from its own guess again; once the rounds have settled, the first
+ * dead entry and everything behind it write nothing); then the counts of blocks
+ * and the sums of DC differences are scanned across the workgroup and each decoder decodes once more from its true state and writes.
+ * Workgroups never wait for one another.  Every store address comes from block counters checked against the geometry; blocks past a
+ * segment's share are dropped, padding bits and stray bytes before a marker are not an error.
+ * STATUS: one int32 per image in device memory, 0 or the first defect by (segment, block): 1 no DC code, 2 no AC code, 3 a zero run
+ * past coefficient 63, 4 a DC coefficient outside 16 bits, 5 truncated (a needed symbol ends past the segment's bits, or the segment
+ * holds fewer blocks than it must).  The call is asynchronous: read the word after synchronising; es_jpeg_status_text gives the text.
+ * LIMIT: files below 256 MiB.  Every call here returns -1 while a plan records.  es_jpeg_entropy_decode_parallel_host is the twin: the
+ * same __host__ __device__ code and the same rounds on the CPU.
+ * --------------------------------------------------------------------------------------------------------- */
+#define ES_JPEG_TABLES_BYTES 8560
+typedef struct { uint32_t begin, end; } es_jpeg_segment;    /* [begin, end): offsets from the file's first byte */
+/* host-only: the number of segments: ceil(MCUs / restart_interval), 1 without DRI (0 with es_last_error() on a bad info) */
+size_t es_jpeg_segment_count(const es_jpeg_info* info);
+/* host-only: segments: HOST [es_jpeg_segment_count]; tables: HOST, ES_JPEG_TABLES_BYTES (the Huffman tables of each component,
+ * flattened); qtables: HOST uint16 [components][64] as es_jpeg_entropy_decode_host writes them.  0, or -1 with the serial decoder's
+ * reason (a missing or misnumbered RSTn marker, no EOI after the scan, ...). */
+int es_jpeg_scan_prepare_host(const uint8_t* bytes, size_t n, const es_jpeg_info* info, es_jpeg_segment* segments, void* tables,
+                              uint16_t* qtables);
+/* host-only: bytes of device scratch es_jpeg_entropy_decode needs (one status word per segment); 0 with es_last_error() */
+size_t es_jpeg_entropy_decode_workspace_bytes(const es_jpeg_info* infos, int count);
+/* bytes_dev[i]: DEVICE copy of file i, bytes_n[i] readable bytes (every offset of segments_dev is cut to it); segments_dev[i] /
+ * tables_dev[i]: DEVICE copies of what es_jpeg_scan_prepare_host wrote, 4-byte aligned; subseq_bytes: 0 (the default, 128) or >= 4;
+ * coeffs_dev[i]: DEVICE int16 [es_jpeg_coeff_count], 16-byte aligned, every value written (zeroed by a memset node first);
+ * status_dev: DEVICE int32 [count].  Asynchronous on `stream`, nothing is allocated: capturable. */
+int es_jpeg_entropy_decode(const es_jpeg_info* infos, int count, const uint8_t* const* bytes_dev, const size_t* bytes_n,
+                           const es_jpeg_segment* const* segments_dev, const void* const* tables_dev, int subseq_bytes,
+                           int16_t* const* coeffs_dev, int32_t* status_dev, void* workspace, size_t workspace_bytes, void* stream);
+/* host-only: the twin, everything in HOST memory.  threads: 1 .. 1024, stands for the workgroup's size; status: int32 [count];
+ * rounds_out (may be NULL): the largest number of synchronise rounds a segment of these images took. */
+int es_jpeg_entropy_decode_parallel_host(const es_jpeg_info* infos, int count, const uint8_t* const* bytes, const size_t* bytes_n,
+                                         const es_jpeg_segment* const* segments, const void* const* tables, int subseq_bytes, int threads,
+                                         int16_t* const* coeffs, int32_t* status, int32_t* rounds_out);
+const char* es_jpeg_status_text(int code);
+/* Parse + prepare on the host, ONE upload of the files, segments and tables from pinned staging, Huffman decoding on the device,
+ * es_jpeg_reconstruct: the host never touches a coefficient.  Up to 64 files.  es_jpeg_decode_dev_staging_bytes returns the size of
+ * staging_dev (DEVICE, 16-byte aligned: the upload, then coefficients and scratch) and stores in *upload_bytes the size of
+ * staging_host (HOST, pinned, 16-byte aligned; untouched until the copy has run).  status_dev: DEVICE int32 [count], as above.
+ * workspace: es_jpeg_reconstruct_workspace_bytes.  Nothing is allocated. */
+size_t es_jpeg_decode_dev_staging_bytes(const es_jpeg_info* infos, const size_t* n, int count, size_t* upload_bytes);
+int es_jpeg_decode_dev_u8(const uint8_t* const* bytes, const size_t* n, int count, const es_image_u8* out, int subseq_bytes,
+                          int32_t* status_dev, void* staging_host, size_t staging_host_bytes, void* staging_dev, size_t staging_dev_bytes,
+                          void* workspace, size_t workspace_bytes, void* stream);
 
 /* =========================================================================================================
  * JPEG encoding (csrc/jpeg.h, csrc/jpeg_encode.hip): uint8 [H, W, 3] RGB (or [H, W] gray) on the device -> the bytes of the file that
